@@ -15,9 +15,13 @@ value = units of all ranks / max-over-ranks time (weak scaling).
 
 Synthetic data: no checkpoint or dataset exists offline -> weights ~ N(0, 0.02) from a fixed seed,
 token ids uniform random.  Inputs are resident in HBM before the timed region.
-Prints ONE JSON line (rank 0) with `roofline` (dominant elementwise pass, HIP events on the launch
-stream, rotating over a > 256 MiB pool so HBM rather than Infinity-Cache traffic is timed) and
-`cpu_baseline` (the C restatement of the reference path on this host's cores, N = 1 only).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the steps and prints the line;
+with `--full` the line also carries `roofline` (dominant elementwise pass, HIP events on the launch
+stream, rotating over a > 256 MiB pool so HBM rather than Infinity-Cache traffic is timed),
+`cpu_baseline` (the C restatement of the reference path on this host's cores, N = 1 only) and
+`secondary` (the other one-GPU configurations, default workload only).
+`--dump-outputs DIR` writes what the timed path returned in its last step as DIR/<name>.npy (float32):
+the window NLL (LLaMA), the start / end logits (BERT QA) or the training loss (RoBERTa).
 """
 import argparse
 import ctypes
@@ -73,10 +77,15 @@ def parse():
                          "which the reference does not do")
     ap.add_argument("--force-dist", action="store_true",
                     help="debug: initialise torch.distributed (nccl) and take the multi-rank code path even with one rank")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure the roofline legs, the CPU baseline and the secondary legs (the plain run times "
+                         "the steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline legs")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the three short secondary legs (the other BASELINE configs that fit one GPU) appended to the default line")
+                    help="with --full: skip the short secondary legs (the other BASELINE configs that fit one GPU) appended to the default line")
     ap.add_argument("--dry-run", action="store_true",
                     help="plumbing check without a GPU: tiny LLaMA on the CPU, gloo instead of RCCL, same sharding / timing / "
                          "gather code (the line is marked invalid)")
@@ -86,6 +95,8 @@ def parse():
     if a.model is not None and a.model != model and a.workload == "llama-7b-e4m3":
         # the pre-workload spelling: --model llama-2-13b --activation posit8_2 --weight posit8_2
         pass
+    if not a.full:                                  # a plain run measures the headline only
+        a.no_cpu_baseline = a.no_roofline = a.no_secondary = True
     a.kind = kind
     a.model = a.model or model
     a.activation = a.activation or act
@@ -116,8 +127,8 @@ SECONDARY = ("bert-base-squad-e4m3", "llama-13b-posit8_2", "roberta-mrpc-int8-e5
 
 def secondary_legs(budget_s=190.0):
     """The other BASELINE.json configs that fit one GPU, three timed steps each, AFTER the headline leg (which alone is `value`): each
-    one runs as a child process of its own (`bench.py --workload ...`: model built, timed, freed), so the driver's default command
-    times them too.  A leg that fails or runs out of budget is reported as such, never fatal."""
+    one runs as a child process of its own (`bench.py --workload ...`: model built, timed, freed), so `bench.py --full` times them
+    too.  A leg that fails or runs out of budget is reported as such, never fatal."""
     import subprocess
     out = {}
     t_all = time.perf_counter()
@@ -373,6 +384,14 @@ def linears_in_window_leg(model, device, M):
         return {"error": f"{type(e).__name__}: {e}"}
 
 
+def dump_outputs(dirname, arrays):
+    """`--dump-outputs`: each tensor of `arrays` (name -> tensor, read after the timed region) as DIR/<name>.npy in float32."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), t.detach().float().cpu().numpy().astype(np.float32))
+
+
 def native_library_note():
     """{} for the product library; names the file when QT_HIP_LIB made the package load another one (tools/ only)."""
     from quantized_training import _native
@@ -505,12 +524,13 @@ def encoder_workload(a, device, world, rank, multi, sync):
             sync()
             t0 = time.perf_counter()
             for i in range(a.steps):
-                run(batches[a.warmup + i])
+                last = run(batches[a.warmup + i])
             sync()
             if multi:
                 dist.barrier()
             sync()
             el = time.perf_counter() - t0
+        outputs = {"start_logits": last.start_logits, "end_logits": last.end_logits}
         what = (f"BERT-base QA model (12 layers, hidden 768, random init) SQuAD-style eval batch [{B}, {S}], fake-quant activation={a.activation} "
                 f"weight={a.weight}, --quantize_forward gemm (weights re-quantized every forward)")
         launch = "hipGraph replay"
@@ -551,12 +571,13 @@ def encoder_workload(a, device, world, rank, multi, sync):
         sync()
         t0 = time.perf_counter()
         for i in range(a.steps):
-            step.replay(batches[3 + a.warmup + i])
+            last = step.replay(batches[3 + a.warmup + i])
         sync()
         if multi:
             dist.barrier()
         sync()
         el = time.perf_counter() - t0
+        outputs = {"loss": last}
         what = (f"RoBERTa-base classifier (12 layers, hidden 768, random init) MRPC-style TRAINING step [{B}, {S}]: fake-quant activation={a.activation} "
                 f"weight={a.weight}, E5M2 gradients (--quantize_backprop gemm,residual), dropout {drop:g}, clip 1.0, AdamW")
         launch = "hipGraph replay (forward + backward + optimizer)"
@@ -569,6 +590,8 @@ def encoder_workload(a, device, world, rank, multi, sync):
     el = float(t.item())
     if rank != 0:
         return None
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, outputs)
     total = elems * a.steps * world
     out = {"metric": "quantized_elements_per_sec", "value": total / el, "unit": "elements/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
            "ms_per_step": el / a.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
@@ -654,8 +677,9 @@ def main():
     windows = harness.wikitext_windows(tokens.shape[1], a.max_length, a.stride)
     mine = harness.shard_round_robin(windows, rank, world)
     need = a.warmup + a.steps
-    assert len(mine) >= need, "not enough windows"
-    batches = [(tokens[:, b:e].to(device), t) for (b, e, t) in mine[:need]]   # resident before timing
+    # resident before timing; more steps than this rank has windows go round its windows again
+    resident = [(tokens[:, b:e].to(device), t) for (b, e, t) in mine[:need]]
+    batches = [resident[i % len(resident)] for i in range(need)]
 
     nlls = []
     graph_used = False
@@ -707,6 +731,8 @@ def main():
     allnll = harness.gather_in_order(local, a.steps * world, rank, world) if multi else local
 
     out = None
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"window_nll": allnll[-world:]})     # the last step of every rank
     if rank == 0:
         total_elems = elems_per_step * a.steps * world
         hidden, layers = model.config.hidden_size, model.config.num_hidden_layers

@@ -1,4 +1,4 @@
-"""Copies the rocprofv3 summaries of the last tools/gpu_session_bench.sh run from gpurun_out/ into
+"""Copies the rocprofv3 summaries of the last tools/gpu_session_bench.sh run from its output directory ($OUT, default session_out/) into
 profiles/ (tracked) and derives the per-launch HBM traffic of the dominant kernel from the PMC passes
 (FETCH_SIZE x2 on gfx950 for 16-B/lane streaming reads, MI355X_MICROARCH.md HBM section)."""
 import csv
@@ -11,13 +11,14 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1] if len(sys.argv) > 1 else "r01"
+SRC = os.path.join(ROOT, os.environ.get("OUT", "session_out"))     # the session scripts' output directory
 FRESH_S = float(os.environ.get("FRESH_HOURS", "4")) * 3600.0
 out = os.path.join(ROOT, "profiles")
 os.makedirs(out, exist_ok=True)
 
 
 def one(pattern):
-    f = glob.glob(os.path.join(ROOT, "gpurun_out", pattern))
+    f = glob.glob(os.path.join(SRC, pattern))
     return max(f, key=os.path.getmtime) if f else None          # the latest session's file, whatever its numeric prefix
 
 
@@ -29,7 +30,7 @@ def pmc(path, name, kernel="fq_kernel"):
 
 shutil.copy(one("prof_bench/*/*kernel_stats.csv"), os.path.join(out, f"{tag}_bench_kernel_stats.csv"))
 shutil.copy(one("prof_roofline/*/*kernel_stats.csv"), os.path.join(out, f"{tag}_roofline_kernel_stats.csv"))
-shutil.copy(os.path.join(ROOT, "gpurun_out", "bench_n1.json"), os.path.join(out, f"{tag}_bench_n1.json"))
+shutil.copy(os.path.join(SRC, "bench_n1.json"), os.path.join(out, f"{tag}_bench_n1.json"))
 rows = list(csv.DictReader(open(os.path.join(out, f"{tag}_roofline_kernel_stats.csv"))))
 bench = json.load(open(os.path.join(out, f"{tag}_bench_n1.json")))
 n = 4096 * 11008
@@ -92,7 +93,7 @@ def clean(src, dst):
 
 
 # per-window breakdown of the headline run, the LLaMA-2-13B posit(8,2) leg, block-scaled path, kernel experiments
-G = os.path.join(ROOT, "gpurun_out")
+G = SRC
 for src, dst in (("window_breakdown.txt", "window_breakdown.txt"), ("window_breakdown_13b_posit.txt", "13b_posit8_2_window_breakdown.txt"),
                  ("bench_13b_posit8_2.json", "13b_posit8_2_bench.json"), ("mx_gemm.log", "mx_gemm.txt"), ("mx_linear.log", "mx_linear.txt"),
                  ("mx_quant.log", "mx_quant.txt"), ("mx_wide.log", "mx_wide_ablation.txt"), ("tile_fetch.log", "tile_fetch_probe.txt"),
