@@ -58,11 +58,8 @@ __device__ __forceinline__ int chunk_off(int row, int chunk) { return row * 128 
 __device__ __forceinline__ uint32_t lds_addr(const void *p) {
     return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)p;
 }
-// LDS-DMA as inline asm (16 bytes per lane, 1 KiB per wave): hipcc's wait-count model then does not see a pending LDS access
-// and keeps counted waits for the ordinary loads (mask, fragments); the DMA is waited for explicitly (vmcnt(0) + barrier)
-__device__ __forceinline__ void dma16(const uint8_t *src, uint32_t dst) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 1\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(dst) : "memory");
-}
+// (LDS-DMA: dma16, qt_device.h; the ordinary loads -- mask, fragments -- keep counted waits, the DMA is waited for explicitly with
+// vmcnt(0) + barrier)
 
 // F: operand format of q, k, v and p (0 = E4M3, 1 = E5M2)
 //

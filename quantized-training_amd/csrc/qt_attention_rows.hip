@@ -72,11 +72,6 @@ __device__ __forceinline__ int chunk_off(int row, int chunk) { return row * kRow
 __device__ __forceinline__ uint32_t lds_addr(const void *p) {
     return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)p;
 }
-// LDS-DMA as inline asm (hipcc's wait-count model then keeps counted waits for ordinary loads, see qt_attention_fp8.hip): a uniform
-// base (SGPR pair) + a 32-bit lane offset; the 64 lanes' 16 bytes land linearly at `dst`
-__device__ __forceinline__ void dma16(const void *base, uint32_t off, uint32_t dst) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 1\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(off), "s"(base), "s"(dst) : "memory");
-}
 __device__ __forceinline__ float max3(float x, float y, float z) {
     float d;
     asm("v_max3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(x), "v"(y), "v"(z));

@@ -146,9 +146,6 @@ struct UniformDiv {
     __device__ __forceinline__ float operator()(float x) const { return x / s; }
 };
 
-// Internal kind (not part of the C ABI): a table format whose map is odd-symmetric (qt_format.p0 == 1, see qt_format_for);
-// only entries 0 .. 0x7FFF are staged and the sign goes back on finite non-zero and infinite results.
-constexpr int kFmtLutHalf = 4;
 constexpr int kFmtRows = 5;      // QT_FMT_LUT with the row words behind the map (qt_format.p1 bit 0): the row form, table of rows in LDS
 
 template <int KIND>
@@ -171,10 +168,6 @@ struct Rounder {
             if ((fmt.p1 & 16) && img == 0x80000000u) r = qt_f2u(fmt.fhi);
             if (__builtin_expect(p.y & 1u, 0)) r = (uint32_t)glut[img >> 16] << 16;
             return r;
-        } else if constexpr (KIND == kFmtLutHalf) {
-            const uint32_t t = lds[(img >> 16) & 0x7FFFu];
-            const uint32_t sign = ((t - 1u) < 0x7F80u) ? (img & 0x80000000u) : 0u;        // zero and NaN results carry no sign
-            return (t << 16) | sign;
         } else if constexpr (KIND == QT_FMT_LUT) {
             return (uint32_t)lds[img >> 16] << 16;
         } else if constexpr (KIND == QT_FMT_FP_SAT) {
@@ -314,5 +307,21 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
     return v;
 }
 
+// ---- 16-byte LDS-DMA (global_load_lds_dwordx4): each of the wave's 64 lanes brings 16 bytes from global memory, and they land
+// linearly at LDS bytes dst .. dst + 1023 (dst wave-uniform).  The instruction takes its LDS address from M0.  M0 is reserved by
+// the compiler, which may keep values of its own there, and an "m0" clobber only draws a warning: so M0 is written in the same
+// asm statement that reads it, never in one of its own.
+// Inline asm rather than __builtin_amdgcn_global_load_lds: with the builtin, hipcc's wait-count model sees a pending access to LDS
+// and turns every wait for an ordinary load into vmcnt(0), which also waits for the DMA pieces in flight.  Hidden from the model,
+// the waits for ordinary loads stay counted ones (at worst too strict, never too lax: uncounted entries only make the real queue
+// longer than the one hipcc waits on), and the caller waits for the DMA itself with counted vmcnt.
+// Per-lane source address:
+__device__ __forceinline__ void dma16(const void *src, uint32_t dst) {
+    asm volatile("s_mov_b32 m0, %1\n\ts_nop 1\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(dst) : "memory");
+}
+// Wave-uniform base (SGPR pair) + 32-bit lane offset:
+__device__ __forceinline__ void dma16(const void *base, uint32_t off, uint32_t dst) {
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 1\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(off), "s"(base), "s"(dst) : "memory");
+}
 
 }  // namespace

@@ -129,8 +129,8 @@ __global__ __launch_bounds__(BLOCK) void fq_kernel(const void *__restrict__ xv, 
                                                   size_t n, qt_format fmt, const uint16_t *__restrict__ lut,
                                                   const float *__restrict__ scale, uint32_t *amax_out) {
     Rounder<KIND> rnd{fmt, nullptr};
-    if constexpr (KIND == QT_FMT_LUT || KIND == kFmtLutHalf) {
-        constexpr int kVecs = (KIND == kFmtLutHalf ? QT_MAP_ENTRIES / 2 : QT_MAP_ENTRIES) * 2 / 16;   // 64 KiB: two workgroups per CU
+    if constexpr (KIND == QT_FMT_LUT) {
+        constexpr int kVecs = QT_MAP_ENTRIES * 2 / 16;
         __shared__ uint4 s_lut[kVecs];
         if (yv) {
             const uint4 *g = (const uint4 *)lut;
@@ -257,7 +257,7 @@ __global__ __launch_bounds__(256) void fq_gather_vec_kernel(const void *__restri
 // of a workgroup at a few points of the chain / LayerNorm-backward kernels.  QT_EW_STAMPS = device address of [launch][512 workgroups][32]
 // slots; every launch the host issues takes the next region (a captured graph keeps the region of its capture).
 #ifdef QT_TUNING_BUILD
-#define QT_EW_STAMP_FIELD unsigned long long *dbg; int ablate;
+#define QT_EW_STAMP_FIELD unsigned long long *dbg;
 #define QT_EW_STAMP(a, slot)                                                                                                     \
     do {                                                                                                                         \
         if ((a).dbg && blockIdx.x < 512 && (threadIdx.x & 63) == 0 && (threadIdx.x == 0 || threadIdx.x == blockDim.x - 64))      \
@@ -302,7 +302,6 @@ struct ChainArgs {
     int pre_op;
     const uint4 *x2;
     uint4 *pre_out;
-    int table_in_lds;         // table formats: stage the row words in LDS (else gather them from global memory)
     QT_EW_STAMP_FIELD
 };
 
@@ -331,14 +330,7 @@ __global__ __launch_bounds__(kChainBlock) void fq_chain_kernel(ChainArgs a, qt_f
     __shared__ uint4 s_rows[KIND == kFmtRows ? 512 : 1];
     QT_EW_STAMP(a, 0);
     QT_EW_STAMP_HEAD(a, 0x100 + NS * 16 + (a.colsum_stage >= 0 ? 1 : 0) + (a.pre_op << 1));
-    // (a run-time choice of where the row table lies makes its pointer generic: every row gather becomes a flat_load.  The product build
-    // always stages the table; the tuning build keeps the switch.)
-#ifdef QT_TUNING_BUILD
-    const bool rows_in_lds = a.table_in_lds != 0;
-#else
-    constexpr bool rows_in_lds = true;
-#endif
-    const Rounder<KIND> rnd = chain_rounder<KIND>(fmt, lut, s_rows, kChainBlock, rows_in_lds);
+    const Rounder<KIND> rnd = chain_rounder<KIND>(fmt, lut, s_rows, kChainBlock);
     QT_EW_STAMP(a, 1);
     const int t = threadIdx.x;
     const int v = t % kChainStripV, rl = t / kChainStripV;
@@ -378,26 +370,10 @@ __global__ __launch_bounds__(kChainBlock) void fq_chain_kernel(ChainArgs a, qt_f
                 const long r = r0 + (long)u * kChainRowLanes;
                 if (r >= r_end) continue;
                 const size_t idx = (size_t)(r * a.cv + cvec);
-#ifdef QT_TUNING_BUILD
-                // QT_CHAIN_ABLATE (timing only, results are garbage): 1 = no GELU arithmetic, 2 = no fake-quantizer stages
-                const uint4 val = (a.ablate & 1) ? q[u] : chain_prologue(a.pre_op, q[u], q2[u]);
-                if (a.pre_op && a.pre_out) a.pre_out[idx] = val;
-                uint4 res[NS];
-                if (a.ablate & 2) {
-#pragma unroll
-                    for (int i = 0; i < NS; ++i) {
-                        res[i] = val;
-                        if (a.st[i].out) a.st[i].out[idx] = val;
-                    }
-                } else {
-                    chain_stages<KIND, NS>(a.st, sc, rnd, val, idx, amax, res);
-                }
-#else
                 const uint4 val = chain_prologue(a.pre_op, q[u], q2[u]);
                 if (a.pre_op && a.pre_out) a.pre_out[idx] = val;
                 uint4 res[NS];
                 chain_stages<KIND, NS>(a.st, sc, rnd, val, idx, amax, res);
-#endif
 #pragma unroll
                 for (int i = 0; i < NS; ++i) {
                     if (a.colsum_stage == i) {
@@ -870,13 +846,13 @@ __device__ __forceinline__ uint4 fq8_closed16(const uint4 v0, const uint4 v1, co
 template <bool OBS, bool BOTH, bool E5M2>
 __global__ __launch_bounds__(256) void fq8_kernel(const uint4 *__restrict__ x, uint4 *__restrict__ y, uint4 *__restrict__ y8,
                                                   size_t npair, qt_format fmt, const float *__restrict__ scale,
-                                                  uint32_t *amax_out, bool hw) {
+                                                  uint32_t *amax_out) {
     float s = scale ? qt_bf2f(qt_f2bf(*scale)) : 1.0f;
     const bool unit = (s == 1.0f);
     const UniformDiv dv(s);
     uint32_t amax = 0;
     if constexpr (!BOTH) {
-        if (unit && hw) {                             // FP8 code only, scale 1: hardware conversion (see fq8_fast16)
+        if (unit) {                                   // FP8 code only, scale 1: hardware conversion (see fq8_fast16)
             uint32_t mag = 0;
             for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < npair; i += (size_t)gridDim.x * 256) {
                 const uint4 v0 = x[2 * i], v1 = x[2 * i + 1];
@@ -893,7 +869,7 @@ __global__ __launch_bounds__(256) void fq8_kernel(const uint4 *__restrict__ x, u
         }
     }
     if constexpr (BOTH && !OBS) {
-        if (unit && hw) {                             // bf16 + FP8 code, scale 1: same conversion, decoded back for the bf16 copy
+        if (unit) {                                   // bf16 + FP8 code, scale 1: same conversion, decoded back for the bf16 copy
             for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < npair; i += (size_t)gridDim.x * 256) {
                 const uint4 v0 = x[2 * i], v1 = x[2 * i + 1];
                 uint32_t a[4] = {v0.x, v0.y, v0.z, v0.w}, b[4] = {v1.x, v1.y, v1.z, v1.w};
@@ -1286,15 +1262,14 @@ __global__ __launch_bounds__(256) void fq_pc_vec_kernel(const uint4 *__restrict_
     }
 }
 
-// Table formats on large per-channel tensors: the value map staged in LDS (the whole 128 KiB, or its non-negative 64 KiB half
-// for odd-symmetric maps: then two workgroups per CU) by a persistent 1024-thread workgroup, ONE WAVE PER ROW -- the row's
+// Table formats on large per-channel tensors: the whole 128 KiB value map staged in LDS by a persistent 1024-thread workgroup, ONE WAVE PER ROW -- the row's
 // scale in a register, amax reduced inside the wave, no workgroup barrier in the row loop.  The kernel above gathers from
 // the L2-resident table instead (3.0-3.1 TB/s on a [4096, 11008] weight).
 template <int IO, int KINDL>
 __global__ __launch_bounds__(1024) void fq_pc_vec_lds_kernel(const uint4 *__restrict__ x, uint4 *__restrict__ y, size_t rows,
                                                              size_t C, size_t vpr, qt_format fmt, const uint16_t *__restrict__ lut,
                                                              const float *__restrict__ scale, uint32_t *amax_out) {
-    constexpr int kVecs = (KINDL == kFmtLutHalf ? QT_MAP_ENTRIES / 2 : QT_MAP_ENTRIES) * 2 / 16;
+    constexpr int kVecs = QT_MAP_ENTRIES * 2 / 16;
     __shared__ uint4 s_lut[kVecs];
     {
         const uint4 *g = (const uint4 *)lut;
@@ -1515,17 +1490,6 @@ constexpr size_t kLutLdsMinElems = (size_t)1 << 21;
 #ifdef QT_TUNING_BUILD
 int g_variant = 0;        // tools/exp_stream.py: selects a launch geometry for bf16 closed-form passes
 #endif
-// Observed SHORT passes (the [2048, 768 .. 3072] tensors of a training step): 16-byte loads in flight per lane, i.e. how few
-// workgroups -- and same-address atomics on the freshly zeroed amax slot -- the launch has.  (Measured in the training step, round 5:
-// 1 or 2 makes no difference, 9.0 against 9.1 us per launch.)
-inline int obs_unroll() {
-#ifdef QT_TUNING_BUILD
-    static const int v = getenv("QT_OBS_UNR") ? atoi(getenv("QT_OBS_UNR")) : 1;
-    return v;
-#else
-    return 1;
-#endif
-}
 int g_blocks_per_cu = 32;
 
 template <int IO, int KIND, int BLOCK, int UNR, int NT>
@@ -1555,18 +1519,10 @@ int launch_fq_kind(const void *x, void *y, size_t n, const qt_format &fmt, const
             int row_blocks = 0;
 #ifdef QT_TUNING_BUILD
             static const int e_row_blocks = getenv("QT_ROW_BLOCKS") ? atoi(getenv("QT_ROW_BLOCKS")) : 0;   // tools/ only: workgroups per CU
-            static const int row_wide = getenv("QT_ROW_WIDE") ? atoi(getenv("QT_ROW_WIDE")) : 0;           // tools/ only: 1024-thread workgroups
             row_blocks = e_row_blocks;
-            if (row_wide) {
-                unsigned grid = grid_for(nv, (size_t)1024, row_blocks ? row_blocks : 4);
-                if (amax) fq_kernel<IO, kFmtRows, true, 1024><<<grid, 1024, 0, st>>>(x, y, nv, n, fmt, lut, scale, amax);
-                else fq_kernel<IO, kFmtRows, false, 1024><<<grid, 1024, 0, st>>>(x, y, nv, n, fmt, lut, scale, amax);
-                return launch_status();
-            }
 #endif
             if (IO == kIoBf16 && nv <= kRowsDirectMaxVecs) {           // short pass: the table where it lies (fq_rows_direct_kernel)
-                if (amax && obs_unroll() == 2) fq_rows_direct_kernel<IO, true, 1024, 2><<<grid_for(nv, 2048, 2), 1024, 0, st>>>(x, y, nv, n, fmt, lut, scale, amax);
-                else if (amax) fq_rows_direct_kernel<IO, true, 1024><<<grid_for(nv, 1024, 2), 1024, 0, st>>>(x, y, nv, n, fmt, lut, scale, amax);
+                if (amax) fq_rows_direct_kernel<IO, true, 1024><<<grid_for(nv, 1024, 2), 1024, 0, st>>>(x, y, nv, n, fmt, lut, scale, amax);
                 else fq_rows_direct_kernel<IO, false, 256><<<grid_for(nv, 256, 8), 256, 0, st>>>(x, y, nv, n, fmt, lut, scale, amax);
                 return launch_status();
             }
@@ -1596,20 +1552,6 @@ int launch_fq_kind(const void *x, void *y, size_t n, const qt_format &fmt, const
     }
     const size_t nvec = n / kPer;
     if constexpr (KIND == QT_FMT_LUT) {
-        // (Odd-symmetric maps could stage only their non-negative half -- 64 KiB, two workgroups per CU.  Measured SLOWER on bf16
-        // [4096, 11008]: posit8_1 4.37 against 4.79 TB/s with the whole table: putting the sign back costs three more VALU operations
-        // per element than the second workgroup's waves recover.  Tuning build only.)
-#ifdef QT_TUNING_BUILD
-        static const int half_mode = getenv("QT_LUT_HALF") ? atoi(getenv("QT_LUT_HALF")) : 0;
-        if (fmt.p0 == 1 && half_mode) {
-            unsigned grid = grid_for(nvec, (size_t)kLutBlock * 4 * 4, 2);
-            if (amax)
-                fq_kernel<IO, kFmtLutHalf, true, kLutBlock, 4><<<grid, kLutBlock, 0, st>>>(x, y, nvec, n, fmt, lut, scale, amax);
-            else
-                fq_kernel<IO, kFmtLutHalf, false, kLutBlock, 4><<<grid, kLutBlock, 0, st>>>(x, y, nvec, n, fmt, lut, scale, amax);
-            return launch_status();
-        }
-#endif
         unsigned grid = grid_for(nvec, (size_t)kLutBlock * 4 * 4, 1);
         if (amax)
             fq_kernel<IO, KIND, true, kLutBlock, 4><<<grid, kLutBlock, 0, st>>>(x, y, nvec, n, fmt, lut, scale, amax);
@@ -1641,9 +1583,7 @@ int launch_fq_kind(const void *x, void *y, size_t n, const qt_format &fmt, const
         }
 #endif
         unsigned grid = grid_for(nvec, (size_t)kAluBlock * kUnroll, g_blocks_per_cu);
-        if (amax && nvec <= kRowsDirectMaxVecs && obs_unroll() == 2)     // observed short pass: an eighth of the workgroups, two loads in flight per lane
-            fq_kernel<IO, KIND, true, 1024, 2><<<grid_for(nvec, 2048, 2), 1024, 0, st>>>(x, y, nvec, n, fmt, lut, scale, amax);
-        else if (amax && nvec <= kRowsDirectMaxVecs)     // observed short pass: a quarter of the workgroups, i.e. of the same-address atomics
+        if (amax && nvec <= kRowsDirectMaxVecs)     // observed short pass: a quarter of the workgroups, i.e. of the same-address atomics
             fq_kernel<IO, KIND, true, 1024><<<grid_for(nvec, 1024, 2), 1024, 0, st>>>(x, y, nvec, n, fmt, lut, scale, amax);
         else if (amax)
             fq_kernel<IO, KIND, true, kAluBlock><<<grid, kAluBlock, 0, st>>>(x, y, nvec, n, fmt, lut, scale, amax);
@@ -1819,12 +1759,8 @@ int qt_fake_quant_bf16_fp8(const uint16_t *x, uint16_t *y, uint8_t *y8, size_t n
     const uint4 *xv = (const uint4 *)x;
     uint4 *yv = (uint4 *)y;
     uint4 *y8v = (uint4 *)y8;
-    bool hw = true;
-#ifdef QT_TUNING_BUILD
-    hw = getenv("QT_FQ8_CLOSED_FORM") == nullptr;                        // tools/ only: A/B for DESIGN.md's measurement
-#endif
 #define QT_FQ8(OBS, BOTH, E5)                                                                                  \
-    fq8_kernel<OBS, BOTH, E5><<<grid, 256, 0, st>>>(xv, yv, y8v, nvec, *fmt, scale, amax, hw)
+    fq8_kernel<OBS, BOTH, E5><<<grid, 256, 0, st>>>(xv, yv, y8v, nvec, *fmt, scale, amax)
     if (e5m2) {
         if (amax) { if (y) QT_FQ8(true, true, true); else QT_FQ8(true, false, true); }
         else      { if (y) QT_FQ8(false, true, true); else QT_FQ8(false, false, true); }
@@ -1874,10 +1810,7 @@ static int chain_launch(const uint16_t *x_dev, const uint16_t *x2_dev, int pre_o
     ChainArgs a{};
     a.x = (const uint4 *)x_dev; a.rows = rows; a.cv = (int)(cols / 8); a.nstage = nstage;
     a.pre_op = pre_op; a.x2 = (const uint4 *)x2_dev; a.pre_out = (uint4 *)pre_out_dev;
-    a.table_in_lds = 1;
 #ifdef QT_TUNING_BUILD
-    if (const char *e = getenv("QT_CHAIN_LDS")) a.table_in_lds = atoi(e);                          // tools/ only
-    if (const char *e = getenv("QT_CHAIN_ABLATE")) a.ablate = atoi(e);                             // tools/ only: timing, garbage results
     a.dbg = ew_stamp_region();
 #endif
     for (int i = 0; i < nstage; ++i) {

@@ -181,8 +181,7 @@ static int format_basic(const char *dtype, qt_format *out) {
 }
 
 // Table formats whose map is odd-symmetric -- map[-v] = -map[v] for every finite non-zero result, zero results +0 and NaN
-// results canonical on both sides (posit, fpN_eXmY, NormalFloat ...) -- are marked p0 = 1: the device kernels then stage
-// only the non-negative half of the table (64 KiB of LDS instead of 128) and put the sign back on the looked-up value.
+// results canonical on both sides (posit, fpN_eXmY, NormalFloat ...) -- are marked p0 = 1.
 int qt_format_for(const char *dtype, qt_format *out) {
     const int rc = format_basic(dtype, out);
     if (rc != QT_OK || out->kind != QT_FMT_LUT) return rc;

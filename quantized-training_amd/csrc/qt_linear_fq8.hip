@@ -68,7 +68,6 @@ struct Args {
     int tiles_m, tiles_n, nseg;
     int gbase, gextra;        // column tile j covers gbase + (j < gextra) groups of 16 columns
     int nb;                   // ceil(4 * widest tile / 8): weight DMA pieces the widest tile needs per wave
-    int dbg;                  // tuning switches (QT_FQ8_DEBUG): 2 = no multiplications, 128 = no issue stagger
     Segment seg[kMaxSeg];
     // pair mode (qt_mlp_fq8_bf16): seg[0] = gate, seg[1] = up weights [N][K]; the virtual column groups alternate gate / up
     // (group 2 P: gate rows 16 P .., group 2 P + 1: the same rows of up), gbase / gextra count PAIRS, and the epilogue writes
@@ -180,33 +179,19 @@ __device__ __forceinline__ void silu_mul4(const float (&gt)[4], const float (&up
     w1 = pack_bf16x2(p[2], p[3]);
 }
 
-// ABL (timing experiments only, QT_FQ8_ABLATE; results are garbage): 1 no multiplications, 2 no weight items (load / convert /
-// ds_write), 3 no activation DMA, 4 no fragment reads and no multiplications.  Measured at 1024 x 11008 x 4096 (55.6 us whole):
-// 48.8 / 39.5 / 47.9 / 48.5 us -- the k loop is paced by the operand streams (76 KB per step and CU), not by the matrix core.
-// PF > 0 (round 6): every wave also touches, PF k tiles ahead, its share of the weight lines this column tile will need -- one 4-byte
-// load per 128-byte line, result never read.  The tiles_m workgroups that share a column tile run in lock step on one XCD, so today all
-// of them wait out the HBM miss of each weight line together (TCC: 19 % misses, but every weight request sees the miss latency);
-// brought into that XCD's L2 ahead of time the demand loads are L2 hits.  Measured ceiling of the idea: -12 % (every column tile
-// reading the first tile's weights, QT_FQ8_DEBUG=256, round 5).  Each workgroup prefetches 1 / tiles_m of the tile's lines.
-template <int FX, int FW, int NB, bool PAIR = false, int ABL = 0, int PF = 0>
+template <int FX, int FW, int NB, bool PAIR = false>
 struct LinearFq8R {
     static constexpr int kADepth = 3;
-    // ABL == 20 (not an ablation: the two-register-set variant): every weight piece has TWO register sets, so a weight request has two
-    // steps to land instead of one.  The requests are inline-asm loads with hand-counted waits: hipcc cannot count the (hidden)
+    // W2, the widest tiles (NB == 6): every weight piece has TWO register sets, so a weight request has two steps to land instead of
+    // one (2 - 6 % faster there).  The requests are inline-asm loads with hand-counted waits: hipcc cannot count the (hidden)
     // activation DMA entries that share the wave's in-order queue, and its own waits for ordinary loads came out up to eight entries
     // too strict -- which is what kept a second register set from paying off in round 2.  The k loop is unrolled by two so that each
     // set lives in fixed registers (nothing rotates: a register written by a load in flight must never be copied).
-    static constexpr bool W2 = (ABL == 20);
+    static constexpr bool W2 = (NB == 6);
     static constexpr int kWSets = W2 ? 2 : 1;
-    static constexpr int kWWait = 2 * NB + 3;               // queue entries allowed behind a weight request when its registers are read
-    // PF kernels count exactly.  A weight request of set S is read two steps after it was issued; behind it in the queue are the rest
-    // of its own step's requests, one whole step (4 activation pieces + NB requests) and the reading step's 4 pieces and first requests:
-    // 2 NB + 7, plus the two prefetch loads issued at the two step starts in between.  (2 NB + 3 above is that count for step 0, whose
-    // requests were issued back to back in the prologue; kept for every step it is four entries too strict -- harmless while every
-    // entry is an L2 hit that lands within a step, but a prefetch load is an HBM miss by design and must never be waited for.)
-    static constexpr int kWWaitFirst = 2 * NB + 3 + (PF > 0 ? 1 : 0);
-    static constexpr int kWWaitSteady = PF > 0 ? 2 * NB + 9 : kWWait;
-    static constexpr int kStepWait = 4 + 2 * NB + (PF > 0 ? 1 : 0);      // behind the activation pieces of the step that starts
+    // queue entries allowed behind a weight request when its registers are read: the count for step 0, whose requests were issued
+    // back to back in the prologue; for the later steps it is four entries too strict, harmless while every entry lands within a step
+    static constexpr int kWWait = 2 * NB + 3;
     static constexpr int kWBytes = NB * 4 * 1024;           // FP8 weight tile: up to 8 NB pieces of 4 rows x 128 bytes
     static constexpr int kLds = kADepth * kABytes + 2 * kWBytes;
     static constexpr int kItems = 4 + NB;
@@ -248,13 +233,7 @@ struct LinearFq8R {
 #pragma unroll
         for (int i = 0; i < NB; ++i) {
             const int p = w + 8 * i, pb = p < npieces ? p : (w & 3);          // surplus pieces repeat one (same bytes, same place)
-#ifdef QT_TUNING_BUILD
-            // timing probe (QT_FQ8_DEBUG=256, results are garbage): every column tile reads the FIRST tile's weights, so the weight
-            // stream hits in L2 -- the upper bound of anything that would bring the weights into L2 ahead of the demand loads
-            const int grp = ((a.dbg & 256) ? 0 : tg0) + (pb >> 2);
-#else
             const int grp = tg0 + (pb >> 2);
-#endif
             const int row = pb * 4 + (l >> 4), c = l & 15;
             if constexpr (PAIR) {
                 const uint16_t *wb = (grp & 1) ? a.seg[1].w : a.seg[0].w;
@@ -266,67 +245,22 @@ struct LinearFq8R {
             gw[i] = ub[i] + w_lane;
             wdst[i] = row * 128 + (((c >> 1) ^ ((row >> 1) & 7)) << 4) + (c & 1) * 8;
         }
-        // ---- L2 prefetch of the weight stream (PF > 0): this wave's lines of the tile's 32 nt lines per k tile (two per weight row)
-        const uint8_t *pf_base = nullptr;                     // wave-uniform: first row this wave touches, k tile 0
-        uint32_t pf_lane = 0;                                  // the lane's line inside the wave's span
-        if constexpr (PF > 0) {
-            const int tm_ = m0 / kTM;
-            if constexpr (PAIR) {
-                // waves 0-3: the gate rows of the tile's pairs, waves 4-7: the up rows; rows [P0 16, (P0 + nt / 2) 16) of each matrix
-                const int lines = 16 * nt;                                        // per matrix and k tile
-                const int lc = (lines + a.tiles_m - 1) / a.tiles_m, lw = (lc + 3) / 4;
-                int first = tm_ * lc + (w & 3) * lw;
-                first = first < lines - 1 ? first : lines - 1;
-                const int mine = min(lw, lines - first);
-                const int ln = first + min(l, mine - 1);
-                const uint16_t *wb = (w >> 2) ? a.seg[1].w : a.seg[0].w;
-                pf_base = (const uint8_t *)wb + (long)((tg0 / 2) * 16) * a.K * 2;
-                pf_lane = (uint32_t)(ln >> 1) * (uint32_t)a.K * 2u + (uint32_t)(ln & 1) * 128u;
-            } else {
-                const int lines = 32 * nt;
-                const int lc = (lines + a.tiles_m - 1) / a.tiles_m, lw = (lc + 7) / 8;
-                int first = tm_ * lc + w * lw;
-                first = first < lines - 1 ? first : lines - 1;
-                // the span stays inside the weight that holds its first row (a tile may straddle two weights of a q / k / v launch)
-                const int grp0 = tg0 + (first >> 5);
-                const SegRef sg = seg_lookup(a, grp0);
-                int seg_end_grp = tg0 + nt;                                       // first group past this weight inside the tile
-                if (a.nseg > 1 && a.seg[1].g0 > grp0 && a.seg[1].g0 < seg_end_grp) seg_end_grp = a.seg[1].g0;
-                if (a.nseg > 2 && a.seg[2].g0 > grp0 && a.seg[2].g0 < seg_end_grp) seg_end_grp = a.seg[2].g0;
-                if (a.nseg > 3 && a.seg[3].g0 > grp0 && a.seg[3].g0 < seg_end_grp) seg_end_grp = a.seg[3].g0;
-                const int last = (seg_end_grp - tg0) * 32 - 1;
-                const int mine = min(lw, last - first + 1);
-                const int ln = first + min(l, mine - 1) - (grp0 - tg0) * 32;       // line relative to group grp0's first row
-                pf_base = (const uint8_t *)sg.w + (long)((grp0 - sg.g0) * 16) * a.K * 2;
-                pf_lane = (uint32_t)(ln >> 1) * (uint32_t)a.K * 2u + (uint32_t)(ln & 1) * 128u;
-            }
-        }
-        uint32_t pf_sink = 0;
-        auto prefetch_w = [&](int kt) __attribute__((always_inline)) {
-            if constexpr (PF > 0)
-                asm volatile("global_load_dword %0, %1, %2" : "=v"(pf_sink) : "v"(pf_lane), "s"(pf_base + (long)kt * (2 * kBK)) : "memory");
-        };
         u32x4 wr[kWSets][NB];
         auto load_w_asm = [](u32x4 &dst, uint32_t lane_off, const uint8_t *base) __attribute__((always_inline)) {
             asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(dst) : "v"(lane_off), "s"(base) : "memory");
         };
-        auto wait_w_asm = [](u32x4 &reg, auto first) __attribute__((always_inline)) {
-            asm volatile("s_waitcnt vmcnt(%1)" : "+v"(reg) : "n"(decltype(first)::value ? kWWaitFirst : kWWaitSteady) : "memory");
+        auto wait_w_asm = [](u32x4 &reg) __attribute__((always_inline)) {
+            asm volatile("s_waitcnt vmcnt(%1)" : "+v"(reg) : "n"(kWWait) : "memory");
         };
-        // (sc: the register set, + 2 when the step is the k loop's first -- its wait count differs, see kWWaitFirst)
+        // (sc: the weight register set, 0 or 1)
         auto load_w = [&](auto ic, auto sc, int kt) __attribute__((always_inline)) {
-            constexpr int I = decltype(ic)::value, S = decltype(sc)::value & 1;
+            constexpr int I = decltype(ic)::value, S = decltype(sc)::value;
             if constexpr (W2) load_w_asm(wr[S][I], w_lane, ub[I] + (long)kt * (2 * kBK));
             else wr[S][I] = *(const u32x4 *)(gw[I] + (long)kt * (2 * kBK));
         };
-        // The activation DMA as inline asm: with the builtin, hipcc's wait-count model sees a pending "flat" access to LDS and turns
-        // every wait for a weight register into vmcnt(0), which also waits for the step's own DMA pieces.  Hidden from the model the
-        // waits become counted ones that are at most four entries too strict (never too lax: uncounted entries only make the real
-        // queue longer than the one hipcc waits on).
+        // The activations come by LDS-DMA (dma16, qt_device.h), hidden from hipcc's wait-count model: its waits for the weight
+        // registers stay counted ones instead of vmcnt(0), which would also wait for the step's own DMA pieces.
         // (asm statements sit in non-generic lambdas: inside a generic one clang rejects operands captured by reference)
-        auto dma16 = [](const uint8_t *src, uint32_t dst) __attribute__((always_inline)) {
-            asm volatile("s_mov_b32 m0, %1\n\ts_nop 1\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(dst) : "memory");
-        };
         auto ds_write64 = [](uint32_t addr, u32x2 v) __attribute__((always_inline)) {
             asm volatile("ds_write_b64 %0, %1" ::"v"(addr), "v"(v) : "memory");
         };
@@ -334,8 +268,8 @@ struct LinearFq8R {
             asm volatile("ds_write_b32 %0, %1" ::"v"(addr), "v"(v) : "memory");
         };
         auto store_w = [&](auto ic, auto sc, uint32_t wbase) __attribute__((always_inline)) {
-            constexpr int I = decltype(ic)::value, S = decltype(sc)::value & 1;
-            if constexpr (W2) wait_w_asm(wr[S][I], std::integral_constant<bool, (decltype(sc)::value >= 2)>{});
+            constexpr int I = decltype(ic)::value, S = decltype(sc)::value;
+            if constexpr (W2) wait_w_asm(wr[S][I]);
             const u32x2 codes = {cvt_bf16x4<FW == 1>(wr[S][I].x, wr[S][I].y), cvt_bf16x4<FW == 1>(wr[S][I].z, wr[S][I].w)};
             const uint32_t addr = wbase + wdst[I];
             ds_write64(addr, codes);
@@ -345,12 +279,8 @@ struct LinearFq8R {
         auto item = [&](auto ic, auto sc, int ka, uint32_t as, uint32_t ws, int kb) __attribute__((always_inline)) {
             constexpr int I = decltype(ic)::value;
             if constexpr (I < 4) {
-                if constexpr (ABL != 3 && ABL != 5 && ABL != 6 && ABL != 8 && ABL != 10) dma16(ga[I] + (long)ka * kBK, as + (w * 4 + I) * 1024);
-            } else if constexpr (ABL == 7 || ABL == 8 || ABL == 10 || ABL == 11) {
-                // transport probe: the weight piece travels by LDS-DMA (raw bf16 into the FP8 ring's space, results are garbage) instead of
-                // through registers + conversion + ds_write
-                dma16(gw[I - 4] + (long)kb * (2 * kBK), lds_addr(lds) + kADepth * kABytes + (w * NB + (I - 4)) * 1024);
-            } else if constexpr (ABL != 2 && ABL != 5 && ABL != 6 && ABL != 9) {
+                dma16(ga[I] + (long)ka * kBK, as + (w * 4 + I) * 1024);
+            } else {
                 store_w(std::integral_constant<int, I - 4>{}, sc, ws);
                 load_w(std::integral_constant<int, I - 4>{}, sc, kb);
             }
@@ -385,18 +315,14 @@ struct LinearFq8R {
         auto compute = [&](auto sc, uint32_t sa_, uint32_t sb_, int ka, uint32_t as, uint32_t ws, int kb) __attribute__((always_inline)) {
             if constexpr (NTW > 0) {
                 u32x4 fa_lo[4], fa_hi[4], fb_lo[3], fb_hi[3];
-                if constexpr (ABL != 4 && ABL != 6 && (ABL < 9 || ABL >= 20)) {
-                    fa_lo[0] = ds_read128<0 * 2048>(sa_ + a_lo); fa_hi[0] = ds_read128<0 * 2048>(sa_ + a_hi);
-                    fa_lo[1] = ds_read128<1 * 2048>(sa_ + a_lo); fa_hi[1] = ds_read128<1 * 2048>(sa_ + a_hi);
-                    fa_lo[2] = ds_read128<2 * 2048>(sa_ + a_lo); fa_hi[2] = ds_read128<2 * 2048>(sa_ + a_hi);
-                    fa_lo[3] = ds_read128<3 * 2048>(sa_ + a_lo); fa_hi[3] = ds_read128<3 * 2048>(sa_ + a_hi);
-                }
+                fa_lo[0] = ds_read128<0 * 2048>(sa_ + a_lo); fa_hi[0] = ds_read128<0 * 2048>(sa_ + a_hi);
+                fa_lo[1] = ds_read128<1 * 2048>(sa_ + a_lo); fa_hi[1] = ds_read128<1 * 2048>(sa_ + a_hi);
+                fa_lo[2] = ds_read128<2 * 2048>(sa_ + a_lo); fa_hi[2] = ds_read128<2 * 2048>(sa_ + a_hi);
+                fa_lo[3] = ds_read128<3 * 2048>(sa_ + a_lo); fa_hi[3] = ds_read128<3 * 2048>(sa_ + a_hi);
                 auto read_b = [&](auto jc) __attribute__((always_inline)) {
                     constexpr int J = decltype(jc)::value;
-                    if constexpr (ABL != 4 && ABL != 6 && (ABL < 9 || ABL >= 20)) {
-                        fb_lo[J % 3] = ds_read128<J * 2048>(sb_ + b_lo);
-                        fb_hi[J % 3] = ds_read128<J * 2048>(sb_ + b_hi);
-                    }
+                    fb_lo[J % 3] = ds_read128<J * 2048>(sb_ + b_lo);
+                    fb_hi[J % 3] = ds_read128<J * 2048>(sb_ + b_hi);
                 };
                 v8i fa[4];
                 auto step = [&](auto jc) __attribute__((always_inline)) {
@@ -423,11 +349,9 @@ struct LinearFq8R {
                     }
                     const v8i fb = v8i{(int)fb_lo[P].x, (int)fb_lo[P].y, (int)fb_lo[P].z, (int)fb_lo[P].w,
                                        (int)fb_hi[P].x, (int)fb_hi[P].y, (int)fb_hi[P].z, (int)fb_hi[P].w};
-                    if constexpr (ABL != 1 && ABL != 4 && ABL != 6 && (ABL < 9 || ABL >= 20)) {
 #pragma unroll
-                        for (int i = 0; i < 4; ++i)
-                            acc[i][J] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fb, fa[i], acc[i][J], FW, FX, 0, kUnitE8M0, 0, kUnitE8M0);
-                    }
+                    for (int i = 0; i < 4; ++i)
+                        acc[i][J] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fb, fa[i], acc[i][J], FW, FX, 0, kUnitE8M0, 0, kUnitE8M0);
                     items(std::integral_constant<int, item_lo(J, NTW)>{}, std::integral_constant<int, item_hi(J, NTW)>{}, sc, ka, as, ws, kb);
                     __builtin_amdgcn_sched_barrier(0);
                 };
@@ -464,9 +388,8 @@ struct LinearFq8R {
         auto one_step = [&](auto sc, int kt, int ahead) __attribute__((always_inline)) {
             // this wave's FP8 codes of step kt are written (lgkmcnt) and its activation pieces have landed: they are older in the
             // vector-memory queue than the weight loads of step kt, which the conversions of the previous step waited for
-            asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(W2 ? kStepWait : 4 + 2 * NB) : "memory");
+            asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(4 + 2 * NB) : "memory");
             __builtin_amdgcn_s_barrier();                    // ... every wave's; and every wave is done with step kt - 1
-            if constexpr (PF > 0) prefetch_w(min(kt + PF, klast));
             const int ka = min(kt + 2, klast), kb = min(kt + ahead, klast);
             const uint32_t sa_ = l0 + a_slot * kABytes, sb_ = w0 + (kt & 1) * kWBytes, ws = w0 + ((kt + 1) & 1) * kWBytes;
             compute(sc, sa_, sb_, ka, l0 + a_tgt * kABytes, ws, kb);
@@ -480,24 +403,22 @@ struct LinearFq8R {
             // k tile 0: requested, awaited, converted into FP8 tile 0; then set 1 <- k tile 1, set 0 <- k tile 2.  Step kt converts k tile
             // kt + 1 out of set (kt + 1) & 1 into FP8 tile (kt + 1) & 1 and refills that set with k tile kt + 3.
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if constexpr (ABL != 2) {
-                auto conv0 = [&](auto ic) __attribute__((always_inline)) {
-                    constexpr int I = decltype(ic)::value;
-                    asm volatile("" : "+v"(wr[0][I]));
-                    const u32x2 codes = {cvt_bf16x4<FW == 1>(wr[0][I].x, wr[0][I].y), cvt_bf16x4<FW == 1>(wr[0][I].z, wr[0][I].w)};
-                    ds_write64(w0 + wdst[I], codes);
-                };
-                conv0(std::integral_constant<int, 0>{});
-                if constexpr (NB > 1) conv0(std::integral_constant<int, 1>{});
-                if constexpr (NB > 2) conv0(std::integral_constant<int, 2>{});
-                if constexpr (NB > 3) conv0(std::integral_constant<int, 3>{});
-                if constexpr (NB > 4) conv0(std::integral_constant<int, 4>{});
-                if constexpr (NB > 5) conv0(std::integral_constant<int, 5>{});
-            }
+            auto conv0 = [&](auto ic) __attribute__((always_inline)) {
+                constexpr int I = decltype(ic)::value;
+                asm volatile("" : "+v"(wr[0][I]));
+                const u32x2 codes = {cvt_bf16x4<FW == 1>(wr[0][I].x, wr[0][I].y), cvt_bf16x4<FW == 1>(wr[0][I].z, wr[0][I].w)};
+                ds_write64(w0 + wdst[I], codes);
+            };
+            conv0(std::integral_constant<int, 0>{});
+            if constexpr (NB > 1) conv0(std::integral_constant<int, 1>{});
+            if constexpr (NB > 2) conv0(std::integral_constant<int, 2>{});
+            if constexpr (NB > 3) conv0(std::integral_constant<int, 3>{});
+            if constexpr (NB > 4) conv0(std::integral_constant<int, 4>{});
+            if constexpr (NB > 5) conv0(std::integral_constant<int, 5>{});
             load_all(kS1, min(1, klast));
             load_all(kS0, min(2, klast));
             int kt = 0;
-            one_step(std::integral_constant<int, 2 + (kWSets - 1)>{}, kt, 3);          // (set 1, first step)
+            one_step(kS1, kt, 3);
             for (kt = 1; kt + 1 < nk; kt += 2) {
                 one_step(kS0, kt, 3);
                 one_step(kS1, kt + 1, 3);
@@ -513,7 +434,6 @@ struct LinearFq8R {
 #pragma unroll
             for (int i = 0; i < NB; ++i) asm volatile("" : "+v"(wr[0][i]), "+v"(wr[kWSets - 1][i]));
         }
-        if constexpr (PF > 0) asm volatile("" : "+v"(pf_sink));          // the prefetch loads' landing register stays reserved until here
         // Overflowed or non-finite weights (and NaN activations) leave NaN / Inf in the accumulators: such a tile is redone
         // by slow_tile.  The workgroup-wide vote goes through LDS (the rings are dead here).
         bool bad = false;
@@ -525,11 +445,6 @@ struct LinearFq8R {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) bad |= (qt_f2u(acc[i][j][e]) & 0x7F800000u) == 0x7F800000u;
         }
-        // (ABL 20 is the shipped two-register-set loop, not an ablation.  Rounds 3 and 4 cleared `bad` for it as well, so the widest
-        // tiles -- gate / up, q / k / v -- never took the redo path: an overflowing weight came out as NaN instead of saturating.  No
-        // test held such a weight in a twelve-group tile; tests/test_gpu_parity.py::test_linear_fq8_wide_tiles_redo_overflowing_weights
-        // does now.)
-        if constexpr (ABL != 0 && ABL != 20) bad = false;
         __syncthreads();
         volatile int *flag = (volatile int *)(lds + 8 * 64 * (6 * 32 + 8));     // past the eight waves' epilogue tiles
         if (w == 0 && l == 0) *flag = 0;
@@ -753,29 +668,18 @@ __device__ __forceinline__ void slow_tile_pair(const Args &a, int m0, int tg0, i
 // the weight registers, the LDS latency in front of the first multiplication -- are then ~0.7 of a 1.0 us step (1024 x 4096 x
 // 11008: 85 us for 86 steps).  Here a step is 256 deep: half as many of those, twice the work to cover them.  Activations two
 // steps of 64 KiB (the DMA of step s + 1 lands during step s), FP8 weight tiles 2 x 2 x 8 KiB: 160 KiB of LDS.
-// ABL (timing experiments, QT_FQ8_R2_ABLATE): 2 no weight items, 3 no activation DMA, 5 neither (fragment reads + multiplications only)
-template <int FX, int FW, int ABL = 0>
+template <int FX, int FW>
 struct LinearFq8R2 {
     static constexpr int NB = 2;                            // weight pieces per wave and k tile
     static constexpr int kAStage = 2 * kABytes, kWTile = NB * 4 * 1024, kWStage = 2 * kWTile;
     static constexpr int kLds = 2 * kAStage + 2 * kWStage;
     static constexpr int kItems = 8 + 2 * NB;               // per step and wave: 8 activation DMA pieces, 4 weight items
-    // ABL == 30 (not an ablation -- variant RX, "register-extended rings"): the kernel uses half the register file, and its k loop is
-    // paced by how many operand bytes a CU has in flight (one step of each operand: 96 KB against a latency of 1.1 - 2.2 us).  RX
-    // requests BOTH operands into registers two steps ahead (two register sets each: 64 + 32 VGPRs; inline-asm loads, hand-counted
-    // waits, the loop unrolled by two so that nothing rotates) and moves them into the LDS stage of the next step with ds_write
-    // (activations as they are, weights converted) -- twice the bytes in flight with the same 160 KiB of LDS.  EXPERIMENT, opt-in
-    // (QT_FQ8_R2_ABLATE=30; exact, all parity checks pass): it is NOT faster -- 1024 x 4096 x 11008 74.0 us against 71.9, 4096^3-shaped o
-    // projection 30.3 against 28.8 -- so the narrow-tile loop is not limited by the bytes it has in flight.
-    static constexpr bool RX = (ABL == 30);
-    static constexpr int kRxWait = 2 * kItems - 1;          // queue entries behind a request issued two steps earlier at the same place
     // items of group gi (k half h = gi / NTW, column group J = gi % NTW) out of G = 2 NTW: DMA pieces on the first half of the
     // groups, weight items (convert + ds_write + reload) on the second half
     static constexpr int item_lo(int gi, int G) { return gi < G / 2 ? gi * 8 / (G / 2) : 8 + (gi - G / 2) * (2 * NB) / (G - G / 2); }
     static constexpr int item_hi(int gi, int G) { return gi < G / 2 ? (gi + 1) * 8 / (G / 2) : 8 + (gi - G / 2 + 1) * (2 * NB) / (G - G / 2); }
     static constexpr int writes_in(int gi, int G) {
         const int lo = item_lo(gi, G), hi = item_hi(gi, G);
-        if (RX) return hi - lo;                              // every item ends in one ds_write
         return (hi > 8 ? hi : 8) - (lo > 8 ? lo : 8);
     }
 
@@ -790,12 +694,8 @@ struct LinearFq8R2 {
             const int row = (w * 4 + i) * 8 + (l >> 3), slot = l & 7;
             ga[i] = a.x8 + (long)min(m0 + row, a.M - 1) * a.K + ((slot ^ ((row >> 1) & 7)) << 4);
         }
-        uint32_t aoff[4];                                      // RX: the lane's part of ga[i] (the base a.x8 + k offset is wave-uniform)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) aoff[i] = (uint32_t)(ga[i] - a.x8);
         const int npieces = nt * 4;
         const uint8_t *gw[NB];
-        const uint8_t *ub[NB];                                 // wave-uniform part of gw
         const uint32_t w_lane = (uint32_t)(l >> 4) * (uint32_t)a.K * 2u + (uint32_t)(l & 15) * 16u;
         uint32_t wdst[NB];
 #pragma unroll
@@ -804,48 +704,20 @@ struct LinearFq8R2 {
             const int grp = tg0 + (pb >> 2);
             const int row = pb * 4 + (l >> 4), c = l & 15;
             const SegRef sg = seg_lookup(a, grp);
-            ub[i] = (const uint8_t *)sg.w + ((long)((grp - sg.g0) * 16 + (pb & 3) * 4) * a.K) * 2;
-            gw[i] = ub[i] + w_lane;
+            gw[i] = (const uint8_t *)sg.w + ((long)((grp - sg.g0) * 16 + (pb & 3) * 4) * a.K) * 2 + w_lane;
             wdst[i] = row * 128 + (((c >> 1) ^ ((row >> 1) & 7)) << 4) + (c & 1) * 8;
         }
         u32x4 wr[2 * NB];                                      // [k half][piece]
-        u32x4 ar[RX ? 2 : 1][RX ? 8 : 1], wx[RX ? 2 : 1][RX ? 2 * NB : 1];      // RX: [set][item]
-        auto load_asm = [](u32x4 &dst, uint32_t lane_off, const uint8_t *base) __attribute__((always_inline)) {
-            asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(dst) : "v"(lane_off), "s"(base) : "memory");
-        };
-        auto wait_asm = [](u32x4 &reg) __attribute__((always_inline)) {
-            asm volatile("s_waitcnt vmcnt(%1)" : "+v"(reg) : "n"(kRxWait) : "memory");
-        };
-        auto ds_write128 = [](uint32_t addr, u32x4 v) __attribute__((always_inline)) {
-            asm volatile("ds_write_b128 %0, %1" ::"v"(addr), "v"(v) : "memory");
-        };
-        const uint32_t a_lane = (uint32_t)l * 16u;
-        auto dma16 = [](const uint8_t *src, uint32_t dst) __attribute__((always_inline)) {
-            asm volatile("s_mov_b32 m0, %1\n\ts_nop 1\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(dst) : "memory");
-        };
         auto ds_write64 = [](uint32_t addr, u32x2 v) __attribute__((always_inline)) {
             asm volatile("ds_write_b64 %0, %1" ::"v"(addr), "v"(v) : "memory");
         };
         // item 0-7: activation piece (k half I / 4, piece I % 4) of step sa into `as`; item 8 + i: weight registers i (k half i / NB,
         // piece i % NB, holding step sb - 1) converted into the FP8 tiles at `ws`, then reloaded with step sb
-        auto item = [&](auto ic, auto sc, int sa, uint32_t as, uint32_t ws, int sb) __attribute__((always_inline)) {
-            constexpr int I = decltype(ic)::value, S = decltype(sc)::value;
-            if constexpr (RX) {
-                // sb: the step these registers are refilled with (two ahead of the one they hold); the set in hand holds step sa's operands
-                if constexpr (I < 8) {
-                    wait_asm(ar[S][I]);
-                    ds_write128(as + (I >> 2) * kABytes + (w * 4 + (I & 3)) * 1024 + a_lane, ar[S][I]);
-                    load_asm(ar[S][I], aoff[I & 3], a.x8 + (long)(2 * sb + (I >> 2)) * kBK);
-                } else {
-                    constexpr int Wi = I - 8, H = Wi / NB, P = Wi % NB;
-                    wait_asm(wx[S][Wi]);
-                    const u32x2 codes = {cvt_bf16x4<FW == 1>(wx[S][Wi].x, wx[S][Wi].y), cvt_bf16x4<FW == 1>(wx[S][Wi].z, wx[S][Wi].w)};
-                    ds_write64(ws + H * kWTile + wdst[P], codes);
-                    load_asm(wx[S][Wi], w_lane, ub[P] + (long)(2 * sb + H) * (2 * kBK));
-                }
-            } else if constexpr (I < 8) {
-                if constexpr (ABL != 3 && ABL != 5) dma16(ga[I & 3] + (long)(2 * sa + (I >> 2)) * kBK, as + (I >> 2) * kABytes + (w * 4 + (I & 3)) * 1024);
-            } else if constexpr (ABL != 2 && ABL != 5) {
+        auto item = [&](auto ic, int sa, uint32_t as, uint32_t ws, int sb) __attribute__((always_inline)) {
+            constexpr int I = decltype(ic)::value;
+            if constexpr (I < 8) {
+                dma16(ga[I & 3] + (long)(2 * sa + (I >> 2)) * kBK, as + (I >> 2) * kABytes + (w * 4 + (I & 3)) * 1024);
+            } else {
                 constexpr int Wi = I - 8, H = Wi / NB, P = Wi % NB;
                 const u32x2 codes = {cvt_bf16x4<FW == 1>(wr[Wi].x, wr[Wi].y), cvt_bf16x4<FW == 1>(wr[Wi].z, wr[Wi].w)};
                 const uint32_t addr = ws + H * kWTile + wdst[P];
@@ -853,21 +725,21 @@ struct LinearFq8R2 {
                 wr[Wi] = *(const u32x4 *)(gw[P] + (long)(2 * sb + H) * (2 * kBK));
             }
         };
-        auto items = [&](auto lo, auto hi, auto sc, int sa, uint32_t as, uint32_t ws, int sb) __attribute__((always_inline)) {
+        auto items = [&](auto lo, auto hi, int sa, uint32_t as, uint32_t ws, int sb) __attribute__((always_inline)) {
             constexpr int LO = decltype(lo)::value, HI = decltype(hi)::value;
             static_assert(HI - LO <= 12, "at most twelve items");
-            if constexpr (LO + 0 < HI) item(std::integral_constant<int, LO + 0>{}, sc, sa, as, ws, sb);
-            if constexpr (LO + 1 < HI) item(std::integral_constant<int, LO + 1>{}, sc, sa, as, ws, sb);
-            if constexpr (LO + 2 < HI) item(std::integral_constant<int, LO + 2>{}, sc, sa, as, ws, sb);
-            if constexpr (LO + 3 < HI) item(std::integral_constant<int, LO + 3>{}, sc, sa, as, ws, sb);
-            if constexpr (LO + 4 < HI) item(std::integral_constant<int, LO + 4>{}, sc, sa, as, ws, sb);
-            if constexpr (LO + 5 < HI) item(std::integral_constant<int, LO + 5>{}, sc, sa, as, ws, sb);
-            if constexpr (LO + 6 < HI) item(std::integral_constant<int, LO + 6>{}, sc, sa, as, ws, sb);
-            if constexpr (LO + 7 < HI) item(std::integral_constant<int, LO + 7>{}, sc, sa, as, ws, sb);
-            if constexpr (LO + 8 < HI) item(std::integral_constant<int, LO + 8>{}, sc, sa, as, ws, sb);
-            if constexpr (LO + 9 < HI) item(std::integral_constant<int, LO + 9>{}, sc, sa, as, ws, sb);
-            if constexpr (LO + 10 < HI) item(std::integral_constant<int, LO + 10>{}, sc, sa, as, ws, sb);
-            if constexpr (LO + 11 < HI) item(std::integral_constant<int, LO + 11>{}, sc, sa, as, ws, sb);
+            if constexpr (LO + 0 < HI) item(std::integral_constant<int, LO + 0>{}, sa, as, ws, sb);
+            if constexpr (LO + 1 < HI) item(std::integral_constant<int, LO + 1>{}, sa, as, ws, sb);
+            if constexpr (LO + 2 < HI) item(std::integral_constant<int, LO + 2>{}, sa, as, ws, sb);
+            if constexpr (LO + 3 < HI) item(std::integral_constant<int, LO + 3>{}, sa, as, ws, sb);
+            if constexpr (LO + 4 < HI) item(std::integral_constant<int, LO + 4>{}, sa, as, ws, sb);
+            if constexpr (LO + 5 < HI) item(std::integral_constant<int, LO + 5>{}, sa, as, ws, sb);
+            if constexpr (LO + 6 < HI) item(std::integral_constant<int, LO + 6>{}, sa, as, ws, sb);
+            if constexpr (LO + 7 < HI) item(std::integral_constant<int, LO + 7>{}, sa, as, ws, sb);
+            if constexpr (LO + 8 < HI) item(std::integral_constant<int, LO + 8>{}, sa, as, ws, sb);
+            if constexpr (LO + 9 < HI) item(std::integral_constant<int, LO + 9>{}, sa, as, ws, sb);
+            if constexpr (LO + 10 < HI) item(std::integral_constant<int, LO + 10>{}, sa, as, ws, sb);
+            if constexpr (LO + 11 < HI) item(std::integral_constant<int, LO + 11>{}, sa, as, ws, sb);
         };
         constexpr auto kI0 = std::integral_constant<int, 0>{};
         constexpr auto kIA = std::integral_constant<int, 8>{};
@@ -882,7 +754,7 @@ struct LinearFq8R2 {
         const uint32_t b_lo = a_chunk_off(jbase * 16 + r, g), b_hi = a_chunk_off(jbase * 16 + r, 4 + g);
 
         // one k half (activations at sa_, FP8 weights at sb_) of a step, carrying the step's items of its groups
-        auto half = [&](auto hc, auto sc, uint32_t sa_, uint32_t sb_, int sa, uint32_t as, uint32_t ws, int sb) __attribute__((always_inline)) {
+        auto half = [&](auto hc, uint32_t sa_, uint32_t sb_, int sa, uint32_t as, uint32_t ws, int sb) __attribute__((always_inline)) {
             constexpr int H = decltype(hc)::value, G = 2 * NTW;
             u32x4 fa_lo[4], fa_hi[4], fb_lo[2], fb_hi[2];
             fa_lo[0] = ds_read128<0 * 2048>(sa_ + a_lo); fa_hi[0] = ds_read128<0 * 2048>(sa_ + a_hi);
@@ -914,7 +786,7 @@ struct LinearFq8R2 {
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
                     acc[i][J] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fb, fa[i], acc[i][J], FW, FX, 0, kUnitE8M0, 0, kUnitE8M0);
-                items(std::integral_constant<int, item_lo(gi, G)>{}, std::integral_constant<int, item_hi(gi, G)>{}, sc, sa, as, ws, sb);
+                items(std::integral_constant<int, item_lo(gi, G)>{}, std::integral_constant<int, item_hi(gi, G)>{}, sa, as, ws, sb);
                 __builtin_amdgcn_sched_barrier(0);
             };
             step(std::integral_constant<int, 0>{});
@@ -922,14 +794,11 @@ struct LinearFq8R2 {
         };
 
         const uint32_t l0 = lds_addr(lds), w0 = l0 + 2 * kAStage;
-        constexpr auto kS0 = std::integral_constant<int, 0>{};
-        constexpr auto kS1 = std::integral_constant<int, RX ? 1 : 0>{};
-        if constexpr (!RX) {
         // prologue: activations of step 0 on their way; weights of step 0 converted into FP8 stage 0, those of step 1 in registers
-        items(kI0, kIA, kS0, 0, l0, w0, 0);
+        items(kI0, kIA, 0, l0, w0, 0);
 #pragma unroll
         for (int i = 0; i < 2 * NB; ++i) wr[i] = *(const u32x4 *)(gw[i % NB] + (long)(i / NB) * (2 * kBK));
-        items(kIA, kIN, kS0, 0, l0, w0, min(1, slast));
+        items(kIA, kIN, 0, l0, w0, min(1, slast));
         for (int s = 0; s < ns; ++s) {
             // the weight loads of step s + 1 are the newest entries of this wave's queue; its DMA pieces of step s are older
             asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(2 * NB) : "memory");
@@ -938,65 +807,13 @@ struct LinearFq8R2 {
             const uint32_t sa_ = l0 + (s & 1) * kAStage, sb_ = w0 + (s & 1) * kWStage;
             const uint32_t as = l0 + ((s + 1) & 1) * kAStage, ws = w0 + ((s + 1) & 1) * kWStage;
             if constexpr (NTW > 0) {
-                half(std::integral_constant<int, 0>{}, kS0, sa_, sb_, sa, as, ws, sb);
-                half(std::integral_constant<int, 1>{}, kS0, sa_ + kABytes, sb_ + kWTile, sa, as, ws, sb);
+                half(std::integral_constant<int, 0>{}, sa_, sb_, sa, as, ws, sb);
+                half(std::integral_constant<int, 1>{}, sa_ + kABytes, sb_ + kWTile, sa, as, ws, sb);
             } else {
-                items(kI0, kIN, kS0, sa, as, ws, sb);
+                items(kI0, kIN, sa, as, ws, sb);
             }
-        }
-        } else {
-            // RX prologue: step 0's operands requested into set 0, awaited, moved into stage 0; then set 1 <- step 1, set 0 <- step 2, in
-            // the order the loop issues them (activation items, then weight items), so that the loop's constant wait count holds from
-            // its first step.  Step s moves step s + 1 out of set (s + 1) & 1 into stage (s + 1) & 1 and refills that set with step s + 3.
-            auto request = [&](auto sc, int step) __attribute__((always_inline)) {
-                constexpr int S = decltype(sc)::value;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) load_asm(ar[S][i], aoff[i & 3], a.x8 + (long)(2 * step + (i >> 2)) * kBK);
-#pragma unroll
-                for (int i = 0; i < 2 * NB; ++i) load_asm(wx[S][i], w_lane, ub[i % NB] + (long)(2 * step + i / NB) * (2 * kBK));
-            };
-            request(kS0, 0);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                asm volatile("" : "+v"(ar[0][i]));
-                ds_write128(l0 + (i >> 2) * kABytes + (w * 4 + (i & 3)) * 1024 + a_lane, ar[0][i]);
-            }
-#pragma unroll
-            for (int i = 0; i < 2 * NB; ++i) {
-                asm volatile("" : "+v"(wx[0][i]));
-                const u32x2 codes = {cvt_bf16x4<FW == 1>(wx[0][i].x, wx[0][i].y), cvt_bf16x4<FW == 1>(wx[0][i].z, wx[0][i].w)};
-                ds_write64(w0 + (i / NB) * kWTile + wdst[i % NB], codes);
-            }
-            request(kS1, min(1, slast));
-            request(kS0, min(2, slast));
-            auto rx_step = [&](auto sc, int s) __attribute__((always_inline)) {
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // this wave's ds_writes into the stage about to be read
-                __builtin_amdgcn_s_barrier();                               // ... every wave's; and every wave is done with step s - 1
-                const int sa = min(s + 1, slast), sb = min(s + 3, slast);
-                const uint32_t sa_ = l0 + (s & 1) * kAStage, sb_ = w0 + (s & 1) * kWStage;
-                const uint32_t as = l0 + ((s + 1) & 1) * kAStage, ws = w0 + ((s + 1) & 1) * kWStage;
-                if constexpr (NTW > 0) {
-                    half(std::integral_constant<int, 0>{}, sc, sa_, sb_, sa, as, ws, sb);
-                    half(std::integral_constant<int, 1>{}, sc, sa_ + kABytes, sb_ + kWTile, sa, as, ws, sb);
-                } else {
-                    items(kI0, kIN, sc, sa, as, ws, sb);
-                }
-            };
-            int s = 0;
-            for (; s + 1 < ns; s += 2) {
-                rx_step(kS1, s);
-                rx_step(kS0, s + 1);
-            }
-            if (s < ns) rx_step(kS1, s);
         }
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        if constexpr (RX) {                                   // requests past the last step were still landing in these registers
-#pragma unroll
-            for (int i = 0; i < 8; ++i) asm volatile("" : "+v"(ar[0][i]), "+v"(ar[1][i]));
-#pragma unroll
-            for (int i = 0; i < 2 * NB; ++i) asm volatile("" : "+v"(wx[0][i]), "+v"(wx[1][i]));
-        }
         bool bad = false;
         if constexpr (NTW > 0) {
 #pragma unroll
@@ -1012,7 +829,7 @@ struct LinearFq8R2 {
         __syncthreads();
         if (bad) *flag = 1;
         __syncthreads();
-        if ((ABL == 0 || RX) && *flag) return true;
+        if (*flag) return true;
         if constexpr (NTW > 0) {
             constexpr int kRowB = NTW * 32 + 8;
             const uint32_t tbase = l0 + w * (64 * (6 * 32 + 8));
@@ -1064,7 +881,7 @@ struct LinearFq8R2 {
 #define QT_FQ8_STAMP_END
 #endif
 
-template <int FX, int FW, int ABL = 0>
+template <int FX, int FW>
 __global__ __launch_bounds__(512, 1) void linear_fq8r2_kernel(Args a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_r2[];
     const int t = threadIdx.x, l = t & 63, w = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -1081,7 +898,7 @@ __global__ __launch_bounds__(512, 1) void linear_fq8r2_kernel(Args a) {
     const int nt0 = (nt + 1) >> 1;
     const int wn = w >> 2;
     const int ntw = wn == 0 ? nt0 : nt - nt0, jbase = wn == 0 ? 0 : nt0;
-    using L = LinearFq8R2<FX, FW, ABL>;
+    using L = LinearFq8R2<FX, FW>;
     QT_FQ8_STAMP_BEGIN
     bool redo;
     switch (ntw) {                                          // wave-uniform
@@ -1093,7 +910,7 @@ __global__ __launch_bounds__(512, 1) void linear_fq8r2_kernel(Args a) {
     QT_FQ8_STAMP_END
 }
 
-template <int FX, int FW, int NB, bool PAIR, int ABL = 0>
+template <int FX, int FW, int NB, bool PAIR>
 __global__ __launch_bounds__(512, 1) void linear_fq8r_kernel(Args a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_r[];
     const int t = threadIdx.x, l = t & 63, w = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -1114,7 +931,7 @@ __global__ __launch_bounds__(512, 1) void linear_fq8r_kernel(Args a) {
     const int nt0 = unit * ((nu + 1) >> 1);
     const int wn = w >> 2;
     const int ntw = wn == 0 ? nt0 : nt - nt0, jbase = wn == 0 ? 0 : nt0;
-    using L = LinearFq8R<FX, FW, NB, PAIR, ABL>;
+    using L = LinearFq8R<FX, FW, NB, PAIR>;
     QT_FQ8_STAMP_BEGIN
     bool redo;
     switch (ntw) {                                          // wave-uniform
@@ -1143,87 +960,46 @@ int cu_count() {
     return n;
 }
 
-template <int FX, int FW, int NB, bool PAIR = false, int ABL = 0>
+template <int FX, int FW, int NB, bool PAIR = false>
 int launch_r_nb(const Args &a, hipStream_t st) {
     constexpr int kLds = LinearFq8R<FX, FW, NB, PAIR>::kLds;
     static QtOncePerDevice configured;      
     if (configured.needed()) {
-        const hipError_t e = hipFuncSetAttribute((const void *)linear_fq8r_kernel<FX, FW, NB, PAIR, ABL>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
+        const hipError_t e = hipFuncSetAttribute((const void *)linear_fq8r_kernel<FX, FW, NB, PAIR>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
         if (e != hipSuccess) return (int)e;
         configured.done();
     }
-    linear_fq8r_kernel<FX, FW, NB, PAIR, ABL><<<a.tiles_m * a.tiles_n, 512, kLds, st>>>(a);
+    linear_fq8r_kernel<FX, FW, NB, PAIR><<<a.tiles_m * a.tiles_n, 512, kLds, st>>>(a);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? QT_OK : (int)e;
 }
 
-template <int FX, int FW, int ABL = 0>
+template <int FX, int FW>
 int launch_r2(const Args &a, hipStream_t st) {
     constexpr int kLds = LinearFq8R2<FX, FW>::kLds;
     static QtOncePerDevice configured;      
     if (configured.needed()) {
-        const hipError_t e = hipFuncSetAttribute((const void *)linear_fq8r2_kernel<FX, FW, ABL>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
+        const hipError_t e = hipFuncSetAttribute((const void *)linear_fq8r2_kernel<FX, FW>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
         if (e != hipSuccess) return (int)e;
         configured.done();
     }
-    linear_fq8r2_kernel<FX, FW, ABL><<<a.tiles_m * a.tiles_n, 512, kLds, st>>>(a);
+    linear_fq8r2_kernel<FX, FW><<<a.tiles_m * a.tiles_n, 512, kLds, st>>>(a);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? QT_OK : (int)e;
 }
 
 template <int FX, int FW>
 int launch(const Args &a, hipStream_t st) {
-    // Two weight register sets (LinearFq8R::W2 = "ABL 20": a weight request has two steps to land) on the widest tiles, where it
-    // measured 2 - 6 % faster.  Narrow tiles (nb <= 2, K a multiple of two k tiles) run variant R2, two k tiles per step.
-    bool w2 = true, r2 = true;
-#ifdef QT_TUNING_BUILD
-    // tools/ only: timing ablations (results are garbage), the register-extended variant RX of R2 (exact, not faster) and A / B switches
-    w2 = !(getenv("QT_FQ8_W2") && atoi(getenv("QT_FQ8_W2")) == 0);
-    r2 = !(getenv("QT_FQ8_R2") && atoi(getenv("QT_FQ8_R2")) == 0);
-#endif
+    // The widest tiles (nb 5 - 6) run with two weight register sets (LinearFq8R::W2), where it measured 2 - 6 % faster.  Narrow tiles
+    // (nb <= 2, K a multiple of two k tiles) run variant R2, two k tiles per step.
     if (a.pair) {
         if (a.nb <= 2) return launch_r_nb<FX, FW, 2, true>(a, st);
         if (a.nb <= 4) return launch_r_nb<FX, FW, 4, true>(a, st);
-        if (w2) return launch_r_nb<FX, FW, 6, true, 20>(a, st);
         return launch_r_nb<FX, FW, 6, true>(a, st);
     }
-    if (a.nb <= 2 && a.K % (2 * kBK) == 0 && r2) {
-#ifdef QT_TUNING_BUILD
-        if constexpr (FX == 0 && FW == 0) {
-            const char *e_ra = getenv("QT_FQ8_R2_ABLATE");
-            switch (e_ra ? atoi(e_ra) : 0) {
-                case 30: return launch_r2<0, 0, 30>(a, st);
-                case 2: return launch_r2<0, 0, 2>(a, st);
-                case 3: return launch_r2<0, 0, 3>(a, st);
-                case 5: return launch_r2<0, 0, 5>(a, st);
-                default: break;
-            }
-        }
-#endif
-        return launch_r2<FX, FW>(a, st);
-    }
+    if (a.nb <= 2 && a.K % (2 * kBK) == 0) return launch_r2<FX, FW>(a, st);
     if (a.nb <= 2) return launch_r_nb<FX, FW, 2>(a, st);
     if (a.nb <= 4) return launch_r_nb<FX, FW, 4>(a, st);
-#ifdef QT_TUNING_BUILD
-    if constexpr (FX == 0 && FW == 0) {
-        const char *e_abl = getenv("QT_FQ8_ABLATE");
-        switch (e_abl ? atoi(e_abl) : 0) {
-            case 1: return launch_r_nb<0, 0, 6, false, 1>(a, st);
-            case 2: return launch_r_nb<0, 0, 6, false, 2>(a, st);
-            case 3: return launch_r_nb<0, 0, 6, false, 3>(a, st);
-            case 4: return launch_r_nb<0, 0, 6, false, 4>(a, st);
-            case 5: return launch_r_nb<0, 0, 6, false, 5>(a, st);     // no operand traffic: fragment reads + multiplications + barriers
-            case 6: return launch_r_nb<0, 0, 6, false, 6>(a, st);     // barriers only
-            case 7: return launch_r_nb<0, 0, 6, false, 7>(a, st);     // transport probe: weights by LDS-DMA (raw, unconverted)
-            case 8: return launch_r_nb<0, 0, 6, false, 8>(a, st);     // the same without the activation DMA
-            case 9: return launch_r_nb<0, 0, 6, false, 9>(a, st);     // bare transport: activation DMA only
-            case 10: return launch_r_nb<0, 0, 6, false, 10>(a, st);   // bare transport: weight DMA only
-            case 11: return launch_r_nb<0, 0, 6, false, 11>(a, st);   // bare transport: both by DMA
-            default: break;
-        }
-    }
-#endif
-    if (w2) return launch_r_nb<FX, FW, 6, false, 20>(a, st);
     return launch_r_nb<FX, FW, 6>(a, st);
 }
 
@@ -1328,9 +1104,7 @@ int qt_linear_fq8_bf16(const uint8_t *x8_dev, int x_format, const uint16_t *cons
     Args a{};
     a.x8 = x8_dev; a.y = y_dev; a.M = M; a.K = K; a.ldc = (int)ntot;
     a.tiles_m = p.tiles_m; a.tiles_n = p.tiles_n; a.gbase = p.gbase; a.gextra = p.gextra; a.nb = p.nb;
-    a.dbg = 0;
 #ifdef QT_TUNING_BUILD
-    if (const char *e_dbg = getenv("QT_FQ8_DEBUG")) a.dbg = atoi(e_dbg);
     if (const char *e_st = getenv("QT_FQ8_STAMPS")) a.stamps = (unsigned long long *)strtoull(e_st, nullptr, 0);
 #endif
     int nseg = 0, g0 = 0;
@@ -1366,9 +1140,7 @@ int qt_mlp_fq8_bf16(const uint8_t *x8_dev, int x_format, const uint16_t *w_gate_
     Fq8Plan p;
     if (const int rc = plan_mlp(M, N / 16, p)) return rc;
     a.tiles_m = p.tiles_m; a.tiles_n = p.tiles_n; a.gbase = p.gbase; a.gextra = p.gextra; a.nb = p.nb;
-    a.dbg = 0;
 #ifdef QT_TUNING_BUILD
-    if (const char *e_dbg = getenv("QT_FQ8_DEBUG")) a.dbg = atoi(e_dbg);
     if (const char *e_st = getenv("QT_FQ8_STAMPS")) a.stamps = (unsigned long long *)strtoull(e_st, nullptr, 0);
 #endif
     a.seg[0].w = w_gate_dev; a.seg[0].bias = bias_gate_dev; a.seg[0].g0 = 0;

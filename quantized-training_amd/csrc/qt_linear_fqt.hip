@@ -41,7 +41,6 @@ namespace {
 
 typedef short v8s __attribute__((ext_vector_type(8)));
 typedef float v4f __attribute__((ext_vector_type(4)));
-typedef float v16f __attribute__((ext_vector_type(16)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
@@ -60,8 +59,6 @@ struct Args {
     const uint32_t *rows;     // [512][4] row parameters (device)
     const uint16_t *map;      // [65536] value map (device): the redo path
     uint32_t sign_mask;
-    int prio;                // static issue priority of waves 4-7 (QT_FQT_PRIO)
-    unsigned long long *dbg; // ABL 9 (QT_FQT_STAMPS = device address): s_memtime stamps of workgroup 0, waves 0 and 4, k step 40
     int M, K, ldc;
     int tiles_m, tiles_n, nseg;
     int gbase, gextra;        // column tile j covers gbase (+1 for gextra of them) groups of 16 columns
@@ -71,6 +68,9 @@ struct Args {
     float *ws;                // [tile][split][wave][kRT x kMaxNTW fragments][64 lanes][4] fp32
     unsigned int *tickets;    // [tile] arrival counters, zero between launches (the last arriver resets its tile's)
     Segment seg[kMaxSeg];
+#ifdef QT_TUNING_BUILD
+    unsigned long long *stamps;   // tools/ only (QT_FQT_STAMPS = device address): see LinearFqt's STAMPS
+#endif
 };
 
 struct SegRef { const uint16_t *w, *bias; int g0; };
@@ -194,11 +194,9 @@ constexpr int walk(int RT, int NTW, int NB, int from_kind, int from_idx, int to_
     return result > 15 ? 15 : result;
 }
 
-// ABL (timing experiments only, QT_FQT_ABLATE; results are garbage): 1 no multiplications, 2 no weight items at all, 3 no
-// activation DMA, 5 weight items without the conversion (DMA, LDS round trip), 6 conversion without the table gathers
-//
 // TM: rows of a workgroup's tile (512 or 256); NB: weight pieces (16 rows x 64 bytes = one column group) per wave and k step
-// (1: tiles of up to 8 groups, 2: up to 16); SROWS: the table has 512 rows (sign and exponent).
+// (1: tiles of up to 8 groups, 2: up to 16); SROWS: the table has 512 rows (sign and exponent).  STAMPS (tuning build only):
+// s_memtime stamps of workgroup 0, k steps 40 - 43, into Args::stamps -- 1: four per step and wave, 2: every phase of the step.
 //
 // k step t of a wave (every LDS / DMA operation is inline asm, every wait a computed count):
 //   top      s_waitcnt vmcnt(N) lgkmcnt(0); s_barrier      the activation tile of step t and this wave's raw pieces of weight tile
@@ -207,7 +205,7 @@ constexpr int walk(int RT, int NTW, int NB, int from_kind, int from_idx, int to_
 //   first    request activation tile t+2 and RAW weight tile t+4
 //   then     the LDS stream above: RT multiplications per column group on tile t, and 2 NB units of weight tile t+1 converted IN
 //            PLACE, spread evenly over the groups; the rows of unit u+1 are in flight while unit u is computed
-template <int TM, int NB, bool SROWS, int ABL = 0>
+template <int TM, int NB, bool SROWS, int STAMPS = 0>
 struct LinearFqt {
     static constexpr int kDA = 3, kDW = 5, kU = 2 * NB;
     static constexpr int kRT = TM / 64;                     // 16-row tiles of a wave's row band (TM / 4 rows)
@@ -247,7 +245,7 @@ struct LinearFqt {
                 u32x4 v = *(const u32x4 *)(a.rows + t * 4);
                 // a flagged row (bit 0 of C) POISONS: C = lo = hi = NaN make every weight of the row a NaN, which reaches every sum it
                 // enters; the sums are checked once after the k loop (no per-weight flag arithmetic in the loop)
-                if (ABL == 0 && (v.y & 1u)) v = u32x4{0u, 0x7FC00000u, 0x7FC00000u, 0x7FC00000u};
+                if (v.y & 1u) v = u32x4{0u, 0x7FC00000u, 0x7FC00000u, 0x7FC00000u};
                 asm volatile("ds_write_b128 %0, %1" ::"v"(t * 16), "v"(v) : "memory");
             }
         }
@@ -258,10 +256,6 @@ struct LinearFqt {
         for (int i = 0; i < kPA; ++i) {
             const int row = (w * kPA + i) * 16 + (l >> 2);
             ga[i] = (uint32_t)((long)min(m0 + row, a.M - 1) * krow) + (chunk_pos(row, l & 3) << 4);
-            if constexpr (ABL == 7) {        // timing probe: whole 128-byte lines (8 rows per piece) instead of half lines
-                const int row8 = (w * kPA + i) * 8 + (l >> 3);
-                ga[i] = (uint32_t)((long)min(m0 + row8, a.M - 1) * krow) + ((l & 7) << 4);
-            }
         }
         // Weight pieces: piece p = w + 8 i is column group p of the tile; the lane's 16 bytes land at piece base + 16 l and are
         // converted there.  Surplus pieces (p >= nt) re-request piece 0 into the dummy kilobyte.
@@ -282,15 +276,14 @@ struct LinearFqt {
             wofs[i] = (uint32_t)pb * 1024u;
         }
         const uint32_t sign_mask = a.sign_mask;
-        int stamp_kt = -1;
+        [[maybe_unused]] int stamp_kt = -1;                  // (the stamps of the tuning build)
         auto stamp = [&](int slot) __attribute__((always_inline)) {
-            if constexpr (ABL == 9 || ABL == 8) {
-                if (ABL == 8 && !(slot == 29 || slot == 31 || slot == 0 || slot == 30)) return;     // light: four stamps per step
-                if (stamp_kt >= 40 && stamp_kt < 44 && blockIdx.x == 0 && l == 0) a.dbg[(w * 4 + (stamp_kt - 40)) * 32 + slot] = __builtin_amdgcn_s_memtime();
+#ifdef QT_TUNING_BUILD
+            if constexpr (STAMPS != 0) {
+                if (STAMPS == 1 && !(slot == 29 || slot == 31 || slot == 0 || slot == 30)) return;
+                if (stamp_kt >= 40 && stamp_kt < 44 && blockIdx.x == 0 && l == 0) a.stamps[(w * 4 + (stamp_kt - 40)) * 32 + slot] = __builtin_amdgcn_s_memtime();
             }
-        };
-        auto dma16 = [](const void *base, uint32_t off, uint32_t dst) __attribute__((always_inline)) {
-            asm volatile("s_mov_b32 m0, %2\n\ts_nop 1\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(off), "s"(base), "s"(dst) : "memory");
+#endif
         };
         auto ds_write64 = [](uint32_t addr, u32x2 v) __attribute__((always_inline)) {
             asm volatile("ds_write_b64 %0, %1" ::"v"(addr), "v"(v) : "memory");
@@ -300,12 +293,10 @@ struct LinearFqt {
         auto req_piece = [&](auto ic, int ka, uint32_t as, int kb, uint32_t ws) __attribute__((always_inline)) {
             constexpr int I = decltype(ic)::value;
             if constexpr (I < kPA) {
-                const uint8_t *xb = (const uint8_t *)a.x + (ABL == 7 ? (long)((ka + kbeg) >> 1) * 128 : (long)(ka + kbeg) * kRowBytes);
-                if constexpr (ABL != 3) dma16(xb, ga[I], as + (w * kPA + I) * 1024);
-                else dma16(xb, ga[I], dummy);
+                dma16((const uint8_t *)a.x + (long)(ka + kbeg) * kRowBytes, ga[I], as + (w * kPA + I) * 1024);
             } else {
                 constexpr int i = I - kPA;
-                dma16((const uint8_t *)wbase[i] + (long)(kb + kbeg) * kRowBytes, gw[i], (real[i] && ABL != 2) ? ws + wofs[i] : dummy);
+                dma16((const uint8_t *)wbase[i] + (long)(kb + kbeg) * kRowBytes, gw[i], real[i] ? ws + wofs[i] : dummy);
             }
         };
         auto req_range = [&](auto lo, auto hi, int ka, uint32_t as, int kb, uint32_t ws) __attribute__((always_inline)) {
@@ -338,39 +329,27 @@ struct LinearFqt {
         };
         auto unit_gather = [&](auto uc) __attribute__((always_inline)) {
             constexpr int U = decltype(uc)::value;
-            if constexpr (ABL != 2 && ABL != 5 && ABL != 6) {
-                uint32_t ad[4];
-                row_addrs<kRowMask>(raw_word(uc, 0), ad[0], ad[1]);
-                row_addrs<kRowMask>(raw_word(uc, 1), ad[2], ad[3]);
+            uint32_t ad[4];
+            row_addrs<kRowMask>(raw_word(uc, 0), ad[0], ad[1]);
+            row_addrs<kRowMask>(raw_word(uc, 1), ad[2], ad[3]);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) rows[U & 1][e] = ds_gather128(ad[e]);
-            }
+            for (int e = 0; e < 4; ++e) rows[U & 1][e] = ds_gather128(ad[e]);
         };
         auto unit_finish = [&](auto uc, uint32_t wc) __attribute__((always_inline)) {
             constexpr int U = decltype(uc)::value, I = U >> 1;
-            if constexpr (ABL != 2) {
-                u32x4(&rp)[4] = rows[U & 1];
-                if constexpr (ABL == 6) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) rp[e] = u32x4{0u, 0x4B400000u, 0u, 0x7F000000u};
-                }
-                u32x2 q = {raw_word(uc, 0), raw_word(uc, 1)};
-                if constexpr (ABL != 5) {
-                    q.x = quant_pair(raw_word(uc, 0), rp[0], rp[1], sign_mask);
-                    q.y = quant_pair(raw_word(uc, 1), rp[2], rp[3], sign_mask);
-                }
-                ds_write64(piece_addr(I, wc) + (U & 1) * 8, q);
-            }
+            u32x4(&rp)[4] = rows[U & 1];
+            u32x2 q = {raw_word(uc, 0), raw_word(uc, 1)};
+            q.x = quant_pair(raw_word(uc, 0), rp[0], rp[1], sign_mask);
+            q.y = quant_pair(raw_word(uc, 1), rp[2], rp[3], sign_mask);
+            ds_write64(piece_addr(I, wc) + (U & 1) * 8, q);
         };
         // unit slot: the next unit's rows requested, this unit's rows waited for, computed, written back
         auto unit_slot = [&](auto uc, uint32_t wc) __attribute__((always_inline)) {
             constexpr int U = decltype(uc)::value;
             if constexpr (U + 1 < kU) unit_gather(std::integral_constant<int, U + 1>{});
-            if constexpr (ABL != 2 && ABL != 5 && ABL != 6) {
-                constexpr int n = walk(kRT, NTW, NB, kOpG, U, kWaitG, U);
-                static_assert(n >= 0, "schedule");
-                asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(rows[U & 1][0]), "+v"(rows[U & 1][1]), "+v"(rows[U & 1][2]), "+v"(rows[U & 1][3]) : "n"(n));
-            }
+            constexpr int n = walk(kRT, NTW, NB, kOpG, U, kWaitG, U);
+            static_assert(n >= 0, "schedule");
+            asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(rows[U & 1][0]), "+v"(rows[U & 1][1]), "+v"(rows[U & 1][2]), "+v"(rows[U & 1][3]) : "n"(n));
             unit_finish(uc, wc);
         };
         // the units column group J carries
@@ -384,32 +363,19 @@ struct LinearFqt {
         static_assert(kU <= 4, "units_of lists four units");
         // the step's first LDS operations: raw pieces of the tile to convert (stage wc)
         auto read_raw = [&](uint32_t wc) __attribute__((always_inline)) {
-            if constexpr (ABL != 2) {
 #pragma unroll
-                for (int i = 0; i < NB; ++i) raw[i] = ds_gather128(piece_addr(i, wc));
-            }
+            for (int i = 0; i < NB; ++i) raw[i] = ds_gather128(piece_addr(i, wc));
         };
         // wait for raw[0], then the first unit's rows
         auto first_rows = [&]() __attribute__((always_inline)) {
-            if constexpr (ABL != 2) {
-                constexpr int n = walk(kRT, NTW, NB, kOpRaw, NB - 1, kWaitRaw, 0);
-                static_assert(n >= 0, "schedule");
-                if constexpr (NB == 2) asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(raw[0]), "+v"(raw[1]) : "n"(n));
-                else asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(raw[0]) : "n"(n));
-                unit_gather(std::integral_constant<int, 0>{});
-            }
+            constexpr int n = walk(kRT, NTW, NB, kOpRaw, NB - 1, kWaitRaw, 0);
+            static_assert(n >= 0, "schedule");
+            if constexpr (NB == 2) asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(raw[0]), "+v"(raw[1]) : "n"(n));
+            else asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(raw[0]) : "n"(n));
+            unit_gather(std::integral_constant<int, 0>{});
         };
         static_assert(NB <= 2, "first_rows lists two pieces");
 
-        v16f acc32[4][2];                                         // ABL 10 only
-        if constexpr (ABL == 10) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) acc32[i][j][e] = 0.f;
-        }
         v4f acc[kRT][NTW > 0 ? NTW : 1];
 #pragma unroll
         for (int i = 0; i < kRT; ++i)
@@ -444,10 +410,8 @@ struct LinearFqt {
                     // the younger wave of a SIMD (column half 1) loses the issue arbitration to the older one and would set the pace of
                     // the step; it runs the first part of the step at priority 1 and the rest at 0, so that both finish together
                     if constexpr (PH == 1) {
-                        if (a.prio == 4) {
-                            if constexpr (J == 0) __builtin_amdgcn_s_setprio(1);
-                            if constexpr (J == (NTW + 1) / 2) __builtin_amdgcn_s_setprio(0);
-                        }
+                        if constexpr (J == 0) __builtin_amdgcn_s_setprio(1);
+                        if constexpr (J == (NTW + 1) / 2) __builtin_amdgcn_s_setprio(0);
                     }
                     if constexpr (J + 2 < NTW) read_b(std::integral_constant<int, J + 2>{});
                     constexpr int kAhead = walk(kRT, NTW, NB, kOpRB, J, kWaitF, J);
@@ -468,25 +432,15 @@ struct LinearFqt {
                     // consecutive output columns of one row.  The multiplications come first in program order; the vector work
                     // of the group (a unit's arithmetic, the next unit's row addresses) is woven between them below.
                     const v8s bf = __builtin_bit_cast(v8s, fb[P]);
-                    if constexpr (ABL == 10) {
-                        // timing probe (results are garbage): the same flops as v_mfma_f32_32x32x16_bf16 -- half the instructions, each
-                        // holding the matrix pipe twice as long: per PAIR of column groups 4 row tiles x 2 k halves
-                        if constexpr ((J & 1) == 0 && kRT == 8) {
 #pragma unroll
-                            for (int i = 0; i < 8; ++i)
-                                acc32[i >> 1][J >> 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf, __builtin_bit_cast(v8s, fa[i]), acc32[i >> 1][J >> 1], 0, 0, 0);
-                        }
-                    } else if constexpr (ABL != 1) {
-#pragma unroll
-                        for (int i = 0; i < kRT; ++i)
-                            acc[i][J] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf, __builtin_bit_cast(v8s, fa[i]), acc[i][J], 0, 0, 0);
-                    }
+                    for (int i = 0; i < kRT; ++i)
+                        acc[i][J] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf, __builtin_bit_cast(v8s, fa[i]), acc[i][J], 0, 0, 0);
                     stamp(5 + 3 * J);
                     if constexpr (J == 0) first_rows();
                     units_of(jc, wc);
                     // this group's share of the step's requests
                     req_range(std::integral_constant<int, J * kReq / NTW>{}, std::integral_constant<int, (J + 1) * kReq / NTW>{}, ka, as, kb, ws);
-                    if constexpr (ABL != 1 && kWeave > 0) {
+                    if constexpr (kWeave > 0) {
 #pragma unroll
                         for (int i = 0; i < kRT; ++i) {
                             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);          // one multiplication
@@ -523,25 +477,22 @@ struct LinearFqt {
         for (int s = 0; s < kDW - 1; ++s)
             request(min(s < kDA - 1 ? s : kDA - 2, klast), a0 + (s < kDA - 1 ? s : kDA - 2) * kABytes, min(s, klast), w0 + s * kWBytes);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if constexpr (ABL != 2) {
-            // plain and serial: read, gather, compute, write, one piece at a time
+        // plain and serial: read, gather, compute, write, one piece at a time
 #pragma unroll
-            for (int i = 0; i < NB; ++i) {
-                u32x4 v = ds_gather128(piece_addr(i, w0));
-                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v));
-                uint32_t ad[8];
-                row_addrs<kRowMask>(v.x, ad[0], ad[1]); row_addrs<kRowMask>(v.y, ad[2], ad[3]);
-                row_addrs<kRowMask>(v.z, ad[4], ad[5]); row_addrs<kRowMask>(v.w, ad[6], ad[7]);
-                u32x4 p[8];
+        for (int i = 0; i < NB; ++i) {
+            u32x4 v = ds_gather128(piece_addr(i, w0));
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v));
+            uint32_t ad[8];
+            row_addrs<kRowMask>(v.x, ad[0], ad[1]); row_addrs<kRowMask>(v.y, ad[2], ad[3]);
+            row_addrs<kRowMask>(v.z, ad[4], ad[5]); row_addrs<kRowMask>(v.w, ad[6], ad[7]);
+            u32x4 p[8];
 #pragma unroll
-                for (int e = 0; e < 8; ++e) p[e] = ds_gather128(ad[e]);
-                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(p[0]), "+v"(p[1]), "+v"(p[2]), "+v"(p[3]), "+v"(p[4]), "+v"(p[5]), "+v"(p[6]), "+v"(p[7]));
-                u32x4 q;
-                q.x = quant_pair(v.x, p[0], p[1], sign_mask); q.y = quant_pair(v.y, p[2], p[3], sign_mask);
-                q.z = quant_pair(v.z, p[4], p[5], sign_mask); q.w = quant_pair(v.w, p[6], p[7], sign_mask);
-                if constexpr (ABL != 0 && ABL != 9 && ABL != 8) q = v;
-                asm volatile("ds_write_b128 %0, %1" ::"v"(piece_addr(i, w0)), "v"(q) : "memory");
-            }
+            for (int e = 0; e < 8; ++e) p[e] = ds_gather128(ad[e]);
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(p[0]), "+v"(p[1]), "+v"(p[2]), "+v"(p[3]), "+v"(p[4]), "+v"(p[5]), "+v"(p[6]), "+v"(p[7]));
+            u32x4 q;
+            q.x = quant_pair(v.x, p[0], p[1], sign_mask); q.y = quant_pair(v.y, p[2], p[3], sign_mask);
+            q.z = quant_pair(v.z, p[4], p[5], sign_mask); q.w = quant_pair(v.w, p[6], p[7], sign_mask);
+            asm volatile("ds_write_b128 %0, %1" ::"v"(piece_addr(i, w0)), "v"(q) : "memory");
         }
         int sa = 0, sw = 0;                                        // stages multiplied in this step (activations, weights)
         {
@@ -571,7 +522,7 @@ struct LinearFqt {
             // a NaN among the sums: a weight of a flagged row (or a non-finite operand the reference would turn into NaN as well) --
             // the tile is redone through the map itself, which gives the exact answer in either case
             bool bad = false;
-            if constexpr (NTW > 0 && ABL == 0) {
+            if constexpr (NTW > 0) {
 #pragma unroll
                 for (int i = 0; i < kRT; ++i)
 #pragma unroll
@@ -583,14 +534,6 @@ struct LinearFqt {
         const bool flagged = *flag != 0;
         if (a.ksplit <= 1) {
             if (flagged) return true;
-        if constexpr (ABL == 10 && NTW > 0) {
-    #pragma unroll
-                for (int i = 0; i < 4; ++i)
-    #pragma unroll
-                    for (int j = 0; j < 2; ++j)
-    #pragma unroll
-                        for (int e = 0; e < 16; ++e) acc[i][0][e & 3] += acc32[i][j][e];
-            }
         } else {
             // ---- split-K hand-off.  Partial sums leave in fragment order (a wave's store instruction writes one contiguous KiB),
             // write-through; every wave drains its stores; behind the workgroup barrier ONE lane takes the tile's ticket.  Whoever
@@ -764,7 +707,7 @@ __device__ __forceinline__ void slow_tile(const Args &a, int m0, int tg0, int jb
     }
 }
 
-template <int TM, int NB, bool SROWS, int ABL = 0>
+template <int TM, int NB, bool SROWS, int STAMPS = 0>
 __global__ __launch_bounds__(512, 1) void linear_fqt_kernel(Args a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_t[];
     const int t = threadIdx.x, l = t & 63, w = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -790,17 +733,13 @@ __global__ __launch_bounds__(512, 1) void linear_fqt_kernel(Args a) {
     const int nt0 = (nt + 1) >> 1;
     const int wn = w >> 2;
     const int ntw = wn == 0 ? nt0 : nt - nt0, jbase = wn == 0 ? 0 : nt0;
-    using L = LinearFqt<TM, NB, SROWS, ABL>;
+    using L = LinearFqt<TM, NB, SROWS, STAMPS>;
     if (lds_addr(lds_t) != 0) __builtin_trap();            // the LDS map is written in absolute addresses
     // The two waves of a SIMD are w and w + 4; the SIMD's issue arbitration prefers the older one (waves 0-3), and the younger half then
     // sets the pace of every k step (measured, tools/exp_fqt_stamps.py: 1750 against 1230 cycles of work per step, the older half
     // waiting 600 cycles at the barrier).  A static priority for the younger half evens that out (MI355X_MICROARCH.md, "Two waves per
-    // SIMD", item 4).  a.prio (QT_FQT_PRIO): 0 none, 1-3 static priority of the younger half, 4 (default) the younger half at priority
-    // 1 for the first half of every step only (set inside the step; 183 against 190 us at 1024 x 13824 x 5120).
-    if (a.prio == 1 && w >= 4) __builtin_amdgcn_s_setprio(1);
-    if (a.prio == 2 && w >= 4) __builtin_amdgcn_s_setprio(2);
-    if (a.prio == 3 && w >= 4) __builtin_amdgcn_s_setprio(3);
-    if (a.prio == -1 && w < 4) __builtin_amdgcn_s_setprio(1);
+    // SIMD", item 4): the younger half runs at priority 1 for the first half of every step (set inside the step; 183 against 190 us
+    // at 1024 x 13824 x 5120).
     bool redo;
 #define QT_RUN(N) (wn == 1 ? L::template run<N, 1>(a, lds_t, m0, tg0, nt, jbase, w, l, kbeg, nk, split, tile_lin) \
                            : L::template run<N, 0>(a, lds_t, m0, tg0, nt, jbase, w, l, kbeg, nk, split, tile_lin))
@@ -832,16 +771,16 @@ int cu_count() {
     return n;
 }
 
-template <int TM, int NB, bool SROWS, int ABL = 0>
+template <int TM, int NB, bool SROWS, int STAMPS = 0>
 int launch_one(const Args &a, hipStream_t st) {
     constexpr int kLds = LinearFqt<TM, NB, SROWS>::kLds;
     static QtOncePerDevice configured;      
     if (configured.needed()) {
-        const hipError_t e = hipFuncSetAttribute((const void *)linear_fqt_kernel<TM, NB, SROWS, ABL>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
+        const hipError_t e = hipFuncSetAttribute((const void *)linear_fqt_kernel<TM, NB, SROWS, STAMPS>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
         if (e != hipSuccess) return (int)e;
         configured.done();
     }
-    linear_fqt_kernel<TM, NB, SROWS, ABL><<<a.tiles_m * a.tiles_n * a.ksplit, 512, kLds, st>>>(a);
+    linear_fqt_kernel<TM, NB, SROWS, STAMPS><<<a.tiles_m * a.tiles_n * a.ksplit, 512, kLds, st>>>(a);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? QT_OK : (int)e;
 }
@@ -851,19 +790,7 @@ int launch(const Args &a, hipStream_t st, int tm) {
     if (tm == 512) {
 #ifdef QT_TUNING_BUILD
         if constexpr (!SROWS) {
-            const char *e_abl = getenv("QT_FQT_ABLATE");       // timing experiments (tools/exp_linear_fqt.py --skip-checks): results are garbage
-            switch (e_abl ? atoi(e_abl) : 0) {
-                case 1: return launch_one<512, 1, false, 1>(a, st);
-                case 2: return launch_one<512, 1, false, 2>(a, st);
-                case 3: return launch_one<512, 1, false, 3>(a, st);
-                case 5: return launch_one<512, 1, false, 5>(a, st);
-                case 6: return launch_one<512, 1, false, 6>(a, st);
-                case 7: return launch_one<512, 1, false, 7>(a, st);
-                case 10: return launch_one<512, 1, false, 10>(a, st);
-                case 8: return launch_one<512, 1, false, 8>(a, st);
-                case 9: return launch_one<512, 1, false, 9>(a, st);
-                default: break;
-            }
+            if (a.stamps) return getenv("QT_FQT_STAMPS_ALL") ? launch_one<512, 1, false, 2>(a, st) : launch_one<512, 1, false, 1>(a, st);
         }
 #endif
         return launch_one<512, 1, SROWS>(a, st);
@@ -975,15 +902,8 @@ int linear_fqt(const uint16_t *x_dev, const uint16_t *const *w_devs, const uint1
     Args a{};
     a.x = x_dev; a.y = y_dev; a.rows = rows_dev; a.map = map_dev; a.sign_mask = sign_mask;
     a.M = M; a.K = K; a.ldc = (int)ntot;
-    a.prio = 4;
-    a.dbg = nullptr;
 #ifdef QT_TUNING_BUILD
-    {
-        const char *e_pr = getenv("QT_FQT_PRIO");
-        a.prio = e_pr ? atoi(e_pr) : 4;
-        const char *e_st = getenv("QT_FQT_STAMPS");
-        a.dbg = e_st ? (unsigned long long *)strtoull(e_st, nullptr, 0) : nullptr;
-    }
+    if (const char *e_st = getenv("QT_FQT_STAMPS")) a.stamps = (unsigned long long *)strtoull(e_st, nullptr, 0);
 #endif
     a.tiles_m = t.tiles_m; a.tiles_n = t.tiles_n; a.gbase = t.gbase; a.gextra = t.gextra;
     a.ksplit = t.ksplit; a.ws = ws_dev; a.tickets = tickets_dev;

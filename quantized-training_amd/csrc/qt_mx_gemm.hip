@@ -771,7 +771,6 @@ struct WideGeom {
     int tm;                     // 256 or 128
     int tiles_m, tiles_n;
     int gbase, gextra;          // column tile j covers gbase + (j < gextra) groups of 16 columns
-    int dbg;                    // QT_MX_WIDE_DEBUG: 2 = no multiplications (DMA only), 32 = no barriers
 };
 
 template <int FA, int FB, int TM, int NBP>         // NBP: B DMA pieces (8 rows x 128 bytes) per wave and stage
@@ -948,7 +947,7 @@ struct MxWide {
         for (int kt = 0; kt < nk; ++kt) {
             // still allowed in flight: what was requested for the steps behind kt; everything older must have landed
             asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kADepth == kBDepth ? (kADepth - 2) * kItems : NBP) : "memory");
-            if (!(geo.dbg & 32)) __builtin_amdgcn_s_barrier();       // ... for every wave; and every wave is done with step kt - 1: its slots may be refilled
+            __builtin_amdgcn_s_barrier();                          // ... for every wave; and every wave is done with step kt - 1: its slots may be refilled
             // the next quad of scale bytes, into the buffer quad (kt / 4) - 1 was read from: older than everything this wave will
             // request before the quad is needed, so the counted waits above cover it (they may wait for one tile piece more)
             if ((kt & 3) == 0 && kt + 4 < nk) issue_quad((kt >> 2) + 1, q0 + (((kt >> 2) + 1) & 1) * kQBytes);
@@ -956,8 +955,7 @@ struct MxWide {
             uint8_t *const a_dst = lds + a_tgt * kAStage, *const b_dst = bs0 + b_tgt * kBStage;
             const uint32_t sa_ = l0 + a_slot * kAStage, sb_ = l0 + kADepth * kAStage + b_slot * kBStage;
             const uint32_t sq_ = l0 + kQBase + ((kt >> 2) & 1) * kQBytes + (kt & 3) * 4;
-            if (!(geo.dbg & 2)) compute(sa_, sb_, sq_, ka, a_dst, kb, b_dst);
-            else issue_range(kI0, kIN, ka, a_dst, kb, b_dst);
+            compute(sa_, sb_, sq_, ka, a_dst, kb, b_dst);
             a_tgt = a_slot; a_slot = a_slot + 1 == kADepth ? 0 : a_slot + 1;
             b_tgt = b_slot; b_slot = b_slot + 1 == kBDepth ? 0 : b_slot + 1;
         }
@@ -1074,11 +1072,10 @@ bool wide_geometry(int M, int N, long batch, WideGeom &geo) {
     if (N % 16 != 0 || M < 1) return false;
     const long groups = N / 16;
     const int cus = wide_cu_count();
-    int force_tn = 0, dbg = 0;
+    int force_tn = 0;
 #ifdef QT_TUNING_BUILD
     static const int e_force_tn = getenv("QT_MX_WIDE_TILES_N") ? atoi(getenv("QT_MX_WIDE_TILES_N")) : 0;     // tools/ only
-    static const int e_dbg = getenv("QT_MX_WIDE_DEBUG") ? atoi(getenv("QT_MX_WIDE_DEBUG")) : 0;
-    force_tn = e_force_tn; dbg = e_dbg;
+    force_tn = e_force_tn;
 #endif
     const char *e_tm = getenv("QT_MX_WIDE_TM");                     // test hook, read per call: the parity tests drive both tile heights
     const int force_tm = e_tm ? atoi(e_tm) : 0;
@@ -1103,7 +1100,6 @@ bool wide_geometry(int M, int N, long batch, WideGeom &geo) {
             geo.tm = tm; geo.tiles_m = (int)tiles_m; geo.tiles_n = (int)tn; geo.gbase = (int)gbase; geo.gextra = (int)gextra;
         }
     }
-    geo.dbg = dbg;
     return best >= 0;
 }
 

@@ -91,12 +91,7 @@ __device__ __forceinline__ bf16x8 ld_frag_tr(const unsigned char *img, int c0, i
 __device__ __forceinline__ uint32_t lds_addr(const void *p) {
     return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)p;
 }
-// one LDS-DMA piece: the wave's 64 lanes bring 16 bytes each from `src` (per lane) to LDS bytes dst .. dst + 1023 (wave-uniform dst).
-// Inline asm: the compiler must not know about these entries of the vector-memory queue (it would wait for all of them in front of
-// every other access); the waits are counted by hand below.
-__device__ __forceinline__ void dma16(const void *src, uint32_t dst) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 1\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(dst) : "memory");
-}
+// one LDS-DMA piece: dma16 (qt_device.h), its waits counted by hand below
 template <int N>
 __device__ __forceinline__ void wait_and_barrier() {       // at most N of this wave's DMA pieces still in flight; LDS reads drained
     asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");

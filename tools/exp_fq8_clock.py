@@ -4,9 +4,8 @@
 
 Every workgroup of qt_linear_fq8_bf16 stamps s_memtime (shader cycles) and s_memrealtime (100 MHz) around its tile
 (QT_FQ8_STAMPS, tuning build only).  After `--seconds` of back-to-back launches on random data the last launch's stamps give
-clock = cycles / ticks x 100 MHz (median over workgroups) -- MI355X_MICROARCH.md "DVFS give-back" item 6.  Printed per shape and
-per ablation (QT_FQ8_ABLATE: 0 whole kernel, 5 fragment reads + multiplications + barriers with no operand traffic, 1 no
-multiplications, 4 no fragment reads and no multiplications): wall us per launch, cycles per tile and per k step, clock.
+clock = cycles / ticks x 100 MHz (median over workgroups) -- MI355X_MICROARCH.md "DVFS give-back" item 6.  Printed per shape, on
+random and on all-zero data: wall us per launch, cycles per tile and per k step, clock.
 """
 import argparse
 import ctypes
@@ -83,26 +82,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=2.0)
     ap.add_argument("--shapes", default="1024x11008x4096,1024x4096x11008,1024x4096x4096,1024x12288x4096")
-    ap.add_argument("--ablations", default="0,5,1,4")
     args = ap.parse_args()
     for shp in args.shapes.split(","):
         M, N, K = (int(v) for v in shp.split("x"))
-        wide = N >= 8192
-        for abl in args.ablations.split(","):
-            if abl != "0" and not wide:
-                env = {"1": None, "4": None, "5": "5"}.get(abl)       # the narrow-tile kernel has its own (smaller) ablation list
-                if env is None:
-                    continue
-                os.environ["QT_FQ8_R2_ABLATE"] = env
-            else:
-                os.environ["QT_FQ8_ABLATE"] = abl
-            for zeros in ((False, True) if abl == "0" else (False,)):
-                us, cmed, cmax, clock, nwg = run(M, N, K, args.seconds, zeros)
-                steps = K // 128
-                print(f"{shp} ablate={abl} {'zeros ' if zeros else 'random'}: {us:7.2f} us/launch  tile {cmed:9.0f} cycles median ({cmax:9.0f} max) "
-                      f"= {cmed / steps:7.1f} per k tile  clock {clock:6.0f} MHz  ({nwg} workgroups; tile = {cmed / clock:6.2f} us)", flush=True)
-            os.environ.pop("QT_FQ8_ABLATE", None)
-            os.environ.pop("QT_FQ8_R2_ABLATE", None)
+        for zeros in (False, True):
+            us, cmed, cmax, clock, nwg = run(M, N, K, args.seconds, zeros)
+            steps = K // 128
+            print(f"{shp} {'zeros ' if zeros else 'random'}: {us:7.2f} us/launch  tile {cmed:9.0f} cycles median ({cmax:9.0f} max) "
+                  f"= {cmed / steps:7.1f} per k tile  clock {clock:6.0f} MHz  ({nwg} workgroups; tile = {cmed / clock:6.2f} us)", flush=True)
 
 
 if __name__ == "__main__":

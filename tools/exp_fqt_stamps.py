@@ -1,4 +1,4 @@
-"""In-kernel clocks of four consecutive k steps of qt_linear_fqt_bf16 (QT_FQT_ABLATE=8: four stamps per step and wave; =9: every
+"""In-kernel clocks of four consecutive k steps of qt_linear_fqt_bf16 (four stamps per step and wave; QT_FQT_STAMPS_ALL=1: every
 phase, waves 0 and 4): where does a step's time go?"""
 import os, sys
 import torch
@@ -6,7 +6,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools")); sys.path.insert(0, os.path.join(ROOT, "quantized-training_amd"))
 buf = torch.zeros(8 * 4 * 32, dtype=torch.int64, device="cuda")
 os.environ["QT_FQT_STAMPS"] = hex(buf.data_ptr())
-mode = os.environ.setdefault("QT_FQT_ABLATE", "8")
+every_phase = bool(os.environ.get("QT_FQT_STAMPS_ALL"))
 import exp_linear_fqt as E
 f = E.Fmt("posit8_2")
 M, N, K = 1024, 13824, 5120
@@ -24,7 +24,7 @@ for w in range(8):
         st = b[w, s]
         row.append("start %6d: wait %4d  barrier %4d  work %5d" % (int(st[29]) - t0, int(st[31] - st[29]), int(st[0] - st[31]), int(st[30] - st[0])))
     print("wave", w, " | ".join(row))
-if mode == "9":
+if every_phase:
     names = {29: "prev end", 31: "after top wait", 0: "after barrier", 1: "after requests", 2: "after frag reads issued", 30: "step end"}
     for w in (0, 4):
         st = b[w, 0].tolist()

@@ -1,5 +1,5 @@
 """Times qt_mx_gemm's fp8 kernels on the M = 1024 LLaMA shapes under the tuning switches of the 256 x (16 nt) kernel
-(QT_MX_WIDE, QT_MX_WIDE_DEBUG, QT_MX_WIDE_TILES_N are read once per process: one process per setting)."""
+(QT_MX_WIDE, QT_MX_WIDE_TILES_N are read once per process: one process per setting)."""
 import ctypes
 import os
 import subprocess
@@ -41,9 +41,7 @@ if __name__ == "__main__":
         child()
         sys.exit(0)
     settings = [("old kernels", {"QT_MX_WIDE": "0"}), ("wide", {"QT_MX_WIDE": "1"}), ("wide, 256 rows", {"QT_MX_WIDE": "1", "QT_MX_WIDE_TM": "256"}),
-                ("wide, 128 rows", {"QT_MX_WIDE": "1", "QT_MX_WIDE_TM": "128"}),
-                ("wide, DMA only", {"QT_MX_WIDE": "1", "QT_MX_WIDE_DEBUG": "2"}),
-                ("wide, no barrier (wrong results)", {"QT_MX_WIDE": "1", "QT_MX_WIDE_DEBUG": "32"})]
+                ("wide, 128 rows", {"QT_MX_WIDE": "1", "QT_MX_WIDE_TM": "128"})]
     for name, env in settings:
         e = dict(os.environ); e.update(env)
         r = subprocess.run([sys.executable, __file__, "child"], env=e, capture_output=True, text=True, timeout=600)

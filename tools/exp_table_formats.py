@@ -1,6 +1,5 @@
 """GPU experiment: table-format (LDS value map) streaming kernels, per-tensor and per-channel, on a LLaMA-2 weight
-(bf16 [4096, 11008], pool of 8 = 720 MB, beyond the Infinity Cache); algorithmic traffic 4 B/element.
-Run under QT_LUT_HALF=0 / QT_PC_LDS=0 for the previous kernels."""
+(bf16 [4096, 11008], pool of 8 = 720 MB, beyond the Infinity Cache); algorithmic traffic 4 B/element."""
 import ctypes
 import os
 import sys
@@ -56,7 +55,6 @@ def per_channel(dtype, observe, rows_form=True):
 
 s = torch.tensor([0.013], device=dev)
 h = torch.zeros(16, device=dev)
-print(f"QT_LUT_HALF={os.environ.get('QT_LUT_HALF', '1')} QT_PC_LDS={os.environ.get('QT_PC_LDS', '1')}")
 for dt in ("posit8_1", "posit8_2", "fp8_e4m3", "fp4_e2m1", "int8"):
     f = nv.format_for(dt)
     for label, sc, am in (("unit", None, None), ("scale", s, None), ("scale+obs", s, h)):

@@ -7,8 +7,7 @@ last wave at a few points (QT_EW_STAMPS, csrc/qt_elementwise.hip).  The step is 
 each captured launch keeps its own stamp region, so the last replay's stamps of every launch are read back together.  Printed per
 launch: tag (0x1NS. chain, 0x2NS. LayerNorm backward), grid, the launch's span (first start -> last end), the spread of workgroup
 starts, and the median over workgroups of each phase (us after the workgroup's own start; the last four columns of a chain launch: round 1
-loads arrived / round 1 done / round 2 loads arrived / round 2 done; QT_CHAIN_ABLATE=1 / 2 / 3 times the launches without their GELU
-arithmetic / fake-quantizer stages / both).
+loads arrived / round 1 done / round 2 loads arrived / round 2 done).
 """
 import os
 import sys
