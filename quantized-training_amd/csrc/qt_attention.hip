@@ -57,8 +57,6 @@ struct AttnArgs {
                               // scale and is applied to the result on its way out (qt_attention_fq_out_bf16)
 };
 
-__device__ __forceinline__ float bf16_round(float f) { return qt_u2f(pack_bf16x2(f, 0.0f) << 16); }
-
 // UNIT: the probabilities' fake-quantizer has no scale tensor (scale == 1 exactly).  OBS: its amax is observed.
 template <int D, int KIND, bool UNIT, bool OBS>
 __global__ __launch_bounds__(256) void attention_fq_kernel(AttnArgs a) {
@@ -442,8 +440,7 @@ int launch_attn_kind(const AttnArgs &a, hipStream_t st) {
     else if (unit) attention_fq_kernel<D, KIND, true, false><<<grid, 256, 0, st>>>(a);
     else if (obs) attention_fq_kernel<D, KIND, false, true><<<grid, 256, 0, st>>>(a);
     else attention_fq_kernel<D, KIND, false, false><<<grid, 256, 0, st>>>(a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? QT_OK : (int)e;
+    return qt_launch_status();
 }
 
 template <int D>
@@ -471,11 +468,7 @@ static int attention_fq_launch(const uint16_t *q, const uint16_t *k, const uint1
     if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) & 15u) || ((uintptr_t)mask & 7u) ||
         (mask && ((mask_sb | mask_sh | mask_sq) & 3)))
         return QT_ERR_UNALIGNED;
-    int p8 = 0;
-    if (fmt->kind == QT_FMT_FP_SAT && !scale) {
-        if (fmt->p0 == 3 && fmt->p1 == -6 && fmt->fhi == 448.0f) p8 = 1;
-        else if (fmt->p0 == 2 && fmt->p1 == -14 && fmt->fhi == 57344.0f) p8 = 2;
-    }
+    const int p8 = scale ? 0 : qt_fp8_code(fmt);
     if (out_fq && (scale || fmt->kind == QT_FMT_IDENTITY)) return QT_ERR_BAD_ARG;      // unit scale, a real format
     // causal-style masks make late query blocks heavier: balance the slots when the grid is not a multiple that the mirrored order
     // already serves
@@ -483,8 +476,7 @@ static int attention_fq_launch(const uint16_t *q, const uint16_t *k, const uint1
 #ifdef QT_TUNING_BUILD
     if (const char *e = getenv("QT_ATTN_SNAKE")) snake_mode = atoi(e);     // tools/ only: 0 keeps the mirrored order
 #endif
-    int cus = 0, dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+    const int cus = qt_cu_count();
     const long total = (long)((Sq + kBQ - 1) / kBQ) * B * H;
     const int snake = (snake_mode && mask && total > cus && total % (2L * cus) != 0) ? cus : 0;
     if ((row_live != nullptr) != (irregular != nullptr) || (row_live && !mask)) return QT_ERR_BAD_ARG;

@@ -24,16 +24,14 @@
 
 #include "../../include/qt_hip.h"
 #include "qt_device.h"
+#include "qt_attention_split.h"
 #include "qt_value_codes.h"
 #include "qt_formats.h"
 
 namespace {
 
 typedef int v8i __attribute__((ext_vector_type(8)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kBlock = 128, kMaxBlocks = 8;                                    // one K / V^T block: 128 keys x 128 B = 16 KiB of codes
 constexpr int kUnit = 127;                                                        // E8M0 2^0
 
 struct AttnArgs {
@@ -52,12 +50,7 @@ struct AttnArgs {
     const int *mask_irregular;          // optional, device: 0 = qt_mask_row_live_checked found every row "zeros, then the minimum" (as mask_simple)
 };
 
-__device__ __forceinline__ float blo(uint32_t w) { return qt_u2f(w << 16); }
-__device__ __forceinline__ float bhi(uint32_t w) { return qt_u2f(w & 0xFFFF0000u); }
 __device__ __forceinline__ int chunk_off(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-__device__ __forceinline__ uint32_t lds_addr(const void *p) {
-    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)p;
-}
 // (LDS-DMA: dma16, qt_device.h; the ordinary loads -- mask, fragments -- keep counted waits, the DMA is waited for explicitly with
 // vmcnt(0) + barrier)
 
@@ -91,12 +84,6 @@ __device__ __forceinline__ uint32_t prob_codes(uint32_t p0, uint32_t p1) {
         o = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(o, __builtin_bit_cast(v2bf, p1), 1.0f, true);
     }
     return __builtin_bit_cast(uint32_t, o);
-}
-
-__device__ __forceinline__ float max3(float x, float y, float z) {
-    float d;
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(x), "v"(y), "v"(z));
-    return d;
 }
 
 // scores of the four tiles t0 .. t0 + 3 of one K block.  MODE 0: no mask arithmetic; 1: row-extent mask applied from my_live
@@ -134,13 +121,13 @@ __device__ __forceinline__ void score_half(const uint8_t *blk, int t0, const v8i
             continue;
         }
         uint32_t w0 = pack_bf16x2(s[j][0], s[j][1]), w1 = pack_bf16x2(s[j][2], s[j][3]);     // the matmul's bf16 output
-        w0 = pack_bf16x2(blo(w0) * scaling, bhi(w0) * scaling);
-        w1 = pack_bf16x2(blo(w1) * scaling, bhi(w1) * scaling);
+        w0 = pack_bf16x2(bf_lo(w0) * scaling, bf_hi(w0) * scaling);
+        w1 = pack_bf16x2(bf_lo(w1) * scaling, bf_hi(w1) * scaling);
         if (MODE == 2) {
-            w0 = pack_bf16x2(blo(w0) + blo(m[j].x), bhi(w0) + bhi(m[j].x));
-            w1 = pack_bf16x2(blo(w1) + blo(m[j].y), bhi(w1) + bhi(m[j].y));
+            w0 = pack_bf16x2(bf_lo(w0) + bf_lo(m[j].x), bf_hi(w0) + bf_hi(m[j].x));
+            w1 = pack_bf16x2(bf_lo(w1) + bf_lo(m[j].y), bf_hi(w1) + bf_hi(m[j].y));
         }
-        float v[4] = {blo(w0), bhi(w0), blo(w1), bhi(w1)};
+        float v[4] = {bf_lo(w0), bf_hi(w0), bf_lo(w1), bf_hi(w1)};
         if (MODE == 1) {
             // x + 0 = x; bf16(x + min) = min for every finite x (NaN stays NaN): the mask's effect without reading it
             const int left = my_live - (key0 + j * 16);                    // columns of this lane's four still inside its row's extent
@@ -168,26 +155,8 @@ __global__ __launch_bounds__(512, (MB == 4 && D == 64) ? 4 : 1) void attention_f
     const int qb = nqb - 1 - (int)blockIdx.y;                              // the heaviest blocks of rows of every head first under a causal mask
     const int q0 = qb * 64;
     const int qrow = q0 + wq * 16 + r, qc = min(qrow, a.Sq - 1);
-    // extents: nlive = key blocks holding an unmasked column of one of the 64 rows; wmax / wmin = the largest / smallest extent among
-    // this wave's 16 rows; my_live = this lane's row (0: a fully masked row, which attends to every key alike)
-    int nlive = nkb, wmax = a.Sk, wmin = a.Sk, my_live = a.Sk;
-    if (a.row_live) {
-        const int qq = min(q0 + l, a.Sq - 1);
-        int lv = a.row_live[b * a.lsb + h * a.lsh + qq * a.lsq];
-        my_live = a.row_live[b * a.lsb + h * a.lsh + qc * a.lsq];
-        if (lv <= 0) lv = a.Sk;
-        int hi = my_live <= 0 ? a.Sk : my_live, lo = max(my_live, 0);       // a fully masked row is walked to the end and masked from column 0
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) lv = max(lv, __shfl_xor(lv, off, 64));
-#pragma unroll
-        for (int off = 8; off >= 1; off >>= 1) {
-            hi = max(hi, __shfl_xor(hi, off, 64));
-            lo = min(lo, __shfl_xor(lo, off, 64));
-        }
-        nlive = __builtin_amdgcn_readfirstlane(min(nkb, (lv + kBlock - 1) / kBlock));
-        wmax = __builtin_amdgcn_readfirstlane(hi);
-        wmin = __builtin_amdgcn_readfirstlane(lo);
-    }
+    int nlive, wmax, wmin, my_live;                                        // the row extents: split_row_extents
+    split_row_extents(a, b, h, q0, qc, l, nkb, nlive, wmax, wmin, my_live);
     const int niter = (nlive + 1) / 2;                                     // iteration i: blocks 2 i and 2 i + 1
     const bool simple = a.mask && a.row_live && (a.mask_simple || (a.mask_irregular && *a.mask_irregular == 0)), full = a.mask && !simple;
     if (!simple) wmin = a.Sk;                                              // extents then only bound the walk; inside them the mask is read
@@ -361,20 +330,13 @@ __global__ __launch_bounds__(512, (MB == 4 && D == 64) ? 4 : 1) void attention_f
             }
         }
     }
-    // ---- the two partial sums meet in LDS: group 1 parks its accumulators ([64 rows][128 d] fp32), group 0 adds and stores
-    __syncthreads();
-    float *part = (float *)lds;
-    constexpr int kPartRow = D + 4;                                       // floats per row: the pad spreads the 16 rows of a store over the banks
+    // ---- the two partial sums meet in LDS: group 1 parks its accumulators, group 0 adds and stores
     const int prow = wq * 16 + r;
-    if (grp == 1) {
-#pragma unroll
-        for (int dt = 0; dt < kDT; ++dt) *(float4 *)(part + prow * kPartRow + dt * 16 + 4 * g) = float4{acc[dt][0], acc[dt][1], acc[dt][2], acc[dt][3]};
-    }
-    __syncthreads();
+    split_park_partials(lds, acc, grp, prow, g);
     if (grp == 0 && qrow < a.Sq) {
 #pragma unroll
         for (int dt = 0; dt < kDT; ++dt) {
-            const float4 o = *(const float4 *)(part + prow * kPartRow + dt * 16 + 4 * g);
+            const float4 o = split_partial_sums<kDT>(lds, prow, dt, g);
             acc[dt][0] += o.x; acc[dt][1] += o.y; acc[dt][2] += o.z; acc[dt][3] += o.w;
         }
         const long o0 = (((long)b * a.Sq + qrow) * a.H + h) * D + 4 * g;
@@ -407,17 +369,6 @@ __global__ __launch_bounds__(256) void value_codes_t_kernel(const uint16_t *v, u
     value_codes_block<E5M2, D>(tile, v, vt8, (int)blockIdx.x, (long)blockIdx.y, H, Sk, sb, sh, sk, fmt);
 }
 
-int status() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? QT_OK : (int)e;
-}
-
-bool fp8_closed_form(const qt_format *f, bool &e5m2) {
-    if (!f || f->kind != QT_FMT_FP_SAT) return false;
-    e5m2 = f->p0 == 2 && f->p1 == -14 && f->fhi == 57344.0f;
-    return e5m2 || (f->p0 == 3 && f->p1 == -6 && f->fhi == 448.0f);
-}
-
 template <int F, int D, int MB>
 int launch_split_mb(const AttnArgs &a, long BH, int nqb, hipStream_t st) {
     constexpr int kLds = MB * kBlock * D + 2 * 2 * 64 * 4;               // every block of a sweep + the row statistics
@@ -429,7 +380,7 @@ int launch_split_mb(const AttnArgs &a, long BH, int nqb, hipStream_t st) {
         configured.done();
     }
     attention_fp8_split_kernel<F, D, MB><<<dim3((unsigned)BH, (unsigned)nqb), 512, kLds, st>>>(a);
-    return status();
+    return qt_launch_status();
 }
 
 template <int F, int D>
@@ -447,10 +398,10 @@ extern "C" {
 int qt_value_codes_t(const uint16_t *v_dev, uint8_t *vt8_dev, long B, long H, long Sk, int head_dim, long stride_b, long stride_h, long stride_k,
                      const qt_format *fmt, void *stream) {
     if (B * H * Sk == 0) return QT_OK;
-    bool e5m2 = false;
-    if (!v_dev || !vt8_dev || B < 0 || H < 1 || Sk < 0 || Sk % kBlock != 0 || B * H > 65535 || (head_dim != 64 && head_dim != 128) ||
-        !fp8_closed_form(fmt, e5m2))
+    const int f8 = qt_fp8_code(fmt);
+    if (!v_dev || !vt8_dev || B < 0 || H < 1 || Sk < 0 || Sk % kBlock != 0 || B * H > 65535 || (head_dim != 64 && head_dim != 128) || !f8)
         return QT_ERR_BAD_ARG;
+    const bool e5m2 = f8 == 2;
     if ((((uintptr_t)v_dev | (uintptr_t)vt8_dev) & 15u) || ((stride_b | stride_h | stride_k) & 7)) return QT_ERR_UNALIGNED;
     const dim3 grid((unsigned)(Sk / kBlock), (unsigned)(B * H));
     hipStream_t st = (hipStream_t)stream;
@@ -461,7 +412,7 @@ int qt_value_codes_t(const uint16_t *v_dev, uint8_t *vt8_dev, long B, long H, lo
         if (e5m2) value_codes_t_kernel<true, 64><<<grid, 256, 0, st>>>(v_dev, vt8_dev, (int)H, Sk, stride_b, stride_h, stride_k, *fmt);
         else value_codes_t_kernel<false, 64><<<grid, 256, 0, st>>>(v_dev, vt8_dev, (int)H, Sk, stride_b, stride_h, stride_k, *fmt);
     }
-    return status();
+    return qt_launch_status();
 }
 
 int qt_attention_fp8(const uint8_t *q8_dev, const uint8_t *k8_dev, const uint8_t *vt8_dev, int operand_format, const uint16_t *mask_dev,
@@ -475,8 +426,7 @@ int qt_attention_fp8(const uint8_t *q8_dev, const uint8_t *k8_dev, const uint8_t
     if ((((uintptr_t)q8_dev | (uintptr_t)k8_dev | (uintptr_t)vt8_dev) & 15u) || ((uintptr_t)out_dev & 7u) ||
         (mask_dev && ((((uintptr_t)mask_dev) & 7u) || ((mask_sb | mask_sh | mask_sq) & 3))))
         return QT_ERR_UNALIGNED;
-    bool oe5 = false;
-    if (out8_dev && (!fp8_closed_form(out_format, oe5) || ((uintptr_t)out8_dev & 3u))) return QT_ERR_BAD_ARG;
+    if (out8_dev && (!qt_fp8_code(out_format) || ((uintptr_t)out8_dev & 3u))) return QT_ERR_BAD_ARG;
     AttnArgs a{q8_dev, k8_dev, vt8_dev, mask_dev, mask_sb, mask_sh, mask_sq, row_live_dev, live_sb, live_sh, live_sq, mask_is_simple ? 1 : 0,
                out_dev, H, Sq, Sk, scaling, out8_dev, out8_dev ? *out_format : qt_format{}, mask_irregular_dev};
     const int nqb = (Sq + 63) / 64;

@@ -29,16 +29,14 @@
 
 #include "../../include/qt_hip.h"
 #include "qt_device.h"
+#include "qt_attention_split.h"
 #include "qt_value_rows.h"
 
 namespace {
 
 typedef short v8s __attribute__((ext_vector_type(8)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef float float2_t __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kBlock = 128, kMaxBlocks = 8, kD = 128;
+constexpr int kD = 128;
 constexpr int kRowB = 256;                       // bytes of a K row (128 d) and of a V^T row segment (128 keys)
 constexpr int kBuf = kBlock * kRowB;             // one block: 32 KiB
 constexpr int kSlots = 3;                        // ring slots: the block being multiplied and two in flight
@@ -65,19 +63,8 @@ struct Args {
 #endif
 };
 
-__device__ __forceinline__ float blo(uint32_t w) { return qt_u2f(w << 16); }
-__device__ __forceinline__ float bhi(uint32_t w) { return qt_u2f(w & 0xFFFF0000u); }
 // byte offset of 16-byte chunk `chunk` of row `row` inside a block image
 __device__ __forceinline__ int chunk_off(int row, int chunk) { return row * kRowB + ((chunk ^ (row & 15)) << 4); }
-__device__ __forceinline__ uint32_t lds_addr(const void *p) {
-    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)p;
-}
-__device__ __forceinline__ float max3(float x, float y, float z) {
-    float d;
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(x), "v"(y), "v"(z));
-    return d;
-}
-
 // scores of the four tiles t0 .. t0 + 3 of one K block (this wave's half of it).  MODE 0: no mask arithmetic; 1: row-extent mask applied
 // from my_live (tiles from `tiles` on lie beyond every row of the wave); 2: additive mask read from mrow
 template <int MODE>
@@ -115,13 +102,13 @@ __device__ __forceinline__ void score_half(const uint8_t *blk, int t0, const v8s
             continue;
         }
         uint32_t w0 = pack_bf16x2(s[j][0], s[j][1]), w1 = pack_bf16x2(s[j][2], s[j][3]);     // the matmul's bf16 output
-        w0 = pack_bf16x2(blo(w0) * scaling, bhi(w0) * scaling);                             // attn_scaling (MulFunctional), bf16
-        w1 = pack_bf16x2(blo(w1) * scaling, bhi(w1) * scaling);
+        w0 = pack_bf16x2(bf_lo(w0) * scaling, bf_hi(w0) * scaling);                             // attn_scaling (MulFunctional), bf16
+        w1 = pack_bf16x2(bf_lo(w1) * scaling, bf_hi(w1) * scaling);
         if (MODE == 2) {
-            w0 = pack_bf16x2(blo(w0) + blo(m[j].x), bhi(w0) + bhi(m[j].x));                 // + mask, bf16
-            w1 = pack_bf16x2(blo(w1) + blo(m[j].y), bhi(w1) + bhi(m[j].y));
+            w0 = pack_bf16x2(bf_lo(w0) + bf_lo(m[j].x), bf_hi(w0) + bf_hi(m[j].x));                 // + mask, bf16
+            w1 = pack_bf16x2(bf_lo(w1) + bf_lo(m[j].y), bf_hi(w1) + bf_hi(m[j].y));
         }
-        float v[4] = {blo(w0), bhi(w0), blo(w1), bhi(w1)};
+        float v[4] = {bf_lo(w0), bf_hi(w0), bf_lo(w1), bf_hi(w1)};
         if (MODE == 1) {
             // x + 0 = x; bf16(x + min) = min for every finite x (NaN stays NaN): the mask's effect without reading it
             const int left = my_live - (key0 + j * 16);                    // columns of this lane's four still inside its row's extent
@@ -153,26 +140,8 @@ __global__ __launch_bounds__(512, 1) void attention_rows_split_kernel(Args a) {
         rnd.lds = (const uint16_t *)s_rows;
         rnd.glut = a.lut;
     }
-    // extents: nlive = key blocks holding an unmasked column of one of the 64 rows; wmax / wmin = the largest / smallest extent among
-    // this wave's 16 rows; my_live = this lane's row (0: a fully masked row, which attends to every key alike)
-    int nlive = nkb, wmax = a.Sk, wmin = a.Sk, my_live = a.Sk;
-    if (a.row_live) {
-        const int qq = min(q0 + l, a.Sq - 1);
-        int lv = a.row_live[b * a.lsb + h * a.lsh + qq * a.lsq];
-        my_live = a.row_live[b * a.lsb + h * a.lsh + qc * a.lsq];
-        if (lv <= 0) lv = a.Sk;
-        int hi = my_live <= 0 ? a.Sk : my_live, lo = max(my_live, 0);       // a fully masked row is walked to the end and masked from column 0
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) lv = max(lv, __shfl_xor(lv, off, 64));
-#pragma unroll
-        for (int off = 8; off >= 1; off >>= 1) {
-            hi = max(hi, __shfl_xor(hi, off, 64));
-            lo = min(lo, __shfl_xor(lo, off, 64));
-        }
-        nlive = __builtin_amdgcn_readfirstlane(min(nkb, (lv + kBlock - 1) / kBlock));
-        wmax = __builtin_amdgcn_readfirstlane(hi);
-        wmin = __builtin_amdgcn_readfirstlane(lo);
-    }
+    int nlive, wmax, wmin, my_live;                                        // the row extents: split_row_extents
+    split_row_extents(a, b, h, q0, qc, l, nkb, nlive, wmax, wmin, my_live);
     const int niter = (nlive + 1) / 2;                                     // iteration i: blocks 2 i and 2 i + 1
     const bool simple = a.mask && a.row_live && a.mask_irregular && *a.mask_irregular == 0, full = a.mask && !simple;
     if (!simple) wmin = a.Sk;                                              // extents then only bound the walk; inside them the mask is read
@@ -364,21 +333,14 @@ __global__ __launch_bounds__(512, 1) void attention_rows_split_kernel(Args a) {
         }
     }
     stamp(53);
-    // ---- the two partial sums meet in LDS: group 1 parks its accumulators ([64 rows][128 d] fp32), group 0 adds and stores
-    __syncthreads();
-    float *part = (float *)lds;
-    constexpr int kPartRow = kD + 4;                                       // floats per row: the pad spreads the 16 rows of a store over the banks
+    // ---- the two partial sums meet in LDS: group 1 parks its accumulators, group 0 adds and stores
     const int prow = wq * 16 + r;
-    if (grp == 1) {
-#pragma unroll
-        for (int dt = 0; dt < kDT; ++dt) *(float4 *)(part + prow * kPartRow + dt * 16 + 4 * g) = float4{acc[dt][0], acc[dt][1], acc[dt][2], acc[dt][3]};
-    }
-    __syncthreads();
+    split_park_partials(lds, acc, grp, prow, g);
     if (grp == 0 && qrow < a.Sq) {
         uint16_t *orow = a.out + (((long)b * a.Sq + qrow) * a.H + h) * kD + 4 * g;
 #pragma unroll
         for (int dt = 0; dt < kDT; ++dt) {
-            const float4 o = *(const float4 *)(part + prow * kPartRow + dt * 16 + 4 * g);
+            const float4 o = split_partial_sums<kDT>(lds, prow, dt, g);
             uint32_t o0 = pack_bf16x2(acc[dt][0] + o.x, acc[dt][1] + o.y), o1 = pack_bf16x2(acc[dt][2] + o.z, acc[dt][3] + o.w);
             if (a.out_fq) {                                                // the output projection's input fake-quantizer (same format, unit scale)
                 const uint32_t ow[2] = {o0, o1};
@@ -410,11 +372,6 @@ __global__ __launch_bounds__(256) void value_t_rows_kernel(const uint16_t *v, ui
     value_t_rows_block<kBlock>(tile, rnd, v, vt, H, Sk, sb, sh, sk, (long)blockIdx.y, (int)blockIdx.x, (int)threadIdx.x);
 }
 
-int status() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? QT_OK : (int)e;
-}
-
 bool rows_format(const qt_format *f) { return f && f->kind == QT_FMT_LUT && (f->p1 & 1); }
 
 }  // namespace
@@ -429,7 +386,7 @@ int qt_value_t_rows(const uint16_t *v_dev, uint16_t *vt_dev, long B, long H, lon
     if ((((uintptr_t)v_dev | (uintptr_t)vt_dev | (uintptr_t)lut_dev) & 15u) || ((stride_b | stride_h | stride_k) & 7)) return QT_ERR_UNALIGNED;
     value_t_rows_kernel<<<dim3((unsigned)(Sk / kBlock), (unsigned)(B * H)), 256, 0, (hipStream_t)stream>>>(v_dev, vt_dev, (int)H, Sk, stride_b, stride_h,
                                                                                                          stride_k, *fmt, lut_dev);
-    return status();
+    return qt_launch_status();
 }
 
 int qt_attention_rows_bf16(const uint16_t *q_dev, const uint16_t *k_dev, const uint16_t *vt_dev, const uint16_t *mask_dev, long mask_sb, long mask_sh,
@@ -459,7 +416,7 @@ int qt_attention_rows_bf16(const uint16_t *q_dev, const uint16_t *k_dev, const u
         configured.done();
     }
     attention_rows_split_kernel<<<dim3((unsigned)(B * H), (unsigned)((Sq + 63) / 64)), 512, kLds, (hipStream_t)stream>>>(a);
-    return status();
+    return qt_launch_status();
 }
 
 }  // extern "C"

@@ -660,11 +660,6 @@ __global__ __launch_bounds__(kThreads) void attn_train_bwd_kernel(AttnTrainBwdAr
     stamp(10);
 }
 
-inline int launch_rc() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? QT_OK : (int)e;
-}
-
 template <typename ARGS, typename F_ROWS, typename F_SAT, typename F_INT>
 int dispatch(const qt_format *fmt, const uint16_t *lut, F_ROWS rows, F_SAT sat, F_INT in) {
     switch (fmt->kind) {
@@ -676,7 +671,7 @@ int dispatch(const qt_format *fmt, const uint16_t *lut, F_ROWS rows, F_SAT sat, 
         case QT_FMT_INT: in(); break;
         default: return QT_ERR_BAD_DTYPE;
     }
-    return launch_rc();
+    return qt_launch_status();
 }
 
 bool shape_ok(long batch, int heads, int positions, int head_dim) {

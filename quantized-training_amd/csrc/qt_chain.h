@@ -34,12 +34,6 @@ __device__ __forceinline__ float fx_decode(long long fx, int E, const FxPlan &f)
     return fx >= (f.poison >> 1) ? qt_u2f(0x7FC00000u) : ldexpf((float)fx, E - f.shift);
 }
 
-#ifndef QT_BF_LO_HI
-#define QT_BF_LO_HI
-__device__ __forceinline__ float bf_lo(uint32_t w) { return qt_u2f(w << 16); }          // the two bf16 halves of a packed word
-__device__ __forceinline__ float bf_hi(uint32_t w) { return qt_u2f(w & 0xFFFF0000u); }
-#endif
-
 template <int IO, int KIND, int DIV, bool OBS>
 __device__ __forceinline__ uint4 fq_vec_d(uint4 v, const UniformDiv &dv, const Rounder<KIND> &rnd, uint32_t &amax, bool &bad) {
     if constexpr (IO == kIoBf16 && KIND == kFmtRows) {

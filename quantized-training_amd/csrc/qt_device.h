@@ -34,15 +34,49 @@ struct QtOncePerDevice {
 
 #include "qt_formats.h"
 
+// Status of the launch just made: QT_OK or the HIP error code.
+inline int qt_launch_status() {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? QT_OK : (int)e;
+}
+
+// Compute units of the current device, looked up once per process (256 if the query fails).
+inline int qt_cu_count() {
+    static int n = 0;
+    if (n == 0) {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n = v;
+        else n = 256;
+    }
+    return n;
+}
+
 namespace {
 
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 typedef float float2_t __attribute__((ext_vector_type(2)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));      // native vector: usable as a "+v" asm operand
 
 // two floats -> packed bf16x2 (RNE, NaN stays NaN): v_cvt_pk_bf16_f32
 __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
     float2_t v = {lo, hi};
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
+}
+
+// the two bf16 halves of a packed word, and a float rounded to bf16 (RNE) but kept as float
+__device__ __forceinline__ float bf_lo(uint32_t w) { return qt_u2f(w << 16); }
+__device__ __forceinline__ float bf_hi(uint32_t w) { return qt_u2f(w & 0xFFFF0000u); }
+__device__ __forceinline__ float bf16_round(float f) { return qt_u2f(pack_bf16x2(f, 0.0f) << 16); }
+
+__device__ __forceinline__ float max3(float x, float y, float z) {
+    float d;
+    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(x), "v"(y), "v"(z));
+    return d;
+}
+
+// LDS byte address of a pointer into __shared__ memory
+__device__ __forceinline__ uint32_t lds_addr(const void *p) {
+    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)p;
 }
 
 // four on-grid values -> four OCP FP8 bytes (exact for values the format holds)
@@ -322,6 +356,44 @@ __device__ __forceinline__ void dma16(const void *src, uint32_t dst) {
 // Wave-uniform base (SGPR pair) + 32-bit lane offset:
 __device__ __forceinline__ void dma16(const void *base, uint32_t off, uint32_t dst) {
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 1\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(off), "s"(base), "s"(dst) : "memory");
+}
+
+template <int OFF>
+__device__ __forceinline__ u32x4 ds_read128(uint32_t addr) {
+    u32x4 v;
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
+    return v;
+}
+
+// ---- the column segments of the fused GEMMs (qt_linear_fq8.hip, qt_linear_fqt.hip): up to four weights that share one activation
+// are the segments of one launch, their 16-column groups concatenated.  A is the kernel's Args (fields seg[4], nseg, gbase, gextra,
+// tiles_n).
+struct Segment {
+    const uint16_t *w;        // [n][K] bf16
+    const uint16_t *bias;     // [n] bf16 or NULL
+    int g0;                   // first 16-column group of this weight in the concatenation of all weights
+};
+
+// The weight holding column group `grp`, by compile-time indices only: a run-time index into the kernel-argument struct makes
+// hipcc copy the whole struct to scratch memory and read its fields from there.
+struct SegRef { const uint16_t *w, *bias; int g0; };
+template <class A>
+__device__ __forceinline__ SegRef seg_lookup(const A &a, int grp) {
+    SegRef r{a.seg[0].w, a.seg[0].bias, a.seg[0].g0};
+    if (a.nseg > 1 && grp >= a.seg[1].g0) r = SegRef{a.seg[1].w, a.seg[1].bias, a.seg[1].g0};
+    if (a.nseg > 2 && grp >= a.seg[2].g0) r = SegRef{a.seg[2].w, a.seg[2].bias, a.seg[2].g0};
+    if (a.nseg > 3 && grp >= a.seg[3].g0) r = SegRef{a.seg[3].w, a.seg[3].bias, a.seg[3].g0};
+    return r;
+}
+
+// Column tile tn of tiles_n: first unit (16-column group, or gate / up pair) and unit count.  The gextra tiles that are one unit wider
+// are spread evenly over the tile index (tile tn starts at floor(tn * units / tiles_n)): with all of them in front, the XCDs that own
+// the first tiles (tile ids are contiguous per XCD) carry up to a fifth more work than the others and the launch waits for them.
+template <class A>
+__device__ __forceinline__ void tile_span(const A &a, int tn, int &first, int &count) {
+    const long units = (long)a.gbase * a.tiles_n + a.gextra;
+    first = (int)(tn * units / a.tiles_n);
+    count = (int)((tn + 1) * units / a.tiles_n) - first;
 }
 
 }  // namespace

@@ -1472,11 +1472,6 @@ int num_cus() {
     return cus;
 }
 
-inline int launch_status() {
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? QT_OK : (int)e;
-}
-
 inline unsigned grid_for(size_t work_items, size_t per_block, int blocks_per_cu) {
     size_t want = (work_items + per_block - 1) / per_block;
     size_t cap = (size_t)num_cus() * blocks_per_cu;
@@ -1502,7 +1497,7 @@ int launch_variant(const void *x, void *y, size_t n, const qt_format &fmt, const
         fq_kernel<IO, KIND, true, BLOCK, UNR, NT><<<grid, BLOCK, 0, st>>>(x, y, nvec, n, fmt, lut, scale, amax);
     else
         fq_kernel<IO, KIND, false, BLOCK, UNR, NT><<<grid, BLOCK, 0, st>>>(x, y, nvec, n, fmt, lut, scale, amax);
-    return launch_status();
+    return qt_launch_status();
 }
 
 template <int IO, int KIND>
@@ -1524,21 +1519,21 @@ int launch_fq_kind(const void *x, void *y, size_t n, const qt_format &fmt, const
             if (IO == kIoBf16 && nv <= kRowsDirectMaxVecs) {           // short pass: the table where it lies (fq_rows_direct_kernel)
                 if (amax) fq_rows_direct_kernel<IO, true, 1024><<<grid_for(nv, 1024, 2), 1024, 0, st>>>(x, y, nv, n, fmt, lut, scale, amax);
                 else fq_rows_direct_kernel<IO, false, 256><<<grid_for(nv, 256, 8), 256, 0, st>>>(x, y, nv, n, fmt, lut, scale, amax);
-                return launch_status();
+                return qt_launch_status();
             }
             unsigned grid = grid_for(nv, (size_t)kAluBlock * kUnroll, row_blocks ? row_blocks : 8);
             if (amax)
                 fq_kernel<IO, kFmtRows, true, kAluBlock><<<grid, kAluBlock, 0, st>>>(x, y, nv, n, fmt, lut, scale, amax);
             else
                 fq_kernel<IO, kFmtRows, false, kAluBlock><<<grid, kAluBlock, 0, st>>>(x, y, nv, n, fmt, lut, scale, amax);
-            return launch_status();
+            return qt_launch_status();
         }
         if (aligned && y != nullptr && n >= 4096 && n < kLutLdsMinElems) {
             const size_t nv = n / kPer;
             unsigned grid = grid_for(nv, 256, 8);
             if (amax) fq_gather_vec_kernel<IO, true><<<grid, 256, 0, st>>>(x, y, nv, n, fmt, lut, scale, amax);
             else fq_gather_vec_kernel<IO, false><<<grid, 256, 0, st>>>(x, y, nv, n, fmt, lut, scale, amax);
-            return launch_status();
+            return qt_launch_status();
         }
     }
     if (gather) {
@@ -1548,7 +1543,7 @@ int launch_fq_kind(const void *x, void *y, size_t n, const qt_format &fmt, const
             fq_gather_kernel<IO, KIND, true><<<grid, 256, 0, st>>>(x, y, n, fmt, lut, scale, amax);
         else
             fq_gather_kernel<IO, KIND, false><<<grid, 256, 0, st>>>(x, y, n, fmt, lut, scale, amax);
-        return launch_status();
+        return qt_launch_status();
     }
     const size_t nvec = n / kPer;
     if constexpr (KIND == QT_FMT_LUT) {
@@ -1590,7 +1585,7 @@ int launch_fq_kind(const void *x, void *y, size_t n, const qt_format &fmt, const
         else
             fq_kernel<IO, KIND, false, kAluBlock><<<grid, kAluBlock, 0, st>>>(x, y, nvec, n, fmt, lut, scale, amax);
     }
-    return launch_status();
+    return qt_launch_status();
 }
 
 template <int IO>
@@ -1629,14 +1624,14 @@ int launch_pc_kind(const void *x, void *y, size_t outer, size_t C, size_t inner,
                 if ((fmt.p1 & 1) && y) {
                 unsigned grid = grid_for(outer * C, 1, 16);
                 fq_pc_vec_kernel<IO, kFmtRows><<<grid, 256, 0, st>>>((const uint4 *)x, (uint4 *)y, outer * C, C, inner / kPer, fmt, lut, scale, amax);
-                return launch_status();
+                return qt_launch_status();
             }
             if (y && outer * C * inner >= kLutLdsMinElems) {          // the 128 KiB table in LDS, a wave per row (3.0 -> 3.8 TB/s)
                 const size_t rows = outer * C;
                 unsigned grid = grid_for(rows, 16, 1);
                 fq_pc_vec_lds_kernel<IO, QT_FMT_LUT><<<grid, 1024, 0, st>>>((const uint4 *)x, (uint4 *)y, rows, C, inner / kPer, fmt,
                                                                           lut, scale, amax);
-                return launch_status();
+                return qt_launch_status();
             }
         }
         unsigned grid = grid_for(outer * C, 1, 16);
@@ -1646,7 +1641,7 @@ int launch_pc_kind(const void *x, void *y, size_t outer, size_t C, size_t inner,
         unsigned grid = grid_for(outer * C, 1, 16);
         fq_pc_kernel<IO, KIND><<<grid, 256, 0, st>>>(x, y, outer, C, inner, fmt, lut, scale, amax);
     }
-    return launch_status();
+    return qt_launch_status();
 }
 
 template <int IO>
@@ -1673,7 +1668,7 @@ int launch_qdq(const void *x, void *y, size_t n, const QdqArgs &a, const void *s
     if (!x || !y || !scale) return QT_ERR_BAD_ARG;
     unsigned grid = grid_for(n, 256 * 4, 8);
     qdq_kernel<IO><<<grid, 256, 0, (hipStream_t)stream>>>(x, y, n, a, scale, zp);
-    return launch_status();
+    return qt_launch_status();
 }
 
 
@@ -1698,7 +1693,7 @@ int launch_mx(const void *x, void *y, void *sf, size_t rows, size_t cols, int bs
         case QT_FMT_IDENTITY: fq_mx_kernel<IO, QT_FMT_IDENTITY><<<grid, 256, 0, st>>>(xv, yv, sf, nvec, group, *fmt, lut, quant_max, scale_lut); break;
         default: return QT_ERR_BAD_ARG;
     }
-    return launch_status();
+    return qt_launch_status();
 }
 
 }  // namespace
@@ -1716,7 +1711,7 @@ int qt_scale_update(float *history_dev, int L, int C, float *scale_dev, float qu
     if (!history_dev || !scale_dev || L < 1 || C < 1) return QT_ERR_BAD_ARG;
     unsigned grid = (unsigned)((C + 127) / 128);
     scale_update_kernel<<<grid, 128, 0, (hipStream_t)stream>>>(history_dev, L, C, scale_dev, quant_max, force_pow2);
-    return launch_status();
+    return qt_launch_status();
 }
 
 int qt_scale_update_multi(float *const *history_ptrs_dev, const int *L_dev, const int *C_dev, float *const *scale_ptrs_dev,
@@ -1725,7 +1720,7 @@ int qt_scale_update_multi(float *const *history_ptrs_dev, const int *L_dev, cons
     if (!history_ptrs_dev || !L_dev || !C_dev || !scale_ptrs_dev || !quant_max_dev || !force_pow2_dev || count < 0) return QT_ERR_BAD_ARG;
     scale_update_multi_kernel<<<(unsigned)count, 128, 0, (hipStream_t)stream>>>(history_ptrs_dev, L_dev, C_dev, scale_ptrs_dev,
                                                                                quant_max_dev, force_pow2_dev);
-    return launch_status();
+    return qt_launch_status();
 }
 
 int qt_fake_quant_bf16(const uint16_t *x, uint16_t *y, size_t n, const qt_format *fmt, const uint16_t *lut,
@@ -1748,10 +1743,9 @@ int qt_fake_quant_pc_f32(const float *x, float *y, size_t outer, size_t C, size_
 int qt_fake_quant_bf16_fp8(const uint16_t *x, uint16_t *y, uint8_t *y8, size_t n, const qt_format *fmt,
                            const float *scale, uint32_t *amax, void *stream) {
     if (n == 0) return QT_OK;
-    if (!x || !y8 || !fmt || fmt->kind != QT_FMT_FP_SAT) return QT_ERR_BAD_ARG;
-    const bool e5m2 = fmt->p0 == 2 && fmt->p1 == -14 && fmt->fhi == 57344.0f;
-    const bool e4m3 = fmt->p0 == 3 && fmt->p1 == -6 && fmt->fhi == 448.0f;
-    if (!e5m2 && !e4m3) return QT_ERR_BAD_ARG;
+    const int f8 = qt_fp8_code(fmt);
+    if (!x || !y8 || !f8) return QT_ERR_BAD_ARG;
+    const bool e5m2 = f8 == 2;
     if ((n & 15) || (((uintptr_t)x | (uintptr_t)y | (uintptr_t)y8) & 15u)) return QT_ERR_UNALIGNED;
     const size_t nvec = n / 16;
     const unsigned grid = grid_for(nvec, 256, g_blocks_per_cu);
@@ -1769,7 +1763,7 @@ int qt_fake_quant_bf16_fp8(const uint16_t *x, uint16_t *y, uint8_t *y8, size_t n
         else      { if (y) QT_FQ8(false, true, false); else QT_FQ8(false, false, false); }
     }
 #undef QT_FQ8
-    return launch_status();
+    return qt_launch_status();
 }
 
 // strips x bands of one chain launch: about one workgroup per CU, bands of whole 64-row groups, at most 32 bands
@@ -1849,7 +1843,7 @@ static int chain_launch(const uint16_t *x_dev, const uint16_t *x2_dev, int pre_o
     }
 #undef QT_CHAIN_NS
 #undef QT_CHAIN
-    return launch_status();
+    return qt_launch_status();
 }
 
 int qt_fake_quant_chain_bf16(const uint16_t *x_dev, long rows, long cols, const qt_chain_stage *stages, int nstage, const qt_format *fmt,
@@ -1928,7 +1922,7 @@ int qt_layernorm_train_bf16(const uint16_t *x_dev, const uint16_t *weight_dev, c
     hipStream_t st = (hipStream_t)stream;
     auto grid = [&](int block) { return (rows + block / 64 - 1) / (block / 64); };
     QT_LN_DISPATCH(ln_train_fwd_kernel, a, grid)
-    return launch_status();
+    return qt_launch_status();
 }
 
 // workgroups of the backward launch (512 threads = 8 waves, one row per wave): its partial sums are part_dev[that many][3][cols] fp32
@@ -1966,10 +1960,10 @@ int qt_layernorm_train_backward_bf16(const uint16_t *grad_out_dev, const uint16_
     a.dbg = ew_stamp_region();
 #endif
     QT_LN_DISPATCH(ln_train_bwd_kernel, a, grid)
-    if (const int rc = launch_status()) return rc;
+    if (const int rc = qt_launch_status()) return rc;
     ln_train_reduce_kernel<<<dim3((unsigned)((cols + 63) / 64), colsum_stage >= 0 ? 3u : 2u), 256, 0, st>>>(part_dev, (int)groups, (int)cols, grad_weight_dev,
                                                                                                       grad_bias_dev, colsum_out_dev);
-    return launch_status();
+    return qt_launch_status();
 }
 
 size_t qt_fake_quant_chain_ws_bytes(long rows, long cols) {
@@ -2006,15 +2000,14 @@ int qt_fake_quant_rows_bf16(const uint16_t *x, uint16_t *y, long d0, long d1, lo
         default: return QT_ERR_BAD_ARG;
     }
 #undef QT_ROWS
-    return launch_status();
+    return qt_launch_status();
 }
 
 int qt_fake_quant_bf16_fp8_multi(const uint16_t *const *xs, const size_t *ns, int count, uint8_t *y8, const qt_format *fmt,
                                  void *stream) {
-    if (!xs || !ns || !y8 || !fmt || count < 1 || count > 4 || fmt->kind != QT_FMT_FP_SAT) return QT_ERR_BAD_ARG;
-    const bool e5m2 = fmt->p0 == 2 && fmt->p1 == -14 && fmt->fhi == 57344.0f;
-    const bool e4m3 = fmt->p0 == 3 && fmt->p1 == -6 && fmt->fhi == 448.0f;
-    if (!e5m2 && !e4m3) return QT_ERR_BAD_ARG;
+    const int f8 = qt_fp8_code(fmt);
+    if (!xs || !ns || !y8 || !f8 || count < 1 || count > 4) return QT_ERR_BAD_ARG;
+    const bool e5m2 = f8 == 2;
     MultiArgs a{};
     size_t run = 0;
     for (int i = 0; i < 4; ++i) {
@@ -2034,22 +2027,21 @@ int qt_fake_quant_bf16_fp8_multi(const uint16_t *const *xs, const size_t *ns, in
     hipStream_t st = (hipStream_t)stream;
     if (e5m2) fq8_multi_kernel<true><<<grid, 256, 0, st>>>(a, (uint4 *)y8, *fmt);
     else fq8_multi_kernel<false><<<grid, 256, 0, st>>>(a, (uint4 *)y8, *fmt);
-    return launch_status();
+    return qt_launch_status();
 }
 
 int qt_fake_quant_multi_bf16_fp8(const qt_fq8_item *items_dev, int count, unsigned long long total_tiles, const qt_format *fmt, void *stream) {
     if (count == 0 || total_tiles == 0) return QT_OK;
-    if (!items_dev || !fmt || count < 0 || total_tiles > 0x7FFFFFFFull || fmt->kind != QT_FMT_FP_SAT) return QT_ERR_BAD_ARG;
-    const bool e5m2 = fmt->p0 == 2 && fmt->p1 == -14 && fmt->fhi == 57344.0f;
-    const bool e4m3 = fmt->p0 == 3 && fmt->p1 == -6 && fmt->fhi == 448.0f;
-    if (!e5m2 && !e4m3) return QT_ERR_BAD_ARG;
+    const int f8 = qt_fp8_code(fmt);
+    if (!items_dev || !f8 || count < 0 || total_tiles > 0x7FFFFFFFull) return QT_ERR_BAD_ARG;
+    const bool e5m2 = f8 == 2;
     if ((uintptr_t)items_dev & 7u) return QT_ERR_UNALIGNED;
     static_assert(sizeof(qt_fq8_item) == sizeof(qt_fq8_item_dev), "layout of qt_fq8_item");
     const qt_fq8_item_dev *it = (const qt_fq8_item_dev *)items_dev;
     hipStream_t st = (hipStream_t)stream;
     if (e5m2) fq8_items_kernel<true><<<(unsigned)total_tiles, 256, 0, st>>>(it, count, *fmt);
     else fq8_items_kernel<false><<<(unsigned)total_tiles, 256, 0, st>>>(it, count, *fmt);
-    return launch_status();
+    return qt_launch_status();
 }
 
 int qt_fake_quant_multi_bf16(const qt_fq_item *items_dev, int count, unsigned long long total_tiles, const qt_format *fmt,
@@ -2070,23 +2062,22 @@ int qt_fake_quant_multi_bf16(const qt_fq_item *items_dev, int count, unsigned lo
         case QT_FMT_INT: fq_multi_kernel<QT_FMT_INT><<<grid, kMultiBlock, 0, st>>>(it, count, *fmt, lut_dev); break;
         default: return QT_ERR_BAD_ARG;
     }
-    return launch_status();
+    return qt_launch_status();
 }
 
 int qt_fake_quant_rows_bf16_fp8(const uint16_t *x, uint16_t *y, uint8_t *y8, long d0, long d1, long d2, long inner, long s0,
                                 long s1, long s2, const qt_format *fmt, void *stream) {
     if (d0 * d1 * d2 * inner == 0) return QT_OK;
-    if (!x || !y8 || !fmt || d0 < 0 || d1 < 0 || d2 < 0 || inner < 0 || fmt->kind != QT_FMT_FP_SAT) return QT_ERR_BAD_ARG;
-    const bool e5m2 = fmt->p0 == 2 && fmt->p1 == -14 && fmt->fhi == 57344.0f;
-    const bool e4m3 = fmt->p0 == 3 && fmt->p1 == -6 && fmt->fhi == 448.0f;
-    if (!e5m2 && !e4m3) return QT_ERR_BAD_ARG;
+    const int f8 = qt_fp8_code(fmt);
+    if (!x || !y8 || !f8 || d0 < 0 || d1 < 0 || d2 < 0 || inner < 0) return QT_ERR_BAD_ARG;
+    const bool e5m2 = f8 == 2;
     if ((inner & 7) || ((s0 | s1 | s2) & 7) || (((uintptr_t)x | (uintptr_t)y) & 15u) || ((uintptr_t)y8 & 7u)) return QT_ERR_UNALIGNED;
     RowsArgs a{x, y, d1, d2, inner / 8, s0, s1, s2, (size_t)(d0 * d1 * d2 * (inner / 8))};          // y may be NULL: FP8 codes only
     const unsigned grid = grid_for(a.nvec, 256, 32);
     hipStream_t st = (hipStream_t)stream;
     if (e5m2) fq_rows_kernel<QT_FMT_FP_SAT, false, 2><<<grid, 256, 0, st>>>(a, *fmt, nullptr, nullptr, nullptr, (uint2 *)y8);
     else fq_rows_kernel<QT_FMT_FP_SAT, false, 1><<<grid, 256, 0, st>>>(a, *fmt, nullptr, nullptr, nullptr, (uint2 *)y8);
-    return launch_status();
+    return qt_launch_status();
 }
 
 int qt_fake_quant_mx_bf16(const uint16_t *x, uint16_t *y, uint16_t *sf, size_t rows, size_t cols, int block_size,
@@ -2115,7 +2106,7 @@ int qt_vmap_f16(const uint16_t *x, uint16_t *y, size_t n, const qt_format *fmt, 
     unsigned grid = grid_for(n, 256 * 4, 8);
     vmap_f16_kernel<<<grid, 256, 0, (hipStream_t)stream>>>((const _Float16 *)x, (_Float16 *)y, n, *fmt,
                                                           fmt->kind == QT_FMT_LUT ? lut : nullptr);
-    return launch_status();
+    return qt_launch_status();
 }
 
 int qt_quantize_bf16(const uint16_t *x, uint16_t *y, size_t n, const qt_format *fmt, const uint16_t *lut,
@@ -2146,14 +2137,14 @@ int qt_round_fp8_f32(const float *x, float *y, size_t n, int mbits, float fp8_ma
     if (!x || !y || mbits < 1 || mbits > 22 || !(fp8_min > 0.0f)) return QT_ERR_BAD_ARG;
     unsigned grid = grid_for(n, 256 * 4, 8);
     round_fp8_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(x, y, n, mbits, qt_internal_fp8_emin(fp8_min), fp8_max);
-    return launch_status();
+    return qt_launch_status();
 }
 int qt_round_posit_f32(const float *x, float *y, size_t n, int nbits, int es, void *stream) {
     if (n == 0) return QT_OK;
     if (!x || !y || nbits < 3 || nbits > 24 || es < 0 || es > 4 || ((nbits - 2) << es) > 126) return QT_ERR_BAD_ARG;
     unsigned grid = grid_for(n, 256 * 4, 8);
     round_posit_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(x, y, n, nbits, es, qt_internal_posit_threshold(nbits, es));
-    return launch_status();
+    return qt_launch_status();
 }
 
 int qt_posit_quantize_f32(const float *x, float *y, int32_t *pbits, size_t n, int nbits, int es, int round_to_even, void *stream) {
@@ -2162,7 +2153,7 @@ int qt_posit_quantize_f32(const float *x, float *y, int32_t *pbits, size_t n, in
     unsigned grid = grid_for(n, 256 * 4, 8);
     posit_bits_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(x, y, pbits, n, nbits, es,
                                                           round_to_even ? qt_internal_posit_threshold(nbits, es) : 0.0f);
-    return launch_status();
+    return qt_launch_status();
 }
 
 int qt_bench_fake_quant_bf16(const uint16_t *x, uint16_t *y, size_t n, const qt_format *fmt, const uint16_t *lut,

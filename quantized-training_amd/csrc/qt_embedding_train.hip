@@ -125,6 +125,5 @@ extern "C" int qt_embedding_backward_bf16(const uint16_t *grad_dev, const long *
     const dim3 g1((unsigned)((n + kChunk - 1) / kChunk), (unsigned)((nvec + kEmbBlock - 1) / kEmbBlock));
     embed_partials_kernel<<<g1, kEmbBlock, 0, st>>>((const uint4 *)grad_dev, ids_dev, n, nvec, padding_idx, (uint4 *)partials_dev);
     embed_fold_kernel<<<(unsigned)n, kEmbBlock, 0, st>>>((const uint4 *)partials_dev, ids_dev, n, nvec, padding_idx, (uint4 *)grad_weight_dev);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? QT_OK : (int)e;
+    return qt_launch_status();
 }

@@ -59,6 +59,15 @@ QT_HD uint32_t qt_fp_sat_u32(uint32_t u, int mbits, int emin, float fmax) {
     return a >= 0x7F800000u ? QT_NAN32 : ru;                       // fp8.py:36: non-finite -> NaN
 }
 
+// Host: is `f` exactly OCP E4M3 (1) or E5M2 (2) in the closed form above, which the kernels may convert with the hardware?  0 for
+// anything else, NULL included.
+inline int qt_fp8_code(const qt_format *f) {
+    if (!f || f->kind != QT_FMT_FP_SAT) return 0;
+    if (f->p0 == 3 && f->p1 == -6 && f->fhi == 448.0f) return 1;
+    if (f->p0 == 2 && f->p1 == -14 && f->fhi == 57344.0f) return 2;
+    return 0;
+}
+
 // ---- intN / uintN: clamp(round_half_even(v), lo, hi) on the bf16 value (fake_quantize.py:43-52)
 // torch.clamp is min(max(v, lo), hi) with std::max/min operand order: -0.0 and NaN pass through.
 QT_HD uint32_t qt_int_img(uint32_t u, float lo, float hi) {

@@ -397,8 +397,7 @@ int launch_one(const GemmArgs &g, int batches, hipStream_t st) {
     }
     dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, batches);
     gemm_fq_kernel<BMODE, OBS_B, B_NN><<<grid, kThreads, kLdsBytes, st>>>(g);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? QT_OK : (int)e;
+    return qt_launch_status();
 }
 
 template <int BMODE, bool OBS_B>

@@ -45,7 +45,6 @@ namespace {
 
 typedef int v8i __attribute__((ext_vector_type(8)));
 typedef float v4f __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));      // native vector: usable as a "+v" asm operand
 typedef short v2s __attribute__((ext_vector_type(2)));
 typedef __bf16 v2bf __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) void lds_void;
@@ -54,12 +53,6 @@ typedef const __attribute__((address_space(1))) void glb_void;
 constexpr int kTM = 256, kBK = 128, kMaxSeg = 4, kMaxNT = 12;
 constexpr int kABytes = kTM * kBK;                  // one activation tile: 32 KiB of FP8 codes
 constexpr int kUnitE8M0 = 127;                      // 2^0
-
-struct Segment {
-    const uint16_t *w;        // [n][K] bf16
-    const uint16_t *bias;     // [n] bf16 or NULL
-    int g0;                   // first 16-column group of this weight in the concatenation of all weights
-};
 
 struct Args {
     const uint8_t *x8;        // [M][K] FP8 codes
@@ -79,38 +72,6 @@ struct Args {
     unsigned long long *stamps;   // tools/ only (QT_FQ8_STAMPS = device address): per workgroup {cycles, 100 MHz ticks} around the tile
 #endif
 };
-
-// Column tile tn of tiles_n: first unit (16-column group, or gate / up pair) and unit count.  The gextra tiles that are one unit wider
-// are spread evenly over the tile index (tile tn starts at floor(tn * units / tiles_n)): with all of them in front, the XCDs that own
-// the first tiles (tile ids are contiguous per XCD) carry up to a fifth more work than the others and the launch waits for them.
-__device__ __forceinline__ void tile_span(const Args &a, int tn, int &first, int &count);
-
-// The weight holding column group `grp`, by compile-time indices only: a run-time index into the kernel-argument struct makes
-// hipcc copy the whole struct to scratch memory and read its fields from there.
-struct SegRef { const uint16_t *w, *bias; int g0; };
-__device__ __forceinline__ SegRef seg_lookup(const Args &a, int grp) {
-    SegRef r{a.seg[0].w, a.seg[0].bias, a.seg[0].g0};
-    if (a.nseg > 1 && grp >= a.seg[1].g0) r = SegRef{a.seg[1].w, a.seg[1].bias, a.seg[1].g0};
-    if (a.nseg > 2 && grp >= a.seg[2].g0) r = SegRef{a.seg[2].w, a.seg[2].bias, a.seg[2].g0};
-    if (a.nseg > 3 && grp >= a.seg[3].g0) r = SegRef{a.seg[3].w, a.seg[3].bias, a.seg[3].g0};
-    return r;
-}
-
-__device__ __forceinline__ void tile_span(const Args &a, int tn, int &first, int &count) {
-    const long units = (long)a.gbase * a.tiles_n + a.gextra;
-    first = (int)(tn * units / a.tiles_n);
-    count = (int)((tn + 1) * units / a.tiles_n) - first;
-}
-
-__device__ __forceinline__ uint32_t lds_addr(const void *p) {
-    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)p;
-}
-template <int OFF>
-__device__ __forceinline__ u32x4 ds_read128(uint32_t addr) {
-    u32x4 v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-    return v;
-}
 
 // activation tile: row-major 128-byte rows, chunk index XOR ((row >> 1) & 7)
 __device__ __forceinline__ int a_chunk_off(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
@@ -165,15 +126,14 @@ __device__ __forceinline__ uint32_t exact_bf16x4(uint32_t p0, uint32_t p1) {
 // multiplications behind it); past the last k tile the last one is requested again.
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ float bf_round(float f) { return qt_u2f(pack_bf16x2(f, 0.0f) << 16); }      // round to bf16, keep as float
 // silu(g) * u on four (gate, up) pairs, with the roundings of the module chain (LlamaMLP: bf16 GEMM outputs, SiLU in fp32 rounded
 // to bf16, product rounded to bf16 -- the arithmetic of silu_mul_kernel, csrc/qt_model_ops.hip): two packed bf16 words
 __device__ __forceinline__ void silu_mul4(const float (&gt)[4], const float (&up)[4], uint32_t &w0, uint32_t &w1) {
     float p[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        const float g = bf_round(gt[e]), u = bf_round(up[e]);
-        p[e] = bf_round(g / (1.0f + expf(-g))) * u;
+        const float g = bf16_round(gt[e]), u = bf16_round(up[e]);
+        p[e] = bf16_round(g / (1.0f + expf(-g))) * u;
     }
     w0 = pack_bf16x2(p[0], p[1]);
     w1 = pack_bf16x2(p[2], p[3]);
@@ -950,16 +910,6 @@ __global__ __launch_bounds__(512, 1) void linear_fq8r_kernel(Args a) {
     QT_FQ8_STAMP_END
 }
 
-int cu_count() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n = v;
-        else n = 256;
-    }
-    return n;
-}
-
 template <int FX, int FW, int NB, bool PAIR = false>
 int launch_r_nb(const Args &a, hipStream_t st) {
     constexpr int kLds = LinearFq8R<FX, FW, NB, PAIR>::kLds;
@@ -970,8 +920,7 @@ int launch_r_nb(const Args &a, hipStream_t st) {
         configured.done();
     }
     linear_fq8r_kernel<FX, FW, NB, PAIR><<<a.tiles_m * a.tiles_n, 512, kLds, st>>>(a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? QT_OK : (int)e;
+    return qt_launch_status();
 }
 
 template <int FX, int FW>
@@ -984,8 +933,7 @@ int launch_r2(const Args &a, hipStream_t st) {
         configured.done();
     }
     linear_fq8r2_kernel<FX, FW><<<a.tiles_m * a.tiles_n, 512, kLds, st>>>(a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? QT_OK : (int)e;
+    return qt_launch_status();
 }
 
 template <int FX, int FW>
@@ -1022,7 +970,7 @@ int plan_fq8(int M, long groups, Fq8Plan &p) {
         if (max_nt < 1 || max_nt > kMaxNT) max_nt = kMaxNT;
     }
 #endif
-    const int cus = cu_count();
+    const int cus = qt_cu_count();
     p.tiles_m = (M + kTM - 1) / kTM;
     const long tn_min = (groups + max_nt - 1) / max_nt;
     const long rounds = (p.tiles_m * tn_min + cus - 1) / cus;
@@ -1042,7 +990,7 @@ int plan_fq8(int M, long groups, Fq8Plan &p) {
 // pair mode (qt_mlp_fq8_bf16): column tiles in gate / up pairs, at most six pairs (twelve column groups) each, whole rounds over the
 // CUs; gbase / gextra count PAIRS
 int plan_mlp(int M, long pairs, Fq8Plan &p) {
-    const int cus = cu_count();
+    const int cus = qt_cu_count();
     p.tiles_m = (M + kTM - 1) / kTM;
     const long tn_min = (pairs + 5) / 6;
     const long rounds = (p.tiles_m * tn_min + cus - 1) / cus;

@@ -41,17 +41,10 @@ namespace {
 
 typedef short v8s __attribute__((ext_vector_type(8)));
 typedef float v4f __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kBK = 32, kRowBytes = 64, kMaxSeg = 4;
 constexpr int kGroupBytes = 16 * kRowBytes;         // one 16-row group of a tile = one DMA piece: 1 KiB
-
-struct Segment {
-    const uint16_t *w;        // [n][K] bf16
-    const uint16_t *bias;     // [n] bf16 or NULL
-    int g0;                   // first 16-column group of this weight in the concatenation of all weights
-};
 
 struct Args {
     const uint16_t *x;        // [M][K] bf16 values of fq(x)
@@ -72,33 +65,6 @@ struct Args {
     unsigned long long *stamps;   // tools/ only (QT_FQT_STAMPS = device address): see LinearFqt's STAMPS
 #endif
 };
-
-struct SegRef { const uint16_t *w, *bias; int g0; };
-// by compile-time indices only: a run-time index into the kernel-argument struct makes hipcc copy it to scratch
-__device__ __forceinline__ SegRef seg_lookup(const Args &a, int grp) {
-    SegRef r{a.seg[0].w, a.seg[0].bias, a.seg[0].g0};
-    if (a.nseg > 1 && grp >= a.seg[1].g0) r = SegRef{a.seg[1].w, a.seg[1].bias, a.seg[1].g0};
-    if (a.nseg > 2 && grp >= a.seg[2].g0) r = SegRef{a.seg[2].w, a.seg[2].bias, a.seg[2].g0};
-    if (a.nseg > 3 && grp >= a.seg[3].g0) r = SegRef{a.seg[3].w, a.seg[3].bias, a.seg[3].g0};
-    return r;
-}
-
-// column tile tn of tiles_n: first 16-column group and group count (the wider tiles spread evenly over the tile index)
-__device__ __forceinline__ void tile_span(const Args &a, int tn, int &first, int &count) {
-    const long units = (long)a.gbase * a.tiles_n + a.gextra;
-    first = (int)(tn * units / a.tiles_n);
-    count = (int)((tn + 1) * units / a.tiles_n) - first;
-}
-
-__device__ __forceinline__ uint32_t lds_addr(const void *p) {
-    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)p;
-}
-template <int OFF>
-__device__ __forceinline__ u32x4 ds_read128(uint32_t addr) {
-    u32x4 v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-    return v;
-}
 
 // Split-K hand-off between workgroups: every byte is stored write-through (sc1) and loaded past the L1 (sc1); the stores are drained
 // (s_waitcnt vmcnt(0)) in front of the workgroup barrier that precedes the ticket's atomic add.
@@ -761,16 +727,6 @@ __global__ __launch_bounds__(512, 1) void linear_fqt_kernel(Args a) {
     if (redo) slow_tile<TM>(a, m0, tg0, jbase, ntw, w, l);
 }
 
-int cu_count() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n = v;
-        else n = 256;
-    }
-    return n;
-}
-
 template <int TM, int NB, bool SROWS, int STAMPS = 0>
 int launch_one(const Args &a, hipStream_t st) {
     constexpr int kLds = LinearFqt<TM, NB, SROWS>::kLds;
@@ -781,8 +737,7 @@ int launch_one(const Args &a, hipStream_t st) {
         configured.done();
     }
     linear_fqt_kernel<TM, NB, SROWS, STAMPS><<<a.tiles_m * a.tiles_n * a.ksplit, 512, kLds, st>>>(a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? QT_OK : (int)e;
+    return qt_launch_status();
 }
 
 template <bool SROWS>
@@ -819,7 +774,7 @@ struct Tiling {
 constexpr int kMinSplitSteps = 24;     // a split shorter than this does not pay for its prologue and the hand-off
 
 Tiling make_tiling(int M, long groups, int K, bool may_split) {
-    const int cus = cu_count();
+    const int cus = qt_cu_count();
     int force_tn = 0, force_tm = 0, force_ks = 0;
 #ifdef QT_TUNING_BUILD
     const char *e_tn = getenv("QT_FQT_TILES_N"), *e_tm = getenv("QT_FQT_TM"), *e_ks = getenv("QT_FQT_KSPLIT");          // tools/ only

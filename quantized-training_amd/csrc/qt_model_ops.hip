@@ -17,10 +17,6 @@
 
 namespace {
 
-__device__ __forceinline__ float bf_lo(uint32_t w) { return qt_u2f(w << 16); }
-__device__ __forceinline__ float bf_hi(uint32_t w) { return qt_u2f(w & 0xFFFF0000u); }
-__device__ __forceinline__ float rbf(float f) { return qt_u2f(pack_bf16x2(f, 0.0f) << 16); }      // round to bf16, keep as float
-
 constexpr int kNormThreads = 256;
 constexpr int kNormMaxVec = 8;        // 16-byte vectors per thread: rows up to 256 * 8 * 8 = 16384 elements
 
@@ -105,7 +101,7 @@ __global__ __launch_bounds__(kNormThreads) void rmsnorm_kernel(const uint4 *__re
             uint32_t o[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const float h0 = rbf(bf_lo(q[j]) * r), h1 = rbf(bf_hi(q[j]) * r);
+                const float h0 = bf16_round(bf_lo(q[j]) * r), h1 = bf16_round(bf_hi(q[j]) * r);
                 o[j] = pack_bf16x2(bf_lo(g[j]) * h0, bf_hi(g[j]) * h1);
             }
 #pragma unroll
@@ -142,7 +138,7 @@ __global__ __launch_bounds__(256) void silu_mul_kernel(const uint4 *__restrict__
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const float g0 = bf_lo(p[j]), g1 = bf_hi(p[j]);
-            const float s0 = rbf(g0 / (1.0f + expf(-g0))), s1 = rbf(g1 / (1.0f + expf(-g1)));
+            const float s0 = bf16_round(g0 / (1.0f + expf(-g0))), s1 = bf16_round(g1 / (1.0f + expf(-g1)));
             o[j] = pack_bf16x2(s0 * bf_lo(q[j]), s1 * bf_hi(q[j]));
         }
         y[i] = uint4{o[0], o[1], o[2], o[3]};
@@ -169,7 +165,7 @@ __global__ __launch_bounds__(256) void silu_mul_map_kernel(const uint4 *__restri
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const float g0 = bf_lo(p[j]), g1 = bf_hi(p[j]);
-            const float s0 = rbf(g0 / (1.0f + expf(-g0))), s1 = rbf(g1 / (1.0f + expf(-g1)));
+            const float s0 = bf16_round(g0 / (1.0f + expf(-g0))), s1 = bf16_round(g1 / (1.0f + expf(-g1)));
             pr[j] = pack_bf16x2(s0 * bf_lo(q[j]), s1 * bf_hi(q[j]));
         }
         fq_rows_words<4, false>(pr, o, rnd);
@@ -192,7 +188,7 @@ __global__ __launch_bounds__(256) void silu_mul_fq8_kernel(const uint4 *__restri
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const float g0 = bf_lo(p[j]), g1 = bf_hi(p[j]);
-            const float s0 = rbf(g0 / (1.0f + expf(-g0))), s1 = rbf(g1 / (1.0f + expf(-g1)));
+            const float s0 = bf16_round(g0 / (1.0f + expf(-g0))), s1 = bf16_round(g1 / (1.0f + expf(-g1)));
             o[j] = pack_bf16x2(s0 * bf_lo(q[j]), s1 * bf_hi(q[j]));                        // the unquantized product, bf16
         }
         const uint2 codes = fq8_hw_vec8<E5M2>(o, fmt);
@@ -229,8 +225,8 @@ __device__ __forceinline__ void rope_one(const RopeArgs &a, size_t i) {
     uint32_t o[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        const float a0 = rbf(bf_lo(X[j]) * bf_lo(C[j])), a1 = rbf(bf_hi(X[j]) * bf_hi(C[j]));
-        const float b0 = rbf(sgn * bf_lo(P[j]) * bf_lo(S[j])), b1 = rbf(sgn * bf_hi(P[j]) * bf_hi(S[j]));
+        const float a0 = bf16_round(bf_lo(X[j]) * bf_lo(C[j])), a1 = bf16_round(bf_hi(X[j]) * bf_hi(C[j]));
+        const float b0 = bf16_round(sgn * bf_lo(P[j]) * bf_lo(S[j])), b1 = bf16_round(sgn * bf_hi(P[j]) * bf_hi(S[j]));
         o[j] = pack_bf16x2(a0 + b0, a1 + b1);
     }
     *(uint4 *)(a.y + i * 8) = uint4{o[0], o[1], o[2], o[3]};
@@ -289,7 +285,7 @@ __device__ __forceinline__ void rope_fq_token(const RopeFqArgs &a, size_t bs0, u
             const float sgn = low ? -1.0f : 1.0f;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                float a0 = rbf(bf_lo(X[j]) * bf_lo(C[j])), a1 = rbf(bf_hi(X[j]) * bf_hi(C[j]));
+                float a0 = bf16_round(bf_lo(X[j]) * bf_lo(C[j])), a1 = bf16_round(bf_hi(X[j]) * bf_hi(C[j]));
                 if (!CODES && a.inner) {
                     if (a.map) {                                         // table format: the same map as the result's (host-checked)
                         const Rounder<kFmtRows> rin{a.fmt, a.rows_lds, a.map};
@@ -300,7 +296,7 @@ __device__ __forceinline__ void rope_fq_token(const RopeFqArgs &a, size_t bs0, u
                         a1 = qt_u2f(qt_fp_sat_u32(qt_f2u(a1), a.inner_fmt.p0, a.inner_fmt.p1, a.inner_fmt.fhi));
                     }
                 }
-                const float b0 = rbf(sgn * bf_lo(P[j]) * bf_lo(S[j])), b1 = rbf(sgn * bf_hi(P[j]) * bf_hi(S[j]));
+                const float b0 = bf16_round(sgn * bf_lo(P[j]) * bf_lo(S[j])), b1 = bf16_round(sgn * bf_hi(P[j]) * bf_hi(S[j]));
                 out[j] = pack_bf16x2(a0 + b0, a1 + b1);                  // the rotary output, bf16
             }
         }
@@ -546,13 +542,6 @@ __global__ __launch_bounds__(256) void gelu_kernel(const uint4 *__restrict__ x, 
     }
 }
 
-int fp8_code_of(const qt_format *f) {                       // 1 E4M3, 2 E5M2, 0 neither
-    if (!f || f->kind != QT_FMT_FP_SAT) return 0;
-    if (f->p0 == 2 && f->p1 == -14 && f->fhi == 57344.0f) return 2;
-    if (f->p0 == 3 && f->p1 == -6 && f->fhi == 448.0f) return 1;
-    return 0;
-}
-
 template <int G, bool ADD, int NV>
 void launch_layernorm_nv(const LnArgs &a, int fq, unsigned blocks, hipStream_t st) {
     if (fq == 2) layernorm_kernel<G, 2, ADD, NV><<<blocks, 256, 0, st>>>(a);
@@ -565,11 +554,6 @@ void launch_layernorm(const LnArgs &a, int fq, unsigned blocks, hipStream_t st) 
     if (a.nvec <= 2 * G) launch_layernorm_nv<G, ADD, 2>(a, fq, blocks, st);
     else if (a.nvec <= 4 * G) launch_layernorm_nv<G, ADD, 4>(a, fq, blocks, st);
     else launch_layernorm_nv<G, ADD, 8>(a, fq, blocks, st);
-}
-
-int launch_status() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? QT_OK : (int)e;
 }
 
 template <int FQ, bool ADD, int EXTRA>
@@ -725,16 +709,15 @@ int qt_rmsnorm_bf16(const uint16_t *x, const uint16_t *weight, uint16_t *y, long
     launch_rms<0, false, 0>((unsigned)rows, (int)(cols / 8), (hipStream_t)stream, (const uint4 *)x, (const uint4 *)weight, (uint4 *)y,
                                                                                 (int)(cols / 8), 1.0f / (float)cols, eps, nullptr,
                                                                                 qt_format{});
-    return launch_status();
+    return qt_launch_status();
 }
 
 int qt_rmsnorm_fq8_bf16(const uint16_t *x, const uint16_t *weight, uint16_t *y, uint8_t *y8, long rows, long cols, float eps,
                         const qt_format *fmt, void *stream) {
     if (rows * cols == 0) return QT_OK;
-    if (!x || !weight || !y8 || !fmt || rows < 0 || cols < 0 || fmt->kind != QT_FMT_FP_SAT) return QT_ERR_BAD_ARG;       // y NULL: codes only
-    const bool e5m2 = fmt->p0 == 2 && fmt->p1 == -14 && fmt->fhi == 57344.0f;
-    const bool e4m3 = fmt->p0 == 3 && fmt->p1 == -6 && fmt->fhi == 448.0f;
-    if (!e5m2 && !e4m3) return QT_ERR_BAD_ARG;
+    const int f8 = qt_fp8_code(fmt);
+    if (!x || !weight || !y8 || !f8 || rows < 0 || cols < 0) return QT_ERR_BAD_ARG;       // y NULL: codes only
+    const bool e5m2 = f8 == 2;
     if (cols % 8 || cols > (long)kNormThreads * kNormMaxVec * 8 || (((uintptr_t)x | (uintptr_t)weight | (uintptr_t)y) & 15u) ||
         ((uintptr_t)y8 & 7u))
         return QT_ERR_UNALIGNED;
@@ -744,14 +727,14 @@ int qt_rmsnorm_fq8_bf16(const uint16_t *x, const uint16_t *weight, uint16_t *y, 
     else
         launch_rms<1, false, 0>((unsigned)rows, (int)(cols / 8), (hipStream_t)stream, (const uint4 *)x, (const uint4 *)weight, (uint4 *)y,
                                                                                     (int)(cols / 8), 1.0f / (float)cols, eps, (uint2 *)y8, *fmt);
-    return launch_status();
+    return qt_launch_status();
 }
 
 int qt_add_rmsnorm_bf16(const uint16_t *x, const uint16_t *residual, const uint16_t *weight, uint16_t *sum, uint16_t *y, uint8_t *y8,
                         long rows, long cols, float eps, const qt_format *fmt, void *stream) {
     if (rows * cols == 0) return QT_OK;
     if (!x || !residual || !weight || !sum || (!y && !y8) || rows < 0 || cols < 0) return QT_ERR_BAD_ARG;              // y NULL with y8: codes only
-    const int fq = y8 ? fp8_code_of(fmt) : 0;
+    const int fq = y8 ? qt_fp8_code(fmt) : 0;
     if (y8 && !fq) return QT_ERR_BAD_ARG;
     if (cols % 8 || cols > (long)kNormThreads * kNormMaxVec * 8 ||
         (((uintptr_t)x | (uintptr_t)residual | (uintptr_t)weight | (uintptr_t)sum | (uintptr_t)y) & 15u) || ((uintptr_t)y8 & 7u))
@@ -763,7 +746,7 @@ int qt_add_rmsnorm_bf16(const uint16_t *x, const uint16_t *residual, const uint1
     if (fq == 2) launch_rms<2, true, 0>((unsigned)rows, nvec, st, (const uint4 *)x, (const uint4 *)weight, (uint4 *)y, nvec, inv, eps, (uint2 *)y8, f, (const uint4 *)residual, (uint4 *)sum);
     else if (fq == 1) launch_rms<1, true, 0>((unsigned)rows, nvec, st, (const uint4 *)x, (const uint4 *)weight, (uint4 *)y, nvec, inv, eps, (uint2 *)y8, f, (const uint4 *)residual, (uint4 *)sum);
     else launch_rms<0, true, 0>((unsigned)rows, nvec, st, (const uint4 *)x, (const uint4 *)weight, (uint4 *)y, nvec, inv, eps, nullptr, f, (const uint4 *)residual, (uint4 *)sum);
-    return launch_status();
+    return qt_launch_status();
 }
 
 int qt_add_rmsnorm_sumfq_bf16(const uint16_t *x, const uint16_t *residual, const uint16_t *weight, uint16_t *sum, uint16_t *y, uint8_t *y8,
@@ -771,7 +754,7 @@ int qt_add_rmsnorm_sumfq_bf16(const uint16_t *x, const uint16_t *residual, const
     if (!sum_fmt) return qt_add_rmsnorm_bf16(x, residual, weight, sum, y, y8, rows, cols, eps, fmt, stream);
     if (rows * cols == 0) return QT_OK;
     if (!x || !residual || !weight || !sum || !y || rows < 0 || cols < 0) return QT_ERR_BAD_ARG;
-    const int fq = y8 ? fp8_code_of(fmt) : 0, sfq = fp8_code_of(sum_fmt);
+    const int fq = y8 ? qt_fp8_code(fmt) : 0, sfq = qt_fp8_code(sum_fmt);
     if ((y8 && !fq) || !sfq) return QT_ERR_BAD_ARG;
     if (cols % 8 || cols > (long)kNormThreads * kNormMaxVec * 8 ||
         (((uintptr_t)x | (uintptr_t)residual | (uintptr_t)weight | (uintptr_t)sum | (uintptr_t)y) & 15u) || ((uintptr_t)y8 & 7u))
@@ -783,7 +766,7 @@ int qt_add_rmsnorm_sumfq_bf16(const uint16_t *x, const uint16_t *residual, const
     if (fq == 2) launch_rms<2, true, 0>((unsigned)rows, nvec, st, (const uint4 *)x, (const uint4 *)weight, (uint4 *)y, nvec, inv, eps, (uint2 *)y8, f, (const uint4 *)residual, (uint4 *)sum, NormExtra{}, sfq, *sum_fmt);
     else if (fq == 1) launch_rms<1, true, 0>((unsigned)rows, nvec, st, (const uint4 *)x, (const uint4 *)weight, (uint4 *)y, nvec, inv, eps, (uint2 *)y8, f, (const uint4 *)residual, (uint4 *)sum, NormExtra{}, sfq, *sum_fmt);
     else launch_rms<0, true, 0>((unsigned)rows, nvec, st, (const uint4 *)x, (const uint4 *)weight, (uint4 *)y, nvec, inv, eps, nullptr, f, (const uint4 *)residual, (uint4 *)sum, NormExtra{}, sfq, *sum_fmt);
-    return launch_status();
+    return qt_launch_status();
 }
 
 int qt_rmsnorm_consumers_bf16(const uint16_t *x, const uint16_t *residual, const uint16_t *weight, uint16_t *sum, uint16_t *y, long rows,
@@ -794,7 +777,7 @@ int qt_rmsnorm_consumers_bf16(const uint16_t *x, const uint16_t *residual, const
     int code[3] = {0, 0, 0};
     for (int i = 0; i < consumers; ++i) {
         if (!y8[i] || !fmt[i] || ((uintptr_t)y8[i] & 7u)) return QT_ERR_BAD_ARG;
-        code[i] = fp8_code_of(fmt[i]);
+        code[i] = qt_fp8_code(fmt[i]);
         if (!code[i]) return QT_ERR_BAD_ARG;
     }
     if (cols % 8 || cols > (long)kNormThreads * kNormMaxVec * 8 ||
@@ -820,7 +803,7 @@ int qt_rmsnorm_consumers_bf16(const uint16_t *x, const uint16_t *residual, const
         case 6: launch_norm_consumers<2, true, 1>(x, residual, weight, sum, y, y8[0], rows, nvec, inv, eps, *fmt[0], ex, st); break;
         default: launch_norm_consumers<2, true, 2>(x, residual, weight, sum, y, y8[0], rows, nvec, inv, eps, *fmt[0], ex, st); break;
     }
-    return launch_status();
+    return qt_launch_status();
 }
 
 static int launch_layernorm_any(const LnArgs &a, int fq, bool with_residual, void *stream);
@@ -829,7 +812,7 @@ int qt_layernorm_bf16(const uint16_t *x, const uint16_t *residual, const uint16_
                       uint16_t *yq, uint8_t *y8, long rows, long cols, float eps, const qt_format *fmt, void *stream) {
     if (rows * cols == 0) return QT_OK;
     if (!x || !weight || !bias || !y || rows < 0 || cols < 0 || (yq && !y8)) return QT_ERR_BAD_ARG;
-    const int fq = y8 ? fp8_code_of(fmt) : 0;
+    const int fq = y8 ? qt_fp8_code(fmt) : 0;
     if (y8 && !fq) return QT_ERR_BAD_ARG;
     if (cols % 8 || cols > (long)kNormThreads * kNormMaxVec * 8 ||
         (((uintptr_t)x | (uintptr_t)residual | (uintptr_t)weight | (uintptr_t)bias | (uintptr_t)y | (uintptr_t)yq) & 15u) || ((uintptr_t)y8 & 7u))
@@ -847,7 +830,7 @@ int qt_layernorm_consumers_bf16(const uint16_t *x, const uint16_t *residual, con
     int code[3] = {0, 0, 0};
     for (int i = 0; i < consumers; ++i) {
         if (!y8[i] || !fmt[i] || ((uintptr_t)y8[i] & 7u)) return QT_ERR_BAD_ARG;
-        code[i] = fp8_code_of(fmt[i]);
+        code[i] = qt_fp8_code(fmt[i]);
         if (!code[i]) return QT_ERR_BAD_ARG;
     }
     if (cols % 8 || cols > (long)kNormThreads * kNormMaxVec * 8 ||
@@ -875,13 +858,13 @@ static int launch_layernorm_any(const LnArgs &a, int fq, bool with_residual, voi
         if (residual) launch_layernorm<256, true>(a, fq, (unsigned)rows, st);
         else launch_layernorm<256, false>(a, fq, (unsigned)rows, st);
     }
-    return launch_status();
+    return qt_launch_status();
 }
 
 int qt_gelu_bf16(const uint16_t *x, uint16_t *y, uint8_t *y8, size_t n, const qt_format *fmt, void *stream) {
     if (n == 0) return QT_OK;
     if (!x || (!y && !y8)) return QT_ERR_BAD_ARG;
-    const int fq = y8 ? fp8_code_of(fmt) : 0;
+    const int fq = y8 ? qt_fp8_code(fmt) : 0;
     if (y8 && !fq) return QT_ERR_BAD_ARG;
     if ((n & 7) || (((uintptr_t)x | (uintptr_t)y) & 15u) || ((uintptr_t)y8 & 7u)) return QT_ERR_UNALIGNED;
     const size_t nvec = n / 8;
@@ -891,7 +874,7 @@ int qt_gelu_bf16(const uint16_t *x, uint16_t *y, uint8_t *y8, size_t n, const qt
     if (fq == 2) gelu_kernel<2><<<(unsigned)blocks, 256, 0, st>>>((const uint4 *)x, (uint4 *)y, (uint2 *)y8, nvec, *fmt);
     else if (fq == 1) gelu_kernel<1><<<(unsigned)blocks, 256, 0, st>>>((const uint4 *)x, (uint4 *)y, (uint2 *)y8, nvec, *fmt);
     else gelu_kernel<0><<<(unsigned)blocks, 256, 0, st>>>((const uint4 *)x, (uint4 *)y, nullptr, nvec, qt_format{});
-    return launch_status();
+    return qt_launch_status();
 }
 
 int qt_silu_mul_bf16(const uint16_t *gate, const uint16_t *up, uint16_t *y, size_t rows, size_t cols, size_t gate_row_stride,
@@ -906,18 +889,16 @@ int qt_silu_mul_bf16(const uint16_t *gate, const uint16_t *up, uint16_t *y, size
     if (blocks > 256 * 32) blocks = 256 * 32;
     silu_mul_kernel<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>((const uint4 *)gate, (const uint4 *)up, (uint4 *)y, nvec,
                                                                        cols / 8, gate_row_stride / 8, up_row_stride / 8);
-    return launch_status();
+    return qt_launch_status();
 }
 
 int qt_silu_mul_fq8_bf16(const uint16_t *gate, const uint16_t *up, uint16_t *y, uint8_t *y8, size_t rows, size_t cols,
                          size_t gate_row_stride, size_t up_row_stride, const qt_format *fmt, void *stream) {
     const size_t n = rows * cols;
     if (n == 0) return QT_OK;
-    if (!gate || !up || !y || !y8 || !fmt || fmt->kind != QT_FMT_FP_SAT || gate_row_stride < cols || up_row_stride < cols)
-        return QT_ERR_BAD_ARG;
-    const bool e5m2 = fmt->p0 == 2 && fmt->p1 == -14 && fmt->fhi == 57344.0f;
-    const bool e4m3 = fmt->p0 == 3 && fmt->p1 == -6 && fmt->fhi == 448.0f;
-    if (!e5m2 && !e4m3) return QT_ERR_BAD_ARG;
+    const int f8 = qt_fp8_code(fmt);
+    if (!gate || !up || !y || !y8 || !f8 || gate_row_stride < cols || up_row_stride < cols) return QT_ERR_BAD_ARG;
+    const bool e5m2 = f8 == 2;
     if ((cols & 7) || ((gate_row_stride | up_row_stride) & 7) || (((uintptr_t)gate | (uintptr_t)up | (uintptr_t)y) & 15u) ||
         ((uintptr_t)y8 & 7u))
         return QT_ERR_UNALIGNED;
@@ -930,7 +911,7 @@ int qt_silu_mul_fq8_bf16(const uint16_t *gate, const uint16_t *up, uint16_t *y, 
     else
         silu_mul_fq8_kernel<false><<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>((const uint4 *)gate, (const uint4 *)up, (uint4 *)y, (uint2 *)y8, nvec, *fmt,
                                                                                       cols / 8, gate_row_stride / 8, up_row_stride / 8);
-    return launch_status();
+    return qt_launch_status();
 }
 
 int qt_rope_bf16(const uint16_t *q, const uint16_t *k, const uint16_t *cos, const uint16_t *sin, uint16_t *q_out,
@@ -945,7 +926,7 @@ int qt_rope_bf16(const uint16_t *q, const uint16_t *k, const uint16_t *cos, cons
     size_t blocks = (aq.nvec + ak.nvec + 255) / 256;
     if (blocks > 256 * 32) blocks = 256 * 32;
     rope_kernel<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(aq, ak);
-    return launch_status();
+    return qt_launch_status();
 }
 
 static int rope_fq_launch(const uint16_t *q, const uint16_t *k, const uint16_t *cos, const uint16_t *sin, uint16_t *q_out, uint16_t *k_out,
@@ -962,12 +943,10 @@ static int rope_fq_launch(const uint16_t *q, const uint16_t *k, const uint16_t *
         return QT_ERR_UNALIGNED;
     if (q_row_stride < Hq * D || k_row_stride < Hk * D || (q_row_stride | k_row_stride) % 8) return QT_ERR_BAD_ARG;
     if (((uintptr_t)q_out8 | (uintptr_t)k_out8) & 7u) return QT_ERR_UNALIGNED;
-    auto is_e5m2 = [](const qt_format *f) { return f->p0 == 2 && f->p1 == -14 && f->fhi == 57344.0f; };
-    auto is_e4m3 = [](const qt_format *f) { return f->p0 == 3 && f->p1 == -6 && f->fhi == 448.0f; };
-    if ((q_out8 && !is_e5m2(fmt_q) && !is_e4m3(fmt_q)) || (k_out8 && !is_e5m2(fmt_k) && !is_e4m3(fmt_k))) return QT_ERR_BAD_ARG;
-    RopeFqArgs aq{{q, q_out, cos, sin, B, S, Hq, D, (size_t)(B * S * Hq * D / 8), q_row_stride / 8}, *fmt_q, q_out8, is_e5m2(fmt_q) ? 1 : 0,
+    if ((q_out8 && !qt_fp8_code(fmt_q)) || (k_out8 && !qt_fp8_code(fmt_k))) return QT_ERR_BAD_ARG;
+    RopeFqArgs aq{{q, q_out, cos, sin, B, S, Hq, D, (size_t)(B * S * Hq * D / 8), q_row_stride / 8}, *fmt_q, q_out8, qt_fp8_code(fmt_q) == 2 ? 1 : 0,
                   inner_q ? 1 : 0, inner_q ? *inner_q : qt_format{}, nullptr, nullptr};
-    RopeFqArgs ak{{k, k_out, cos, sin, B, S, Hk, D, (size_t)(B * S * Hk * D / 8), k_row_stride / 8}, *fmt_k, k_out8, is_e5m2(fmt_k) ? 1 : 0,
+    RopeFqArgs ak{{k, k_out, cos, sin, B, S, Hk, D, (size_t)(B * S * Hk * D / 8), k_row_stride / 8}, *fmt_k, k_out8, qt_fp8_code(fmt_k) == 2 ? 1 : 0,
                   inner_k ? 1 : 0, inner_k ? *inner_k : qt_format{}, nullptr, nullptr};
     if (Hq * D / 8 > 0xFFFFFFFFl || Hk * D / 8 > 0xFFFFFFFFl || B > 0x7FFFFFFFl || S > 0x7FFFFFFFl) return QT_ERR_BAD_ARG;
     const long nv_max = (Hq > Hk ? Hq : Hk) * D / 8;                      // vectors of a token: a workgroup takes 256 / that many tokens
@@ -977,16 +956,14 @@ static int rope_fq_launch(const uint16_t *q, const uint16_t *k, const uint16_t *
     hipStream_t st = (hipStream_t)stream;
     if (!v) {
         rope_fq_kernel<<<(unsigned)blocks, 256, 0, st>>>(aq, ak, tpb);
-        return launch_status();
+        return qt_launch_status();
     }
     // the value job: v is [B][Hk][S][D] by strides, D contiguous; vt8 [B][Hk][D][S]
-    if (!vt8 || !fmt_v || fmt_v->kind != QT_FMT_FP_SAT || (!is_e5m2(fmt_v) && !is_e4m3(fmt_v)) || (D != 64 && D != 128) || S % 128 != 0 ||
-        B * Hk > 65535)
-        return QT_ERR_BAD_ARG;
+    if (!vt8 || !qt_fp8_code(fmt_v) || (D != 64 && D != 128) || S % 128 != 0 || B * Hk > 65535) return QT_ERR_BAD_ARG;
     if ((((uintptr_t)v | (uintptr_t)vt8) & 15u) || ((v_sb | v_sh | v_sk) & 7)) return QT_ERR_UNALIGNED;
     ValueArgs av{v, vt8, v_sb, v_sh, v_sk, S, (int)Hk, (int)(S / 128), *fmt_v};
     const unsigned total = (unsigned)blocks + (unsigned)(B * Hk * (S / 128));
-    const bool ve5 = is_e5m2(fmt_v);
+    const bool ve5 = qt_fp8_code(fmt_v) == 2;
     if (D == 128) {
         const bool codes = aq.y8 && ak.y8 && !aq.inner && !ak.inner && !aq.map && !ak.map;       // (one mode for the whole launch)
         if (codes && !ve5) rope_fq_value_kernel<false, 128, true><<<total, 256, 0, st>>>(aq, ak, av, (unsigned)blocks, tpb);
@@ -998,7 +975,7 @@ static int rope_fq_launch(const uint16_t *q, const uint16_t *k, const uint16_t *
         else if (ve5) rope_fq_value_kernel<true, 64><<<total, 256, 0, st>>>(aq, ak, av, (unsigned)blocks, tpb);
         else rope_fq_value_kernel<false, 64><<<total, 256, 0, st>>>(aq, ak, av, (unsigned)blocks, tpb);
     }
-    return launch_status();
+    return qt_launch_status();
 }
 
 int qt_rope_fq_bf16(const uint16_t *q, const uint16_t *k, const uint16_t *cos, const uint16_t *sin, uint16_t *q_out,
@@ -1032,7 +1009,7 @@ int qt_rmsnorm_map_bf16(const uint16_t *x, const uint16_t *residual, const uint1
     const float inv = 1.0f / (float)cols;
     if (residual) launch_rms<3, true, 0>((unsigned)rows, nvec, st, (const uint4 *)x, (const uint4 *)weight, (uint4 *)y, nvec, inv, eps, nullptr, *fmt, (const uint4 *)residual, (uint4 *)sum, NormExtra{}, quantize_sum ? 3 : 0, qt_format{}, map);
     else launch_rms<3, false, 0>((unsigned)rows, nvec, st, (const uint4 *)x, (const uint4 *)weight, (uint4 *)y, nvec, inv, eps, nullptr, *fmt, nullptr, nullptr, NormExtra{}, 0, qt_format{}, map);
-    return launch_status();
+    return qt_launch_status();
 }
 
 int qt_silu_mul_map_bf16(const uint16_t *gate, const uint16_t *up, uint16_t *y, size_t rows, size_t cols, size_t gate_row_stride,
@@ -1047,7 +1024,7 @@ int qt_silu_mul_map_bf16(const uint16_t *gate, const uint16_t *up, uint16_t *y, 
     if (blocks > 256 * 32) blocks = 256 * 32;
     silu_mul_map_kernel<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>((const uint4 *)gate, (const uint4 *)up, (uint4 *)y, nvec, *fmt, map, cols / 8,
                                                                           gate_row_stride / 8, up_row_stride / 8);
-    return launch_status();
+    return qt_launch_status();
 }
 
 int qt_rope_map_bf16(const uint16_t *q, const uint16_t *k, const uint16_t *cos, const uint16_t *sin, uint16_t *q_out, uint16_t *k_out, long B,
@@ -1066,7 +1043,7 @@ int qt_rope_map_bf16(const uint16_t *q, const uint16_t *k, const uint16_t *cos, 
     size_t blocks = ((size_t)B * (size_t)S + tpb - 1) / tpb;
     if (blocks > 256 * 64) blocks = 256 * 64;
     rope_fq_kernel<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(aq, ak, tpb);
-    return launch_status();
+    return qt_launch_status();
 }
 
 static int rope_map_value_launch(const uint16_t *q, const uint16_t *k, const uint16_t *cos, const uint16_t *sin, uint16_t *q_out, uint16_t *k_out,
@@ -1096,7 +1073,7 @@ static int rope_map_value_launch(const uint16_t *q, const uint16_t *k, const uin
     }
     const unsigned total = aw.blocks + (unsigned)blocks + (unsigned)(B * Hk * (S / 64));
     rope_map_value_kernel<<<total, 256, 0, (hipStream_t)stream>>>(aq, ak, av, aw, (unsigned)blocks, tpb);
-    return launch_status();
+    return qt_launch_status();
 }
 
 int qt_rope_map_value(const uint16_t *q, const uint16_t *k, const uint16_t *cos, const uint16_t *sin, uint16_t *q_out, uint16_t *k_out, long B,
@@ -1131,7 +1108,7 @@ int qt_causal_lm_loss_bf16(const uint16_t *logits, const long long *labels, long
     hipStream_t st = (hipStream_t)stream;
     nll_rows_kernel<<<(unsigned)rows, 256, 0, st>>>(logits, labels, seq_len, vocab, row_stride, ignore_index, row_loss_scratch);
     nll_mean_kernel<<<1, 256, 0, st>>>(row_loss_scratch, rows, loss_out);
-    return launch_status();
+    return qt_launch_status();
 }
 
 int qt_colsum_bf16(const uint16_t *x_dev, uint16_t *out_dev, long rows, long cols, void *stream) {
@@ -1140,8 +1117,7 @@ int qt_colsum_bf16(const uint16_t *x_dev, uint16_t *out_dev, long rows, long col
     if (!x_dev || !out_dev || cols % 8 != 0) return QT_ERR_BAD_ARG;
     if ((uintptr_t)x_dev & 15u) return QT_ERR_UNALIGNED;
     colsum_kernel<<<(unsigned)((cols + 31) / 32), 256, 0, (hipStream_t)stream>>>(x_dev, out_dev, rows, cols);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? QT_OK : (int)e;
+    return qt_launch_status();
 }
 
 }  // extern "C"

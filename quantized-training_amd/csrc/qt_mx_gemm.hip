@@ -310,9 +310,6 @@ struct DmaTile {                                    // one wave-instruction = kR
 // see while an LDS-DMA is in flight (the DMA's LDS store carries no alias scope, so nothing can be proven about it),
 // which would drain the ring on every step.  An asm ds_read has no memory operand for that rule to act on; the price is
 // that the lgkmcnt wait before the first use is ours to place (one s_waitcnt lgkmcnt(0) after the batch of reads).
-__device__ __forceinline__ uint32_t lds_addr(const void *p) {
-    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)p;
-}
 __device__ __forceinline__ uint4 asm_ds_read_b128(uint32_t addr) {
     uint4 v;
     asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr));
@@ -1056,22 +1053,12 @@ __global__ __launch_bounds__(512, 1) void mx_gemm_wide_kernel(MxGemmArgs a, Wide
     }
 }
 
-int wide_cu_count() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n = v;
-        else n = 256;
-    }
-    return n;
-}
-
 // Tiling of the wide kernel.  For each row-tile height: as many column tiles as make whole rounds over the CUs (each at most
 // 12 / 16 groups of 16 columns); the height with fewer operand bytes per CU, rounds x (TM + widest tile), wins.
 bool wide_geometry(int M, int N, long batch, WideGeom &geo) {
     if (N % 16 != 0 || M < 1) return false;
     const long groups = N / 16;
-    const int cus = wide_cu_count();
+    const int cus = qt_cu_count();
     int force_tn = 0;
 #ifdef QT_TUNING_BUILD
     static const int e_force_tn = getenv("QT_MX_WIDE_TILES_N") ? atoi(getenv("QT_MX_WIDE_TILES_N")) : 0;     // tools/ only
@@ -1114,8 +1101,7 @@ int launch_wide_nbp(const MxGemmArgs &g, const WideGeom &geo, long batch, hipStr
         configured.done();
     }
     mx_gemm_wide_kernel<FA, FB, TM, NBP><<<dim3((unsigned)(geo.tiles_m * geo.tiles_n), (unsigned)batch), 512, kLds, st>>>(g, geo);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? QT_OK : (int)e;
+    return qt_launch_status();
 }
 
 template <int FA, int FB>
@@ -1185,11 +1171,6 @@ __global__ __launch_bounds__(256) void mx_pack_kernel(PackArgs p) {
     }
 }
 
-int launch_status() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? QT_OK : (int)e;
-}
-
 }  // namespace
 
 extern "C" {
@@ -1206,7 +1187,7 @@ int qt_mx_pack(const void *x_dev, const void *scale_dev, int is_f32, uint8_t *co
     unsigned grid = (unsigned)((total + 255) / 256);
     if (grid > 65535u * 4u) grid = 65535u * 4u;
     mx_pack_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(p);
-    return launch_status();
+    return qt_launch_status();
 }
 
 int qt_mx_gemm(const uint8_t *a_codes, const uint8_t *a_e8m0, int a_format, const uint8_t *b_codes, const uint8_t *b_e8m0,
@@ -1254,7 +1235,7 @@ int qt_mx_gemm(const uint8_t *a_codes, const uint8_t *a_e8m0, int a_format, cons
     if (big && a_format == FA && b_format == FB) {                                                                 \
         const dim3 bgrid((unsigned)big_tiles, (unsigned)batch);                                                    \
         mx_gemm_big_kernel<FA, FB><<<bgrid, 512, 0, st>>>(g);                                                      \
-        return launch_status();                                                                                    \
+        return qt_launch_status();                                                                                 \
     }
     QT_MX_BIG(0, 0) QT_MX_BIG(0, 1) QT_MX_BIG(1, 0) QT_MX_BIG(1, 1) QT_MX_BIG(4, 4) QT_MX_BIG(0, 4)
     QT_MX_BIG(2, 2) QT_MX_BIG(3, 3) QT_MX_BIG(2, 4) QT_MX_BIG(3, 4)
@@ -1267,7 +1248,7 @@ int qt_mx_gemm(const uint8_t *a_codes, const uint8_t *a_e8m0, int a_format, cons
         } else {                                                                                                   \
             mx_gemm_dma_kernel<FA, FB, 1><<<grid, 256, kLds, st>>>(g);                                             \
         }                                                                                                          \
-        return launch_status();                                                                                    \
+        return qt_launch_status();                                                                                 \
     }
     QT_MX_DMA(0, 0) QT_MX_DMA(0, 1) QT_MX_DMA(1, 0) QT_MX_DMA(1, 1) QT_MX_DMA(4, 4) QT_MX_DMA(0, 4)
     QT_MX_DMA(2, 2) QT_MX_DMA(3, 3) QT_MX_DMA(2, 4) QT_MX_DMA(3, 4)
@@ -1283,7 +1264,7 @@ int qt_mx_gemm(const uint8_t *a_codes, const uint8_t *a_e8m0, int a_format, cons
             configured.done();                                                                                      \
         }                                                                                                          \
         mx_gemm_kernel<FA, FB><<<grid, 256, kLds, st>>>(g);                                                        \
-        return launch_status();                                                                                    \
+        return qt_launch_status();                                                                                 \
     }
     QT_MX(0, 0) QT_MX(0, 1) QT_MX(1, 0) QT_MX(1, 1) QT_MX(2, 2) QT_MX(3, 3) QT_MX(4, 4) QT_MX(0, 4) QT_MX(2, 4) QT_MX(3, 4)
 #undef QT_MX
@@ -1308,7 +1289,7 @@ int qt_q8_gemm(const int8_t *a_codes, const int8_t *b_codes, void *c_dev, int c_
     const long big_tiles = (long)((M + 255) / 256) * ((N + 255) / 256);
     if (dma_ok && M >= 512 && N >= 512 && big_tiles >= 192) {
         mx_gemm_big_kernel<0, 0, true><<<dim3((unsigned)big_tiles, (unsigned)batch), 512, 0, st>>>(g);
-        return launch_status();
+        return qt_launch_status();
     }
     if (dma_ok) {
         if ((long)grid.x * grid.y <= 2L * 256) {
@@ -1317,7 +1298,7 @@ int qt_q8_gemm(const int8_t *a_codes, const int8_t *b_codes, void *c_dev, int c_
             constexpr int kLds = Tile<0>::kBytes + Tile<0>::kBytes + 1024;
             mx_gemm_dma_kernel<0, 0, 1, true><<<grid, 256, kLds, st>>>(g);
         }
-        return launch_status();
+        return qt_launch_status();
     }
     constexpr int kLds = 4 * Tile<0>::kBytes;
     static QtOncePerDevice configured;      
@@ -1327,7 +1308,7 @@ int qt_q8_gemm(const int8_t *a_codes, const int8_t *b_codes, void *c_dev, int c_
         configured.done();
     }
     mx_gemm_kernel<0, 0, true><<<grid, 256, kLds, st>>>(g);
-    return launch_status();
+    return qt_launch_status();
 }
 
 }  // extern "C"

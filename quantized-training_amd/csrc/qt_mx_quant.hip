@@ -236,11 +236,6 @@ __global__ __launch_bounds__(LDS_TABLE ? 1024 : 256) void quantize_mx_kernel(MxQ
     }
 }
 
-int launch_status() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? QT_OK : (int)e;
-}
-
 int num_cus() {
     static int n = 0;
     if (!n) {
@@ -289,7 +284,7 @@ int launch(const void *x, void *q, void *sf, uint8_t *codes, uint8_t *e8m0, size
             size_t want = (a.nvec + 255) / 256, cap = (size_t)num_cus() * 32;                                      \
             quantize_mx_kernel<IO, false, PB><<<(unsigned)(want < cap ? want : cap), 256, 0, st>>>(a);             \
         }                                                                                                          \
-        return launch_status();                                                                                    \
+        return qt_launch_status();                                                                                 \
     }
     QT_MXQ(0) QT_MXQ(8) QT_MXQ(6) QT_MXQ(4)
 #undef QT_MXQ

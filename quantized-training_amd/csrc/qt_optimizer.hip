@@ -25,13 +25,7 @@ namespace {
 
 constexpr int kOptBlock = 256, kOptVecs = 4, kOptChunk = kOptBlock * kOptVecs * 8;      // 8192 elements per workgroup
 
-inline int opt_launch_status() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? QT_OK : (int)e;
-}
-
-__device__ __forceinline__ float bf_at(uint32_t w, int h) { return h ? qt_u2f(w & 0xFFFF0000u) : qt_u2f(w << 16); }
-__device__ __forceinline__ float bf16_round(float x) { return qt_u2f(pack_bf16x2(x, 0.0f) << 16); }
+__device__ __forceinline__ float bf_at(uint32_t w, int h) { return h ? bf_hi(w) : bf_lo(w); }
 
 // ---- sum of squares of one chunk -------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kOptBlock) void adamw_sumsq_kernel(const qt_adamw_tensor *__restrict__ tensors, const int32_t *__restrict__ chunk_tensor,
@@ -275,5 +269,5 @@ extern "C" int qt_clip_adamw_bf16(qt_adamw_tensor *tensors_dev, const int32_t *c
     adamw_finalize_kernel<<<1, 1024, 0, st>>>(tensors_dev, ntensors, norm_sq, max_norm, bias_corr, scalars, total_norm_out_dev, phases & 1,
                                               (phases & 2) ? 1 : 0);
     if ((phases & 2) && nchunks > 0) adamw_apply_kernel<<<(unsigned)nchunks, kOptBlock, 0, st>>>(tensors_dev, chunk_tensor_dev, bias_corr, scalars, clip ? 1 : 0);
-    return opt_launch_status();
+    return qt_launch_status();
 }

@@ -321,8 +321,7 @@ int launch_softmax(const SoftmaxArgs &a, hipStream_t st) {
         if (grid < 1) grid = 1;
         if (g == 16) softmax_fq_kernel<KIND, 1, 16><<<grid, 256, 0, st>>>(a);
         else softmax_fq_kernel<KIND, 1, 32><<<grid, 256, 0, st>>>(a);
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? QT_OK : (int)e;
+        return qt_launch_status();
     }
     switch (nv) {
         case 1: softmax_fq_kernel<KIND, 1><<<grid, 256, 0, st>>>(a); break;
@@ -330,8 +329,7 @@ int launch_softmax(const SoftmaxArgs &a, hipStream_t st) {
         case 3: case 4: softmax_fq_kernel<KIND, 4><<<grid, 256, 0, st>>>(a); break;
         default: softmax_fq_kernel<KIND, kMaxVec><<<grid, 256, 0, st>>>(a); break;
     }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? QT_OK : (int)e;
+    return qt_launch_status();
 }
 
 }  // namespace
@@ -385,8 +383,7 @@ extern "C" int qt_mask_row_live(const uint16_t *mask, long rows, long cols, long
     if (rows == 0) return QT_OK;
     if (!mask || !out || rows < 0 || cols < 0 || row_stride < cols) return QT_ERR_BAD_ARG;
     mask_row_live_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, (hipStream_t)stream>>>(mask, rows, cols, row_stride, out, nullptr);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? QT_OK : (int)e;
+    return qt_launch_status();
 }
 
 extern "C" int qt_mask_row_live_checked(const uint16_t *mask, long rows, long cols, long row_stride, int *out, int *irregular_dev, void *stream) {
@@ -395,8 +392,7 @@ extern "C" int qt_mask_row_live_checked(const uint16_t *mask, long rows, long co
     if (rows == 0) return QT_OK;
     if (!mask || !out || rows < 0 || cols < 0 || row_stride < cols) return QT_ERR_BAD_ARG;
     mask_row_live_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, (hipStream_t)stream>>>(mask, rows, cols, row_stride, out, irregular_dev);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? QT_OK : (int)e;
+    return qt_launch_status();
 }
 
 extern "C" int qt_softmax_fq_bf16_fp8_live(const uint16_t *scores, const uint16_t *mask, uint8_t *out8, long batch, int heads, int q_len,
@@ -404,11 +400,9 @@ extern "C" int qt_softmax_fq_bf16_fp8_live(const uint16_t *scores, const uint16_
                                            const int *row_live, long live_sb, long live_sh, long live_sq, void *stream) {
     const long rows = batch * heads * q_len;
     if (rows == 0 || cols == 0) return QT_OK;
-    if (!scores || !out8 || !fmt || !mask || !row_live || batch < 0 || heads < 1 || q_len < 1 || cols < 0 || fmt->kind != QT_FMT_FP_SAT)
-        return QT_ERR_BAD_ARG;
-    const bool e5m2 = fmt->p0 == 2 && fmt->p1 == -14 && fmt->fhi == 57344.0f;
-    const bool e4m3 = fmt->p0 == 3 && fmt->p1 == -6 && fmt->fhi == 448.0f;
-    if (!e5m2 && !e4m3) return QT_ERR_BAD_ARG;
+    const int f8 = qt_fp8_code(fmt);
+    if (!scores || !out8 || !f8 || !mask || !row_live || batch < 0 || heads < 1 || q_len < 1 || cols < 0) return QT_ERR_BAD_ARG;
+    const bool e5m2 = f8 == 2;
     if (cols > 64L * 8 * kMaxVec) return QT_ERR_BAD_ARG;
     if ((cols & 7) || (((uintptr_t)scores | (uintptr_t)mask) & 15u) || ((uintptr_t)out8 & 7u) || ((mask_sb | mask_sh | mask_sq) & 7))
         return QT_ERR_UNALIGNED;
@@ -422,10 +416,9 @@ extern "C" int qt_softmax_fq_bf16_fp8(const uint16_t *scores, const uint16_t *ma
                                       const qt_format *fmt, void *stream) {
     const long rows = batch * heads * q_len;
     if (rows == 0 || cols == 0) return QT_OK;
-    if (!scores || !out8 || !fmt || batch < 0 || heads < 1 || q_len < 1 || cols < 0 || fmt->kind != QT_FMT_FP_SAT) return QT_ERR_BAD_ARG;
-    const bool e5m2 = fmt->p0 == 2 && fmt->p1 == -14 && fmt->fhi == 57344.0f;
-    const bool e4m3 = fmt->p0 == 3 && fmt->p1 == -6 && fmt->fhi == 448.0f;
-    if (!e5m2 && !e4m3) return QT_ERR_BAD_ARG;
+    const int f8 = qt_fp8_code(fmt);
+    if (!scores || !out8 || !f8 || batch < 0 || heads < 1 || q_len < 1 || cols < 0) return QT_ERR_BAD_ARG;
+    const bool e5m2 = f8 == 2;
     if (cols > 64L * 8 * kMaxVec) return QT_ERR_BAD_ARG;
     if ((cols & 7) || (((uintptr_t)scores | (uintptr_t)out | (uintptr_t)mask) & 15u) || ((uintptr_t)out8 & 7u) ||
         (mask && ((mask_sb | mask_sh | mask_sq) & 7)))
@@ -472,8 +465,7 @@ int launch_softmax_bwd(const SoftmaxBwdArgs &a, const qt_format &fmt, const uint
     else if (nvec <= 64) softmax_bwd_kernel<KIND, NS, 1, 64><<<grid, 256, 0, st>>>(a, fmt, lut);
     else if (nvec <= 128) softmax_bwd_kernel<KIND, NS, 2, 64><<<grid, 256, 0, st>>>(a, fmt, lut);
     else softmax_bwd_kernel<KIND, NS, 4, 64><<<grid, 256, 0, st>>>(a, fmt, lut);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? QT_OK : (int)e;
+    return qt_launch_status();
 }
 }  // namespace
 

@@ -108,6 +108,5 @@ extern "C" int qt_grad_fanin_bf16(const uint16_t *first_dev, const qt_fanin_item
         case QT_FMT_INT: launch_n<QT_FMT_INT>(a, count, grid, *fmt, lut_dev, st); break;
         default: return QT_ERR_BAD_DTYPE;
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? QT_OK : (int)e;
+    return qt_launch_status();
 }

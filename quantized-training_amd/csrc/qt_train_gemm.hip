@@ -88,9 +88,6 @@ __device__ __forceinline__ bf16x8 ld_frag_tr(const unsigned char *img, int c0, i
     return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
 }
 
-__device__ __forceinline__ uint32_t lds_addr(const void *p) {
-    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)p;
-}
 // one LDS-DMA piece: dma16 (qt_device.h), its waits counted by hand below
 template <int N>
 __device__ __forceinline__ void wait_and_barrier() {       // at most N of this wave's DMA pieces still in flight; LDS reads drained
@@ -349,16 +346,6 @@ __global__ __launch_bounds__(256) void train_gemm_skinny_kernel(SkinnyArgs a) {
     }
 }
 
-int cu_count() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n = v;
-        else n = 256;
-    }
-    return n;
-}
-
 template <bool TA, bool TB, int BM, int BN, int SS = 0>
 int launch_tile(Args &a, hipStream_t st) {
     constexpr int kStages = SS ? SS : Ring<BM, BN>::kStages;
@@ -374,8 +361,7 @@ int launch_tile(Args &a, hipStream_t st) {
     a.tiles_m = (a.M + BM - 1) / BM;
     a.tiles_n = (a.N + BN - 1) / BN;
     train_gemm_kernel<TA, TB, BM, BN, SS><<<a.count * a.tiles_m * a.tiles_n, kThreads, kLds, st>>>(a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? QT_OK : (int)e;
+    return qt_launch_status();
 }
 
 // Tile choice, a fixed rule of the layout, the problem sizes and the CU count (no timing: every process and rank cuts a shape the same
@@ -385,7 +371,7 @@ int launch_tile(Args &a, hipStream_t st) {
 //   transposed A (wgrad):             128 x 128 tiles under the same condition (3072 x 768: 144 tiles), else 64 x 64 (768 x 768: 144 tiles).
 // A 256 x 128 tile and whole-CU rings of 6-8 stages were built and measured too: no faster (19.4 against 19.0 us at 2048 x 3072 x 768).
 void pick_tile(const Args &a, bool trans_a, int &bm, int &bn) {
-    const int cus = cu_count();
+    const int cus = qt_cu_count();
     const int big_m = 128, big_n = trans_a ? 128 : 64;
     const long tiles = (long)a.count * ((a.M + big_m - 1) / big_m) * ((a.N + big_n - 1) / big_n);
     if (tiles * 2 >= cus) { bm = big_m; bn = big_n; }
@@ -403,7 +389,7 @@ int launch(Args &a, hipStream_t st, int force_bm, int force_bn) {
         // these kernels: a CU moves its operands at 85-100 GB/s whatever the tile, and 768 tiles of 128 x 64 are three per CU -- two
         // together, then one alone at a third of the rate.  128 x 192 tiles are one per CU (2048 x 3072: 256; q / k / v together: 192)
         // and need 491 KB per CU instead of 885.
-        const int cus = cu_count();
+        const int cus = qt_cu_count();
         const long tm = (a.M + 127) / 128;
         const long t64 = (long)a.count * tm * ((a.N + 63) / 64), t192 = (long)a.count * tm * (a.N / 192);
         if (!force_bm && !force_bn && a.N % 192 == 0 && t64 > 2L * cus && t192 * 10 >= 7L * cus) return launch_tile<false, false, 128, 192>(a, st);
@@ -440,8 +426,7 @@ int launch_backward(Args &w, Args &d, hipStream_t st) {
     d.tiles_n = (d.N + 63) / 64;
     const long grid = (long)w.count * w.tiles_m * w.tiles_n + (long)d.count * d.tiles_m * d.tiles_n;
     train_gemm_backward_kernel<BMW, BNW><<<(unsigned)grid, kThreads, kLds, st>>>(w, d);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? QT_OK : (int)e;
+    return qt_launch_status();
 }
 
 }  // namespace
@@ -490,8 +475,7 @@ int qt_train_gemm_bf16(const qt_gemm_problem *problems, int count, int trans_a, 
         if (((uintptr_t)p.c | (uintptr_t)p.bias) & 1u) return QT_ERR_UNALIGNED;
         const SkinnyArgs sa{p.a, p.b, p.bias, p.c, M, N, K, lda, ldb, ldc};
         train_gemm_skinny_kernel<<<(unsigned)(((long)M * N + 3) / 4), 256, 0, (hipStream_t)stream>>>(sa);
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? QT_OK : (int)e;
+        return qt_launch_status();
     }
     // (what the package's callers check before they come here; anything else keeps the library GEMM)
     if (K < 4 * kBK || K % kBK != 0 || M % 8 != 0 || N % 8 != 0 || M < 8 || N < 8 || lda % 8 != 0 || ldb % 8 != 0 || ldc % 4 != 0) return QT_ERR_BAD_ARG;
