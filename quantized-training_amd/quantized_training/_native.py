@@ -275,6 +275,12 @@ def check(code, what=""):
         raise QtError(f"libqt_hip {what}: {msg} (code {code})")
 
 
+def declined(code, dtype=False):
+    """True when a native entry point did not take the problem (shape, alignment; with `dtype`, the dtype too) and the caller goes on
+    to its next route; any other non-zero code is an error for check()."""
+    return code in (QT_ERR_BAD_ARG, QT_ERR_UNALIGNED) or (dtype and code == QT_ERR_BAD_DTYPE)
+
+
 def build_map_u16(dtype):
     """uint16[65536] numpy array of bf16 bit patterns (host)."""
     import numpy as np

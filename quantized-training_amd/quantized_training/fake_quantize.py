@@ -24,7 +24,7 @@ from typing import Optional
 import torch
 from torch.ao.quantization import FakeQuantizeBase
 
-from . import _native
+from . import _native, handover
 from .quantizer.quantizer import QScheme
 
 __all__ = [
@@ -164,45 +164,6 @@ def _launch_format(fmt, lut):
 # ----------------------------------------------------------------------------------------------
 # device plumbing
 # ----------------------------------------------------------------------------------------------
-def handover_valid(t):
-    """Producer kernels hand results to their consumers through Python attributes on the tensor (`_qt_fq_done_by`,
-    `_qt_fp8`, ...), stamped with the tensor's version counter (`_qt_ver`): an in-place modification in between (a user
-    forward hook, `add_`) makes them stale, and the consumer then does its own pass."""
-    return getattr(t, "_qt_ver", None) == t._version
-
-
-_LAZY = {}          # data_ptr -> weakref of a tensor whose values were not written (its FP8 codes were): views of it lose the attribute
-
-
-def note_lazy(t):
-    """Registers t (model_fusions._mark_lazy, rope_fq) so that a VIEW of it -- a reshape between the producer and the consuming hook
-    drops Python attributes -- is still recognised by materialize_lazy.  The entry dies with the tensor."""
-    import weakref
-    ptr = t.data_ptr()
-    _LAZY[ptr] = weakref.ref(t)
-    weakref.finalize(t, lambda p=ptr: _LAZY.pop(p, None) if (_LAZY.get(p) is not None and _LAZY[p]() is None) else None)
-
-
-def materialize_lazy(t):
-    """A producer that knew its consumer multiplies FP8 codes wrote ONLY the codes of fq(t) (t._qt_lazy; model_fusions.rope_fq).  The
-    fake-quantized values are exactly what the codes decode to, so whoever asks for them after all gets them here."""
-    if t.__dict__.get("_qt_lazy", False):
-        t.copy_(t._qt_fp8.to(t.dtype))
-        t._qt_lazy = False
-        t._qt_ver = t._version
-        return
-    if _LAZY:
-        ref = _LAZY.get(t.data_ptr())
-        base = ref() if ref is not None else None
-        if (base is not None and base is not t and base.__dict__.get("_qt_lazy", False) and base.device == t.device and base.dtype == t.dtype
-                and base.numel() == t.numel() and t.is_contiguous()):
-            # a view of a lazy tensor (same storage, same extent): decode through the owner
-            stamped = getattr(t, "_qt_ver", None) == t._version
-            materialize_lazy(base)
-            if stamped:
-                t._qt_ver = t._version
-
-
 def _stream_ptr(t):
     """Current stream of the tensor's device for the native call that follows; that call runs with the tensor's device
     current (`_native.note_device`), so `model.to("cuda:1")` or a `dispatch_model` placement needs no `set_device`."""
@@ -513,7 +474,7 @@ class FusedAmaxObsFakeQuantFunction(torch.autograd.Function):
             _native.check(L.qt_fake_quant_bf16_fp8(
                 x.data_ptr(), y.data_ptr() if y is not None else None, y8.data_ptr(), x.numel(), ctypes.byref(fmt),
                 scale.data_ptr(), amax_history.data_ptr() if observe else None, _stream_ptr(x)), "qt_fake_quant_bf16_fp8")
-            y8 = y8.view(torch.float8_e5m2 if fmt.p0 == 2 else torch.float8_e4m3fn)
+            y8 = handover.fp8_view(y8, fmt)
             if only:
                 return y8
             ctx.mark_non_differentiable(y8)
@@ -808,34 +769,28 @@ class FusedAmaxObsFakeQuantize(FakeQuantizeBase):
                 out = train_fusions.run_chain(self, chain, X)
                 if out is not None:
                     return out
-        done_by = getattr(X, "_qt_fq_done_by", None)
-        if done_by is self and handover_valid(X):
-            # the kernel that produced X already applied this fake-quantizer (and attached X._qt_fp8): the call the
+        done_by = handover.done_by(X, unchecked=True)          # (unchecked read: each use below checks validity itself)
+        if done_by is self and handover.valid(X):
+            # the kernel that produced X already applied this fake-quantizer (and attached its FP8 codes): the call the
             # reference issues here is satisfied by that fused computation, counted once
             _Stats.add(X.numel())
             if not self.__dict__.get("_qt_lazy_ok"):          # (set by model_fusions.codes_only_ok: the consumer decodes on demand)
-                materialize_lazy(X)
+                handover.materialize(X)
             return X
-        also = getattr(X, "_qt_also_done", None)
-        if also is not None and handover_valid(X):
+        also = handover.also_done(X)
+        if also is not None:
             # the producing kernel evaluated this fake-quantizer on its result as well (a norm with several consuming Linears,
             # model_fusions._norm_with_consumers): X holds the fake-quantized values (one format for all the consumers), these are this
             # call's own codes
             for fq, x8 in also:
                 if fq is self:
                     _Stats.add(X.numel())
-                    if X.__dict__.get("_qt_lazy", False) and not self.__dict__.get("_qt_lazy_ok"):
-                        materialize_lazy(X)
-                    out = X.view(X.shape)
-                    out._qt_fp8 = x8
-                    out._qt_ver = out._version
-                    out._qt_origin = (X.data_ptr(), X._version, tuple(X.shape))
-                    if X.__dict__.get("_qt_lazy", False):
-                        out._qt_lazy = True                   # the producer wrote the codes only; this consumer decodes on demand
-                    return out
-        materialize_lazy(X)          # every path below reads X's values: a producer may have written its FP8 codes only
-        if (done_by is not None and self._emit_fp8 and isinstance(done_by, FusedAmaxObsFakeQuantize) and handover_valid(X)
-                and getattr(X, "_qt_fp8", None) is not None and X.is_cuda and X.dtype == torch.bfloat16 and X.is_contiguous()
+                    if handover.is_lazy(X) and not self.__dict__.get("_qt_lazy_ok"):
+                        handover.materialize(X)
+                    return handover.carry(X, x8, X)           # (lazy when the producer wrote the codes only: this consumer decodes on demand)
+        handover.materialize(X)          # every path below reads X's values: a producer may have written its FP8 codes only
+        if (done_by is not None and self._emit_fp8 and isinstance(done_by, FusedAmaxObsFakeQuantize)
+                and handover.codes(X) is not None and X.is_cuda and X.dtype == torch.bfloat16 and X.is_contiguous()
                 and not (torch.is_grad_enabled() and X.requires_grad) and self.producer_fusable() and done_by.producer_fusable()
                 and done_by._qt_format.key() == self._qt_format.key()):
             # X was produced by an identical stateless fake-quantizer (a sibling's: q beside k, v; gate beside up), so it lies on
@@ -846,11 +801,7 @@ class FusedAmaxObsFakeQuantize(FakeQuantizeBase):
             _Stats.add(X.numel())
             x8 = FusedAmaxObsFakeQuantFunction.apply(X, False, True, self.qmap, self.amax_history, self.scale, self.amax_history_len,
                                                       self.quant_max, None, False, False, self._qt_format, "only")
-            out = X.view(X.shape)
-            out._qt_fp8 = x8
-            out._qt_ver = out._version
-            out._qt_origin = (X.data_ptr(), X._version, tuple(X.shape))
-            return out
+            return handover.carry(X, x8, X)
         expect = self.__dict__.get("_qt_expected")
         if expect is not None:
             # same hand-over when the producer's tensor reaches the hook as a view (a reshape in between drops Python
@@ -860,18 +811,11 @@ class FusedAmaxObsFakeQuantize(FakeQuantizeBase):
             if X.data_ptr() == ptr and X.numel() == numel and X._version == version and X.is_contiguous():
                 _Stats.add(numel)
                 if replacement is not None:
-                    out = replacement.view(X.shape)
-                    out._qt_fp8 = x8.view(X.shape)
-                    out._qt_ver = out._version
-                    out._qt_origin = (ptr, version, tuple(X.shape))       # fq(.) of X, for sibling GEMMs
-                    if replacement.__dict__.get("_qt_lazy", False):       # the producer wrote the codes only
-                        out._qt_lazy = True
-                        if not self.__dict__.get("_qt_lazy_ok"):
-                            materialize_lazy(out)
+                    out = handover.carry(replacement, x8.view(X.shape), X)                     # fq(.) of X, for sibling GEMMs
+                    if handover.is_lazy(out) and not self.__dict__.get("_qt_lazy_ok"):         # the producer wrote the codes only
+                        handover.materialize(out)
                     return out
-                X._qt_fp8 = x8
-                X._qt_ver = X._version
-                return X
+                return handover.stamp(X, codes=x8)
         pre = self.__dict__.get("_qt_pre")
         if pre is not None:
             # BatchedWeightFakeQuant computed this call in front of the step (same scale, same amax slot): valid for this -- the very
@@ -923,14 +867,10 @@ class FusedAmaxObsFakeQuantize(FakeQuantizeBase):
             self._emit_fp8 if (self._emit_fp8 and self.fp8_exact()) else None,
         )
         if isinstance(X, tuple):
-            src = orig_in
             X, x8 = X
-            X._qt_fp8 = x8
-            X._qt_ver = X._version
-            X._qt_origin = (src.data_ptr(), src._version, tuple(src.shape))    # which tensor this is fq(.) of (sibling GEMMs)
+            handover.stamp(X, codes=x8, origin=handover.tensor_key(orig_in))      # which tensor this is fq(.) of (sibling GEMMs)
         elif X is not orig_in and self.qscheme is None and not self._observe:
-            X._qt_origin = (orig_in.data_ptr(), orig_in._version, tuple(orig_in.shape))
-            X._qt_ver = X._version
+            handover.stamp(X, origin=handover.tensor_key(orig_in))
 
         if self.outlier_threshold is not None:                              # upstream :401-402
             X = torch.where(mask, X, orig_X)

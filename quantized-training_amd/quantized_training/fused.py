@@ -9,9 +9,8 @@ import os
 
 import torch
 
-from . import _native
-from .fake_quantize import (STATS, FusedAmaxObsFakeQuantFunction, FusedAmaxObsFakeQuantize, _stream_ptr, handover_valid,
-                            launch_scale_update, materialize_lazy)
+from . import _native, handover
+from .fake_quantize import STATS, FusedAmaxObsFakeQuantFunction, FusedAmaxObsFakeQuantize, _stream_ptr, launch_scale_update
 from .quantizer.quantizer import QScheme
 
 _IDENTITY = _native.QtFormat(_native.QT_FMT_IDENTITY, 0, 0, 0.0, 0.0)
@@ -146,7 +145,7 @@ def hip_fq8_linear_or_none(x8, layers):
     nn = (ctypes.c_int * n)(*ns)
     rc = _native.lib().qt_linear_fq8_bf16(x8.data_ptr(), _F8_CODE[x8.dtype], wp, bp, nn, n, 1 if wf.p0 == 2 else 0, y.data_ptr(),
                                            M, K, _stream_ptr(x8))
-    if rc in (_native.QT_ERR_BAD_ARG, _native.QT_ERR_UNALIGNED, _native.QT_ERR_BAD_DTYPE):
+    if _native.declined(rc, dtype=True):
         return None
     _native.check(rc, "qt_linear_fq8_bf16")
     return y
@@ -214,8 +213,6 @@ class SiblingGroup:
         self.stash = None                      # (origin key, product [M, sum N], taken flags)
 
     def eligible(self):
-        def fmt_key(f):
-            return (f.kind, f.p0, f.p1, f.flo, f.fhi)
         K = self.layers[0].weight.shape[1]
         w_fmt = a_fmt = None
         with_bias = self.layers[0].bias is not None
@@ -232,8 +229,8 @@ class SiblingGroup:
             if not (isinstance(afq, FusedAmaxObsFakeQuantize) and afq.producer_fusable()):
                 return False
             if w_fmt is None:
-                w_fmt, a_fmt = fmt_key(fq._qt_format), fmt_key(afq._qt_format)
-            elif fmt_key(fq._qt_format) != w_fmt or fmt_key(afq._qt_format) != a_fmt:
+                w_fmt, a_fmt = fq._qt_format.key(), afq._qt_format.key()
+            elif fq._qt_format.key() != w_fmt or afq._qt_format.key() != a_fmt:
                 return False
         return True
 
@@ -250,14 +247,12 @@ class SiblingGroup:
 
 
 def value_key(value):
-    return (value.data_ptr(), value._version, tuple(value.shape), value.stride())
+    return (*handover.tensor_key(value), value.stride())
 
 
 def _origin_key(x):
-    o = getattr(x, "_qt_origin", None)
-    if o is not None:
-        return o
-    return (x.data_ptr(), x._version, tuple(x.shape))         # the leader's input was handed through by its hook
+    # a hook's output names its origin (unchecked read, as ever: it goes straight to its Linear); the leader's input was handed through by its hook
+    return handover.origin(x, unchecked=True) or handover.tensor_key(x)
 
 
 def hip_mlp_fq8_or_none(x8, gate, up, out_fq, codes_only=False):
@@ -284,7 +279,7 @@ def hip_mlp_fq8_or_none(x8, gate, up, out_fq, codes_only=False):
                                         gate.bias.data_ptr() if gate.bias is not None else None, up.bias.data_ptr() if up.bias is not None else None,
                                         N, 1 if fg.p0 == 2 else 0, None if codes_only else h.data_ptr(), h8.data_ptr(),
                                         ctypes.byref(out_fq._qt_format), M, K, _stream_ptr(x8))      # codes_only: h stays unwritten (`_qt_lazy`)
-    if rc in (_native.QT_ERR_BAD_ARG, _native.QT_ERR_UNALIGNED, _native.QT_ERR_BAD_DTYPE):
+    if _native.declined(rc, dtype=True):
         return None
     _native.check(rc, "qt_mlp_fq8_bf16")
     return h, h8
@@ -392,7 +387,7 @@ class BatchedWeightCodes:
             _native.check(_native.lib().qt_fake_quant_multi_bf16_fp8(items.data_ptr(), count, tiles, ctypes.byref(fmt), _stream_ptr(items)),
                           "qt_fake_quant_multi_bf16_fp8")
             for owner, layers, codes in members:
-                w8 = codes.view(torch.float8_e5m2 if fmt.p0 == 2 else torch.float8_e4m3fn)
+                w8 = handover.fp8_view(codes, fmt)
                 _W8_PRE[id(owner)] = (tuple((l.weight.data_ptr(), l.weight._version) for l in layers), w8)
 
     def forget(self):
@@ -443,7 +438,7 @@ def _sibling_linear_or_none(layer, x, x8):
         ns = (ctypes.c_size_t * n)(*[l.weight.numel() for l in group.layers])
         _native.check(L.qt_fake_quant_bf16_fp8_multi(xs, ns, n, group.buf.data_ptr(), ctypes.byref(fq._qt_format),
                                                      _stream_ptr(x)), "qt_fake_quant_bf16_fp8_multi")
-        w8 = group.buf.view(torch.float8_e5m2 if fq._qt_format.p0 == 2 else torch.float8_e4m3fn)
+        w8 = handover.fp8_view(group.buf, fq)
         _note_weight_pass(group, group.layers)
     bias = group.bias_or_none()
     if bias is False:
@@ -458,11 +453,11 @@ def _sibling_linear_or_none(layer, x, x8):
 
 def fp8_linear_or_none(layer, x):
     """E4M3 / E5M2 fake-quant Linear with scale 1 on the FP8 matrix cores: the activation pass already
-    produced FP8 bytes (x._qt_fp8), the weight pass writes FP8 only (3 B/element of traffic instead of
+    produced FP8 bytes (handover.codes(x)), the weight pass writes FP8 only (3 B/element of traffic instead of
     4 and nothing for the GEMM to re-read in bf16), and the products q_x * q_w are exactly the
     reference's bf16 products; fp32 accumulation, bf16 output.  Library FP8 GEMM (hipBLASLt through
     torch._scaled_mm) -- a plain GEMM on already-quantized operands."""
-    x8 = getattr(x, "_qt_fp8", None) if handover_valid(x) else None
+    x8 = handover.codes(x)
     fq = layer.weight_fake_quant
     if x8 is None or not fp8_gemm_enabled() or not isinstance(fq, FusedAmaxObsFakeQuantize) or not fq.fp8_exact():
         return None
@@ -610,7 +605,7 @@ def fused_linear_or_none(layer, x):
     out = fp8_linear_or_none(layer, x)
     if out is not None:
         return out
-    materialize_lazy(x)                      # every other route reads the values: a producer may have written the FP8 codes only
+    handover.materialize(x)                      # every other route reads the values: a producer may have written the FP8 codes only
     out = fqt_linear_or_none(layer, x)
     if out is not None:
         return out
@@ -749,7 +744,7 @@ def hip_fqt_linear_or_none(x2, layers, tables):
                                               ws.data_ptr() if ws is not None else None, ws.numel() * 4 if ws is not None else 0,
                                               tickets.data_ptr() if tickets is not None else None, tickets.numel() if tickets is not None else 0,
                                               _stream_ptr(x2))
-    if rc in (_native.QT_ERR_BAD_ARG, _native.QT_ERR_UNALIGNED, _native.QT_ERR_BAD_DTYPE):
+    if _native.declined(rc, dtype=True):
         return None
     _native.check(rc, "qt_linear_fqt_ws_bf16")
     return y
@@ -844,7 +839,7 @@ def fqt_linear_or_none(layer, x):
             same = same and all(isinstance(f, FusedAmaxObsFakeQuantize) and f.stateless_map() and str(f.dtype) == str(afq[0].dtype) for f in afq)
             # x is the fake-quantized image of one tensor: a hook's output (`_qt_origin`), or a producer kernel's result that the leader's
             # hook handed through (model_fusions.rmsnorm_map; the siblings' hooks then name it as their origin)
-            shared = getattr(x, "_qt_origin", None) is not None or (getattr(x, "_qt_fq_done_by", None) is not None and handover_valid(x))
+            shared = handover.origin(x, unchecked=True) is not None or handover.done_by(x) is not None      # (origin: unchecked, as in _origin_key)
             if same and shared and _fqt_route(M, Ns, K, x.device):
                 if not x2.is_contiguous():
                     x2 = x2.contiguous()
@@ -989,14 +984,14 @@ def _fp8_probs_times_v_or_none(L, st, scores, mask, msb, msh, msq, scaling, fq_p
         return None
     if (B * H, Q, C, D) in _LT.setdefault("no_pv", set()):
         return None                            # the library had no kernel for this problem last time
-    done = getattr(value, "_qt_fq_done_by", None) if handover_valid(value) else None
-    v8 = getattr(value, "_qt_fp8", None)
+    done = handover.done_by(value)
+    v8 = handover.codes(value, unchecked=True)             # (unchecked read: used only beside the checked `done` below)
     if not (done is fq_v and v8 is not None and value.is_contiguous()):
         v8u = torch.empty((B, H, C, D), dtype=torch.uint8, device=value.device)     # only the codes feed the FP8 P.V GEMM
         _native.check(L.qt_fake_quant_rows_bf16_fp8(value.data_ptr(), None, v8u.data_ptr(), B, H, C, D,
                                                     value.stride(0), value.stride(1), value.stride(2),
                                                     ctypes.byref(fq_v._qt_format), st), "qt_fake_quant_rows_bf16_fp8")
-        v8 = v8u.view(torch.float8_e5m2 if fq_v._qt_format.p0 == 2 else torch.float8_e4m3fn)
+        v8 = handover.fp8_view(v8u, fq_v)
     p8u = torch.empty((B, H, Q, C), dtype=torch.uint8, device=scores.device)
     # (qt_softmax_fq_bf16_fp8_live -- the same pass told each mask row's extent -- is bit-identical and gains a tenth alone on cold
     # buffers, nothing inside the window where the scores the Q.K^T GEMM just wrote are cache-resident: 12.97 against 12.88 ms; it
@@ -1004,7 +999,7 @@ def _fp8_probs_times_v_or_none(L, st, scores, mask, msb, msh, msq, scaling, fq_p
     _native.check(L.qt_softmax_fq_bf16_fp8(scores.data_ptr(), mask.data_ptr() if mask is not None else None, None,
                                            p8u.data_ptr(), B, H, Q, C, msb, msh, msq, float(scaling),
                                            ctypes.byref(fq_p._qt_format), st), "qt_softmax_fq_bf16_fp8")
-    p8 = p8u.view(torch.float8_e5m2 if fq_p._qt_format.p0 == 2 else torch.float8_e4m3fn)
+    p8 = handover.fp8_view(p8u, fq_p)
     out = lt_fp8_gemm(p8.view(B * H, Q, C), v8.view(B * H, C, D), None, b_is_kn=True)
     if out is None:
         _LT["no_pv"].add((B * H, Q, C, D))     # the bf16 path redoes (and counts) the two passes
@@ -1050,8 +1045,8 @@ def _attention_fp8_or_none(attn, query, key, value, attention_mask, scaling, fqs
         return None
 
     def handed(t, fq, rows):
-        t8 = getattr(t, "_qt_fp8", None)
-        if t8 is None or not handover_valid(t) or t._qt_fq_done_by is not fq or not t8.is_contiguous() or tuple(t8.shape) != (B, H, rows, D):
+        t8 = handover.codes(t)
+        if t8 is None or handover.done_by(t) is not fq or not t8.is_contiguous() or tuple(t8.shape) != (B, H, rows, D):
             return None
         return t8
 
@@ -1134,7 +1129,7 @@ def _attention_fp8_or_none(attn, query, key, value, attention_mask, scaling, fqs
                                      ctypes.byref(fq_o._qt_format) if fq_o is not None else None, B, H, Q, C, D, float(scaling), st),
                   "qt_attention_fp8")
     if fq_o is not None:
-        fq_o.expect_prequantized(out, out8.view(torch.float8_e5m2 if fq_o._qt_format.p0 == 2 else torch.float8_e4m3fn))
+        fq_o.expect_prequantized(out, handover.fp8_view(out8, fq_o))
     return out
 
 

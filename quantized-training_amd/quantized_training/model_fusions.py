@@ -21,7 +21,7 @@ import os
 
 import torch
 
-from . import _native
+from . import _native, handover
 from .fake_quantize import FusedAmaxObsFakeQuantize, _stream_ptr
 
 __all__ = ["apply_llama_fusions", "apply_bert_fusions", "rmsnorm", "silu_mul", "rope", "layernorm", "gelu"]
@@ -155,13 +155,8 @@ def _norm_with_consumers(x2, r2, weight, eps, fqs, codes_only=False):
         _native.check(_native.lib().qt_rmsnorm_fq8_bf16(x2.data_ptr(), weight.data_ptr(), None if codes_only else y.data_ptr(), y8.data_ptr(),
                                                         x2.numel() // cols, cols, float(eps), ctypes.byref(f0._qt_format), _stream_ptr(x2)),
                       "qt_rmsnorm_fq8_bf16")
-    codes = _fp8_view(y8, f0)
-    y._qt_fp8 = codes
-    y._qt_fq_done_by = f0
-    y._qt_also_done = [(f, codes) for f in fqs[1:]]
-    y._qt_ver = y._version
-    if codes_only:
-        _mark_lazy(y)                                 # (model_fusions.codes_only_ok: every consumer multiplies the codes)
+    codes = handover.fp8_view(y8, f0)
+    handover.stamp(y, f0, codes, also=[(f, codes) for f in fqs[1:]], lazy=codes_only)     # (codes_only_ok: every consumer multiplies the codes)
     return total, y
 
 
@@ -182,12 +177,7 @@ def rmsnorm_fq(x, weight, eps, fq, codes_only=False):
     _native.check(_native.lib().qt_rmsnorm_fq8_bf16(x2.data_ptr(), weight.data_ptr(), None if codes_only else y.data_ptr(), y8.data_ptr(),
                                                     x2.numel() // cols, cols, float(eps), ctypes.byref(fq._qt_format),
                                                     _stream_ptr(x2)), "qt_rmsnorm_fq8_bf16")
-    y._qt_fp8 = _fp8_view(y8, fq)
-    y._qt_fq_done_by = fq
-    y._qt_ver = y._version
-    if codes_only:
-        _mark_lazy(y)
-    return y
+    return handover.stamp(y, fq, handover.fp8_view(y8, fq), lazy=codes_only)
 
 
 def add_rmsnorm(x, residual, norm, fq=None, codes_only=False):
@@ -213,11 +203,7 @@ def add_rmsnorm(x, residual, norm, fq=None, codes_only=False):
         y8.data_ptr() if y8 is not None else None, x2.numel() // cols, cols, float(norm.variance_epsilon),
         ctypes.byref(fq._qt_format) if fq is not None else None, _stream_ptr(x2)), "qt_add_rmsnorm_bf16")
     if fq is not None:
-        y._qt_fp8 = _fp8_view(y8, fq)
-        y._qt_fq_done_by = fq
-        y._qt_ver = y._version
-        if codes_only:
-            _mark_lazy(y)
+        handover.stamp(y, fq, handover.fp8_view(y8, fq), lazy=codes_only)
     return total, y
 
 
@@ -249,11 +235,7 @@ def consumer_fq_map(linear):
 def _mark_done(y, fqs):
     """y = fq(result) for every fake-quantizer in `fqs` (one stateless format: their calls are idempotent repeats): the first hands y
     through, the others find themselves in `_qt_also_done` (fake_quantize.py, FusedAmaxObsFakeQuantize.forward)."""
-    y._qt_fq_done_by = fqs[0]
-    if len(fqs) > 1:
-        y._qt_also_done = [(f, None) for f in fqs[1:]]
-    y._qt_ver = y._version
-    return y
+    return handover.stamp(y, fqs[0], also=[(f, None) for f in fqs[1:]] or None)
 
 
 def rmsnorm_map(x, residual, weight, eps, fqs, sum_fq=None):
@@ -343,11 +325,8 @@ def _norm_consumer_fq(norm, allow_all=False, allow_map=False):
             if all(f is not None for f in mfqs) and len({f.dtype for f in mfqs}) == 1:
                 return ("map", mfqs)
         return None
-    f0 = fqs[0]._qt_format
-    for f in fqs[1:]:
-        g = f._qt_format
-        if (g.kind, g.p0, g.p1, g.flo, g.fhi) != (f0.kind, f0.p0, f0.p1, f0.flo, f0.fhi):
-            return None
+    if any(f._qt_format.key() != fqs[0]._qt_format.key() for f in fqs[1:]):
+        return None
     if allow_all and 2 <= len(fqs) <= 3 and len({id(f) for f in fqs}) == len(fqs):
         return fqs                                   # all of them in the norm's launch (_norm_with_consumers)
     return fqs[0]
@@ -396,7 +375,7 @@ def consumer_fq(linear):
 def codes_only_ok(linears, producer=None):
     """True when a producer kernel may write ONLY the FP8 codes of its fake-quantized result for these consumers (the bf16 tensor stays
     unwritten, `_qt_lazy`): every consumer is a QAT Linear whose own forward runs (it multiplies the codes, and asks
-    fake_quantize.materialize_lazy for the values on every other route), reached through its single input hook, under no_grad; and
+    handover.materialize for the values on every other route), reached through its single input hook, under no_grad; and
     nobody hooked the producing module (a forward hook would be handed the unwritten tensor)."""
     from . import fused
     from .modules.qat.linear import Linear as QATLinear
@@ -415,24 +394,6 @@ def codes_only_ok(linears, producer=None):
     return True
 
 
-def _mark_lazy(t):
-    """t's values were not written (its FP8 codes were).  QT_LAZY_POISON=1 (tests): fill it with NaN, so that a read that bypasses
-    fake_quantize.materialize_lazy cannot go unnoticed."""
-    if os.environ.get("QT_LAZY_POISON", "0") == "1":
-        stamped = getattr(t, "_qt_ver", None) == t._version
-        t.fill_(float("nan"))
-        if stamped:
-            t._qt_ver = t._version                    # (the fill is not a modification of the result the hand-over describes)
-    t._qt_lazy = True
-    from .fake_quantize import note_lazy
-    note_lazy(t)
-    return t
-
-
-def _fp8_view(t8, fq):
-    return t8.view(torch.float8_e5m2 if fq._qt_format.p0 == 2 else torch.float8_e4m3fn)
-
-
 def silu_mul_fq(gate, up, fq):
     """SiLU * up with `fq` (the down-projection's input fake-quantizer) applied in the same pass; the result is
     marked so that the hook returns it unchanged."""
@@ -443,10 +404,7 @@ def silu_mul_fq(gate, up, fq):
     _native.check(_native.lib().qt_silu_mul_fq8_bf16(g.data_ptr(), u.data_ptr(), y.data_ptr(), y8.data_ptr(), rows, cols,
                                                      rs_g, rs_u, ctypes.byref(fq._qt_format), _stream_ptr(g)),
                   "qt_silu_mul_fq8_bf16")
-    y._qt_fp8 = _fp8_view(y8, fq)
-    y._qt_fq_done_by = fq
-    y._qt_ver = y._version
-    return y
+    return handover.stamp(y, fq, handover.fp8_view(y8, fq))
 
 
 def transpose_fq(out, fq):
@@ -461,7 +419,7 @@ def transpose_fq(out, fq):
                                                             src.stride(0), src.stride(1), src.stride(2),
                                                             ctypes.byref(fq._qt_format), _stream_ptr(out)),
                   "qt_fake_quant_rows_bf16_fp8")
-    fq.expect_prequantized(y, _fp8_view(y8, fq))
+    fq.expect_prequantized(y, handover.fp8_view(y8, fq))
     return y
 
 
@@ -507,7 +465,7 @@ def rope_fq(q, k, cos, sin, fq_q, fq_k, value_job=None):
     value_job = (attn, value, fq_v), set when the FP8 attention kernel is what will consume these tensors (_fp8_attention_plan): the
     launch then also carries that kernel's value-code pass (qt_rope_fq_value), and writes the FP8 codes ONLY -- the kernel multiplies
     codes; should anything else ask for the bf16 values after all (the fake-quantizers' hand-over is the one door to them), they are
-    decoded from the codes then, exactly (fake_quantize.materialize_lazy)."""
+    decoded from the codes then, exactly (handover.materialize)."""
     B, Hq, S, D = q.shape
     Hk = k.shape[1]
     q_out = torch.empty((B, Hq, S, D), dtype=q.dtype, device=q.device)
@@ -529,16 +487,10 @@ def rope_fq(q, k, cos, sin, fq_q, fq_k, value_job=None):
                                                      vt8.data_ptr(), value.stride(0), value.stride(1), value.stride(2),
                                                      ctypes.byref(fq_v._qt_format), _stream_ptr(q)), "qt_rope_fq_value")
         attn.__dict__["_qt_vt8"] = (fused.value_key(value), fq_v, vt8)
-        q_out._qt_lazy = k_out._qt_lazy = True               # bf16 values not written: see the docstring
-    q_out._qt_fq_done_by = fq_q
-    q_out._qt_ver = q_out._version
-    k_out._qt_fq_done_by = fq_k
-    k_out._qt_ver = k_out._version
-    q_out._qt_fp8 = _fp8_view(q8, fq_q)                 # Q.K^T can then run as an FP8 GEMM (functional_modules.py)
-    q_out._qt_ver = q_out._version
-    k_out._qt_fp8 = _fp8_view(k8, fq_k)
-    k_out._qt_ver = k_out._version
-    return q_out, k_out
+    # with the codes Q.K^T can run as an FP8 GEMM (functional_modules.py).  lazy: bf16 values not written, see the docstring (flag alone)
+    lazy = value_job is not None
+    return (handover.stamp(q_out, fq_q, handover.fp8_view(q8, fq_q), lazy=lazy, register=False),
+            handover.stamp(k_out, fq_k, handover.fp8_view(k8, fq_k), lazy=lazy, register=False))
 
 
 # ---- BERT-style blocks -----------------------------------------------------------------------------------------------
@@ -551,36 +503,22 @@ def layernorm(x, norm, residual=None, fq=None, codes_only=False):
     x2 = x.contiguous()
     r2 = residual.contiguous() if residual is not None else None
     y = torch.empty_like(x2)
-    if isinstance(fq, (list, tuple)):
-        if len(fq) > 1:
-            # every consuming Linear's input fake-quantizer in this launch (qt_layernorm_consumers_bf16): each then finds its own codes
-            # (and the shared fake-quantized values) waiting for its next call
-            fqs, n = fq, len(fq)
-            yq = torch.empty_like(x2)
-            # equal formats (checked by _norm_consumer_fq): the consumers' codes are the same bytes -- one evaluation, one tensor
-            y8 = torch.empty(x2.shape, dtype=torch.uint8, device=x2.device)
-            _native.check(_native.lib().qt_layernorm_bf16(
-                x2.data_ptr(), r2.data_ptr() if r2 is not None else None, norm.weight.data_ptr(), norm.bias.data_ptr(), y.data_ptr(),
-                None if codes_only else yq.data_ptr(), y8.data_ptr(), x2.numel() // cols, cols, float(norm.eps),
-                ctypes.byref(fqs[0]._qt_format), _stream_ptr(x2)), "qt_layernorm_bf16")
-            if codes_only:
-                _mark_lazy(yq)
-            for f in fqs:
-                f.expect_prequantized(y, _fp8_view(y8, f), replacement=yq)
-            return y
-        fq = fq[0]
+    # a list: every consuming Linear's input fake-quantizer in this launch; each then finds its own codes (and the shared fake-quantized
+    # values) waiting for its next call.  Equal formats (checked by _norm_consumer_fq): the consumers' codes are the same bytes -- one
+    # evaluation, one tensor
+    fqs = list(fq) if isinstance(fq, (list, tuple)) else [fq] if fq is not None else []
     yq = y8 = None
-    if fq is not None:
+    if fqs:
         yq = torch.empty_like(x2)
         y8 = torch.empty(x2.shape, dtype=torch.uint8, device=x2.device)
     _native.check(_native.lib().qt_layernorm_bf16(
         x2.data_ptr(), r2.data_ptr() if r2 is not None else None, norm.weight.data_ptr(), norm.bias.data_ptr(), y.data_ptr(),
-        yq.data_ptr() if (yq is not None and not codes_only) else None, y8.data_ptr() if y8 is not None else None, x2.numel() // cols, cols,
-        float(norm.eps), ctypes.byref(fq._qt_format) if fq is not None else None, _stream_ptr(x2)), "qt_layernorm_bf16")
-    if fq is not None:
-        if codes_only:
-            _mark_lazy(yq)
-        fq.expect_prequantized(y, _fp8_view(y8, fq), replacement=yq)
+        yq.data_ptr() if (fqs and not codes_only) else None, y8.data_ptr() if fqs else None, x2.numel() // cols, cols,
+        float(norm.eps), ctypes.byref(fqs[0]._qt_format) if fqs else None, _stream_ptr(x2)), "qt_layernorm_bf16")
+    if fqs and codes_only:
+        handover.mark_lazy(yq)
+    for f in fqs:
+        f.expect_prequantized(y, handover.fp8_view(y8, f), replacement=yq)
     return y
 
 
@@ -595,11 +533,7 @@ def gelu(x, fq=None, codes_only=False):
                                              ctypes.byref(fq._qt_format) if fq is not None else None, _stream_ptr(x2)),
                   "qt_gelu_bf16")
     if fq is not None:
-        y._qt_fp8 = _fp8_view(y8, fq)
-        y._qt_fq_done_by = fq
-        y._qt_ver = y._version
-        if lazy:
-            _mark_lazy(y)
+        handover.stamp(y, fq, handover.fp8_view(y8, fq), lazy=lazy)
     return y
 
 
@@ -791,7 +725,7 @@ def _fused_mlp_or_none(self, x):
     the module chain still happens and is counted once: the two input fake-quantizers run as hooks (the second one on the already
     quantized tensor, as before), the two weight fake-quantizers and the consumer's inside the kernel."""
     from . import fused
-    from .fake_quantize import STATS, handover_valid
+    from .fake_quantize import STATS
     from .modules.qat.linear import Linear as QATLinear
     gate, up, down = self.gate_proj, self.up_proj, self.down_proj
     if os.environ.get("QT_FQ8_MLP", "1") == "0" or not fused.fq8_gemm_enabled() or fused._WEIGHT_CACHE["on"]:
@@ -809,9 +743,9 @@ def _fused_mlp_or_none(self, x):
         return None
     # The route is decided before any hook runs (a hook must not run twice): x has to arrive with the FP8 code its producer
     # (the RMSNorm kernel, for its first consumer) attached.
-    x8 = getattr(x, "_qt_fp8", None) if handover_valid(x) else None
+    x8 = handover.codes(x)
     prepared = bool(self.__dict__.get("_qt_prepared"))           # pt2e_fusion.PreparedMLP: no hooks, x comes out of the fake-quantizer's node
-    if x8 is None or (getattr(x, "_qt_fq_done_by", None) is None and not prepared) or not fused.fq8_route_is_fused(x8.reshape(-1, x8.shape[-1]), [gate]):
+    if x8 is None or (handover.done_by(x) is None and not prepared) or not fused.fq8_route_is_fused(x8.reshape(-1, x8.shape[-1]), [gate]):
         return None
     x8f = x8.reshape(-1, x8.shape[-1])
     for l in (gate, up):
@@ -819,7 +753,7 @@ def _fused_mlp_or_none(self, x):
     if not fused.mlp_route_is_one_launch(x8f, gate, up, fq_out):
         return None
     xg = _run_pre_hooks(gate, x)                               # gate's input fake-quantizer: hands the producer's result through, counted
-    x8 = getattr(xg, "_qt_fp8", None) if handover_valid(xg) else None
+    x8 = handover.codes(xg)
     xu = _run_pre_hooks(up, x)                                 # up's own input fake-quantizer: same values, still computed and counted
     if x8 is None:
         return _after_hooks_unfused(self, xg, xu)
@@ -833,12 +767,7 @@ def _fused_mlp_or_none(self, x):
     STATS.add(up.weight.numel())
     h, h8 = got
     y = h.reshape(*x.shape[:-1], gate.weight.shape[0])
-    y._qt_fp8 = _fp8_view(h8.reshape(y.shape), fq_out)
-    y._qt_fq_done_by = fq_out
-    y._qt_ver = y._version
-    if lazy:
-        _mark_lazy(y)
-    return y
+    return handover.stamp(y, fq_out, handover.fp8_view(h8.reshape(y.shape), fq_out), lazy=lazy)
 
 
 def _after_hooks_unfused(self, xg, xu):

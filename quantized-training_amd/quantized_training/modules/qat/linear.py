@@ -48,7 +48,7 @@ def train_gemm_or_none(a, b, bias, trans_a, trans_b, kind):
     _native.note_device(a.device.index)
     rc = _native.lib().qt_train_gemm_bf16(prob, 1, int(trans_a), int(trans_b), M, N, K, a.stride(0), b.stride(0), N,
                                           ctypes.c_void_p(torch.cuda.current_stream(a.device).cuda_stream))
-    if rc in (_native.QT_ERR_BAD_ARG, _native.QT_ERR_UNALIGNED):
+    if _native.declined(rc):
         GEMM_ROUTES.setdefault(key, "library_bf16_gemm")
         return None
     _native.check(rc, "qt_train_gemm_bf16")
@@ -86,7 +86,7 @@ def train_gemm_group(As, Bs, trans_a, trans_b, kind, biases=None, outs=None):
     _native.note_device(a0.device.index)
     rc = _native.lib().qt_train_gemm_bf16(prob, n, int(trans_a), int(trans_b), M, N, K, a0.stride(0), b0.stride(0), N,
                                           ctypes.c_void_p(torch.cuda.current_stream(a0.device).cuda_stream))
-    if rc in (_native.QT_ERR_BAD_ARG, _native.QT_ERR_UNALIGNED):
+    if _native.declined(rc):
         return None
     _native.check(rc, "qt_train_gemm_bf16")
     GEMM_ROUTES.setdefault(f"train:{kind} {n}x({M}x{N}x{K})", "in_tree_bf16_gemm, one launch")
@@ -164,7 +164,7 @@ def train_gemm_backward(gys, ws, xs, kind):
                                                                           gws[i].data_ptr())
     _native.note_device(g0.device.index)
     rc = _native.lib().qt_train_gemm_backward_bf16(items, n, T, O, I, O, I, I, I, I, ctypes.c_void_p(torch.cuda.current_stream(g0.device).cuda_stream))
-    if rc in (_native.QT_ERR_BAD_ARG, _native.QT_ERR_UNALIGNED):
+    if _native.declined(rc):
         return None
     _native.check(rc, "qt_train_gemm_backward_bf16")
     GEMM_ROUTES.setdefault(f"train:dgrad + wgrad {kind}{n}x({T}x{O}x{I})" if n > 1 else f"train:dgrad + wgrad {kind}{T}x{O}x{I}", "in_tree_bf16_gemm, one launch")
@@ -237,7 +237,7 @@ class _LinearColsumBias(torch.autograd.Function):
                 _native.note_device(g.device.index)
                 rc = _native.lib().qt_colsum_bf16(g.data_ptr(), gb.data_ptr(), g.shape[0], g.shape[1],
                                                   ctypes.c_void_p(torch.cuda.current_stream(g.device).cuda_stream))
-                if rc in (_native.QT_ERR_BAD_ARG, _native.QT_ERR_UNALIGNED):
+                if _native.declined(rc):
                     gb = gy2.sum(0)
                 else:
                     _native.check(rc, "qt_colsum_bf16")

@@ -16,6 +16,7 @@ Every class keeps upstream's ``from_observed(float_module)`` constructor.
 import torch
 from torch import nn
 
+from ... import handover
 from .functional_modules import AddFunctional, MatmulFunctional, MulFunctional
 
 __all__ = [
@@ -102,20 +103,14 @@ def quantizable_attention_forward(module, query, key, value, attention_mask, sca
     # The fused core declined (a hooked sub-module, dropout while training, a mask it cannot address, ...).  A producer that
     # expected it may have written only the FP8 codes of q / k (model_fusions.rope_fq, `_qt_lazy`): give the tensors their
     # values BEFORE any view is taken -- a view does not carry the lazy state, and the matmul below would read unwritten memory.
-    from ...fake_quantize import materialize_lazy
-    materialize_lazy(query)
-    materialize_lazy(key)
+    handover.materialize(query)
+    handover.materialize(key)
     if torch.is_grad_enabled() and query.is_cuda:
         from ...train_fusions import attention_or_none
         out = attention_or_none(module, query, key, value, attention_mask, scaling, dropout)     # a training step: the whole core, one launch
         if out is not None:
             return out, None
-    key_t = key.transpose(2, 3)
-    if getattr(key, "_qt_fq_done_by", None) is not None and getattr(key, "_qt_ver", None) == key._version:
-        key_t._qt_ver = key._qt_ver                          # a view shares the version counter
-        key_t._qt_fq_done_by = key._qt_fq_done_by          # fake-quant is elementwise: done for K means done for K^T
-        if getattr(key, "_qt_fp8", None) is not None:
-            key_t._qt_fp8_of_transpose = key._qt_fp8        # FP8 code of K itself ([B, H, S, D], contiguous)
+    key_t = handover.transposed(key, key.transpose(2, 3))
     scores = module.qk_matmul(query, key_t)
     fused = fused_scores_to_probs_or_none(module, scores, attention_mask, scaling, dropout, value)
     if fused is not None:

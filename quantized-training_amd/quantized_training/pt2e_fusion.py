@@ -30,7 +30,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.fx import GraphModule, Node
 
-from . import _native
+from . import _native, handover
 from .fake_quantize import STATS as _FQ_STATS, FusedAmaxObsFakeQuantize, _stream_ptr
 from .modules.qat.linear import Linear as QATLinear
 
@@ -138,7 +138,6 @@ class PreparedRMSNorm(nn.Module):
 def _add_rmsnorm(a, b, weight, eps, fq, sum_fq):
     """(sum, y) in one launch (qt_add_rmsnorm_sumfq_bf16): sum = bf16(a + b), written as sum_fq(sum) when that fake-quantizer sits behind
     it; y = fq(RMSNorm(sum)) with its FP8 codes.  Both results are marked for the fake-quantizer nodes that follow."""
-    from .model_fusions import _fp8_view
     cols = a.shape[-1]
     a2, b2 = a.contiguous(), b.contiguous()
     total = torch.empty_like(a2)
@@ -149,12 +148,9 @@ def _add_rmsnorm(a, b, weight, eps, fq, sum_fq):
         a2.numel() // cols, cols, float(eps), ctypes.byref(fq._qt_format) if fq is not None else None,
         ctypes.byref(sum_fq._qt_format) if sum_fq is not None else None, _stream_ptr(a2)), "qt_add_rmsnorm_sumfq_bf16")
     if fq is not None:
-        y._qt_fp8 = _fp8_view(y8, fq)
-        y._qt_fq_done_by = fq
-        y._qt_ver = y._version
+        handover.stamp(y, fq, handover.fp8_view(y8, fq))
     if sum_fq is not None:
-        total._qt_fq_done_by = sum_fq
-        total._qt_ver = total._version
+        handover.stamp(total, sum_fq)
     return total, y
 
 
@@ -286,7 +282,7 @@ class PreparedAttention(nn.Module):
         q8 = torch.empty((B, H, S, D), dtype=torch.uint8, device=dev)
         k8 = torch.empty((B, H, S, D), dtype=torch.uint8, device=dev)
         vt8 = torch.empty((B, H, D, S), dtype=torch.uint8, device=dev)
-        q_out = torch.empty((B, H, S, D), dtype=q.dtype, device=dev)            # codes only: decoded on demand (materialize_lazy)
+        q_out = torch.empty((B, H, S, D), dtype=q.dtype, device=dev)            # codes only: decoded on demand (handover.materialize)
         k_out = torch.empty((B, H, S, D), dtype=q.dtype, device=dev)
         fmt = lambda f: ctypes.byref(f._qt_format) if f is not None else None   # noqa: E731
         _native.check(_native.lib().qt_rope_fq_inner_value(
@@ -298,17 +294,13 @@ class PreparedAttention(nn.Module):
                 f.__dict__["_qt_calls"] = f.__dict__.get("_qt_calls", 0) + 1
                 _FQ_STATS.add(t.numel())
         for t, t8, f in ((q_out, q8, fq_q), (k_out, k8, fq_k)):
-            t._qt_lazy = True
-            t._qt_fq_done_by = f
-            t._qt_fp8 = mf._fp8_view(t8, f)
-            t._qt_ver = t._version
+            handover.stamp(t, f, handover.fp8_view(t8, f), lazy=True, register=False)      # (they go straight to the core below)
         self.__dict__["_qt_vt8"] = (fused.value_key(v), fq_v, vt8)
         out = fused._attention_fp8_or_none(self, q_out, k_out, v, mask, self.scaling, fqs)
         if out is None:                                        # the kernel declined after all (mask layout): finish on the node sequence
             self.__dict__.pop("_qt_vt8", None)
-            from .fake_quantize import materialize_lazy
-            materialize_lazy(q_out)
-            materialize_lazy(k_out)
+            handover.materialize(q_out)
+            handover.materialize(k_out)
             s = torch.matmul(fq_q(q_out), fq_k(k_out.transpose(2, 3))) * self.scaling
             if mask is not None:
                 s = s + mask

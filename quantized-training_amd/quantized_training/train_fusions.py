@@ -29,6 +29,7 @@ import weakref
 import torch
 
 from . import _native
+from .handover import tensor_key
 
 __all__ = ["plan", "unplan", "enabled", "STATS"]
 
@@ -105,7 +106,7 @@ def put_colsum(g, gb):
     More than 64 entries: the OLDEST go (never all of them); a Linear whose entry went computes its own sums."""
     while len(_COLSUM) >= 64:
         del _COLSUM[next(iter(_COLSUM))]
-    _COLSUM[(g.data_ptr(), g._version, tuple(g.shape))] = (g, gb)
+    _COLSUM[tensor_key(g)] = (g, gb)
 
 
 _LINEAR_GRADS = {}        # (data_ptr, version, shape) of a grad_output -> (that tensor, identity of x and Wq, grad_input, grad_weight): one-shot, like _COLSUM
@@ -187,24 +188,24 @@ def group_qkv_backward(lins, gys):
             del _LINEAR_GRADS[next(iter(_LINEAR_GRADS))]
         # (x and Wq are remembered by address and version, not by reference: Wq carries the step's autograd graph, and a reference that
         # outlives a stream capture's end broke the graph's instantiation)
-        _LINEAR_GRADS[(gy.data_ptr(), gy._version, tuple(gy.shape))] = (gy, (x.data_ptr(), x._version, tuple(x.shape), w.data_ptr(), w._version),
+        _LINEAR_GRADS[tensor_key(gy)] = (gy, (*tensor_key(x), w.data_ptr(), w._version),
                                                                           gx.view(x.shape), gw)
     STATS.qkv_groups += 1
     return True
 
 
 def take_linear_grads(gy, x, w):
-    hit = _LINEAR_GRADS.pop((gy.data_ptr(), gy._version, tuple(gy.shape)), None)
+    hit = _LINEAR_GRADS.pop(tensor_key(gy), None)
     if hit is None:
         return None
     _, ident, gx, gw = hit
-    if ident != (x.data_ptr(), x._version, tuple(x.shape), w.data_ptr(), w._version):
+    if ident != (*tensor_key(x), w.data_ptr(), w._version):
         return None                    # (another forward of the same Linear in between: the node multiplies what IT saved)
     return gx, gw
 
 
 def take_colsum(g):
-    hit = _COLSUM.pop((g.data_ptr(), g._version, tuple(g.shape)), None)
+    hit = _COLSUM.pop(tensor_key(g), None)
     if hit is None:
         return None
     STATS.colsums += 1
@@ -315,7 +316,7 @@ def run_chain(head, chain, X):
         if i == 0:
             continue
         want = X if src < 0 else outs[src]
-        fq.__dict__["_qt_chain_result"] = (want.data_ptr(), want._version, tuple(want.shape), outs[i], want, False)
+        fq.__dict__["_qt_chain_result"] = (*tensor_key(want), outs[i], want, False)
     if need_grad:
         # every member keeps an autograd node of its own (the straight-through gradient, fake_quantize.py:250-252), as in the unchained
         # path: the engine then adds the members' gradients into x in the very order it would have, bit for bit
@@ -334,7 +335,7 @@ def take_member_result(fq, X):
     ptr, version, shape, out, _keep, connected = pend[:6]
     arm = pend[6] if len(pend) > 6 else None
     from .fake_quantize import _Stats, _take_preupdate, _PrecomputedFakeQuant
-    if X.data_ptr() == ptr and X._version == version and tuple(X.shape) == shape and (X.is_contiguous() or X.stride() == _keep.stride()):
+    if tensor_key(X) == (ptr, version, shape) and (X.is_contiguous() or X.stride() == _keep.stride()):
         STATS.members += 1
         _Stats.add(X.numel())
         if fq._observe:
@@ -503,7 +504,7 @@ def _hand_over(members, produced, outs, connected=False, arm=None):
     arm[i]: the backward fake-quantizer to arm for a deferred call once member i took its result (take_deferred)."""
     for i, (fq, src) in enumerate(members):
         want = produced if src < 0 else outs[src]
-        fq.__dict__["_qt_chain_result"] = (want.data_ptr(), want._version, tuple(want.shape), outs[i], want, connected, arm[i] if arm else None)
+        fq.__dict__["_qt_chain_result"] = (*tensor_key(want), outs[i], want, connected, arm[i] if arm else None)
     STATS.chains += 1
 
 
@@ -959,7 +960,7 @@ def _served_call(fq, x, y, numel=None):
     and finds `y` (take_member_result) -- its hooks see the call, its input and its result."""
     from .fake_quantize import _Stats
     if y is not None and _hooked(fq):
-        fq.__dict__["_qt_chain_result"] = (x.data_ptr(), x._version, tuple(x.shape), y, x, False)
+        fq.__dict__["_qt_chain_result"] = (*tensor_key(x), y, x, False)
         with torch.no_grad():
             got = fq(x)
         if got.data_ptr() != y.data_ptr():

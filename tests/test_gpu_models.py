@@ -312,7 +312,7 @@ def test_codes_only_handover_is_invisible(monkeypatch):
     all (the FP8 route declined behind the hook), the values are decoded on demand -- bit-identical again.  Same fake-quant counts."""
     import copy
     from transformers import BertConfig, BertForQuestionAnswering
-    from quantized_training import fused, model_fusions as mf
+    from quantized_training import fused, handover, model_fusions as mf
     from quantized_training.fake_quantize import STATS
     torch.manual_seed(0)
     cfg = BertConfig(hidden_size=256, num_hidden_layers=2, num_attention_heads=4, intermediate_size=1024, vocab_size=300,
@@ -322,12 +322,12 @@ def test_codes_only_handover_is_invisible(monkeypatch):
     att = torch.ones_like(ids)
     att[2, 200:] = 0
     lazy_made = {"n": 0}
-    real_mark = mf._mark_lazy
+    real_mark = handover.mark_lazy
 
     def counting_mark(t):
         lazy_made["n"] += 1
         return real_mark(t)
-    monkeypatch.setattr(mf, "_mark_lazy", counting_mark)
+    monkeypatch.setattr(handover, "mark_lazy", counting_mark)
 
     def run():
         m = copy.deepcopy(base).cuda()
