@@ -444,6 +444,22 @@ typedef struct qt_linear_backward {
 int qt_train_gemm_backward_bf16(const qt_linear_backward *items, int count, int T, int O, int I, long ld_gy, long ld_w, long ld_x, long ld_gx,
                                 long ld_gw, void *stream);
 
+/* ---- A QAT Conv2d's forward convolution as an implicit GEMM (replaces nn.Conv2d._conv_forward -> F.conv2d as called by
+ * modules/qat/conv.py:43-44 with the fake-quantized weight, and by conv_fused.py:103-126 with fq(weight * scale_factor)):
+ *     y[n, ho, wo, co] = sum_{r, s, c} x[n, ho sh - ph + r dh, wo sw - pw + s dw, c] . w[co, r, s, c] (+ bias[co])
+ * x: bf16 NHWC [N][H][W][Cin]; w: bf16 [Cout][kh][kw][Cin] (values the weight fake-quantizer produced; nothing is quantized here);
+ * bias: bf16 [Cout], nullable; y: bf16 NHWC [N][Ho][Wo][Cout].  fp32 accumulation in a fixed order (taps in (r, s) order, channels
+ * ascending), bias added in fp32, one rounding.  groups = 1 and zero padding only.  Cin % 64 == 0, Cout % 8 == 0, x / w 16-byte and
+ * y / bias 8-byte aligned -- anything else returns QT_ERR_BAD_ARG / QT_ERR_UNALIGNED and the caller keeps the library's convolution.
+ * No allocation, no synchronisation: safe under stream capture. */
+int qt_conv2d_bf16(const uint16_t *x, const uint16_t *w, const uint16_t *bias, uint16_t *y, int N, int H, int W, int Cin, int Cout, int kh, int kw,
+                   int sh, int sw, int ph, int pw, int dh, int dw, void *stream);
+/* Host-only query: whether qt_conv2d_bf16 takes the shape (QT_OK / QT_ERR_BAD_ARG; pointers are not part of it) and how it cuts it on
+ * the current device: tile_m x tile_n output tiles (128 x 128, 128 x 64 or 64 x 64), tiles_m x tiles_n workgroups, k_tiles steps of 64
+ * channels of one tap.  Every out pointer is nullable.  The parity tests enumerate it so that every tile shape is covered. */
+int qt_conv2d_plan(int N, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int *tile_m, int *tile_n,
+                   int *tiles_m, int *tiles_n, int *k_tiles);
+
 /* ---- H3's step end: clip_grad_norm_(max_norm) and the AdamW update of every parameter tensor in four launches ------------------------
  *     run_glue_no_trainer.py:655-668   accelerator.clip_grad_norm_(model.parameters(), 1.0); optimizer.step()
  * The arithmetic is torch's, which the reference calls: torch.nn.utils.clip_grad_norm_ on bf16 gradients (per-tensor norms and the

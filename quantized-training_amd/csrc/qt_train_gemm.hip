@@ -29,15 +29,11 @@
 
 #include "../../include/qt_hip.h"
 #include "qt_device.h"
+#include "qt_gemm_ring.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kBK = 64;                 // k tile
-constexpr int kThreads = 512;          // 8 waves: 4 (rows) x 2 (columns); two per SIMD, so one wave's LDS latencies hide under the other's matrix instructions
 constexpr int kMaxProblems = 4;
 
 struct Problem {
@@ -54,9 +50,6 @@ struct Args {
 #endif
 };
 
-// [rows][64 k] image, 128-byte rows: byte offset of 16-byte chunk `ch` (0..7) of row `row`
-__device__ __forceinline__ int off_rows(int row, int ch) { return row * 128 + ((ch ^ ((row >> 1) & 7)) << 4); }
-
 // [64 k][C columns] image read by ds_read_b64_tr_b16.  RB = 2 C bytes per row (128 or 256).  A 32-lane half reads rows r0 + q and r0 + 8 + q
 // (q = 0..3), 32 bytes of the same column group each: eight 32-byte pieces that must fall on eight different bank groups (64 banks x 4 B =
 // eight groups of 32 B).  Row r starts at bank group (r RB / 32) mod 8 -- 0 for RB = 256, 0 or 4 for RB = 128 -- so the column group index
@@ -72,9 +65,6 @@ __device__ __forceinline__ int off_tr(int row, int ch) {       // 16-byte chunk 
     return row * RB + ((((ch >> 1) ^ s_tr<RB>(row))) << 5) + ((ch & 1) << 4);
 }
 
-__device__ __forceinline__ bf16x8 ld_frag_rows(const unsigned char *img, int row, int ch) {
-    return *(const bf16x8 *)(img + off_rows(row, ch));
-}
 // the fragment of 16 columns c0 .. c0 + 15 (c0 a multiple of 16) for k = k0 .. k0 + 31 of a transposed image: lane l receives column
 // c0 + l % 16, k = k0 + 8 (l / 16) .. + 7
 template <int RB>
@@ -88,45 +78,10 @@ __device__ __forceinline__ bf16x8 ld_frag_tr(const unsigned char *img, int c0, i
     return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
 }
 
-// one LDS-DMA piece: dma16 (qt_device.h), its waits counted by hand below
-template <int N>
-__device__ __forceinline__ void wait_and_barrier() {       // at most N of this wave's DMA pieces still in flight; LDS reads drained
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
-}
-
-// The LDS ring: S - 1 k tiles in flight per workgroup.  Small tiles leave room for two workgroups per CU (four waves per SIMD); a ring
-// over the whole CU's LDS for a single workgroup measured SLOWER on every shape (profiles/r06_train_gemm.txt): what these launches lack
-// is waves to overlap, not bytes in flight.
-template <int BM, int BN>
-struct Ring {
-    static constexpr int kStage = (BM + BN) * kBK * 2;                  // 16 / 24 / 32 KiB
-    // (128 x 192: 3 x 40 KiB; a fourth stage -- the whole LDS of a CU -- changes nothing: with 24 multiplications and 16 fragment reads per
-    // wave and k tile that shape is paced by the LDS reads, 0.76 us per k tile, not by the operands in flight)
-    static constexpr int kStages = (BM + BN) <= 128 ? 4 : ((BM + BN) <= 192 ? 3 : ((BM + BN) <= 256 ? 4 : 3));
-    static constexpr int kBytes = kStage * kStages;
-};
-
-// the last S - 1 k tiles: nothing left to request, the queue drains (D k tiles still in flight behind the one being multiplied)
-template <int D, int PIECES, class F>
-__device__ __forceinline__ void drain(int &kt, F &&compute) {
-    wait_and_barrier<D * PIECES>();
-    compute(kt++);
-    if constexpr (D > 0) drain<D - 1, PIECES>(kt, compute);
-}
-
 // One output tile: `tile` of problem P (column tile tile / tiles_m, row tile tile % tiles_m); `lds`: the workgroup's dynamic LDS
 // (Ring<BM, BN>::kBytes of it).
 // the problem of workgroup `block` (compile-time indices only into the kernel arguments: a run-time index, or a reference to the
 // argument struct, copies it to scratch memory)
-// Workgroups go to the eight XCDs round robin (workgroup b to XCD b % 8), each with its own L2.  Where the row-tile count is a multiple
-// of 8 the walk "row tiles of one column tile first" already gives an XCD two or three row tiles for ALL column tiles (it fetches an
-// eighth of A and shares every B tile between its workgroups).  Where it is not (768 / 64 = 12 row tiles: the small weight gradients) an
-// XCD's tiles are scattered over the whole product and every L2 fetches both operands whole; there the tiles are dealt out so that XCD x
-// takes a contiguous run of the walk -- one and a half column tiles with all their row tiles.
-__device__ __forceinline__ int xcd_run(int b, int total) {
-    const int x = b & 7, j = b >> 3, q = total >> 3, r = total & 7;
-    return x * q + (x < r ? x : r) + j;
-}
 #define QT_TG_PICK(a, block, P, tile_)                                     \
     const int tiles_##tile_ = (a).tiles_m * (a).tiles_n;                   \
     const int tile_ = ((a).tiles_m & 7) ? xcd_run((block) % tiles_##tile_, tiles_##tile_) : (block) % tiles_##tile_; \
@@ -267,24 +222,8 @@ __device__ __forceinline__ void gemm_tile(const Problem P, const Dims a, const i
     drain<S - 2, kPieces>(kt, compute);
     QT_TG_STAMP(a, 2);
 
-    // ---- epilogue: lane (r, g) of tile (i, j) holds C[row0 + r][col0 + 4 g .. + 3]
-#pragma unroll
-    for (int j = 0; j < WN; ++j) {
-        const int col = n0 + wc * (BN / 2) + j * 16 + 4 * g;
-        if (col >= a.N) continue;
-        float bv[4] = {0.f, 0.f, 0.f, 0.f};
-        if (P.bias) {
-            const uint2 b = *(const uint2 *)(P.bias + col);
-            bv[0] = qt_u2f(b.x << 16); bv[1] = qt_u2f(b.x & 0xFFFF0000u); bv[2] = qt_u2f(b.y << 16); bv[3] = qt_u2f(b.y & 0xFFFF0000u);
-        }
-#pragma unroll
-        for (int i = 0; i < WM; ++i) {
-            const int row = m0 + wr * (BM / 4) + i * 16 + r;
-            if (row < a.M)
-                *(uint2 *)(P.c + (long)row * a.ldc + col) = uint2{pack_bf16x2(acc[i][j][0] + bv[0], acc[i][j][1] + bv[1]),
-                                                                 pack_bf16x2(acc[i][j][2] + bv[2], acc[i][j][3] + bv[3])};
-        }
-    }
+    // ---- epilogue (qt_gemm_ring.h)
+    store_tile<BM, BN>(acc, P.c, a.ldc, P.bias, m0, n0, a.M, a.N, wr, wc, r, g);
     QT_TG_STAMP(a, 3);
 }
 

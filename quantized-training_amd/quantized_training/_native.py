@@ -112,6 +112,8 @@ SIGNATURES = {
     "qt_linear_fq_bf16": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _OPQ, _OPQ, _P]),
     "qt_train_gemm_bf16": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_long, c_long, c_long, _P]),
     "qt_train_gemm_backward_bf16": (c_int, [_P, c_int, c_int, c_int, c_int, c_long, c_long, c_long, c_long, c_long, _P]),
+    "qt_conv2d_bf16": (c_int, [_P, _P, _P, _P] + [c_int] * 13 + [_P]),
+    "qt_conv2d_plan": (c_int, [c_int] * 13 + [_P] * 5),
     "qt_linear_fq8_plan": (c_int, [c_int, c_long, c_int, c_int, _P, _P, _P, _P, _P]),
     "qt_clip_adamw_plan": (c_long, [_P, c_int, _P, c_long]),
     "qt_clip_adamw_ws_bytes": (c_size_t, [c_int, c_long]),

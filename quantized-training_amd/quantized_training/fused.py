@@ -79,6 +79,8 @@ def routes_report():
     out.update(sorted(GEMM_ROUTES.items()))
     from .optim import ROUTES as OPT_ROUTES                    # clip_grad_norm_ + optimizer.step() (csrc/qt_optimizer.hip or torch's launches)
     out.update(sorted(OPT_ROUTES.items()))
+    from .conv_route import CONV_ROUTES                        # QAT convolutions (csrc/qt_conv.hip or the library's convolution)
+    out.update(sorted(CONV_ROUTES.items()))
     return out
 
 

@@ -3,12 +3,15 @@ each ``--quantize_forward`` / ``--quantize_backprop`` op group covers
 (upstream src/quantized_training/quantization_mappings.py:16-72).
 
 HF model families are looked up lazily and only if `transformers` provides them; families whose
-twins this engine does not build (DistilBERT, GPT-2, Whisper, conv QAT) are absent.  The LoRA QAT layer is
+twins this engine does not build (DistilBERT, GPT-2, Whisper) are absent.  Convolutions are swapped as upstream swaps them
+(:16-25): ``nn.Conv2d`` / ``nn.Conv3d`` and the fused ``ConvBn1d/2d/3d`` of ``fuse_modules_qat``; ``nn.Conv1d`` is not mapped upstream
+either (it only receives the activation hooks of the ``gemm`` group).  The LoRA QAT layer is
 registered for ``peft.tuners.lora.Linear`` when ``peft`` imports (upstream :20).
 """
 import importlib
 from typing import Any, Callable, Dict
 
+import torch.ao.nn.intrinsic as nni
 import torch.nn as nn
 
 from .modules import qat as nnqat
@@ -19,7 +22,12 @@ __all__ = [
 ]
 
 DEFAULT_QAT_MODULE_MAPPINGS: Dict[Callable, Any] = {
+    nn.Conv2d: nnqat.Conv2d,
+    nn.Conv3d: nnqat.Conv3d,
     nn.Linear: nnqat.Linear,
+    nni.ConvBn1d: nnqat.ConvBn1d,
+    nni.ConvBn2d: nnqat.ConvBn2d,
+    nni.ConvBn3d: nnqat.ConvBn3d,
 }
 
 
