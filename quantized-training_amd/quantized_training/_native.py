@@ -8,11 +8,13 @@ import ctypes
 import os
 from ctypes import POINTER, c_char_p, c_float, c_int, c_long, c_size_t, c_uint16, c_uint32, c_void_p
 
+from . import switches
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # QT_HIP_LIB: tools/ only -- load the tuning build (make -C quantized-training_amd tuning) instead of the product library.  Never
 # silent: a warning names the file, and `LIB_OVERRIDDEN` lets callers (bench.py's config) record it.
-LIB_OVERRIDDEN = bool(os.environ.get("QT_HIP_LIB"))
-LIB_PATH = os.environ.get("QT_HIP_LIB") or os.path.join(_HERE, "libqt_hip.so")
+LIB_OVERRIDDEN = bool(switches.raw("QT_HIP_LIB"))
+LIB_PATH = switches.raw("QT_HIP_LIB") or os.path.join(_HERE, "libqt_hip.so")
 if LIB_OVERRIDDEN:
     import warnings
     warnings.warn(f"quantized_training loads {LIB_PATH} instead of its own libqt_hip.so (QT_HIP_LIB is set): a tuning build's ablation "

@@ -10,9 +10,10 @@ The weight handed in is what the twin's weight fake-quantizer returned; nothing 
 copy of the input to channels_last when it does not arrive so (the result IS channels_last, so BN / ReLU / pooling keep the format and
 only the first routed layer of a model pays it), one copy of the small quantized weight to [Cout][kh][kw][Cin], one kernel launch."""
 import ctypes
-import os
 
 import torch
+
+from . import switches
 
 __all__ = ["conv2d_or_none", "conv_gemm_mode", "CONV_ROUTES"]
 
@@ -20,8 +21,7 @@ CONV_ROUTES = {}          # "conv2d N×Cin×H×W → Cout k s p d" -> "in_tree_b
 
 
 def conv_gemm_mode():
-    mode = os.environ.get("QT_CONV_GEMM", "auto")
-    return mode if mode in ("0", "1") else "auto"
+    return switches.mode("QT_CONV_GEMM")
 
 
 def _pair_str(v):

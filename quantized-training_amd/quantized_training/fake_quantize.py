@@ -18,7 +18,6 @@ What is different underneath:
 """
 import ctypes
 import logging
-import os
 from typing import Optional
 
 import torch

@@ -5,31 +5,29 @@ caller then runs the unfused sequence (HIP elementwise fake-quant + library GEMM
 device paths -- there is no CPU fallback for device tensors.
 """
 import ctypes
-import os
 
 import torch
 
-from . import _native, handover
-from .fake_quantize import STATS, FusedAmaxObsFakeQuantFunction, FusedAmaxObsFakeQuantize, _stream_ptr, launch_scale_update
+from . import _native, handover, planner_checks as pc, switches
+from .fake_quantize import STATS, FusedAmaxObsFakeQuantFunction, FusedAmaxObsFakeQuantize, _launch_format, _stream_ptr, launch_scale_update
 from .quantizer.quantizer import QScheme
 
 _IDENTITY = _native.QtFormat(_native.QT_FMT_IDENTITY, 0, 0, 0.0, 0.0)
 
 
 def fused_gemm_enabled():
-    return os.environ.get("QT_FUSED_GEMM", "0") == "1"
+    return switches.on("QT_FUSED_GEMM")
 
 
 def fp8_gemm_enabled():
-    return os.environ.get("QT_FP8_GEMM", "1") != "0"
+    return switches.on("QT_FP8_GEMM")
 
 
 def fq8_gemm_mode():
     """QT_FQ8_GEMM: "auto" (default) -- per problem shape, whichever of the two routes measured faster on its first call;
     "1" -- always the hand-written FP8 GEMM with the weight fake-quantizer in its operand path (qt_linear_fq8_bf16);
     "0" -- always the weight pass + library GEMM pair."""
-    v = os.environ.get("QT_FQ8_GEMM", "auto")
-    return v if v in ("0", "1") else "auto"
+    return switches.mode("QT_FQ8_GEMM")
 
 
 def fq8_gemm_enabled():
@@ -301,7 +299,7 @@ _MLP_TABLE = {
 def mlp_route_is_one_launch(x8, gate, up, out_fq):
     """Whether qt_mlp_fq8_bf16 runs the gated MLP's front half on this problem: QT_FQ8_MLP=2 forces it; else the committed table;
     else one launch where it fills the chip in a single round (a rule, never a measurement: see fq8_route_is_fused)."""
-    if os.environ.get("QT_FQ8_MLP", "1") == "2":              # always (tests, ablations)
+    if switches.mode("QT_FQ8_MLP") == "2":              # always (tests, ablations)
         return True
     K = x8.shape[-1]
     M = x8.numel() // K
@@ -400,7 +398,7 @@ class BatchedWeightCodes:
 
 def _sibling_linear_or_none(layer, x, x8):
     group = layer.__dict__.get("_qt_sibling_group")
-    if group is None or group.value_map_only or os.environ.get("QT_SIBLING_GEMM", "1") == "0" or _WEIGHT_CACHE["on"]:
+    if group is None or group.value_map_only or not switches.on("QT_SIBLING_GEMM") or _WEIGHT_CACHE["on"]:
         return None
     idx = group.layers.index(layer)
     key = _origin_key(x)
@@ -534,7 +532,7 @@ def lt_table_applies():
 
 
 def lt_algo_index(batch, M, N, K, b_is_kn, with_bias):
-    forced = os.environ.get("QT_LT_ALGO")                     # tools only: the tuner's A/B runs
+    forced = switches.raw("QT_LT_ALGO")                     # tools only: the tuner's A/B runs
     idx = int(forced) if forced is not None else _LT_ALGO_TABLE.get((batch, M, N, K, int(bool(b_is_kn)), int(bool(with_bias))), 0)
     if forced is None and idx and not lt_table_applies():
         idx = 0
@@ -546,7 +544,7 @@ def lt_fp8_gemm(a8, b8, bias=None, b_is_kn=False):
     """C = A . op(B) on FP8 operands through qt_fp8_gemm (hipBLASLt; which of its suggestions runs is a committed table, _LT_ALGO_TABLE).  a8 [.., M, K];
     b8 [N, K] (b_is_kn False) or [.., K, N] (True); leading dims of a8 / b8 are a batch.  None when the library route is
     unavailable for this problem (the caller falls back to torch._scaled_mm / bf16)."""
-    if not _LT["ok"] or os.environ.get("QT_LT_GEMM", "1") == "0":
+    if not _LT["ok"] or not switches.on("QT_LT_GEMM"):
         return None
     dev = a8.device
     ws = _LT["ws"].get(dev)
@@ -660,8 +658,7 @@ def fqt_gemm_mode():
     """QT_FQT_GEMM: "auto" (default) -- the fused kernel for the problem shapes where it measured faster than the weight pass +
     library GEMM pair (a fixed rule, `fqt_route_is_fused`: no timing at run time, every rank and every run takes the same route);
     "1" -- wherever the kernel takes the problem; "0" -- never."""
-    v = os.environ.get("QT_FQT_GEMM", "auto")
-    return v if v in ("0", "1") else "auto"
+    return switches.mode("QT_FQT_GEMM")
 
 
 def fqt_tables(fq, device):
@@ -819,9 +816,9 @@ def fqt_linear_or_none(layer, x):
     x2 = x.reshape(-1, K)
     M = x2.shape[0]
     group = layer.__dict__.get("_qt_sibling_group")
-    if group is not None and group.value_map_only and os.environ.get("QT_GATE_UP_GROUP", "1") == "0":      # A/B hook (tools/ab_13b_routes.py)
+    if group is not None and group.value_map_only and not switches.on("QT_GATE_UP_GROUP"):      # A/B hook (tools/ab_13b_routes.py)
         group = None
-    if group is not None and os.environ.get("QT_SIBLING_GEMM", "1") != "0":
+    if group is not None and switches.on("QT_SIBLING_GEMM"):
         idx = group.layers.index(layer)
         Ns = [l.weight.shape[0] for l in group.layers]
         key = _origin_key(x)
@@ -861,9 +858,28 @@ def fqt_linear_or_none(layer, x):
     return y.reshape(*x.shape[:-1], W.shape[0])
 
 
-def _has_hooks(mod, name):
-    holder = getattr(mod, name, None)
-    return holder is not None
+def _probs_fq_launch_args(fq_p, device, st, numel, drop_unit_scale=False):
+    """(fmt, lut, scale_ptr, amax_ptr) with which a softmax / attention launch applies the probabilities' fake-quantizer, after this call's
+    bookkeeping in this order: _move_to, the first call's history resize, the scale update, STATS.add(numel).  No or a switched-off
+    fake-quantizer: the identity format, nothing touched.  drop_unit_scale: no scale pointer for a stateless format whose scale is one."""
+    if fq_p is None or not (fq_p._observe or fq_p._quantize):
+        return _IDENTITY, None, None, None
+    fq_p._move_to(device)
+    fmt = fq_p._qt_format if fq_p._quantize else _IDENTITY
+    if fq_p._observe:
+        if fq_p.amax_history.numel() == 0:
+            fq_p.amax_history.resize_((fq_p.amax_history_len,)).fill_(0.0)
+            fq_p.scale.resize_(()).fill_(1.0)
+        launch_scale_update(fq_p.amax_history, fq_p.scale, fq_p.quant_max, fq_p.force_scale_power_of_two, st)
+    lut = None
+    if fmt.kind == _native.QT_FMT_LUT:
+        fmt = _launch_format(fmt, fq_p.qmap)             # the row form of the map where the allocation carries it
+        lut = fq_p.qmap.data_ptr()
+    unit_scale = drop_unit_scale and fq_p.qscheme is None and getattr(fq_p, "_scale_is_one", True)      # no scale tensor at all
+    scale_ptr = fq_p.scale.data_ptr() if (fq_p._quantize and not unit_scale) else None
+    amax_ptr = fq_p.amax_history.data_ptr() if fq_p._observe else None
+    STATS.add(numel)
+    return fmt, lut, scale_ptr, amax_ptr
 
 
 def fused_scores_to_probs_or_none(attn, scores, attention_mask, scaling, dropout, value):
@@ -872,7 +888,7 @@ def fused_scores_to_probs_or_none(attn, scores, attention_mask, scaling, dropout
     `attn_scaling` and `softmax` carry no activation hooks (the `--quantize_forward gemm` default), no
     dropout is active, bf16 device tensors, and av_matmul's per-tensor fake-quantizers already exist
     (they are created by the first, unfused, call).  Returns (probs_q, attn_output) or None."""
-    if os.environ.get("QT_FUSED_SOFTMAX", "1") == "0":
+    if not switches.on("QT_FUSED_SOFTMAX"):
         return None
     if not (scores.device.type == "cuda" and scores.dtype == torch.bfloat16 and scores.dim() == 4):
         return None
@@ -880,61 +896,37 @@ def fused_scores_to_probs_or_none(attn, scores, attention_mask, scaling, dropout
         return None
     if dropout and attn.training:
         return None
-    if _has_hooks(attn.attn_scaling, "activation_pre_process") or _has_hooks(attn.softmax, "activation_pre_process"):
+    if getattr(attn.attn_scaling, "activation_pre_process", None) is not None or getattr(attn.softmax, "activation_pre_process", None) is not None:
         return None
-    if attn.attn_scaling._forward_hooks or attn.softmax._forward_hooks or attn.av_matmul._forward_hooks:
+    # (their forward hooks only, where fused_attention_or_none also refuses pre-hooks on the first two: kept as found, no reason found)
+    if not (pc.no_output_hook(attn.attn_scaling) and pc.no_output_hook(attn.softmax) and pc.no_output_hook(attn.av_matmul)):
         return None
     holder = getattr(attn.av_matmul, "activation_pre_process", None)
     fq_p = fq_v = None
     if holder is not None:
-        if "0" not in holder or "1" not in holder:
+        fqs = pc.holder_fqs(attn.av_matmul, "activation_pre_process", "0", "1", exact=False)
+        if fqs is None:
             return None                       # first call: let the hook create them
-        fq_p, fq_v = holder["0"], holder["1"]
-        if not isinstance(fq_p, FusedAmaxObsFakeQuantize) or fq_p.is_per_channel or fq_p.outlier_threshold is not None \
-                or fq_p.record_histogram or fq_p.qscheme in (QScheme.MICROSCALING, QScheme.GROUP_WISE_AFFINE):
+        fq_p, fq_v = fqs
+        if not pc.plain_per_tensor(fq_p):
             return None
-    if len(attn.av_matmul._forward_pre_hooks) > (1 if holder is not None else 0):
+    # (AT MOST quantize()'s one pre-hook, where the other planners ask for exactly one: a holder without its hook passes here)
+    if not pc.hook_counts(attn.av_matmul, forward_pre=(0, 1) if holder is not None else 0):
         return None
     B, H, Q, C = scores.shape
     if C % 8 != 0 or C > 4096 or not scores.is_contiguous():
         return None
-    mask = None
-    msb = msh = msq = 0
-    if attention_mask is not None:
-        m = attention_mask[..., :C]
-        if m.dtype != torch.bfloat16 or m.dim() != 4 or m.stride(-1) != 1 or m.device != scores.device:
-            return None
-        if m.shape[0] not in (1, B) or m.shape[1] not in (1, H) or m.shape[2] not in (1, Q):
-            return None
-        msb = m.stride(0) if m.shape[0] == B and B > 1 else 0
-        msh = m.stride(1) if m.shape[1] == H and H > 1 else 0
-        msq = m.stride(2) if m.shape[2] == Q and Q > 1 else 0
-        if (msb | msh | msq) % 8 != 0 or m.data_ptr() % 16 != 0:
-            return None
-        mask = m
+    mk = _mask_strides(attention_mask, B, H, Q, C, scores.device, 8)
+    if mk is False:
+        return None
+    mask, msb, msh, msq = mk
     L = _native.lib()
     st = _stream_ptr(scores)
     fp8_out = _fp8_probs_times_v_or_none(L, st, scores, mask, msb, msh, msq, scaling, fq_p, fq_v, value, mask_owner=attention_mask)
     if fp8_out is not None:
         return None, fp8_out                  # the probabilities exist only as FP8 codes on this path
     out = torch.empty_like(scores)
-    if fq_p is not None and (fq_p._observe or fq_p._quantize):
-        fq_p._move_to(scores.device)
-        fmt = fq_p._qt_format if fq_p._quantize else _IDENTITY
-        if fq_p._observe:
-            if fq_p.amax_history.numel() == 0:
-                fq_p.amax_history.resize_((fq_p.amax_history_len,)).fill_(0.0)
-                fq_p.scale.resize_(()).fill_(1.0)
-            launch_scale_update(fq_p.amax_history, fq_p.scale, fq_p.quant_max, fq_p.force_scale_power_of_two, st)
-        if fmt.kind == _native.QT_FMT_LUT:
-            from .fake_quantize import _launch_format
-            fmt = _launch_format(fmt, fq_p.qmap)             # the row form of the map where the allocation carries it
-        lut = fq_p.qmap.data_ptr() if fmt.kind == _native.QT_FMT_LUT else None
-        scale_ptr = fq_p.scale.data_ptr() if fq_p._quantize else None
-        amax_ptr = fq_p.amax_history.data_ptr() if fq_p._observe else None
-        STATS.add(scores.numel())
-    else:
-        fmt, lut, scale_ptr, amax_ptr = _IDENTITY, None, None, None
+    fmt, lut, scale_ptr, amax_ptr = _probs_fq_launch_args(fq_p, scores.device, st, scores.numel())
     _native.check(L.qt_softmax_fq_bf16(scores.data_ptr(), mask.data_ptr() if mask is not None else None, out.data_ptr(),
                                        B, H, Q, C, msb, msh, msq, float(scaling), ctypes.byref(fmt), lut, scale_ptr,
                                        amax_ptr, st), "qt_softmax_fq_bf16")
@@ -973,7 +965,7 @@ def _fp8_probs_times_v_or_none(L, st, scores, mask, msb, msh, msq, scaling, fq_p
     """When the probabilities' and the values' fake-quantizers are stateless E4M3 / E5M2 ones, both tensors are exactly
     FP8: the score pass writes the probabilities' FP8 code only (1 B/element instead of 2), the value pass writes FP8
     next to bf16, and P.V runs as a batched FP8 GEMM (qt_fp8_gemm).  Same products, fp32 accumulation."""
-    if (os.environ.get("QT_FP8_ATTENTION", "1") == "0" or os.environ.get("QT_LT_GEMM", "1") == "0" or not _LT["ok"]
+    if (not switches.on("QT_FP8_ATTENTION") or not switches.on("QT_LT_GEMM") or not _LT["ok"]
             or fq_p is None or fq_v is None):
         return None
     if not (isinstance(fq_v, FusedAmaxObsFakeQuantize) and fq_p.producer_fusable() and fq_v.producer_fusable()):
@@ -1011,13 +1003,13 @@ def _fp8_probs_times_v_or_none(L, st, scores, mask, msb, msh, msq, scaling, fq_p
     return out.view(B, H, Q, D)
 
 
-def _mask_strides(attention_mask, B, H, Q, C, device, align):
+def _mask_strides(attention_mask, B, H, Q, C, device, align, no_grad=False):
     """(mask view, stride_b, stride_h, stride_q) of a broadcastable additive bf16 mask, or False if it cannot
-    be consumed in place; None mask -> (None, 0, 0, 0)."""
+    be consumed in place (no_grad: or requires grad -- the training launches return no mask gradient); None mask -> (None, 0, 0, 0)."""
     if attention_mask is None:
         return None, 0, 0, 0
     m = attention_mask[..., :C]
-    if m.dtype != torch.bfloat16 or m.dim() != 4 or m.stride(-1) != 1 or m.device != device:
+    if m.dtype != torch.bfloat16 or m.dim() != 4 or m.stride(-1) != 1 or m.device != device or (no_grad and m.requires_grad):
         return False
     if m.shape[0] not in (1, B) or m.shape[1] not in (1, H) or m.shape[2] not in (1, Q):
         return False
@@ -1093,7 +1085,7 @@ def _attention_fp8_or_none(attn, query, key, value, attention_mask, scaling, fqs
 
     vt8 = None
     if (q8 is None and k8 is None and Q == C and key.shape[1] == H and value.shape[1] == H and token_rows(query) is not None
-            and token_rows(key) is not None and os.environ.get("QT_ROPE_VALUE_LAUNCH", "1") != "0"):
+            and token_rows(key) is not None and switches.on("QT_ROPE_VALUE_LAUNCH")):
         # q and k codes and the value codes in ONE launch (qt_rope_fq_value without a rotation): the three calls fq_q, fq_k, fq_v
         q8 = torch.empty((B, H, Q, D), dtype=torch.uint8, device=query.device)
         k8 = torch.empty((B, H, C, D), dtype=torch.uint8, device=query.device)
@@ -1123,7 +1115,7 @@ def _attention_fp8_or_none(attn, query, key, value, attention_mask, scaling, fqs
     # library-GEMM chain): HF reshapes the result before the projection's hook sees it, so the hand-over is an expectation
     from .model_fusions import consumer_fq
     proj = getattr(attn, "o_proj", None) or attn.__dict__.get("_qt_out_proj")       # LLaMA's own / BERT's BertSelfOutput.dense
-    fq_o = consumer_fq(proj) if (proj is not None and os.environ.get("QT_FUSED_PRODUCER_FQ", "1") != "0") else None
+    fq_o = consumer_fq(proj) if (proj is not None and switches.on("QT_FUSED_PRODUCER_FQ")) else None
     out8 = torch.empty((B, Q, H, D), dtype=torch.uint8, device=query.device) if fq_o is not None else None
     _native.check(L.qt_attention_fp8(q8.data_ptr(), k8.data_ptr(), vt8.data_ptr(), 1 if fmt.p0 == 2 else 0,
                                      mask.data_ptr() if mask is not None else None, msb, msh, msq, rl_ptr, lsb, lsh, lsq, 0, irregular_ptr,
@@ -1145,8 +1137,8 @@ def fused_attention_or_none(attn, query, key, value, attention_mask, scaling, dr
     QT_FUSED_ATTENTION: "0" never, "1" whenever applicable, unset = only head_dim 64, where the kernel measured
     faster than the library-GEMM chain (B16 H12 S384: 85 vs 113 us); at head_dim 128 the chain wins (92 vs 122 us at
     B1 H32 S1024), so the chain stays the default there."""
-    mode = os.environ.get("QT_FUSED_ATTENTION", "auto")
-    fp8_kernel = query.dim() == 4 and query.shape[-1] in (64, 128) and os.environ.get("QT_FP8_ATTENTION_KERNEL", "1") != "0"
+    mode = switches.mode("QT_FUSED_ATTENTION")
+    fp8_kernel = query.dim() == 4 and query.shape[-1] in (64, 128) and switches.on("QT_FP8_ATTENTION_KERNEL")
     if mode == "0" or (mode != "1" and query.shape[-1] != 64 and not fp8_kernel):
         return None
     if not (query.device.type == "cuda" and query.dtype == torch.bfloat16 and query.dim() == 4):
@@ -1159,29 +1151,25 @@ def fused_attention_or_none(attn, query, key, value, attention_mask, scaling, dr
     C = key.shape[2]
     if D not in (64, 128) or C % 4 != 0 or key.shape != (B, H, C, D) or value.shape != (B, H, C, D) or B * H > 65535:
         return None
+    # (backward hooks are looked at on none of the four modules: this is the no_grad path -- gradients were declined above)
     for mod in (attn.attn_scaling, attn.softmax):
-        if _has_hooks(mod, "activation_pre_process") or mod._forward_hooks or mod._forward_pre_hooks:
-            return None
-    for mod in (attn.qk_matmul, attn.av_matmul):
-        if mod._forward_hooks:
+        if getattr(mod, "activation_pre_process", None) is not None or not pc.no_forward_hooks(mod):
             return None
     hq, hv = getattr(attn.qk_matmul, "activation_pre_process", None), getattr(attn.av_matmul, "activation_pre_process", None)
     if (hq is None) != (hv is None):
         return None
     fq_q = fq_k = fq_p = fq_v = None
-    if hq is not None:
-        if not all(k in hq for k in ("0", "1")) or not all(k in hv for k in ("0", "1")):
-            return None                       # first call: let the hooks create the fake-quantizers
-        fq_q, fq_k, fq_p, fq_v = hq["0"], hq["1"], hv["0"], hv["1"]
-        for f in (fq_q, fq_k, fq_p, fq_v):
-            if not isinstance(f, FusedAmaxObsFakeQuantize) or f.is_per_channel or f.outlier_threshold is not None \
-                    or f.record_histogram or f.qscheme in (QScheme.MICROSCALING, QScheme.GROUP_WISE_AFFINE):
-                return None
-        if len(attn.qk_matmul._forward_pre_hooks) != 1 or len(attn.av_matmul._forward_pre_hooks) != 1:
-            return None
-    elif attn.qk_matmul._forward_pre_hooks or attn.av_matmul._forward_pre_hooks:
+    # quantize()'s one pre-hook per matmul with its holder, no hook at all without; never a forward hook
+    if not all(pc.quantize_hooks_only(mod, 0 if hq is None else 1) for mod in (attn.qk_matmul, attn.av_matmul)):
         return None
-    if fp8_kernel and fq_q is not None and os.environ.get("QT_FP8_ATTENTION", "1") != "0":
+    if hq is not None:
+        fqs_qk, fqs_av = (pc.holder_fqs(mod, "activation_pre_process", "0", "1", exact=False) for mod in (attn.qk_matmul, attn.av_matmul))
+        if fqs_qk is None or fqs_av is None:
+            return None                       # first call: let the hooks create the fake-quantizers
+        fq_q, fq_k, fq_p, fq_v = *fqs_qk, *fqs_av
+        if not all(pc.plain_per_tensor(f) for f in (fq_q, fq_k, fq_p, fq_v)):
+            return None
+    if fp8_kernel and fq_q is not None and switches.on("QT_FP8_ATTENTION"):
         out = _attention_fp8_or_none(attn, query, key, value, attention_mask, scaling, (fq_q, fq_k, fq_p, fq_v))
         if out is not None:
             return out
@@ -1199,35 +1187,18 @@ def fused_attention_or_none(attn, query, key, value, attention_mask, scaling, dr
     qq = (fq_q(query) if fq_q is not None else query).contiguous()
     kq = (fq_k(key) if fq_k is not None else key).contiguous()          # K, not K^T: elementwise, same statistics
     out = torch.empty((B, Q, H, D), dtype=torch.bfloat16, device=query.device)
-    if fq_p is not None and (fq_p._observe or fq_p._quantize):
-        fq_p._move_to(query.device)
-        fmt = fq_p._qt_format if fq_p._quantize else _IDENTITY
-        if fq_p._observe:
-            if fq_p.amax_history.numel() == 0:
-                fq_p.amax_history.resize_((fq_p.amax_history_len,)).fill_(0.0)
-                fq_p.scale.resize_(()).fill_(1.0)
-            launch_scale_update(fq_p.amax_history, fq_p.scale, fq_p.quant_max, fq_p.force_scale_power_of_two, st)
-        lut = fq_p.qmap.data_ptr() if fmt.kind == _native.QT_FMT_LUT else None
-        if lut is not None:
-            from .fake_quantize import _launch_format
-            fmt = _launch_format(fmt, fq_p.qmap)             # the row form of the map where the allocation carries it
-        unit_scale = fq_p.qscheme is None and getattr(fq_p, "_scale_is_one", True)      # no scale tensor at all
-        scale_ptr = fq_p.scale.data_ptr() if (fq_p._quantize and not unit_scale) else None
-        amax_ptr = fq_p.amax_history.data_ptr() if fq_p._observe else None
-        STATS.add(B * H * Q * C)
-    else:
-        fmt, lut, scale_ptr, amax_ptr = _IDENTITY, None, None, None
+    fmt, lut, scale_ptr, amax_ptr = _probs_fq_launch_args(fq_p, query.device, st, B * H * Q * C, drop_unit_scale=True)
     # table formats: the output projection's stateless input fake-quantizer of the SAME format rides on the kernel's epilogue (its hook
     # then hands the result through: fake_quantize.expect_prequantized)
     fq_o = None
-    if (table_p and scale_ptr is None and amax_ptr is None and (fmt.p1 & 1) and os.environ.get("QT_FUSED_PRODUCER_FQ", "1") != "0"
-            and os.environ.get("QT_FUSED_PRODUCER_MAP", "1") != "0"):
+    if (table_p and scale_ptr is None and amax_ptr is None and (fmt.p1 & 1) and switches.on("QT_FUSED_PRODUCER_FQ")
+            and switches.on("QT_FUSED_PRODUCER_MAP")):
         from .model_fusions import consumer_fq_map
         proj = getattr(attn, "o_proj", None) or attn.__dict__.get("_qt_out_proj")
         cand = consumer_fq_map(proj) if proj is not None else None
         if cand is not None and cand.dtype == fq_p.dtype:
             fq_o = cand
-    if not (table_p and scale_ptr is None and amax_ptr is None and fq_v is not None and not _has_table_hooks(fq_v)
+    if not (table_p and scale_ptr is None and amax_ptr is None and fq_v is not None and pc.no_forward_hooks(fq_v)
             and attention_rows_or_none(L, st, qq, kq, value, fq_v, mask, attention_mask, (msb, msh, msq), out, (B, H, Q, C, D), scaling, fmt, lut,
                                        fq_o is not None, attn=attn)):
         vq = (fq_v(value) if fq_v is not None else value).contiguous()
@@ -1236,11 +1207,6 @@ def fused_attention_or_none(attn, query, key, value, attention_mask, scaling, dr
     if fq_o is not None:
         fq_o.expect_prequantized(out, None)
     return out
-
-
-def _has_table_hooks(fq):
-    """A fake-quantizer somebody hooked (forward hooks / pre-hooks) must run as the module it is."""
-    return bool(fq._forward_hooks or fq._forward_pre_hooks)
 
 
 def attention_rows_or_none(L, st, qq, kq, value, fq_v, mask, mask_owner, mask_strides, out, dims, scaling, fmt, lut, out_fq, attn=None):
@@ -1254,7 +1220,6 @@ def attention_rows_or_none(L, st, qq, kq, value, fq_v, mask, mask_owner, mask_st
         return False
     if not (isinstance(fq_v, FusedAmaxObsFakeQuantize) and fq_v.stateless_map() and fq_v._qt_format.kind == _native.QT_FMT_LUT):
         return False
-    from .fake_quantize import _launch_format
     fq_v._move_to(value.device)
     vfmt = _launch_format(fq_v._qt_format, fq_v.qmap)
     if not (vfmt.p1 & 1) or value.dtype != torch.bfloat16 or value.stride(3) != 1 or any(s_ % 8 for s_ in value.stride()[:3]) or value.data_ptr() % 16:

@@ -10,10 +10,11 @@ fake-quantizer's own pass) tells the consumer of its result what it already did.
   _qt_origin            tensor_key of the tensor this one is fq(.) of (sibling GEMMs)
 
 This module is the only code that reads or writes them.  It imports nothing from the package."""
-import os
 import weakref
 
 import torch
+
+from . import switches
 
 
 def valid(t):
@@ -109,7 +110,7 @@ def mark_lazy(t):
     """t's values were not written (its FP8 codes were).  QT_LAZY_POISON=1 (tests): fill it with NaN, so that a read that bypasses
     materialize cannot go unnoticed.  t is registered by its address so that a VIEW of it -- a reshape between the producer and the
     consuming hook drops Python attributes -- is still recognised by materialize; the entry dies with the tensor."""
-    if os.environ.get("QT_LAZY_POISON", "0") == "1":
+    if switches.on("QT_LAZY_POISON"):
         stamped = valid(t)
         t.fill_(float("nan"))
         if stamped:

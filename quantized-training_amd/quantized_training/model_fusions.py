@@ -17,11 +17,10 @@ differs from torch's kernel only through the summation order of its mean / varia
 """
 import ctypes
 import logging
-import os
 
 import torch
 
-from . import _native, handover
+from . import _native, handover, planner_checks as pc, switches
 from .fake_quantize import FusedAmaxObsFakeQuantize, _stream_ptr
 
 __all__ = ["apply_llama_fusions", "apply_bert_fusions", "rmsnorm", "silu_mul", "rope", "layernorm", "gelu"]
@@ -40,7 +39,7 @@ def _declined(what, why):
 
 
 def _enabled():
-    return os.environ.get("QT_FUSED_MODEL_OPS", "1") != "0"
+    return switches.on("QT_FUSED_MODEL_OPS")
 
 
 # ---- the Hugging Face layout the rebound forwards were written against --------------------------------------------------------------
@@ -118,10 +117,6 @@ def _eligible(*tensors):
     if not _enabled() or torch.is_grad_enabled():
         return False
     return all(t.device.type == "cuda" and t.dtype == torch.bfloat16 for t in tensors) and not (tensors and _tracing(tensors[0]))
-
-
-def _hooked(mod):
-    return bool(mod._forward_hooks or mod._forward_pre_hooks or mod._backward_hooks or mod._backward_pre_hooks)
 
 
 # ---- kernels behind tensor-level functions ------------------------------------------------------------------------
@@ -211,7 +206,7 @@ def _add_rmsnorm_or_none(x, residual, norm):
     """The residual add in front of a LlamaRMSNorm absorbed into its kernel, or None (gradients needed, hooks on the norm,
     other dtypes / devices, QT_FUSED_MODEL_OPS=0)."""
     w = getattr(norm, "weight", None)
-    if (norm is None or w is None or norm.__dict__.get("_qt_hf_forward") is None or _hooked(norm) or not _eligible(x, residual, w)
+    if (norm is None or w is None or norm.__dict__.get("_qt_hf_forward") is None or not pc.no_hooks(norm) or not _eligible(x, residual, w)
             or x.shape != residual.shape or x.shape[-1] % 8 != 0 or x.shape[-1] > 16384 or x.numel() == 0 or not w.is_contiguous()):
         return None
     fq = _norm_consumer_fq(norm, allow_all=True, allow_map=True)
@@ -222,14 +217,8 @@ def _add_rmsnorm_or_none(x, residual, norm):
 def consumer_fq_map(linear):
     """consumer_fq for stateless TABLE formats (posit, fpN, ... without `qs`): the input fake-quantizer of a QAT Linear when a producing
     kernel may apply it in its row form (FusedAmaxObsFakeQuantize.map_producer_format), else None."""
-    holder = getattr(linear, "activation_pre_process", None)
-    hooked_once = len(linear._forward_pre_hooks) == 1 or linear.__dict__.get("_qt_prepared")
-    if holder is None or not hooked_once or "0" not in holder or len(holder) != 1 or os.environ.get("QT_FUSED_PRODUCER_MAP", "1") == "0":
-        return None
-    fq = holder["0"]
-    if not isinstance(fq, FusedAmaxObsFakeQuantize) or not fq.stateless_map() or fq._qt_format.kind != _native.QT_FMT_LUT:
-        return None
-    return fq
+    fq = pc.linear_input_fq(linear) if switches.on("QT_FUSED_PRODUCER_MAP") else None
+    return fq if isinstance(fq, FusedAmaxObsFakeQuantize) and fq.stateless_map() and fq._qt_format.kind == _native.QT_FMT_LUT else None
 
 
 def _mark_done(y, fqs):
@@ -277,7 +266,7 @@ def rope_map(q, k, cos, sin, fq_q, fq_k, inner_q=False, inner_k=False, value_job
     """Rotary embedding with qk_matmul's two stateless table-format input fake-quantizers (one format) in the same pass: contiguous
     [B, H, S, D] outputs marked as done for them, or None.
 
-    value_job = (attn, value, fq_v), set when the table-format attention core is what will consume these tensors (_rows_attention_plan):
+    value_job = (attn, value, fq_v), set when the table-format attention core is what will consume these tensors (_attention_value_plan):
     the launch then also carries that kernel's value pass (qt_rope_map_value) and leaves V^T with the attention module for the core's
     call (fused.attention_rows_or_none, which counts fq_v's call when it takes it)."""
     pf = fq_q.map_producer_format(q.device)
@@ -316,7 +305,7 @@ def _norm_consumer_fq(norm, allow_all=False, allow_map=False):
     same stateless format (then the first one's pass is fused here and the siblings', run on the already quantized
     tensor, reproduce it -- the formats are idempotent)."""
     consumers = norm.__dict__.get("_qt_consumers")
-    if not consumers or os.environ.get("QT_FUSED_PRODUCER_FQ", "1") == "0":
+    if not consumers or not switches.on("QT_FUSED_PRODUCER_FQ"):
         return None
     fqs = [consumer_fq(lin) for lin in consumers]
     if any(f is None for f in fqs):
@@ -362,14 +351,8 @@ def silu_mul(gate, up):
 def consumer_fq(linear):
     """The input fake-quantizer of a QAT Linear when a producing kernel may apply it (see
     FusedAmaxObsFakeQuantize.producer_fusable), else None.  It exists only after the layer's first call."""
-    holder = getattr(linear, "activation_pre_process", None)
-    hooked_once = len(linear._forward_pre_hooks) == 1 or linear.__dict__.get("_qt_prepared")    # pt2e_fusion.PreparedLinear: the fake-quantizer is a graph node
-    if holder is None or not hooked_once or "0" not in holder or len(holder) != 1:
-        return None
-    fq = holder["0"]
-    if not isinstance(fq, FusedAmaxObsFakeQuantize) or not fq.producer_fusable():
-        return None
-    return fq
+    fq = pc.linear_input_fq(linear)
+    return fq if isinstance(fq, FusedAmaxObsFakeQuantize) and fq.producer_fusable() else None
 
 
 def codes_only_ok(linears, producer=None):
@@ -379,15 +362,16 @@ def codes_only_ok(linears, producer=None):
     nobody hooked the producing module (a forward hook would be handed the unwritten tensor)."""
     from . import fused
     from .modules.qat.linear import Linear as QATLinear
-    if os.environ.get("QT_CODES_ONLY", "1") == "0" or torch.is_grad_enabled() or not fused.fp8_gemm_enabled() or not linears:
+    if not switches.on("QT_CODES_ONLY") or torch.is_grad_enabled() or not fused.fp8_gemm_enabled() or not linears:
         return False
-    if producer is not None and _hooked(producer):
+    if producer is not None and not pc.no_hooks(producer):
         return False
     for lin in linears:
-        if not isinstance(lin, QATLinear) or type(lin).forward is not QATLinear.forward or lin._forward_hooks or lin.__dict__.get("_qt_prepared"):
+        # (the Linear: its forward hooks only -- consumer_fq below pins its pre-hooks, and backward hooks cannot fire under no_grad)
+        if not isinstance(lin, QATLinear) or type(lin).forward is not QATLinear.forward or not pc.no_output_hook(lin) or lin.__dict__.get("_qt_prepared"):
             return False
         fq = consumer_fq(lin)
-        if fq is None or fq._forward_hooks or fq._forward_pre_hooks:
+        if fq is None or not pc.no_forward_hooks(fq):
             return False
     for lin in linears:
         consumer_fq(lin).__dict__["_qt_lazy_ok"] = True          # (its hook then hands a lazy tensor through instead of decoding it)
@@ -427,7 +411,7 @@ def attention_output(module, out):
     """[B, H, S, D] attention result -> the [B, S, H, D] tensor HF's attention block expects, fused with the output
     projection's input fake-quantizer when that is a stateless FP8 one (LLaMA-style blocks with `o_proj`)."""
     proj = getattr(module, "o_proj", None)
-    if (proj is not None and os.environ.get("QT_FUSED_PRODUCER_FQ", "1") != "0" and _eligible(out) and out.dim() == 4
+    if (proj is not None and switches.on("QT_FUSED_PRODUCER_FQ") and _eligible(out) and out.dim() == 4
             and out.is_contiguous() and out.shape[-1] % 8 == 0 and out.numel() > 0):
         fq = consumer_fq(proj)
         if fq is not None:
@@ -462,7 +446,7 @@ def rope_fq(q, k, cos, sin, fq_q, fq_k, value_job=None):
     """Rotary embedding with qk_matmul's two input fake-quantizers applied in the same pass; outputs are contiguous
     [B, H, S, D] (the layout those hooks write) and marked as done for fq_q / fq_k.
 
-    value_job = (attn, value, fq_v), set when the FP8 attention kernel is what will consume these tensors (_fp8_attention_plan): the
+    value_job = (attn, value, fq_v), set when the FP8 attention kernel is what will consume these tensors (_attention_value_plan): the
     launch then also carries that kernel's value-code pass (qt_rope_fq_value), and writes the FP8 codes ONLY -- the kernel multiplies
     codes; should anything else ask for the bf16 values after all (the fake-quantizers' hand-over is the one door to them), they are
     decoded from the codes then, exactly (handover.materialize)."""
@@ -539,7 +523,7 @@ def gelu(x, fq=None, codes_only=False):
 
 def _layernorm_ok(norm, x, residual=None):
     w, b = getattr(norm, "weight", None), getattr(norm, "bias", None)
-    if type(norm) is not torch.nn.LayerNorm or w is None or b is None or _hooked(norm) or len(norm.normalized_shape) != 1:
+    if type(norm) is not torch.nn.LayerNorm or w is None or b is None or not pc.no_hooks(norm) or len(norm.normalized_shape) != 1:
         return False
     ts = (x, w, b) if residual is None else (x, residual, w, b)
     cols = x.shape[-1]
@@ -552,7 +536,7 @@ def add_layernorm_or_none(block, hidden, residual):
     add is hooked (`--quantize_forward residual`), gradients are needed, or the tensors are not bf16 device tensors."""
     add = getattr(block, "residual", None)
     norm = getattr(block, "LayerNorm", None)
-    if norm is None or add is None or _hooked(add) or not _layernorm_ok(norm, hidden, residual):
+    if norm is None or add is None or not pc.no_hooks(add) or not _layernorm_ok(norm, hidden, residual):
         return None
     return layernorm(hidden, norm, residual, _norm_consumer_fq(norm, allow_all=True), codes_only=codes_only_ok(norm.__dict__.get("_qt_consumers"), norm))
 
@@ -575,7 +559,7 @@ def _is_erf_gelu(act):
 
 def _intermediate_forward(self, hidden_states):
     act = self.intermediate_act_fn
-    if isinstance(act, torch.nn.Module) and not _hooked(act) and _is_erf_gelu(act):
+    if isinstance(act, torch.nn.Module) and pc.no_hooks(act) and _is_erf_gelu(act):
         h = self.dense(hidden_states)
         if torch.is_grad_enabled() and h.is_cuda:
             from . import train_fusions
@@ -584,7 +568,7 @@ def _intermediate_forward(self, hidden_states):
                 return y
         if _eligible(h) and h.numel() % 8 == 0 and h.numel() > 0:
             consumer = self.__dict__.get("_qt_consumer")
-            fq = consumer_fq(consumer) if consumer is not None and os.environ.get("QT_FUSED_PRODUCER_FQ", "1") != "0" else None
+            fq = consumer_fq(consumer) if consumer is not None and switches.on("QT_FUSED_PRODUCER_FQ") else None
             return gelu(h, fq, codes_only=fq is not None and codes_only_ok([consumer], self))
         return act(h)
     return self._qt_hf_forward(hidden_states)
@@ -666,15 +650,15 @@ def _qk_fqs(attn, table=False):
     """(fq_q, fq_k) of attn.qk_matmul when both may be applied by the rotary kernel, else None.  table: stateless table formats (row
     form) instead of exact FP8 ones."""
     mm = getattr(attn, "qk_matmul", None)
-    holder = getattr(mm, "activation_pre_process", None) if mm is not None else None
-    if holder is None or len(mm._forward_pre_hooks) != 1 or mm._forward_hooks or set(holder.keys()) != {"0", "1"}:
+    fqs = pc.holder_fqs(mm, "activation_pre_process", "0", "1")
+    if fqs is None or not pc.quantize_hooks_only(mm):
         return None
-    fq_q, fq_k = holder["0"], holder["1"]
-    for f in (fq_q, fq_k):
+    fq_q, fq_k = fqs
+    for f in fqs:
         if not isinstance(f, FusedAmaxObsFakeQuantize):
             return None
         if table:
-            if not (f.stateless_map() and f._qt_format.kind == _native.QT_FMT_LUT) or os.environ.get("QT_FUSED_PRODUCER_MAP", "1") == "0":
+            if not (f.stateless_map() and f._qt_format.kind == _native.QT_FMT_LUT) or not switches.on("QT_FUSED_PRODUCER_MAP"):
                 return None
         elif not f.producer_fusable():
             return None
@@ -686,7 +670,7 @@ def _qk_fqs(attn, table=False):
 # ---- module-level swaps -------------------------------------------------------------------------------------------
 def _rmsnorm_forward(self, hidden_states):
     pre = getattr(hidden_states, "_qt_prenormed", None)
-    if pre is not None and pre[0] is self and not _hooked(self):
+    if pre is not None and pre[0] is self and pc.no_hooks(self):
         return pre[1]                    # the previous block's kernel added its residual and normalised for this norm
     w = self.weight
     if (_eligible(hidden_states, w) and hidden_states.shape[-1] % 8 == 0 and hidden_states.shape[-1] <= 16384
@@ -697,10 +681,6 @@ def _rmsnorm_forward(self, hidden_states):
             return rmsnorm_fq(hidden_states, w, self.variance_epsilon, fq, codes_only=lazy)
         return rmsnorm(hidden_states, w, self.variance_epsilon)
     return self._qt_hf_forward(hidden_states)
-
-
-def _only_pre_hooks(mod):
-    return not (mod._forward_hooks or mod._backward_hooks or mod._backward_pre_hooks)
 
 
 def _run_pre_hooks(mod, x):
@@ -728,11 +708,11 @@ def _fused_mlp_or_none(self, x):
     from .fake_quantize import STATS
     from .modules.qat.linear import Linear as QATLinear
     gate, up, down = self.gate_proj, self.up_proj, self.down_proj
-    if os.environ.get("QT_FQ8_MLP", "1") == "0" or not fused.fq8_gemm_enabled() or fused._WEIGHT_CACHE["on"]:
+    if not switches.on("QT_FQ8_MLP") or not fused.fq8_gemm_enabled() or fused._WEIGHT_CACHE["on"]:
         return None
-    if not (isinstance(gate, QATLinear) and isinstance(up, QATLinear) and _eligible(x) and _only_pre_hooks(gate) and _only_pre_hooks(up)):
+    if not (isinstance(gate, QATLinear) and isinstance(up, QATLinear) and _eligible(x) and pc.only_pre_hooks(gate) and pc.only_pre_hooks(up)):
         return None
-    if os.environ.get("QT_FUSED_PRODUCER_FQ", "1") == "0":
+    if not switches.on("QT_FUSED_PRODUCER_FQ"):
         return None
     fq_out = consumer_fq(down)
     for l in (gate, up):
@@ -779,23 +759,27 @@ def _after_hooks_unfused(self, xg, xu):
     return silu_mul_fq(gate, up, fq) if fq is not None else silu_mul(gate, up)
 
 
+def silu_mul_for(down, gate, up):
+    """SiLU(gate) * up in one launch, with the input fake-quantizer of the consuming projection `down` (may be None) applied where a
+    kernel can: stateless FP8 formats with their codes, stateless table formats in their row form."""
+    on = down is not None and switches.on("QT_FUSED_PRODUCER_FQ")
+    fq = consumer_fq(down) if on else None
+    if fq is not None:
+        return silu_mul_fq(gate, up, fq)
+    mfq = consumer_fq_map(down) if on else None
+    y = silu_mul_map(gate, up, mfq) if mfq is not None else None
+    return y if y is not None else silu_mul(gate, up)
+
+
 def _mlp_forward(self, x):
-    if not _hooked(self.act_fn) and getattr(self.act_fn, "__class__", None).__name__ in ("SiLU", "SiLUActivation"):
+    if pc.no_hooks(self.act_fn) and getattr(self.act_fn, "__class__", None).__name__ in ("SiLU", "SiLUActivation"):
         y = _fused_mlp_or_none(self, x)
         if y is not None:
             return self.down_proj(y)
         gate = self.gate_proj(x)
         up = self.up_proj(x)
         if _eligible(gate, up) and gate.shape == up.shape and gate.shape[-1] % 8 == 0 and gate.numel() > 0:
-            fq = consumer_fq(self.down_proj)
-            if fq is not None and os.environ.get("QT_FUSED_PRODUCER_FQ", "1") != "0":
-                return self.down_proj(silu_mul_fq(gate, up, fq))
-            mfq = consumer_fq_map(self.down_proj) if os.environ.get("QT_FUSED_PRODUCER_FQ", "1") != "0" else None
-            if mfq is not None:
-                y = silu_mul_map(gate, up, mfq)
-                if y is not None:
-                    return self.down_proj(y)
-            return self.down_proj(silu_mul(gate, up))
+            return self.down_proj(silu_mul_for(self.down_proj, gate, up))
         return self.down_proj(self.act_fn(gate) * up)
     return self._qt_hf_forward(x)
 
@@ -882,35 +866,42 @@ def _rotary_table_forward(self, x, position_ids):
 _ROPE_PATCHED = {"done": False}
 
 
-def _fp8_attention_plan(attn, q, qk_fqs):
-    """(attn, value, fq_v) when the attention core of this call will be qt_attention_fp8 as far as can be told here -- the rotary
-    kernel's outputs go nowhere else (no KV cache), the four fake-quantizers are stateless FP8 ones of one format, the shapes are the
-    kernel's, and the value projection is the q / k / v sibling group's slice (so it exists already) -- else None."""
-    if (os.environ.get("QT_ROPE_VALUE_LAUNCH", "1") == "0" or os.environ.get("QT_FP8_ATTENTION_KERNEL", "1") == "0"
-            or os.environ.get("QT_FP8_ATTENTION", "1") == "0" or os.environ.get("QT_FUSED_ATTENTION", "auto") == "0"
-            or not attn.__dict__.get("_qt_cacheless", False)):
+def _attention_value_plan(attn, q, qk_fqs, table=False):
+    """(attn, value, fq_v) when the attention core of this call will be qt_attention_fp8 -- table: qt_attention_rows_bf16 -- as far as
+    can be told here: the rotary kernel's outputs go nowhere else (no KV cache), the four fake-quantizers are stateless FP8 ones of one
+    format (table: stateless TABLE formats of one dtype in their row form, nobody hooked them), the shapes are the kernel's (table:
+    head_dim 128 only), and the value projection is the q / k / v sibling group's slice (so it exists already) -- else None."""
+    if (not switches.on("QT_ROPE_VALUE_LAUNCH") or not switches.on("QT_FUSED_ATTENTION") or not attn.__dict__.get("_qt_cacheless", False)
+            or not (table or (switches.on("QT_FP8_ATTENTION_KERNEL") and switches.on("QT_FP8_ATTENTION")))):
         return None
     vproj = getattr(attn, "v_proj", None)
     group = vproj.__dict__.get("_qt_sibling_group") if vproj is not None else None
     av = getattr(attn, "av_matmul", None)
-    holder = getattr(av, "activation_pre_process", None) if av is not None else None
-    if (group is None or group.stash is None or holder is None or set(holder.keys()) != {"0", "1"} or vproj not in group.layers
-            or len(av._forward_pre_hooks) != 1 or av._forward_hooks):
+    av_fqs = pc.holder_fqs(av, "activation_pre_process", "0", "1")
+    if group is None or group.stash is None or av_fqs is None or vproj not in group.layers or not pc.quantize_hooks_only(av):
         return None
-    fqs = (*qk_fqs, holder["0"], holder["1"])
-    if not all(isinstance(f, FusedAmaxObsFakeQuantize) and f.producer_fusable() for f in fqs) or len({f._qt_format.key() for f in fqs}) != 1:
+    fqs = (*qk_fqs, *av_fqs)
+    if table:
+        for f in fqs:
+            if not (isinstance(f, FusedAmaxObsFakeQuantize) and f.stateless_map() and f._qt_format.kind == _native.QT_FMT_LUT
+                    and f.map_producer_format(q.device) is not None) or not pc.no_forward_hooks(f):
+                return None
+        if len({str(f.dtype) for f in fqs}) != 1:
+            return None
+    elif not all(isinstance(f, FusedAmaxObsFakeQuantize) and f.producer_fusable() for f in fqs) or len({f._qt_format.key() for f in fqs}) != 1:
         return None
     B, H, S, D = q.shape
     Ns = [l.weight.shape[0] for l in group.layers]
     idx = group.layers.index(vproj)
     y = group.stash[1]
-    if D not in (64, 128) or S % 128 != 0 or S > 1024 or B * H > 65535 or Ns[idx] != H * D or y.shape[0] != B * S or not group.stash[2][idx]:
+    if (D not in ((128,) if table else (64, 128)) or S % 128 != 0 or S > 1024 or B * H > 65535 or Ns[idx] != H * D or y.shape[0] != B * S
+            or not group.stash[2][idx]):
         return None                                            # (grouped-query heads, other lengths: the ordinary order)
     off = sum(Ns[:idx])
     value = y[:, off:off + Ns[idx]].view(B, S, H, D).transpose(1, 2)
     if value.dtype != torch.bfloat16 or any(st % 8 for st in value.stride()[:3]) or value.data_ptr() % 16:
         return None
-    return attn, value, holder["1"]
+    return attn, value, av_fqs[1]
 
 
 def _o_proj_weight_job(attn, q, fq_q, qmap):
@@ -920,11 +911,11 @@ def _o_proj_weight_job(attn, q, fq_q, qmap):
     from . import fused
     from .modules.qat.linear import Linear as QATLinear
     proj = getattr(attn, "o_proj", None)
-    if (os.environ.get("QT_ROPE_WEIGHT_PASS", "1") == "0" or not isinstance(proj, QATLinear) or type(proj).forward is not QATLinear.forward
+    if (not switches.on("QT_ROPE_WEIGHT_PASS") or not isinstance(proj, QATLinear) or type(proj).forward is not QATLinear.forward
             or torch.is_grad_enabled() or fused._WEIGHT_CACHE["on"] or not fused._fqt_weight_ok(proj)):
         return None
     fqw, W = proj.weight_fake_quant, proj.weight
-    if str(fqw.dtype) != str(fq_q.dtype) or fqw._forward_hooks or fqw._forward_pre_hooks:
+    if str(fqw.dtype) != str(fq_q.dtype) or not pc.no_forward_hooks(fqw):
         return None
     if W.dtype != torch.bfloat16 or not W.is_contiguous() or W.numel() % 8 or W.data_ptr() % 16 or W.device != q.device:
         return None
@@ -935,40 +926,6 @@ def _o_proj_weight_job(attn, q, fq_q, qmap):
     if fused.fqt_gemm_mode() != "0" and fused.fqt_route_is_fused(B * S, [W.shape[0]], W.shape[1], q.device):
         return None                                                             # the value-map GEMM converts the weight itself
     return fqw, W
-
-
-def _rows_attention_plan(attn, q, qk_fqs):
-    """(attn, value, fq_v) when the attention core of this call will be qt_attention_rows_bf16 as far as can be told here -- the same
-    conditions as _fp8_attention_plan with the four fake-quantizers stateless TABLE formats of one dtype in their row form, head_dim 128
-    -- else None."""
-    if (os.environ.get("QT_ROPE_VALUE_LAUNCH", "1") == "0" or os.environ.get("QT_FUSED_ATTENTION", "auto") == "0"
-            or not attn.__dict__.get("_qt_cacheless", False)):
-        return None
-    vproj = getattr(attn, "v_proj", None)
-    group = vproj.__dict__.get("_qt_sibling_group") if vproj is not None else None
-    av = getattr(attn, "av_matmul", None)
-    holder = getattr(av, "activation_pre_process", None) if av is not None else None
-    if (group is None or group.stash is None or holder is None or set(holder.keys()) != {"0", "1"} or vproj not in group.layers
-            or len(av._forward_pre_hooks) != 1 or av._forward_hooks):
-        return None
-    fqs = (*qk_fqs, holder["0"], holder["1"])
-    for f in fqs:
-        if not (isinstance(f, FusedAmaxObsFakeQuantize) and f.stateless_map() and f._qt_format.kind == _native.QT_FMT_LUT
-                and f.map_producer_format(q.device) is not None) or f._forward_hooks or f._forward_pre_hooks:
-            return None
-    if len({str(f.dtype) for f in fqs}) != 1:
-        return None
-    B, H, S, D = q.shape
-    Ns = [l.weight.shape[0] for l in group.layers]
-    idx = group.layers.index(vproj)
-    y = group.stash[1]
-    if D != 128 or S % 128 != 0 or S > 1024 or B * H > 65535 or Ns[idx] != H * D or y.shape[0] != B * S or not group.stash[2][idx]:
-        return None
-    off = sum(Ns[:idx])
-    value = y[:, off:off + Ns[idx]].view(B, S, H, D).transpose(1, 2)
-    if value.dtype != torch.bfloat16 or any(st % 8 for st in value.stride()[:3]) or value.data_ptr() % 16:
-        return None
-    return attn, value, holder["1"]
 
 
 def _patch_rope():
@@ -992,13 +949,13 @@ def _patch_rope():
         if ok:
             if cos.shape[0] != q.shape[0]:                      # position ids shared by the batch
                 cos, sin = cos.expand(q.shape[0], -1, -1).contiguous(), sin.expand(q.shape[0], -1, -1).contiguous()
-            if _CURRENT_ATTN and os.environ.get("QT_FUSED_PRODUCER_FQ", "1") != "0":
+            if _CURRENT_ATTN and switches.on("QT_FUSED_PRODUCER_FQ"):
                 fqs = _qk_fqs(_CURRENT_ATTN[-1])
                 if fqs is not None:
-                    return rope_fq(q, k, cos, sin, *fqs, value_job=_fp8_attention_plan(_CURRENT_ATTN[-1], q, fqs))
+                    return rope_fq(q, k, cos, sin, *fqs, value_job=_attention_value_plan(_CURRENT_ATTN[-1], q, fqs))
                 mfqs = _qk_fqs(_CURRENT_ATTN[-1], table=True)
                 if mfqs is not None:
-                    got = rope_map(q, k, cos, sin, *mfqs, value_job=_rows_attention_plan(_CURRENT_ATTN[-1], q, mfqs))
+                    got = rope_map(q, k, cos, sin, *mfqs, value_job=_attention_value_plan(_CURRENT_ATTN[-1], q, mfqs, table=True))
                     if got is not None:
                         return got
             return rope(q, k, cos, sin)

@@ -16,8 +16,8 @@ GEMM_ROUTES = {}          # "train:<kind> MxNxK" -> "in_tree_bf16_gemm" | "libra
 
 
 def train_gemm_enabled():
-    import os
-    return os.environ.get("QT_TRAIN_GEMM", "1") != "0"
+    from ... import switches
+    return switches.on("QT_TRAIN_GEMM")
 
 
 def train_gemm_or_none(a, b, bias, trans_a, trans_b, kind):
@@ -277,9 +277,10 @@ class Linear(nn.Linear):
             self.__dict__["_qt_train_xw"] = (weakref.ref(input), weakref.ref(wq))
             defer = False
             owner = self.__dict__.get("_qt_qkv_member")
-            if owner is not None and not self._forward_hooks:
-                from ... import train_fusions
-                defer = train_fusions.attention_block_active(owner) and train_fusions._on("qkvfwd")
+            if owner is not None:
+                from ... import planner_checks, train_fusions
+                # (a forward hook would see the output before the launch that writes it: train_fusions._mark_qkv_members)
+                defer = planner_checks.no_output_hook(self) and train_fusions.attention_block_active(owner) and train_fusions._on("qkvfwd")
             return _LinearColsumBias.apply(input, wq, b, defer)
         return F.linear(input, wq, b)
 

@@ -1,10 +1,8 @@
 """Hookable wrappers for functional ops so that `quantize()` can attach fake-quantizers to their
 inputs (upstream src/quantized_training/modules/quantizable/functional_modules.py:8-26)."""
-import os
-
 import torch
 
-from ... import handover
+from ... import handover, switches
 
 __all__ = ["AddFunctional", "MulFunctional", "MatmulFunctional"]
 
@@ -58,7 +56,7 @@ class MatmulFunctional(_BinaryOp):
         # Q . K^T with both operands already fake-quantized to exact FP8 values by the kernel that produced them
         # (model_fusions.rope_fq): the same products on the FP8 matrix cores.  The input hooks have run by now.
         q8, k8 = handover.codes(lhs), handover.codes_of_transpose(rhs)
-        if (q8 is not None and k8 is not None and os.environ.get("QT_FP8_ATTENTION", "1") != "0" and lhs.dim() == 4
+        if (q8 is not None and k8 is not None and switches.on("QT_FP8_ATTENTION") and lhs.dim() == 4
                 and q8.shape == lhs.shape and k8.shape[:2] == lhs.shape[:2] and k8.shape[-1] == lhs.shape[-1]
                 and not (torch.is_grad_enabled() and (lhs.requires_grad or rhs.requires_grad))):
             from ...fused import lt_fp8_gemm

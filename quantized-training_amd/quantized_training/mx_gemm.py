@@ -15,11 +15,10 @@ Anything else (codebooks, int formats, block size 16, fp8 scales ...) returns No
 reference formulation.  QT_MX_GEMM=0 disables the native path.
 """
 import ctypes
-import os
 
 import torch
 
-from . import _native
+from . import _native, switches
 from .fake_quantize import _stream_ptr, _table_for
 
 __all__ = ["mx_linear_or_none", "mx_matmul_or_none", "remember_format", "STATS"]
@@ -77,7 +76,7 @@ def remember_format(values, qmap, scale=None, pow2=None):
 
 
 def _enabled():
-    return os.environ.get("QT_MX_GEMM", "1") != "0"
+    return switches.on("QT_MX_GEMM")
 
 
 def _pack(values, scale, fmt_id, block_size, batch, rows, K, x_strides, s_strides, check):

@@ -23,14 +23,13 @@ The pass never changes what is computed, only how many launches it takes; a chai
 import copy
 import ctypes
 import operator
-import os
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 from torch.fx import GraphModule, Node
 
-from . import _native, handover
+from . import _native, handover, switches
 from .fake_quantize import STATS as _FQ_STATS, FusedAmaxObsFakeQuantize, _stream_ptr
 from .modules.qat.linear import Linear as QATLinear
 
@@ -59,13 +58,13 @@ class PreparedLinear(QATLinear):
 
 
 def _producer_ok(fq):
-    return isinstance(fq, FusedAmaxObsFakeQuantize) and fq.producer_fusable() and os.environ.get("QT_FUSED_PRODUCER_FQ", "1") != "0"
+    return isinstance(fq, FusedAmaxObsFakeQuantize) and fq.producer_fusable() and switches.on("QT_FUSED_PRODUCER_FQ")
 
 
 def _table_ok(fq):
     """A stateless table-format fake-quantizer (posit, fpN, ... without `qs`) a producing kernel may apply in its row form."""
     return (isinstance(fq, FusedAmaxObsFakeQuantize) and fq.stateless_map() and fq._qt_format.kind == _native.QT_FMT_LUT
-            and os.environ.get("QT_FUSED_PRODUCER_FQ", "1") != "0" and os.environ.get("QT_FUSED_PRODUCER_MAP", "1") != "0")
+            and switches.on("QT_FUSED_PRODUCER_FQ") and switches.on("QT_FUSED_PRODUCER_MAP"))
 
 
 class PreparedMLP(nn.Module):
@@ -84,16 +83,7 @@ class PreparedMLP(nn.Module):
             return y
         gate, up = self.gate_proj(x), self.up_proj(x)
         if mf._eligible(gate, up) and gate.shape == up.shape and gate.shape[-1] % 8 == 0 and gate.numel() > 0:
-            down = self.__dict__["down_proj"]
-            fq = mf.consumer_fq(down) if down is not None else None
-            if fq is not None and os.environ.get("QT_FUSED_PRODUCER_FQ", "1") != "0":
-                return mf.silu_mul_fq(gate, up, fq)
-            mfq = mf.consumer_fq_map(down) if down is not None and os.environ.get("QT_FUSED_PRODUCER_FQ", "1") != "0" else None
-            if mfq is not None:
-                y = mf.silu_mul_map(gate, up, mfq)
-                if y is not None:
-                    return y
-            return mf.silu_mul(gate, up)
+            return mf.silu_mul_for(self.__dict__["down_proj"], gate, up)
         return F.silu(gate) * up
 
 
@@ -199,7 +189,7 @@ class PreparedAttention(nn.Module):
         from . import fused, model_fusions as mf
         fq_q, fq_k, fq_p, fq_v = self.__dict__["fqs"]
         inner_q, inner_k = self.__dict__["inner"]
-        if os.environ.get("QT_FUSED_ATTENTION", "auto") == "0":
+        if not switches.on("QT_FUSED_ATTENTION"):
             return None
         if not (mf._eligible(q, k, v, cos, sin) and q.dim() == 4 and q.shape == k.shape == v.shape):
             return None
@@ -255,7 +245,7 @@ class PreparedAttention(nn.Module):
         from . import fused, model_fusions as mf
         fqs = self.__dict__["fqs"]
         inner_q, inner_k = self.__dict__["inner"]
-        if os.environ.get("QT_FP8_ATTENTION", "1") == "0" or os.environ.get("QT_FP8_ATTENTION_KERNEL", "1") == "0":
+        if not switches.on("QT_FP8_ATTENTION") or not switches.on("QT_FP8_ATTENTION_KERNEL"):
             return None
         if not (mf._eligible(q, k, v, cos, sin) and q.dim() == 4 and q.shape == k.shape == v.shape):
             return None
@@ -899,7 +889,7 @@ def unfuse_prepared_graph(model: GraphModule):
 def fuse_prepared_graph(model: GraphModule):
     """Rewrite the chains listed in the module docstring of a prepared graph in place; returns the number of rewrites by kind.
     Idempotent; safe on any graph (unrecognised chains are left alone).  `QT_PT2E_FUSE=0` turns it into a no-op."""
-    if os.environ.get("QT_PT2E_FUSE", "1") == "0" or "_qt_unfused_graph" in model.__dict__:
+    if not switches.on("QT_PT2E_FUSE") or "_qt_unfused_graph" in model.__dict__:
         return {}
     model.__dict__["_qt_unfused_graph"] = _copy_graph(model.graph)
     p = _Pass(model)

@@ -22,12 +22,11 @@ Accumulation is exact (int32) where upstream's fp32 / bf16 `aten.linear` rounds,
 bound, not bit for bit.  STATS counts the native launches (tests assert the route was taken).
 """
 import ctypes
-import os
 
 import torch
 from torch.fx import GraphModule
 
-from . import _native
+from . import _native, switches
 from .fake_quantize import _stream_ptr
 
 __all__ = ["fuse_native_gemms", "STATS"]
@@ -268,7 +267,7 @@ def fuse_native_gemms(model: GraphModule) -> int:
 
 
 def enabled_for(model) -> bool:
-    if os.environ.get("QT_PT2E_NATIVE", "1") == "0":
+    if not switches.on("QT_PT2E_NATIVE"):
         return False
     try:
         return next(iter(model.parameters())).device.type == "cuda"

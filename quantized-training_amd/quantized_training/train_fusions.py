@@ -23,12 +23,11 @@ at a LayerNorm's output are summed by that LayerNorm's backward (take_deferred, 
 bit for bit (_EmbeddingTrainFn).  One debug mask, QT_TRAIN_DEBUG (an integer, default 0 = every fusion on; DEBUG_BITS below), switches
 fusions OFF for A/B runs and tests -- rounds 4-5 had grown seven separate switches."""
 import ctypes
-import os
 import weakref
 
 import torch
 
-from . import _native
+from . import _native, planner_checks as pc, switches
 from .handover import tensor_key
 
 __all__ = ["plan", "unplan", "enabled", "STATS"]
@@ -75,11 +74,7 @@ DEBUG_BITS = {"chains": 1, "colsum": 2, "producers": 4, "attention": 8, "fanin":
 
 
 def _on(name):
-    try:
-        mask = int(os.environ.get("QT_TRAIN_DEBUG", "0") or "0", 0)
-    except ValueError:
-        raise ValueError(f"QT_TRAIN_DEBUG={os.environ.get('QT_TRAIN_DEBUG')!r}: an integer mask of {DEBUG_BITS}") from None
-    return not (mask & DEBUG_BITS[name])
+    return not (switches.mask("QT_TRAIN_DEBUG", DEBUG_BITS) & DEBUG_BITS[name])
 
 
 def enabled():
@@ -140,7 +135,7 @@ def _mark_qkv_members(attn, lins):
     (a hook would see the output before the launch that writes it)."""
     import weakref
     from .modules.qat.linear import Linear as QATLinear
-    if not all(type(l) is QATLinear and not l._forward_hooks and l.weight.shape == lins[0].weight.shape and (l.bias is None) == (lins[0].bias is None)
+    if not all(type(l) is QATLinear and pc.no_output_hook(l) and l.weight.shape == lins[0].weight.shape and (l.bias is None) == (lins[0].bias is None)
                for l in lins):
         return
     if not attn.__dict__.get("_qt_qkv_hooks", False):
@@ -255,7 +250,7 @@ def _chain_scratch(nbytes, device):
 
 def run_chain(head, chain, X):
     """Evaluates every member of `chain` on X in one launch; returns the head's result or None (the head then runs alone)."""
-    from .fake_quantize import _launch_format, _stream_ptr, launch_scale_update, _Stats, _take_preupdate
+    from .fake_quantize import _stream_ptr, _Stats
     if not (enabled() and X.is_cuda and X.dtype == torch.bfloat16 and X.is_contiguous() and X.dim() >= 2 and X.numel() > 0
             and X.data_ptr() % 16 == 0):
         return None
@@ -265,16 +260,8 @@ def run_chain(head, chain, X):
         return None
     dev = X.device
     members = chain.members
-    if members[0][0] is not head or not all(_member_ok(fq, dev) for fq, _ in members):
-        return None
-    for fq, _ in members:
-        fq._move_to(dev)
-    fmt0 = _launch_format(head._qt_format, head.qmap)
-    if any(_launch_format(fq._qt_format, fq.qmap).key() != fmt0.key() or str(fq.dtype) != str(head.dtype) for fq, _ in members[1:]):
-        return None
-    if fmt0.kind == _native.QT_FMT_LUT and not (fmt0.p1 & 1):
-        return None
-    if fmt0.kind not in (_native.QT_FMT_LUT, _native.QT_FMT_FP_SAT, _native.QT_FMT_INT):
+    fmt0 = _members_format(members, dev) if members[0][0] is head else None
+    if fmt0 is None:
         return None
     need_grad = torch.is_grad_enabled() and X.requires_grad
     colsum = chain.colsum if _on("colsum") else None
@@ -284,15 +271,7 @@ def run_chain(head, chain, X):
     L = _native.lib()
 
     def launch(x):
-        outs = [torch.empty_like(x) for _ in members]
-        stages = (_native.QtChainStage * len(members))()
-        for i, (fq, src) in enumerate(members):
-            if fq._observe:
-                launch_scale_update(fq.amax_history, fq.scale, fq.quant_max, fq.force_scale_power_of_two, st)
-            stages[i].scale_f32_dev = fq.scale.data_ptr()
-            stages[i].amax_bits_dev = fq.amax_history.data_ptr() if fq._observe else None
-            stages[i].out_dev = outs[i].data_ptr()
-            stages[i].src = src
+        stages, outs = _stages(members, x, st)
         gb = ws = None
         if colsum is not None:
             ws = _chain_scratch(L.qt_fake_quant_chain_ws_bytes(rows, cols), dev)
@@ -358,10 +337,6 @@ def take_member_result(fq, X):
     return None
 
 
-def _fq(holder, key):
-    return holder[key] if holder is not None and key in holder else None
-
-
 def ensure_planned(model):
     """plan(model) whenever the set of fake-quantizers has changed since the last plan (they are created lazily by the first step)."""
     from .fake_quantize import FusedAmaxObsFakeQuantize
@@ -425,16 +400,16 @@ def plan(model):
         if isinstance(dense, QATLinear) and res is not None and ln is not None and getattr(type(mod), "_qt_twin", False):
             drop = getattr(mod, "dropout", None)
             dropping = drop is not None and getattr(drop, "p", 0.0) != 0.0      # the dropout's backward then sits between the add and the dense layer
-            pre = _fq(getattr(res, "error_pre_process", None), "0")
-            p0, p1 = _fq(getattr(res, "error_post_process", None), "0"), _fq(getattr(res, "error_post_process", None), "1")
-            dpre = _fq(getattr(dense, "error_pre_process", None), "0")
-            if pre is None or len(getattr(res, "error_pre_process", {})) != 1:
+            pre = pc.holder_fq(res, "error_pre_process", exact=True)
+            posts = pc.holder_fqs(res, "error_post_process", "0", "1")
+            dpre = pc.holder_fq(dense, "error_pre_process", exact=True)
+            if pre is None:
                 continue
             members = [(pre, -1)]
             colsum = None
-            if p0 is not None and p1 is not None and len(res.error_post_process) == 2:
-                members += [(p0, 0), (p1, 0)]
-                if not dropping and dpre is not None and len(dense.error_pre_process) == 1:
+            if posts is not None:
+                members += [(posts[0], 0), (posts[1], 0)]
+                if not dropping and dpre is not None:
                     members.append((dpre, 1))
                     colsum = (3, dense)
             if len(members) > 1:
@@ -445,15 +420,15 @@ def plan(model):
     for mod in model.modules():
         q, k, v = getattr(mod, "query", None), getattr(mod, "key", None), getattr(mod, "value", None)
         if isinstance(q, QATLinear) and isinstance(k, QATLinear) and isinstance(v, QATLinear) and hasattr(mod, "qk_matmul"):
-            fqs = [_fq(getattr(l, "activation_pre_process", None), "0") for l in (q, k, v)]
-            if all(f is not None and id(f) not in chained for f in fqs) and all(len(l.activation_pre_process) == 1 for l in (q, k, v)):
+            fqs = [pc.holder_fq(l, "activation_pre_process", exact=True) for l in (q, k, v)]
+            if all(f is not None and id(f) not in chained for f in fqs):
                 fqs[0].__dict__["_qt_chain"] = Chain([(fqs[0], -1), (fqs[1], -1), (fqs[2], -1)], name="qkv inputs")
                 chained.update(id(f) for f in fqs)
                 n += 1
     for mod in model.modules():
         if isinstance(mod, QATLinear):
-            dpre = _fq(getattr(mod, "error_pre_process", None), "0")
-            if dpre is not None and id(dpre) not in chained and len(mod.error_pre_process) == 1 and mod.bias is not None:
+            dpre = pc.holder_fq(mod, "error_pre_process", exact=True)
+            if dpre is not None and id(dpre) not in chained and mod.bias is not None:
                 dpre.__dict__["_qt_chain"] = Chain([(dpre, -1)], (0, mod), name="grad_output + bias gradient")
                 chained.add(id(dpre))
                 n += 1
@@ -532,7 +507,7 @@ def take_deferred(fq, X):
         return None                    # (armed[1]: weak reference to the producing node's token -- a graph that was dropped arms nothing)
     shape = armed[0]
     if not (X.is_cuda and X.dtype == torch.bfloat16 and X.is_contiguous() and tuple(X.shape) == shape and X.numel() % 8 == 0 and X.data_ptr() % 16 == 0
-            and not _hooked(fq) and _member_ok(fq, X.device) and _members_format([(fq, -1)], X.device) is not None):
+            and pc.no_forward_hooks(fq) and _member_ok(fq, X.device) and _members_format([(fq, -1)], X.device) is not None):
         return None
     from .fake_quantize import _Stats, _stream_ptr, launch_scale_update
     if fq._observe:
@@ -738,7 +713,7 @@ def _layernorm_plan(norm, x):
     if not (producers_enabled() and torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous()
             and type(norm) is torch.nn.LayerNorm and norm.elementwise_affine and norm.bias is not None and len(norm.normalized_shape) == 1
             and norm.weight.dtype == torch.bfloat16 and x.shape[-1] == norm.normalized_shape[0] and x.shape[-1] % 8 == 0 and x.shape[-1] <= 1024
-            and x.data_ptr() % 16 == 0 and not norm._forward_hooks and not norm._forward_pre_hooks and not norm._backward_hooks):
+            and x.data_ptr() % 16 == 0 and pc.hook_counts(norm, forward_pre=0, forward=0, backward=0)):     # (backward pre-hooks not looked at: no reason found)
         return None
     after = norm.__dict__.get("_qt_dropout_after")
     if after is not None and after.training and after.p > 0.0:
@@ -747,16 +722,14 @@ def _layernorm_plan(norm, x):
     for lin in norm.__dict__.get("_qt_consumers") or []:
         for f in (getattr(lin, "error_post_process", None) or {}).values():
             f.__dict__.pop("_qt_deferred", None)               # (nothing armed by an earlier forward survives this one)
-        holder = getattr(lin, "activation_pre_process", None)
-        fq = _fq(holder, "0")
-        if fq is None or len(holder) != 1:
+        fq = pc.holder_fq(lin, "activation_pre_process", exact=True)
+        if fq is None:
             return None
         consumers.append(fq)
         # the consumer's backward quantizer on its grad_input (quantize.py:147-148, `--quantize_backprop ...,residual`), if it is the only
         # thing hooked onto the Linear's backward: its call may be deferred to this node's fan-in launch
-        ph = getattr(lin, "error_post_process", None)
-        post = _fq(ph, "0") if ph is not None and len(ph) == 1 and len(lin._backward_hooks) == 1 else None
-        posts.append(post if post is not None and _member_ok(post, x.device) and not _hooked(post) else None)
+        post = pc.holder_fq(lin, "error_post_process", exact=True) if pc.hook_counts(lin, backward=1) else None
+        posts.append(post if post is not None and _member_ok(post, x.device) and pc.no_forward_hooks(post) else None)
     if not consumers or len(consumers) > 4 or _members_format([(f, -1) for f in consumers], x.device) is None:
         return None
     return consumers, posts
@@ -781,7 +754,7 @@ def add_layernorm_or_none(block, h, r):
     norm, res = getattr(block, "LayerNorm", None), getattr(block, "residual", None)
     if not (fanin_enabled() and _on("addln") and type(res) is AddFunctional and norm is not None
             and h.shape == r.shape and h.dtype == r.dtype and r.is_cuda and r.is_contiguous() and r.data_ptr() % 16 == 0 and h.requires_grad
-            and not res._forward_hooks and not res._forward_pre_hooks and getattr(res, "activation_pre_process", None) is None):
+            and pc.no_forward_hooks(res) and getattr(res, "activation_pre_process", None) is None):     # (its backward hooks carry the gradient chain)
         return None
     plan_ = _layernorm_plan(norm, h)
     if plan_ is None:
@@ -852,14 +825,12 @@ class _GeluTrainFn(torch.autograd.Function):
 def gelu_or_none(intermediate, h):
     """`intermediate_act_fn(h)` of a BertIntermediate inside a training step, or None."""
     consumer = intermediate.__dict__.get("_qt_consumer")
-    holder = getattr(consumer, "activation_pre_process", None) if consumer is not None else None
-    fq = _fq(holder, "0")
+    fq = pc.holder_fq(consumer, "activation_pre_process", exact=True)
     if not (producers_enabled() and torch.is_grad_enabled() and h.is_cuda and h.dtype == torch.bfloat16 and h.is_contiguous() and h.dim() >= 2
-            and h.shape[-1] % 8 == 0 and h.data_ptr() % 16 == 0 and fq is not None and len(holder) == 1
+            and h.shape[-1] % 8 == 0 and h.data_ptr() % 16 == 0 and fq is not None
             and _members_format([(fq, -1)], h.device) is not None):
         return None
-    dense = getattr(intermediate, "dense", None)
-    head = _fq(getattr(dense, "error_pre_process", None), "0") if dense is not None else None
+    head = pc.holder_fq(getattr(intermediate, "dense", None), "error_pre_process")
     return _GeluTrainFn.apply(h, fq, head)
 
 
@@ -923,35 +894,20 @@ def softmax_or_none(attn, scores, attention_mask, scaling, dropout):
         return None
     for name in ("attn_scaling", "softmax"):
         mod = getattr(attn, name, None)
-        if mod is None or mod._forward_hooks or mod._forward_pre_hooks or mod._backward_hooks or mod._backward_pre_hooks \
-                or getattr(mod, "activation_pre_process", None) is not None:
+        if mod is None or not pc.no_hooks(mod) or getattr(mod, "activation_pre_process", None) is not None:
             return None
     if type(attn.softmax) is not torch.nn.Softmax:             # (the fp32 softmax of the LLaMA twin rounds at other points)
         return None
-    holder = getattr(attn.av_matmul, "activation_pre_process", None)
-    fq_p = _fq(holder, "0")
+    fq_p = pc.holder_fq(attn.av_matmul, "activation_pre_process")
     if fq_p is None or _members_format([(fq_p, -1)], scores.device) is None:
         return None
     B, H, Q, C = scores.shape
-    mask = None
-    strides = (0, 0, 0)
-    if attention_mask is not None:
-        m = attention_mask[..., :C]
-        if m.dtype != torch.bfloat16 or m.dim() != 4 or m.stride(-1) != 1 or m.device != scores.device or m.requires_grad:
-            return None
-        if m.shape[0] not in (1, B) or m.shape[1] not in (1, H) or m.shape[2] not in (1, Q):
-            return None
-        strides = (m.stride(0) if m.shape[0] == B and B > 1 else 0, m.stride(1) if m.shape[1] == H and H > 1 else 0,
-                   m.stride(2) if m.shape[2] == Q and Q > 1 else 0)
-        if (strides[0] | strides[1] | strides[2]) % 8 != 0 or m.data_ptr() % 16 != 0:
-            return None
-        mask = m
-    head = _fq(getattr(attn.qk_matmul, "error_pre_process", None), "0")
-    return _SoftmaxTrainFn.apply(scores, mask, strides, scaling, fq_p, head)
-
-
-def _hooked(fq):
-    return bool(fq._forward_hooks or fq._forward_pre_hooks)
+    from .fused import _mask_strides
+    mk = _mask_strides(attention_mask, B, H, Q, C, scores.device, 8, no_grad=True)
+    if mk is False:
+        return None
+    head = pc.holder_fq(attn.qk_matmul, "error_pre_process")
+    return _SoftmaxTrainFn.apply(scores, mk[0], mk[1:], scaling, fq_p, head)
 
 
 def _served_call(fq, x, y, numel=None):
@@ -959,7 +915,7 @@ def _served_call(fq, x, y, numel=None):
     hook counts it.  A fake-quantizer somebody hooked is called as the module it is, on the tensor the reference's hook would hand it,
     and finds `y` (take_member_result) -- its hooks see the call, its input and its result."""
     from .fake_quantize import _Stats
-    if y is not None and _hooked(fq):
+    if y is not None and not pc.no_forward_hooks(fq):
         fq.__dict__["_qt_chain_result"] = (*tensor_key(x), y, x, False)
         with torch.no_grad():
             got = fq(x)
@@ -1052,8 +1008,8 @@ class _AttentionTrainFn(torch.autograd.Function):
             stages[i].out_dev = None
             stages[i].src = -1
         # g = ev(dO), dS and dS' = eq(dS) stay on the chip -- unless somebody hooked those fake-quantizers and wants to see the calls
-        g = torch.empty((B, S, H, D), dtype=qq.dtype, device=dev) if _hooked(ev) else None
-        ds, dsq = (torch.empty_like(probs), torch.empty_like(probs)) if _hooked(eq) else (None, None)
+        g = torch.empty((B, S, H, D), dtype=qq.dtype, device=dev) if not pc.no_forward_hooks(ev) else None
+        ds, dsq = (torch.empty_like(probs), torch.empty_like(probs)) if not pc.no_forward_hooks(eq) else (None, None)
         if g is not None:
             stages[0].out_dev = g.data_ptr()
         if dsq is not None:
@@ -1065,7 +1021,7 @@ class _AttentionTrainFn(torch.autograd.Function):
         couts = (ctypes.c_void_p * 3)()
         riders = []
         for i, lin in enumerate(ctx.lins or ()):
-            head = _fq(getattr(lin, "error_pre_process", None), "0") if lin is not None else None
+            head = pc.holder_fq(lin, "error_pre_process")
             mem, colsum = _grad_chain(head)
             if mem is None or len(mem) != 1 or _members_format(members + mem, dev) is None:
                 continue
@@ -1128,8 +1084,7 @@ def attention_or_none(attn, query, key, value, attention_mask, scaling, dropout)
         return None
     for name in ("attn_scaling", "softmax"):
         mod = getattr(attn, name, None)
-        if mod is None or mod._forward_hooks or mod._forward_pre_hooks or mod._backward_hooks or mod._backward_pre_hooks \
-                or getattr(mod, "activation_pre_process", None) is not None:
+        if mod is None or not pc.no_hooks(mod) or getattr(mod, "activation_pre_process", None) is not None:
             return None
     if type(attn.softmax) is not torch.nn.Softmax:
         return None
@@ -1137,10 +1092,8 @@ def attention_or_none(attn, query, key, value, attention_mask, scaling, dropout)
     if qk is None or av is None:
         return None
     for mod in (qk, av):
-        ha, he = getattr(mod, "activation_pre_process", None), getattr(mod, "error_pre_process", None)
-        if (mod._forward_hooks or mod._backward_hooks or len(mod._forward_pre_hooks) != 1 or len(mod._backward_pre_hooks) != 1
-                or getattr(mod, "error_post_process", None) is not None or ha is None or he is None or len(ha) != 2 or len(he) != 1
-                or "0" not in ha or "1" not in ha or "0" not in he):
+        if (not pc.quantize_hooks_only(mod, forward_pre=1, backward_pre=1) or getattr(mod, "error_post_process", None) is not None
+                or pc.holder_fqs(mod, "activation_pre_process", "0", "1") is None or pc.holder_fq(mod, "error_pre_process", exact=True) is None):
             return None
     fqs = [qk.activation_pre_process["0"], qk.activation_pre_process["1"], av.activation_pre_process["1"], av.activation_pre_process["0"]]
     efqs = (av.error_pre_process["0"], qk.error_pre_process["0"])
@@ -1148,23 +1101,14 @@ def attention_or_none(attn, query, key, value, attention_mask, scaling, dropout)
     if _members_format([(f, -1) for f in fqs], dev) is None or _members_format([(f, -1) for f in efqs], dev) is None:
         return None
     proj = attn.__dict__.get("_qt_out_proj")
-    holder = getattr(proj, "activation_pre_process", None) if proj is not None else None
-    fq_o = _fq(holder, "0") if holder is not None and len(holder) == 1 else None
+    fq_o = pc.holder_fq(proj, "activation_pre_process", exact=True)
     if fq_o is not None and (fq_o.__dict__.get("_qt_chain") is not None or _members_format([(f, -1) for f in fqs + [fq_o]], dev) is None):
         fq_o = None
-    mask = None
-    strides = (0, 0, 0)
-    if attention_mask is not None:
-        m = attention_mask[..., :S]
-        if m.dtype != torch.bfloat16 or m.dim() != 4 or m.stride(-1) != 1 or m.device != dev or m.requires_grad:
-            return None
-        if m.shape[0] not in (1, B) or m.shape[1] not in (1, H) or m.shape[2] not in (1, S) or m.shape[3] != S:
-            return None
-        strides = (m.stride(0) if m.shape[0] == B and B > 1 else 0, m.stride(1) if m.shape[1] == H and H > 1 else 0,
-                   m.stride(2) if m.shape[2] == S and S > 1 else 0)
-        if (strides[0] | strides[1] | strides[2]) % 8 != 0 or m.data_ptr() % 16 != 0:
-            return None
-        mask = m
+    from .fused import _mask_strides
+    mk = _mask_strides(attention_mask, B, H, S, S, dev, 8, no_grad=True)
+    if mk is False or (mk[0] is not None and mk[0].shape[3] != S):
+        return None
+    mask, strides = mk[0], mk[1:]
     lins = tuple(getattr(attn, n, None) for n in ("query", "key", "value"))
     _mark_qkv_members(attn, lins)
     return _AttentionTrainFn.apply(query, key, value, mask, strides, scaling, fqs, fq_o, efqs, lins, drop_p)
@@ -1208,6 +1152,6 @@ def embedding_or_none(emb, ids):
     if not (producers_enabled() and _on("embedding") and torch.is_grad_enabled() and w.requires_grad and w.is_cuda
             and w.dtype == torch.bfloat16 and w.dim() == 2 and w.shape[1] % 8 == 0 and w.is_contiguous() and ids.is_cuda and ids.dtype == torch.int64
             and 0 < ids.numel() <= 3072 and emb.max_norm is None and not emb.scale_grad_by_freq and not emb.sparse
-            and not emb._forward_hooks and not emb._forward_pre_hooks and not emb._backward_hooks and not emb._backward_pre_hooks):
+            and pc.no_hooks(emb)):
         return None
     return _EmbeddingTrainFn.apply(w, ids, emb.padding_idx)
