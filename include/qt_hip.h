@@ -460,6 +460,41 @@ int qt_conv2d_bf16(const uint16_t *x, const uint16_t *w, const uint16_t *bias, u
 int qt_conv2d_plan(int N, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int *tile_m, int *tile_n,
                    int *tiles_m, int *tiles_n, int *k_tiles);
 
+/* ---- The backward products of that convolution (replace what autograd runs behind modules/qat/conv.py:43-44 and
+ * conv_fused.py:103-126: the library's convolution_backward on the incoming gradient, the saved input and the fake-quantized weight).
+ * All operands are bf16 VALUES in the forward's layouts: gy NHWC [N][Ho][Wo][Cout], x / gx NHWC [N][H][W][Cin], w / gw
+ * [Cout][kh][kw][Cin]; nothing is quantized here.  fp32 accumulation in a fixed order, one rounding; groups = 1, zero padding; the same
+ * bits on every launch.  No allocation, no synchronisation: safe under stream capture.
+ *
+ * Input gradient (modules/qat/conv.py:43-44, conv_fused.py:103-126 under autograd: grad_input):
+ *     gx[n, hi, wi, c] = sum_{r, s, co} gy[n, ho, wo, co] . w[co, r, s, c]   over the taps with hi + ph - r dh = ho sh, wi + pw - s dw = wo sw
+ * EVERY element of gx is written (pixels no tap reaches receive 0): the caller may pass uninitialised memory.  Accepted: Cin % 8 == 0,
+ * Cin >= 8, Cout % 64 == 0 (whole k tiles of 64 output channels; a ragged Cout is declined), strides below 2^20 and the forward's
+ * limits on the geometry; gy / w 16-byte, gx 8-byte aligned.  Anything else returns
+ * QT_ERR_BAD_ARG / QT_ERR_UNALIGNED, nothing is launched, and the caller keeps the library's backward for this product. */
+int qt_conv2d_dgrad_bf16(const uint16_t *gy, const uint16_t *w, uint16_t *gx, int N, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw,
+                         int ph, int pw, int dh, int dw, void *stream);
+/* Weight gradient (modules/qat/conv.py:43-44, conv_fused.py:103-126 under autograd: grad_weight):
+ *     gw[co, r, s, c] = sum_{n, ho, wo} gy[n, ho, wo, co] . x[n, ho sh - ph + r dh, wo sw - pw + s dw, c]
+ * The contraction over the N Ho Wo output pixels is split over `ksplit` workgroups per output tile (qt_conv2d_backward_plan: a fixed
+ * function of the shape and the device's CU count); with ksplit > 1 their fp32 partial sums meet in `ws` (ws_bytes of it, 16-byte
+ * aligned) and are added in split order by the workgroup that draws the tile's last ticket; `tickets` (n_tickets uint32, zero on entry)
+ * are left zero.  Launches that share a workspace must be ordered on one stream.  Accepted: Cin % 8 == 0, Cout % 8 == 0, Cin, Cout >= 8
+ * and the input gradient's limits on the geometry; gy / x 16-byte, gw 8-byte aligned; a missing or too small workspace or ticket array with ksplit > 1 returns QT_ERR_BAD_ARG. */
+int qt_conv2d_wgrad_bf16(const uint16_t *gy, const uint16_t *x, uint16_t *gw, int N, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw,
+                         int ph, int pw, int dh, int dw, float *ws, size_t ws_bytes, uint32_t *tickets, size_t n_tickets, void *stream);
+/* Host-only query for both products: whether the shape is taken (`taken` per product; the return value is QT_OK when either is) and how it is cut on the current
+ * device: tile_m x tile_n output tiles (input gradient: rows = N H W input pixels, columns = Cin, 128 x 128, 128 x 64 or 64 x 64; weight
+ * gradient: rows = Cout, columns = kh kw Cin, 128 x 128 or 64 x 64), tiles_m x tiles_n of them, k_tiles steps of 64 (output channels of
+ * one tap resp. output pixels), ksplit workgroups per tile, and the workspace bytes and ticket count qt_conv2d_wgrad_bf16 then needs.
+ * Either out pointer is nullable.  (The bias gradient needs no kernel of its own: it is qt_colsum_bf16 on the [N Ho Wo][Cout] view of gy.) */
+typedef struct qt_conv2d_product_plan {
+    int taken, tile_m, tile_n, tiles_m, tiles_n, k_tiles, ksplit;
+    size_t ws_bytes, n_tickets;
+} qt_conv2d_product_plan;
+int qt_conv2d_backward_plan(int N, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
+                            qt_conv2d_product_plan *dgrad, qt_conv2d_product_plan *wgrad);
+
 /* ---- H3's step end: clip_grad_norm_(max_norm) and the AdamW update of every parameter tensor in four launches ------------------------
  *     run_glue_no_trainer.py:655-668   accelerator.clip_grad_norm_(model.parameters(), 1.0); optimizer.step()
  * The arithmetic is torch's, which the reference calls: torch.nn.utils.clip_grad_norm_ on bf16 gradients (per-tensor norms and the

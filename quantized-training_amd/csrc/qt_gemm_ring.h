@@ -1,7 +1,9 @@
 // qt_gemm_ring.h -- what the bf16 matrix-core kernels with k-contiguous operands share: the LDS ring of k tiles filled by LDS-DMA, the
 // swizzled [rows][64 k] image, its fragment read, the counted wait + barrier, the drain of the ring and the epilogue of an output tile.
-// Used by qt_train_gemm.hip (the Linear products of a training step) and qt_conv.hip (implicit-GEMM Conv2d): the convolution differs from
-// the GEMM only in WHERE a lane's 16 bytes of the activation image come from.
+// Operands stored with the contraction index as the ROW index are staged as [64 k][columns] images and read through ds_read_b64_tr_b16
+// (s_tr / off_tr / ld_frag_tr).
+// Used by qt_train_gemm.hip (the Linear products of a training step), qt_conv.hip (implicit-GEMM Conv2d) and qt_conv_backward.hip (its
+// input and weight gradients): a convolution differs from the GEMM only in WHERE a lane's 16 bytes of the gathered image come from.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -12,6 +14,7 @@ namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kBK = 64;                 // k tile
 constexpr int kThreads = 512;          // 8 waves: 4 (rows) x 2 (columns); two per SIMD, so one wave's LDS latencies hide under the other's matrix instructions
@@ -21,6 +24,34 @@ __device__ __forceinline__ int off_rows(int row, int ch) { return row * 128 + ((
 
 __device__ __forceinline__ bf16x8 ld_frag_rows(const unsigned char *img, int row, int ch) {
     return *(const bf16x8 *)(img + off_rows(row, ch));
+}
+
+// [64 k][C columns] image read by ds_read_b64_tr_b16.  RB = 2 C bytes per row (128 or 256).  A 32-lane half reads rows r0 + q and r0 + 8 + q
+// (q = 0..3), 32 bytes of the same column group each: eight 32-byte pieces that must fall on eight different bank groups (64 banks x 4 B =
+// eight groups of 32 B).  Row r starts at bank group (r RB / 32) mod 8 -- 0 for RB = 256, 0 or 4 for RB = 128 -- so the column group index
+// is XORed with a value that is distinct over {q, 8 + q} (RB = 256) resp. over the rows of equal parity among them (RB = 128).
+template <int RB>
+__device__ __forceinline__ int s_tr(int row) {
+    static_assert(RB == 128 || RB == 256, "row lengths of 64 and 128 columns (192: 384-byte rows start at bank group 4 r mod 8 like 128-byte ones and take their formula -- built, measured, not used)");
+    if constexpr (RB == 256) return (row & 3) | (((row >> 3) & 1) << 2);
+    else return ((row >> 1) & 1) | (((row >> 3) & 1) << 1);
+}
+template <int RB>
+__device__ __forceinline__ int off_tr(int row, int ch) {       // 16-byte chunk `ch` of k row `row`
+    return row * RB + ((((ch >> 1) ^ s_tr<RB>(row))) << 5) + ((ch & 1) << 4);
+}
+
+// the fragment of 16 columns c0 .. c0 + 15 (c0 a multiple of 16) for k = k0 .. k0 + 31 of a transposed image: lane l receives column
+// c0 + l % 16, k = k0 + 8 (l / 16) .. + 7
+template <int RB>
+__device__ __forceinline__ bf16x8 ld_frag_tr(const unsigned char *img, int c0, int k0, int lane) {
+    const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
+    const int r_lo = k0 + 8 * g + q, r_hi = r_lo + 4;
+    const int cp = c0 >> 4;
+    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(img + r_lo * RB + ((cp ^ s_tr<RB>(r_lo)) << 5) + p * 8));
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(img + r_hi * RB + ((cp ^ s_tr<RB>(r_hi)) << 5) + p * 8));
+    return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
 }
 
 // one LDS-DMA piece: dma16 (qt_device.h), its waits counted by hand below

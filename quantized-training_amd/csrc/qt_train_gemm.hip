@@ -21,7 +21,7 @@
 // staged as they come, [64 k][BM or BN columns], and read through ds_read_b64_tr_b16, gfx950's transposing LDS read (two per
 // fragment): a 16-lane group reads a 4 (k) x 16 (columns) block and every lane receives its column's four k values -- exactly the
 // matrix instruction's operand layout.  The 32-byte column groups of a row are XOR-swizzled so that the 8 rows a 32-lane half touches
-// per read fall on distinct banks (s_tr below).
+// per read fall on distinct banks (s_tr in qt_gemm_ring.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -33,7 +33,6 @@
 
 namespace {
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 constexpr int kMaxProblems = 4;
 
 struct Problem {
@@ -49,34 +48,6 @@ struct Args {
     unsigned long long *dbg;
 #endif
 };
-
-// [64 k][C columns] image read by ds_read_b64_tr_b16.  RB = 2 C bytes per row (128 or 256).  A 32-lane half reads rows r0 + q and r0 + 8 + q
-// (q = 0..3), 32 bytes of the same column group each: eight 32-byte pieces that must fall on eight different bank groups (64 banks x 4 B =
-// eight groups of 32 B).  Row r starts at bank group (r RB / 32) mod 8 -- 0 for RB = 256, 0 or 4 for RB = 128 -- so the column group index
-// is XORed with a value that is distinct over {q, 8 + q} (RB = 256) resp. over the rows of equal parity among them (RB = 128).
-template <int RB>
-__device__ __forceinline__ int s_tr(int row) {
-    static_assert(RB == 128 || RB == 256, "row lengths of 64 and 128 columns (192: 384-byte rows start at bank group 4 r mod 8 like 128-byte ones and take their formula -- built, measured, not used)");
-    if constexpr (RB == 256) return (row & 3) | (((row >> 3) & 1) << 2);
-    else return ((row >> 1) & 1) | (((row >> 3) & 1) << 1);
-}
-template <int RB>
-__device__ __forceinline__ int off_tr(int row, int ch) {       // 16-byte chunk `ch` of k row `row`
-    return row * RB + ((((ch >> 1) ^ s_tr<RB>(row))) << 5) + ((ch & 1) << 4);
-}
-
-// the fragment of 16 columns c0 .. c0 + 15 (c0 a multiple of 16) for k = k0 .. k0 + 31 of a transposed image: lane l receives column
-// c0 + l % 16, k = k0 + 8 (l / 16) .. + 7
-template <int RB>
-__device__ __forceinline__ bf16x8 ld_frag_tr(const unsigned char *img, int c0, int k0, int lane) {
-    const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-    const int r_lo = k0 + 8 * g + q, r_hi = r_lo + 4;
-    const int cp = c0 >> 4;
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(img + r_lo * RB + ((cp ^ s_tr<RB>(r_lo)) << 5) + p * 8));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(img + r_hi * RB + ((cp ^ s_tr<RB>(r_hi)) << 5) + p * 8));
-    return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
 
 // One output tile: `tile` of problem P (column tile tile / tiles_m, row tile tile % tiles_m); `lds`: the workgroup's dynamic LDS
 // (Ring<BM, BN>::kBytes of it).

@@ -55,6 +55,12 @@ class QtAdamwTensor(ctypes.Structure):
                 ("beta2", ctypes.c_double), ("eps", ctypes.c_double), ("weight_decay", ctypes.c_double), ("step", ctypes.c_double)]
 
 
+class QtConv2dProductPlan(ctypes.Structure):
+    """qt_conv2d_product_plan of include/qt_hip.h"""
+    _fields_ = [("taken", c_int), ("tile_m", c_int), ("tile_n", c_int), ("tiles_m", c_int), ("tiles_n", c_int), ("k_tiles", c_int),
+                ("ksplit", c_int), ("ws_bytes", c_size_t), ("n_tickets", c_size_t)]
+
+
 class QtLinearBackward(ctypes.Structure):
     """qt_linear_backward of include/qt_hip.h"""
     _fields_ = [("gy", c_void_p), ("wq", c_void_p), ("x", c_void_p), ("gx", c_void_p), ("gw", c_void_p)]
@@ -116,6 +122,9 @@ SIGNATURES = {
     "qt_train_gemm_backward_bf16": (c_int, [_P, c_int, c_int, c_int, c_int, c_long, c_long, c_long, c_long, c_long, _P]),
     "qt_conv2d_bf16": (c_int, [_P, _P, _P, _P] + [c_int] * 13 + [_P]),
     "qt_conv2d_plan": (c_int, [c_int] * 13 + [_P] * 5),
+    "qt_conv2d_dgrad_bf16": (c_int, [_P, _P, _P] + [c_int] * 13 + [_P]),
+    "qt_conv2d_wgrad_bf16": (c_int, [_P, _P, _P] + [c_int] * 13 + [_P, c_size_t, _P, c_size_t, _P]),
+    "qt_conv2d_backward_plan": (c_int, [c_int] * 13 + [_P, _P]),
     "qt_linear_fq8_plan": (c_int, [c_int, c_long, c_int, c_int, _P, _P, _P, _P, _P]),
     "qt_clip_adamw_plan": (c_long, [_P, c_int, _P, c_long]),
     "qt_clip_adamw_ws_bytes": (c_size_t, [c_int, c_long]),
