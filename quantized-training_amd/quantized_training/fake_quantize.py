@@ -256,7 +256,9 @@ class BatchedWeightFakeQuant:
     at its end, so `weight_fake_quant(W)` of every QAT Linear (modules/qat/linear.py:40-41) can run first -- each with its own scale
     and amax slot, i.e. the per-tensor state machine is the reference's.  The call the Linear then issues finds its result
     (`_qt_pre`: valid for the very next call, and only for that very weight at that very version), counts its elements and returns
-    it with the straight-through gradient.  `pairs`: (fake-quantizer, weight Parameter)."""
+    it with the straight-through gradient.  A weight changed in place between the launch and its call is fake-quantized again by that
+    call's own pass, and its amax slot then holds the maximum over both versions of the weight (the launch's amax stays accumulated).
+    `pairs`: (fake-quantizer, weight Parameter)."""
 
     def __init__(self, pairs, device):
         groups = {}
