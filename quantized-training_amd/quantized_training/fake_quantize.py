@@ -16,6 +16,7 @@ What is different underneath:
     CPU tensors (host-side plumbing, e.g. the MobileBERT-tiny CPU config) use the same formulas
     written with torch ops.
 """
+import collections
 import ctypes
 import logging
 from typing import Optional
@@ -23,8 +24,11 @@ from typing import Optional
 import torch
 from torch.ao.quantization import FakeQuantizeBase
 
-from . import _native, handover
+from . import _native, handover, precomputed
 from .quantizer.quantizer import QScheme
+
+# (forward() tests its own __dict__ for these before it calls into precomputed: a call nothing was left for pays one lookup per slot)
+_PRE, _EXPECTED, _CHAIN_RESULT = precomputed.PRE.name, precomputed.EXPECTED.name, precomputed.CHAIN_RESULT.name
 
 __all__ = [
     "FusedAmaxObsFakeQuantize",
@@ -183,20 +187,9 @@ def _as_flag(v):
 
 
 # ---- batched delayed-scaling update (harness.GraphedTrainStep) --------------------------------------------------------
-_PREUPDATED = set()       # data_ptr of every amax history whose NEXT call's scale update has already been done
-
-
-def _take_preupdate(amax_history) -> bool:
-    p = amax_history.data_ptr()
-    if p in _PREUPDATED:
-        _PREUPDATED.discard(p)
-        return True
-    return False
-
-
 def launch_scale_update(amax_history, scale, quant_max, pow2, stream_ptr):
     """The delayed-scaling update in front of one observed call -- unless BatchedScaleUpdate already did it."""
-    if _take_preupdate(amax_history):
+    if precomputed.take_preupdate(amax_history):
         return
     _native.check(_native.lib().qt_scale_update(amax_history.data_ptr(), int(amax_history.shape[0]), int(scale.numel()),
                                                 scale.data_ptr(), float(quant_max), int(bool(pow2)), stream_ptr),
@@ -230,11 +223,11 @@ class BatchedScaleUpdate:
                                                           self.scale.data_ptr(), self.qmax.data_ptr(), self.pow2.data_ptr(),
                                                           len(self.fqs), _stream_ptr(self.hist)), "qt_scale_update_multi")
         for f in self.fqs:
-            _PREUPDATED.add(f.amax_history.data_ptr())
+            precomputed.mark_preupdated(f.amax_history)
 
     def forget(self):
         for f in self.fqs:
-            _PREUPDATED.discard(f.amax_history.data_ptr())
+            precomputed.forget_preupdated(f.amax_history)
 
 
 class _PrecomputedFakeQuant(torch.autograd.Function):
@@ -250,12 +243,16 @@ class _PrecomputedFakeQuant(torch.autograd.Function):
         return grad_output, None
 
 
+# one launch of BatchedWeightFakeQuant: the [(fake-quantizer, weight)] of one format, where each member's result lands, the device item table
+_WeightGroup = collections.namedtuple("_WeightGroup", "fmt lut members outs items tiles")
+
+
 class BatchedWeightFakeQuant:
     """Every per-tensor weight fake-quantizer of a step as ONE launch per format (qt_fake_quant_multi_bf16) in front of the step
     (harness.GraphedTrainStep, after BatchedScaleUpdate): a weight does not change between the start of a step and the optimizer update
     at its end, so `weight_fake_quant(W)` of every QAT Linear (modules/qat/linear.py:40-41) can run first -- each with its own scale
     and amax slot, i.e. the per-tensor state machine is the reference's.  The call the Linear then issues finds its result
-    (`_qt_pre`: valid for the very next call, and only for that very weight at that very version), counts its elements and returns
+    (precomputed.PRE: valid for the very next call, and only for that very weight at that very version), counts its elements and returns
     it with the straight-through gradient.  A weight changed in place between the launch and its call is fake-quantized again by that
     call's own pass, and its amax slot then holds the maximum over both versions of the weight (the launch's amax stays accumulated).
     `pairs`: (fake-quantizer, weight Parameter)."""
@@ -279,7 +276,7 @@ class BatchedWeightFakeQuant:
                 continue
             lut = fq.qmap if fmt.kind == _native.QT_FMT_LUT else None
             groups.setdefault((fmt.key(), lut.data_ptr() if lut is not None else 0), (fmt, lut, []))[2].append((fq, W))
-        self.groups = []
+        self.groups = []                   # one _WeightGroup per launch
         for fmt, lut, members in groups.values():
             total = sum(W.numel() for _, W in members)
             out = torch.empty(total, dtype=torch.bfloat16, device=device)
@@ -292,24 +289,24 @@ class BatchedWeightFakeQuant:
                 tiles += (nvec + 1023) // 1024
                 outs.append(y)
             items = torch.tensor(rows, dtype=torch.int64, device=device)
-            self.groups.append((fmt, lut, members, outs, items, tiles))
+            self.groups.append(_WeightGroup(fmt, lut, members, outs, items, tiles))
         self.device = device
 
     def __len__(self):
-        return sum(len(g[2]) for g in self.groups)
+        return sum(len(g.members) for g in self.groups)
 
     def launch(self):
-        for fmt, lut, members, outs, items, tiles in self.groups:
-            _native.check(_native.lib().qt_fake_quant_multi_bf16(items.data_ptr(), len(members), tiles, ctypes.byref(fmt),
-                                                                 lut.data_ptr() if lut is not None else None, _stream_ptr(items)),
+        for g in self.groups:
+            _native.check(_native.lib().qt_fake_quant_multi_bf16(g.items.data_ptr(), len(g.members), g.tiles, ctypes.byref(g.fmt),
+                                                                 g.lut.data_ptr() if g.lut is not None else None, _stream_ptr(g.items)),
                           "qt_fake_quant_multi_bf16")
-            for (fq, W), y in zip(members, outs):
-                fq.__dict__["_qt_pre"] = (W.data_ptr(), W._version, y)
+            for (fq, W), y in zip(g.members, g.outs):
+                precomputed.PRE.leave(fq, W, y)
 
     def forget(self):
-        for _, _, members, _, _, _ in self.groups:
-            for fq, _ in members:
-                fq.__dict__["_qt_pre"] = None
+        for g in self.groups:
+            for fq, _ in g.members:
+                precomputed.PRE.drop(fq)
 
 
 def _rows_view(t):
@@ -743,7 +740,7 @@ class FusedAmaxObsFakeQuantize(FakeQuantizeBase):
         `replacement` the quantized values were written into `tensor` itself (FP8 code in x8); with it `tensor` holds
         the unquantized values (it has other readers, e.g. a residual connection) and `replacement` = fq(tensor) as
         bf16.  The tensor is kept referenced until that call so that its storage cannot be recycled in between."""
-        self.__dict__["_qt_expected"] = (tensor.data_ptr(), tensor.numel(), tensor._version, x8, replacement, tensor)
+        precomputed.EXPECTED.leave(self, tensor, (x8, replacement))
 
     def producer_fusable(self) -> bool:
         """True when this fake-quantizer is a pure stateless function a producing kernel may apply on its behalf
@@ -759,7 +756,7 @@ class FusedAmaxObsFakeQuantize(FakeQuantizeBase):
             out = train_fusions.take_deferred(self, X)
             if out is not None:
                 return out
-        if "_qt_chain_result" in self.__dict__ or "_qt_chain" in self.__dict__:
+        if _CHAIN_RESULT in self.__dict__ or "_qt_chain" in self.__dict__:
             # training-step chains (train_fusions.py): a chain launch already evaluated this call, or this call heads a chain
             from . import train_fusions
             out = train_fusions.take_member_result(self, X)
@@ -803,30 +800,27 @@ class FusedAmaxObsFakeQuantize(FakeQuantizeBase):
             x8 = FusedAmaxObsFakeQuantFunction.apply(X, False, True, self.qmap, self.amax_history, self.scale, self.amax_history_len,
                                                       self.quant_max, None, False, False, self._qt_format, "only")
             return handover.carry(X, x8, X)
-        expect = self.__dict__.get("_qt_expected")
-        if expect is not None:
+        if _EXPECTED in self.__dict__:
             # same hand-over when the producer's tensor reaches the hook as a view (a reshape in between drops Python
             # attributes): the producer left the storage it wrote, valid for this -- the very next -- call only
-            self.__dict__["_qt_expected"] = None
-            ptr, numel, version, x8, replacement, _keep = expect
-            if X.data_ptr() == ptr and X.numel() == numel and X._version == version and X.is_contiguous():
-                _Stats.add(numel)
+            expect = precomputed.EXPECTED.take(self, X)
+            if expect is not precomputed.MISS:
+                x8, replacement = expect
+                _Stats.add(X.numel())
                 if replacement is not None:
                     out = handover.carry(replacement, x8.view(X.shape), X)                     # fq(.) of X, for sibling GEMMs
                     if handover.is_lazy(out) and not self.__dict__.get("_qt_lazy_ok"):         # the producer wrote the codes only
                         handover.materialize(out)
                     return out
                 return handover.stamp(X, codes=x8)
-        pre = self.__dict__.get("_qt_pre")
-        if pre is not None:
+        if _PRE in self.__dict__:
             # BatchedWeightFakeQuant computed this call in front of the step (same scale, same amax slot): valid for this -- the very
             # next -- call, on the very tensor it read
-            self.__dict__["_qt_pre"] = None
-            ptr, version, out = pre
-            if X.data_ptr() == ptr and X._version == version and X.shape == out.shape and X.is_contiguous():
+            out = precomputed.PRE.take(self, X)
+            if out is not precomputed.MISS:
                 _Stats.add(X.numel())
                 if self._observe:
-                    _take_preupdate(self.amax_history)                        # the batched scale update served this call
+                    precomputed.take_preupdate(self.amax_history)             # the batched scale update served this call
                 return _PrecomputedFakeQuant.apply(X, out)
         self._move_to(X.device)
 

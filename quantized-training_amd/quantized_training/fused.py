@@ -4,11 +4,12 @@
 caller then runs the unfused sequence (HIP elementwise fake-quant + library GEMM); both are
 device paths -- there is no CPU fallback for device tensors.
 """
+import collections
 import ctypes
 
 import torch
 
-from . import _native, handover, planner_checks as pc, switches
+from . import _native, handover, planner_checks as pc, precomputed, switches
 from .fake_quantize import STATS, FusedAmaxObsFakeQuantFunction, FusedAmaxObsFakeQuantize, _launch_format, _stream_ptr, launch_scale_update
 from .quantizer.quantizer import QScheme
 
@@ -318,10 +319,9 @@ def mlp_route_is_one_launch(x8, gate, up, out_fq):
 # ---- every FP8 weight pass of an evaluation forward as ONE launch (harness.GraphedBatch / GraphedWindow) -------------------------
 # The weight-pass + library-GEMM route issues one codes-only pass per Linear (or per q / k / v group): 36 launches of ~5 us for a
 # BERT-base batch.  The weights are constants of a forward and these fake-quantizers are stateless, so a captured forward may run
-# all of them first, as one launch (qt_fake_quant_multi_bf16_fp8); each call site then finds its codes (valid for the very next use,
-# for those very tensors at those very versions) and counts its elements as before.
+# all of them first, as one launch (qt_fake_quant_multi_bf16_fp8); each call site then finds its codes (precomputed.WEIGHT_CODES, a record
+# on the Linear or its SiblingGroup: valid for the very next use, for those very tensors at those very versions) and counts its elements as before.
 _W8_LOG = None            # while a warm-up forward is being recorded: [(owner, layers)] in call order
-_W8_PRE = {}              # id(owner) -> (((data_ptr, version), ...), codes): what BatchedWeightCodes.launch() left for the next forward
 
 
 def start_weight_pass_log():
@@ -341,13 +341,15 @@ def _note_weight_pass(owner, layers):
 
 
 def _take_weight_codes(owner, layers):
-    pre = _W8_PRE.pop(id(owner), None)
-    if pre is None:
+    """What BatchedWeightCodes.launch() left for this forward of `owner` (precomputed.WEIGHT_CODES), if its weights are still those."""
+    if precomputed.WEIGHT_CODES.name not in owner.__dict__:
         return None
-    stamp, codes = pre
-    if stamp != tuple((l.weight.data_ptr(), l.weight._version) for l in layers):
-        return None
-    return codes
+    codes = precomputed.WEIGHT_CODES.take(owner, [l.weight for l in layers])
+    return None if codes is precomputed.MISS else codes
+
+
+# one launch of BatchedWeightCodes: the [(owner, layers, codes buffer)] of one weight format and the device item table (`count` rows)
+_CodesLaunch = collections.namedtuple("_CodesLaunch", "fmt members items count tiles")
 
 
 class BatchedWeightCodes:
@@ -377,23 +379,22 @@ class BatchedWeightCodes:
                     rows.append([l.weight.data_ptr(), codes.data_ptr() + off, npair, tiles])
                     tiles += (npair + 1023) // 1024
                     off += l.weight.numel()
-            self.launches.append((fmt, members, torch.tensor(rows, dtype=torch.int64, device=device), len(rows), tiles))
+            self.launches.append(_CodesLaunch(fmt, members, torch.tensor(rows, dtype=torch.int64, device=device), len(rows), tiles))
 
     def __len__(self):
-        return sum(len(m) for _, m, _, _, _ in self.launches)
+        return sum(len(b.members) for b in self.launches)
 
     def launch(self):
-        for fmt, members, items, count, tiles in self.launches:
-            _native.check(_native.lib().qt_fake_quant_multi_bf16_fp8(items.data_ptr(), count, tiles, ctypes.byref(fmt), _stream_ptr(items)),
+        for b in self.launches:
+            _native.check(_native.lib().qt_fake_quant_multi_bf16_fp8(b.items.data_ptr(), b.count, b.tiles, ctypes.byref(b.fmt), _stream_ptr(b.items)),
                           "qt_fake_quant_multi_bf16_fp8")
-            for owner, layers, codes in members:
-                w8 = handover.fp8_view(codes, fmt)
-                _W8_PRE[id(owner)] = (tuple((l.weight.data_ptr(), l.weight._version) for l in layers), w8)
+            for owner, layers, codes in b.members:
+                precomputed.WEIGHT_CODES.leave(owner, [l.weight for l in layers], handover.fp8_view(codes, b.fmt))
 
     def forget(self):
-        for _, members, _, _, _ in self.launches:
-            for owner, _, _ in members:
-                _W8_PRE.pop(id(owner), None)
+        for b in self.launches:
+            for owner, _, _ in b.members:
+                precomputed.WEIGHT_CODES.drop(owner)
 
 
 def _sibling_linear_or_none(layer, x, x8):

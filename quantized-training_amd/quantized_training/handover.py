@@ -106,15 +106,25 @@ def is_lazy(t):
     return t.__dict__.get("_qt_lazy", False)
 
 
+def unwritten(shape=None, dtype=None, device=None, like=None, out=None):
+    """The one allocator of a tensor that is handed to its reader BEFORE the launch that writes it has been issued: torch.empty of the
+    shape triple (or `like` a tensor; or `out`, a tensor the caller already allocated), filled with NaN under QT_LAZY_POISON=1 (the
+    tests), so that a read that comes too early cannot go unnoticed."""
+    if out is None:
+        out = torch.empty_like(like) if like is not None else torch.empty(shape, dtype=dtype, device=device)
+    if switches.on("QT_LAZY_POISON"):
+        out.fill_(float("nan"))
+    return out
+
+
 def mark_lazy(t):
-    """t's values were not written (its FP8 codes were).  QT_LAZY_POISON=1 (tests): fill it with NaN, so that a read that bypasses
+    """t's values were not written (its FP8 codes were): it is poisoned as every unwritten tensor is, so that a read that bypasses
     materialize cannot go unnoticed.  t is registered by its address so that a VIEW of it -- a reshape between the producer and the
     consuming hook drops Python attributes -- is still recognised by materialize; the entry dies with the tensor."""
-    if switches.on("QT_LAZY_POISON"):
-        stamped = valid(t)
-        t.fill_(float("nan"))
-        if stamped:
-            t._qt_ver = t._version                    # (the fill is not a modification of the result the hand-over describes)
+    stamped = valid(t)
+    unwritten(out=t)
+    if stamped:
+        t._qt_ver = t._version                        # (the fill is not a modification of the result the hand-over describes)
     t._qt_lazy = True
     ptr = t.data_ptr()
     _LAZY[ptr] = weakref.ref(t)

@@ -20,7 +20,7 @@ import logging
 
 import torch
 
-from . import _native, handover, planner_checks as pc, switches
+from . import _native, handover, planner_checks as pc, precomputed, switches
 from .fake_quantize import FusedAmaxObsFakeQuantize, _stream_ptr
 
 __all__ = ["apply_llama_fusions", "apply_bert_fusions", "rmsnorm", "silu_mul", "rope", "layernorm", "gelu"]
@@ -291,8 +291,8 @@ def rope_map(q, k, cos, sin, fq_q, fq_k, inner_q=False, inner_k=False, value_job
         attn.__dict__["_qt_vt_rows"] = (fused.value_key(value), fq_v, vt)
         if wjob is not None:
             # the output projection's weight_fake_quant(W) call finds its result (valid for the very next call on this weight at this
-            # version, counted there: fake_quantize.py, `_qt_pre`)
-            wjob[0].__dict__["_qt_pre"] = (W.data_ptr(), W._version, wq)
+            # version, counted there: precomputed.PRE, taken by fake_quantize.py's forward)
+            precomputed.PRE.leave(wjob[0], W, wq)
         return _mark_done(q_out, [fq_q]), _mark_done(k_out, [fq_k])
     _native.check(_native.lib().qt_rope_map_bf16(q.data_ptr(), k.data_ptr(), cos.data_ptr(), sin.data_ptr(), q_out.data_ptr(), k_out.data_ptr(),
                                                  B, S, Hq, Hk, D, _row_stride(q), _row_stride(k), ctypes.byref(fmt), qmap.data_ptr(),
@@ -791,7 +791,7 @@ _LAYER_PARAMS = ["self", "hidden_states", "attention_mask", "position_ids", "pas
 def _drop_layer_handovers(layer):
     """One-shot hand-overs a block's kernels leave for each other, dropped at the end of the block whichever route ran (each holds
     10 - 56 MB per layer at 13B widths): the sibling groups' [M, sum N] products once their members have taken their slices, the
-    value pass the rotary launch wrote ahead (`_qt_vt_rows`), the o projection's pre-quantized weight (`_qt_pre`)."""
+    value pass the rotary launch wrote ahead (`_qt_vt_rows`), the o projection's pre-quantized weight (precomputed.PRE)."""
     attn, mlp = getattr(layer, "self_attn", None), getattr(layer, "mlp", None)
     for owner, names in ((attn, ("q_proj", "k_proj", "v_proj", "o_proj")), (mlp, ("gate_proj", "up_proj"))):
         if owner is None:
@@ -808,7 +808,7 @@ def _drop_layer_handovers(layer):
         o = getattr(attn, "o_proj", None)
         fq = getattr(o, "weight_fake_quant", None) if o is not None else None
         if fq is not None and not torch.is_grad_enabled():
-            fq.__dict__["_qt_pre"] = None
+            precomputed.PRE.drop(fq)
 
 
 def _decoder_layer_forward(self, hidden_states, attention_mask=None, position_ids=None, past_key_values=None, use_cache=False,

@@ -9,6 +9,8 @@ from torch.nn.utils.parametrize import (
     type_before_parametrizations,
 )
 
+from ...handover import unwritten
+
 __all__ = ["Linear"]
 
 
@@ -128,7 +130,7 @@ def _defer_forward(x2, w, b):
         return None
     if _FWD_PENDING and (_FWD_PENDING[0][0].shape != x2.shape or _FWD_PENDING[0][1].shape != w.shape):
         flush_forward()
-    y2 = torch.empty((M, N), dtype=torch.bfloat16, device=x2.device)
+    y2 = unwritten((M, N), torch.bfloat16, x2.device)
     _FWD_PENDING.append((x2, w, b, y2))
     if len(_FWD_PENDING) == 3:
         flush_forward()

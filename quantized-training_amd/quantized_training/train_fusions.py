@@ -22,13 +22,14 @@ calls around them in their own launch (_LayerNormTrainFn, _GeluTrainFn, _Softmax
 at a LayerNorm's output are summed by that LayerNorm's backward (take_deferred, _fanin); nn.Embedding's weight gradient is torch's
 bit for bit (_EmbeddingTrainFn).  One debug mask, QT_TRAIN_DEBUG (an integer, default 0 = every fusion on; DEBUG_BITS below), switches
 fusions OFF for A/B runs and tests -- rounds 4-5 had grown seven separate switches."""
+import collections
 import ctypes
 import weakref
 
 import torch
 
-from . import _native, planner_checks as pc, switches
-from .handover import tensor_key
+from . import _native, planner_checks as pc, precomputed, switches
+from .handover import tensor_key, unwritten
 
 __all__ = ["plan", "unplan", "enabled", "STATS"]
 
@@ -91,20 +92,12 @@ class Chain:
         self.name = name
 
 
-_COLSUM = {}              # (data_ptr, version, shape) of a grad_output -> (that tensor, its column sums): one-shot, taken by the Linear's backward
-
-
 def put_colsum(g, gb):
-    """Leaves the column sums of `g` for the Linear whose backward receives `g`.  The entry holds `g` itself: while it exists the address
-    cannot be handed to another tensor, so a key can only ever match the tensor it was made for (an entry nobody takes -- a chain miss, a
-    Linear that did not go through _LinearColsumBias -- used to outlive its tensor and could match a later gradient at the same address).
-    More than 64 entries: the OLDEST go (never all of them); a Linear whose entry went computes its own sums."""
-    while len(_COLSUM) >= 64:
-        del _COLSUM[next(iter(_COLSUM))]
-    _COLSUM[tensor_key(g)] = (g, gb)
-
-
-_LINEAR_GRADS = {}        # (data_ptr, version, shape) of a grad_output -> (that tensor, identity of x and Wq, grad_input, grad_weight): one-shot, like _COLSUM
+    """Leaves the column sums of `g` for the Linear whose backward receives `g` (precomputed.COLSUM: the entry holds `g` itself, so a key
+    can only ever match the tensor it was made for -- an entry nobody takes, after a chain miss or for a Linear that did not go through
+    _LinearColsumBias, used to outlive its tensor and could match a later gradient at the same address; a Linear whose entry went
+    computes its own sums)."""
+    precomputed.COLSUM.put(g, gb)
 
 
 _ATTN_ACTIVE = []         # the self-attention modules whose forward is running (innermost last)
@@ -177,34 +170,30 @@ def group_qkv_backward(lins, gys):
         gws = train_gemm_group(g2, xs, True, True, "wgrad q/k/v")
         if gws is None:
             return False
-    for lin, gy, x2, w, gx, gw in zip(lins, gys, xs, ws, gxs, gws):
+    for lin, gy, w, gx, gw in zip(lins, gys, ws, gxs, gws):
         x = lin.__dict__["_qt_train_xw"][0]()
-        while len(_LINEAR_GRADS) >= 16:
-            del _LINEAR_GRADS[next(iter(_LINEAR_GRADS))]
-        # (x and Wq are remembered by address and version, not by reference: Wq carries the step's autograd graph, and a reference that
-        # outlives a stream capture's end broke the graph's instantiation)
-        _LINEAR_GRADS[tensor_key(gy)] = (gy, (*tensor_key(x), w.data_ptr(), w._version),
-                                                                          gx.view(x.shape), gw)
+        precomputed.LINEAR_GRADS.put(gy, (gx.view(x.shape), gw), _saved_operands(x, w))
     STATS.qkv_groups += 1
     return True
 
 
+def _saved_operands(x, w):
+    """Which x and Wq a Linear node saved, by address and version, not by reference: Wq carries the step's autograd graph, and a reference
+    that outlives a stream capture's end broke the graph's instantiation."""
+    return (*tensor_key(x), w.data_ptr(), w._version)
+
+
 def take_linear_grads(gy, x, w):
-    hit = _LINEAR_GRADS.pop(tensor_key(gy), None)
-    if hit is None:
-        return None
-    _, ident, gx, gw = hit
-    if ident != (*tensor_key(x), w.data_ptr(), w._version):
-        return None                    # (another forward of the same Linear in between: the node multiplies what IT saved)
-    return gx, gw
+    """(grad_input, grad_weight) group_qkv_backward left for the node that receives `gy` and saved these very x and Wq, or None (another
+    forward of the same Linear in between: the node multiplies what IT saved)."""
+    return precomputed.LINEAR_GRADS.take(gy, _saved_operands(x, w))
 
 
 def take_colsum(g):
-    hit = _COLSUM.pop(tensor_key(g), None)
-    if hit is None:
-        return None
-    STATS.colsums += 1
-    return hit[1]
+    gb = precomputed.COLSUM.take(g)
+    if gb is not None:
+        STATS.colsums += 1
+    return gb
 
 
 def _member_ok(fq, device):
@@ -294,8 +283,7 @@ def run_chain(head, chain, X):
     for i, (fq, src) in enumerate(members):
         if i == 0:
             continue
-        want = X if src < 0 else outs[src]
-        fq.__dict__["_qt_chain_result"] = (*tensor_key(want), outs[i], want, False)
+        precomputed.CHAIN_RESULT.leave(fq, X if src < 0 else outs[src], _MemberResult(outs[i], False, None))
     if need_grad:
         # every member keeps an autograd node of its own (the straight-through gradient, fake_quantize.py:250-252), as in the unchained
         # path: the engine then adds the members' gradients into x in the very order it would have, bit for bit
@@ -304,21 +292,24 @@ def run_chain(head, chain, X):
     return outs[0]
 
 
+# what a launch leaves for a member's call: its result; whether that is an output of the producer's own autograd node; what to arm (_hand_over)
+_MemberResult = collections.namedtuple("_MemberResult", "out connected arm")
+
+
 def take_member_result(fq, X):
     """Called at the top of a fake-quantizer's forward: the result a chain launch left for THIS call, or None.  A call that received
     another tensor than the chain predicted drops the speculative amax and proceeds on its own."""
-    pend = fq.__dict__.get("_qt_chain_result")
-    if pend is None:
+    left = precomputed.CHAIN_RESULT.peek(fq)
+    if left is None:
         return None
-    fq.__dict__["_qt_chain_result"] = None
-    ptr, version, shape, out, _keep, connected = pend[:6]
-    arm = pend[6] if len(pend) > 6 else None
-    from .fake_quantize import _Stats, _take_preupdate, _PrecomputedFakeQuant
-    if tensor_key(X) == (ptr, version, shape) and (X.is_contiguous() or X.stride() == _keep.stride()):
+    got = precomputed.CHAIN_RESULT.take(fq, X)
+    from .fake_quantize import _Stats, _PrecomputedFakeQuant
+    if got is not precomputed.MISS:
+        out, connected, arm = got
         STATS.members += 1
         _Stats.add(X.numel())
         if fq._observe:
-            _take_preupdate(fq.amax_history)                   # the batched scale update (or the chain's own) served this call
+            precomputed.take_preupdate(fq.amax_history)        # the batched scale update (or the chain's own) served this call
         if arm is not None:
             # this call's result is an output of the producing kernel's own autograd node (`connected`): what comes back for it goes to
             # that node alone, so the consuming Linear's backward quantizer may leave its call to the node's fan-in launch (take_deferred)
@@ -327,13 +318,13 @@ def take_member_result(fq, X):
             return _PrecomputedFakeQuant.apply(X, out)         # the straight-through gradient of this call (fake_quantize.py:250-252)
         return out
     STATS.misses += 1
+    ptr, version, shape = left.key
     if len(STATS.missed) < 8:
         STATS.missed.append((getattr(fq, "name", "?"), X.data_ptr() == ptr, X._version == version, tuple(X.shape), shape, X.is_contiguous()))
     if fq._observe and fq.amax_history.numel() > 0:
         # the chain has already rolled this quantizer's history for the call and added an amax that belongs to no call: start the slot again
-        from .fake_quantize import _PREUPDATED
         fq.amax_history[0].zero_()
-        _PREUPDATED.add(fq.amax_history.data_ptr())            # ... and do not roll a second time
+        precomputed.mark_preupdated(fq.amax_history)           # ... and do not roll a second time
     return None
 
 
@@ -355,7 +346,7 @@ def unplan(model):
     for m in model.modules():
         if isinstance(m, FusedAmaxObsFakeQuantize):
             m.__dict__.pop("_qt_chain", None)
-            m.__dict__.pop("_qt_chain_result", None)
+            precomputed.CHAIN_RESULT.drop(m)
         elif isinstance(m, torch.nn.LayerNorm):
             m.__dict__.pop("_qt_grad_head", None)
 
@@ -478,8 +469,7 @@ def _hand_over(members, produced, outs, connected=False, arm=None):
     connected: the results are outputs of the producer's autograd node (no straight-through node is added when they are handed out);
     arm[i]: the backward fake-quantizer to arm for a deferred call once member i took its result (take_deferred)."""
     for i, (fq, src) in enumerate(members):
-        want = produced if src < 0 else outs[src]
-        fq.__dict__["_qt_chain_result"] = (*tensor_key(want), outs[i], want, connected, arm[i] if arm else None)
+        precomputed.CHAIN_RESULT.leave(fq, produced if src < 0 else outs[src], _MemberResult(outs[i], connected, arm[i] if arm else None))
     STATS.chains += 1
 
 
@@ -515,7 +505,7 @@ def take_deferred(fq, X):
     STATS.members += 1
     STATS.deferred += 1
     _Stats.add(X.numel())
-    hold = torch.empty_like(X)
+    hold = unwritten(like=X)
     if len(_PENDING) > 64:
         # only entries whose autograd graph is gone (their token died: nothing can deliver those placeholders any more); a placeholder of
         # a backward that is still running is never dropped -- it is uninitialised memory that only its entry can turn into a gradient
@@ -916,7 +906,7 @@ def _served_call(fq, x, y, numel=None):
     and finds `y` (take_member_result) -- its hooks see the call, its input and its result."""
     from .fake_quantize import _Stats
     if y is not None and not pc.no_forward_hooks(fq):
-        fq.__dict__["_qt_chain_result"] = (*tensor_key(x), y, x, False)
+        precomputed.CHAIN_RESULT.leave(fq, x, _MemberResult(y, False, None))
         with torch.no_grad():
             got = fq(x)
         if got.data_ptr() != y.data_ptr():

@@ -681,14 +681,15 @@ def test_builders_equal_the_ordinary_calls(nv):
         assert np.array_equal(bits_of(fq(W)), bits_of(tfq(TW)))
     same_state("warm-up")
 
+    from quantized_training import precomputed as pre
     upd = fqm.BatchedScaleUpdate([fq for fq, _ in mine], dev)
     wq = fqm.BatchedWeightFakeQuant(mine, dev)
     try:
-        launched = {id(fq): y for g in wq.groups for (fq, _), y in zip(g[2], g[3])}          # where the launch leaves each member's result
+        launched = {id(fq): y for g in wq.groups for (fq, _), y in zip(g.members, g.outs)}  # where the launch leaves each member's result
         members = set(launched)
         assert members == {id(p[0][0]) for p in batched + [changed]}, "exactly the eligible pairs are batched"
         assert len(wq) == len(batched) + 1 and len(wq.groups) >= 3
-        assert any(g[0].kind == nv.QT_FMT_LUT and (g[0].p1 & 1) for g in wq.groups)
+        assert any(g.fmt.kind == nv.QT_FMT_LUT and (g.fmt.p1 & 1) for g in wq.groups)
         observing = [fq for fq, _ in mine if fq._observe]
         assert {id(f) for f in upd.fqs} == {id(f) for f in observing} and len(observing) >= 10
 
@@ -699,10 +700,12 @@ def test_builders_equal_the_ordinary_calls(nv):
                     W.add_(bump)
                     TW.add_(bump)
             upd.launch()
-            assert all(f.amax_history.data_ptr() in fqm._PREUPDATED for f in observing)
+            assert all(pre.take_preupdate(f.amax_history) for f in observing)          # every one is marked (taking a mark removes it:
+            for f in observing:                                                        # put it back)
+                pre.mark_preupdated(f.amax_history)
             wq.launch()
-            assert all(fq.__dict__.get("_qt_pre") is not None for fq, _ in mine if id(fq) in members)
-            precomputed = bits_of(changed[0][0].__dict__["_qt_pre"][2])
+            assert all(pre.PRE.peek(fq) is not None for fq, _ in mine if id(fq) in members)
+            precomputed = bits_of(pre.PRE.peek(changed[0][0]).payload)
             with torch.no_grad():
                 changed[0][1].mul_(2)                                                  # amax only grows: the observer state stays comparable
                 changed[1][1].mul_(2)
@@ -718,8 +721,8 @@ def test_builders_equal_the_ordinary_calls(nv):
             torch.cuda.synchronize()
             same_state(rnd)
             for fq, _ in mine:
-                assert fq.__dict__.get("_qt_pre") is None
-                assert fq.amax_history.numel() == 0 or fq.amax_history.data_ptr() not in fqm._PREUPDATED
+                assert pre.PRE.peek(fq) is None
+                assert fq.amax_history.numel() == 0 or not pre.take_preupdate(fq.amax_history)
     finally:
         upd.forget()
         wq.forget()

@@ -1314,7 +1314,8 @@ def test_attention_output_fused_with_projection_input_fake_quant(nv):
         mf.transpose_fq(out, fq)
         other = fq(ref_in)                                      # a different tensor: normal pass, expectation dropped
         assert torch.equal(other.view(torch.int16), want.view(torch.int16))
-        assert fq.__dict__.get("_qt_expected") is None
+        from quantized_training import precomputed
+        assert precomputed.EXPECTED.peek(fq) is None
 
 
 def test_rotary_fused_with_qk_fake_quant(nv):

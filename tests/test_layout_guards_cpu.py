@@ -10,7 +10,7 @@ import pytest
 import torch
 
 import quantized_training as qt
-from quantized_training import model_fusions, train_fusions
+from quantized_training import model_fusions, precomputed, train_fusions
 
 
 def _args(*flags):
@@ -159,7 +159,7 @@ def test_training_plan_declines_a_mutated_tree(caplog):
 def test_colsum_hand_over_never_matches_another_tensor():
     """train_fusions.put_colsum / take_colsum: an entry holds its gradient tensor, so the address cannot be reused while the
     entry exists; 64 entries evict the OLDEST, never all."""
-    train_fusions._COLSUM.clear()
+    precomputed.COLSUM.clear()
     g = torch.randn(4, 8)
     train_fusions.put_colsum(g, "sums of g")
     ptr = g.data_ptr()
@@ -172,13 +172,13 @@ def test_colsum_hand_over_never_matches_another_tensor():
         t = torch.randn(2, 8)
         keep.append(t)
         train_fusions.put_colsum(t, i)
-    assert len(train_fusions._COLSUM) == 64
+    assert len(precomputed.COLSUM) == 64
     assert train_fusions.take_colsum(keep[-1]) == 69 and train_fusions.take_colsum(keep[-1]) is None      # one shot
     assert train_fusions.take_colsum(keep[10]) == 10 and train_fusions.take_colsum(keep[0]) is None       # the oldest went, the others stayed
     t = keep[20]
     t.add_(1.0)                                               # another version of the same tensor is another gradient
     assert train_fusions.take_colsum(t) is None
-    train_fusions._COLSUM.clear()
+    precomputed.COLSUM.clear()
 
 
 def test_train_debug_mask(monkeypatch):

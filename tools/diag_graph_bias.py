@@ -4,7 +4,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "quantized-training_amd")); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch
 import quantized_training as qt
-from quantized_training import harness, train_fusions
+from quantized_training import harness, precomputed, train_fusions
 from test_gpu_models import _args, _TRAIN_FLAGS
 from transformers import RobertaConfig, RobertaForSequenceClassification
 
@@ -38,13 +38,13 @@ def run(mode):
             T.reset()
             loss = m(**b).loss
             loss.backward()
-            stats = (T.colsums, T.chains, T.misses, T.fanins, T.deferred, len(train_fusions._COLSUM), len(train_fusions._PENDING))
+            stats = (T.colsums, T.chains, T.misses, T.fanins, T.deferred, len(precomputed.COLSUM), len(train_fusions._PENDING))
             torch.nn.utils.clip_grad_norm_(m.parameters(), 1.0, error_if_nonfinite=False)
             opt.step()
     else:
         step = Probe(m, opt)
         step.capture(batches[0], warmup=3)
-        stats = (T.colsums, T.chains, T.misses, T.fanins, T.deferred, len(train_fusions._COLSUM), len(train_fusions._PENDING))
+        stats = (T.colsums, T.chains, T.misses, T.fanins, T.deferred, len(precomputed.COLSUM), len(train_fusions._PENDING))
         step.replay(batches[1])
     torch.cuda.synchronize()
     grads = {n: p.grad.detach().float().clone() for n, p in m.named_parameters() if p.grad is not None}

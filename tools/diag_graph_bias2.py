@@ -4,7 +4,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "quantized-training_amd")); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch
 import quantized_training as qt
-from quantized_training import harness, train_fusions
+from quantized_training import harness, precomputed, train_fusions
 from test_gpu_models import _args, _TRAIN_FLAGS
 from transformers import RobertaConfig, RobertaForSequenceClassification
 
@@ -13,7 +13,7 @@ flags = _args(*_TRAIN_FLAGS)
 
 def scratch_state(tag):
     dirty = {str(k): int(v.count_nonzero()) for k, v in train_fusions._SCRATCH.items()}
-    print(f"   [{tag}] chain scratch nonzero bytes {dirty}; _COLSUM {len(train_fusions._COLSUM)} _PENDING {len(train_fusions._PENDING)}", flush=True)
+    print(f"   [{tag}] chain scratch nonzero bytes {dirty}; COLSUM {len(precomputed.COLSUM)} _PENDING {len(train_fusions._PENDING)}", flush=True)
 
 
 def case(cfg, B, S, V, nrep):

@@ -5,7 +5,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "quantized-training_amd")); sys.path.insert(0, ROOT)
 import torch
 import quantized_training as qt
-from quantized_training import harness, train_fusions
+from quantized_training import harness, precomputed, train_fusions
 from transformers import RobertaConfig, RobertaForSequenceClassification
 
 L = int(sys.argv[1]); vocab = int(sys.argv[2]) if len(sys.argv) > 2 else 50265
@@ -21,7 +21,7 @@ harness.train_steps(model, batches[:2], torch.optim.AdamW(model.parameters(), lr
 train_fusions.STATS.reset()
 step = harness.GraphedTrainStep(model, opt)
 step.capture(batches[0], warmup=3)
-print("captured; qkv groups in the captured pass:", train_fusions.STATS.qkv_groups, "pending linear grads", len(train_fusions._LINEAR_GRADS), flush=True)
+print("captured; qkv groups in the captured pass:", train_fusions.STATS.qkv_groups, "pending linear grads", len(precomputed.LINEAR_GRADS), flush=True)
 for i in range(3):
     loss = step.replay(batches[3 + i])
 torch.cuda.synchronize()
