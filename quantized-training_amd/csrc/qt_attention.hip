@@ -28,6 +28,7 @@
 #include <stdlib.h>
 
 #include "qt_device.h"
+#include "qt_dispatch.h"
 
 namespace {
 
@@ -432,26 +433,17 @@ __global__ __launch_bounds__(256) void attention_fq_kernel(AttnArgs a) {
     }
 }
 
-template <int D, int KIND>
-int launch_attn_kind(const AttnArgs &a, hipStream_t st) {
-    dim3 grid((unsigned)(((a.Sq + kBQ - 1) / kBQ) * a.B * a.H));
-    const bool unit = a.scale == nullptr, obs = a.amax != nullptr;
-    if (unit && obs) attention_fq_kernel<D, KIND, true, true><<<grid, 256, 0, st>>>(a);
-    else if (unit) attention_fq_kernel<D, KIND, true, false><<<grid, 256, 0, st>>>(a);
-    else if (obs) attention_fq_kernel<D, KIND, false, true><<<grid, 256, 0, st>>>(a);
-    else attention_fq_kernel<D, KIND, false, false><<<grid, 256, 0, st>>>(a);
-    return qt_launch_status();
-}
-
 template <int D>
 int launch_attn(const AttnArgs &a, hipStream_t st) {
-    switch (a.fmt.kind) {
-        case QT_FMT_LUT: return (a.fmt.p1 & 1) ? launch_attn_kind<D, kFmtRows>(a, st) : launch_attn_kind<D, QT_FMT_LUT>(a, st);
-        case QT_FMT_FP_SAT: return launch_attn_kind<D, QT_FMT_FP_SAT>(a, st);
-        case QT_FMT_INT: return launch_attn_kind<D, QT_FMT_INT>(a, st);
-        case QT_FMT_IDENTITY: return launch_attn_kind<D, QT_FMT_IDENTITY>(a, st);
-        default: return QT_ERR_BAD_ARG;
-    }
+    dim3 grid((unsigned)(((a.Sq + kBQ - 1) / kBQ) * a.B * a.H));
+    const bool taken = qt_pick_kind<kFmtRows, QT_FMT_LUT, QT_FMT_FP_SAT, QT_FMT_INT, QT_FMT_IDENTITY>(a.fmt, [&](auto K) {
+        qt_pick_bool(a.scale == nullptr, [&](auto UNIT) {
+            qt_pick_bool(a.amax != nullptr, [&](auto OBS) {
+                attention_fq_kernel<D, decltype(K)::value, decltype(UNIT)::value, decltype(OBS)::value><<<grid, 256, 0, st>>>(a);
+            });
+        });
+    });
+    return taken ? qt_launch_status() : QT_ERR_BAD_ARG;
 }
 
 }  // namespace

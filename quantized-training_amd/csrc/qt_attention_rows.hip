@@ -410,11 +410,7 @@ int qt_attention_rows_bf16(const uint16_t *q_dev, const uint16_t *k_dev, const u
         a.dbg = e_st ? (unsigned long long *)strtoull(e_st, nullptr, 0) : nullptr;
     }
 #endif
-    static QtOncePerDevice configured;      
-    if (configured.needed()) {
-        if (hipFuncSetAttribute((const void *)attention_rows_split_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLds) != hipSuccess) return QT_ERR_BAD_ARG;
-        configured.done();
-    }
+    if (qt_allow_lds<attention_rows_split_kernel>(kLds)) return QT_ERR_BAD_ARG;
     attention_rows_split_kernel<<<dim3((unsigned)(B * H), (unsigned)((Sq + 63) / 64)), 512, kLds, (hipStream_t)stream>>>(a);
     return qt_launch_status();
 }

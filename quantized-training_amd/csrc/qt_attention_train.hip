@@ -35,6 +35,7 @@
 
 #include "qt_device.h"
 #include "qt_chain.h"
+#include "qt_dispatch.h"
 
 namespace {
 
@@ -660,20 +661,6 @@ __global__ __launch_bounds__(kThreads) void attn_train_bwd_kernel(AttnTrainBwdAr
     stamp(10);
 }
 
-template <typename ARGS, typename F_ROWS, typename F_SAT, typename F_INT>
-int dispatch(const qt_format *fmt, const uint16_t *lut, F_ROWS rows, F_SAT sat, F_INT in) {
-    switch (fmt->kind) {
-        case QT_FMT_LUT:
-            if (!lut || !(fmt->p1 & 1)) return QT_ERR_BAD_DTYPE;
-            rows();
-            break;
-        case QT_FMT_FP_SAT: sat(); break;
-        case QT_FMT_INT: in(); break;
-        default: return QT_ERR_BAD_DTYPE;
-    }
-    return qt_launch_status();
-}
-
 bool shape_ok(long batch, int heads, int positions, int head_dim) {
     return batch > 0 && heads > 0 && batch * heads <= 0x7FFFFFFF && head_dim == kD && positions >= 32 && positions <= kSMax && positions % 32 == 0;
 }
@@ -710,10 +697,10 @@ int qt_attention_train_bf16(const uint16_t *q_dev, const uint16_t *k_dev, const 
 #endif
     hipStream_t st = (hipStream_t)stream;
     const unsigned grid = (unsigned)(batch * heads);
-    return dispatch<AttnTrainFwdArgs>(
-        fmt, lut_dev, [&] { attn_train_fwd_kernel<kFmtRows><<<grid, kThreads, 0, st>>>(a, *fmt, lut_dev); },
-        [&] { attn_train_fwd_kernel<QT_FMT_FP_SAT><<<grid, kThreads, 0, st>>>(a, *fmt, lut_dev); },
-        [&] { attn_train_fwd_kernel<QT_FMT_INT><<<grid, kThreads, 0, st>>>(a, *fmt, lut_dev); });
+    if (!qt_pick_kind_rows<kFmtRows, QT_FMT_FP_SAT, QT_FMT_INT>(
+            *fmt, lut_dev, [&](auto K) { attn_train_fwd_kernel<decltype(K)::value><<<grid, kThreads, 0, st>>>(a, *fmt, lut_dev); }))
+        return QT_ERR_BAD_DTYPE;
+    return qt_launch_status();
 }
 
 size_t qt_attention_train_backward_ws_bytes(int heads) {
@@ -763,10 +750,10 @@ int qt_attention_train_backward_bf16(const uint16_t *grad_out_dev, const uint16_
 #endif
     hipStream_t st = (hipStream_t)stream;
     const unsigned grid = (unsigned)(batch * heads);
-    return dispatch<AttnTrainBwdArgs>(
-        fmt, lut_dev, [&] { attn_train_bwd_kernel<kFmtRows><<<grid, kThreads, 0, st>>>(a, *fmt, lut_dev); },
-        [&] { attn_train_bwd_kernel<QT_FMT_FP_SAT><<<grid, kThreads, 0, st>>>(a, *fmt, lut_dev); },
-        [&] { attn_train_bwd_kernel<QT_FMT_INT><<<grid, kThreads, 0, st>>>(a, *fmt, lut_dev); });
+    if (!qt_pick_kind_rows<kFmtRows, QT_FMT_FP_SAT, QT_FMT_INT>(
+            *fmt, lut_dev, [&](auto K) { attn_train_bwd_kernel<decltype(K)::value><<<grid, kThreads, 0, st>>>(a, *fmt, lut_dev); }))
+        return QT_ERR_BAD_DTYPE;
+    return qt_launch_status();
 }
 
 }  // extern "C"

@@ -193,4 +193,15 @@ __device__ __forceinline__ void chain_amax_commit(const ChainStageDev (&st)[kCha
     }
 }
 
+// ---- host: the stages of a C-ABI call (include/qt_hip.h, qt_chain_stage) checked and turned into the kernels' ChainStageDev
+inline int chain_stage_args(const qt_chain_stage *stages, int nstage, ChainStageDev (&st)[kChainMax]) {
+    if (nstage < 0 || nstage > kChainMax || (nstage > 0 && !stages)) return QT_ERR_BAD_ARG;
+    for (int i = 0; i < nstage; ++i) {
+        if (stages[i].src >= i || stages[i].src < -1) return QT_ERR_BAD_ARG;
+        if ((uintptr_t)stages[i].out_dev & 15u) return QT_ERR_UNALIGNED;
+        st[i] = ChainStageDev{stages[i].scale_f32_dev, stages[i].amax_bits_dev, (uint4 *)stages[i].out_dev, stages[i].src};
+    }
+    return QT_OK;
+}
+
 }  // namespace

@@ -185,12 +185,7 @@ template <int BM, int BN>
 int conv_launch(ConvArgs &a, hipStream_t st) {
     constexpr int kLds = Ring<BM, BN>::kBytes;
     static_assert(kLds <= 160 * 1024, "the ring does not fit a CU's LDS");
-    static QtOncePerDevice configured;
-    if (configured.needed()) {
-        const hipError_t e = hipFuncSetAttribute((const void *)conv2d_kernel<BM, BN>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
-        if (e != hipSuccess) return (int)e;
-        configured.done();
-    }
+    if (const int rc = qt_allow_lds<conv2d_kernel<BM, BN>>(kLds)) return rc;
     conv2d_kernel<BM, BN><<<(unsigned)(a.tiles_m * a.tiles_n), kThreads, kLds, st>>>(a);
     return qt_launch_status();
 }

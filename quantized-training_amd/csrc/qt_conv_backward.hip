@@ -407,22 +407,11 @@ WgradPlan wgrad_plan(const BwdArgs &a) {
     return p;
 }
 
-template <class K>
-int set_lds(K kernel, int bytes, QtOncePerDevice &once) {
-    if (once.needed()) {
-        const hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return (int)e;
-        once.done();
-    }
-    return QT_OK;
-}
-
 template <int BM, int BN>
 int dgrad_launch(BwdArgs &a, hipStream_t st) {
     constexpr int kLds = Ring<BM, BN>::kBytes;
     static_assert(kLds <= 160 * 1024, "the ring does not fit a CU's LDS");
-    static QtOncePerDevice configured;
-    if (const int rc = set_lds(conv2d_dgrad_kernel<BM, BN>, kLds, configured)) return rc;
+    if (const int rc = qt_allow_lds<conv2d_dgrad_kernel<BM, BN>>(kLds)) return rc;
     conv2d_dgrad_kernel<BM, BN><<<(unsigned)(a.tiles_m * a.tiles_n), kThreads, kLds, st>>>(a);
     return qt_launch_status();
 }
@@ -431,8 +420,7 @@ template <int BM, int BN>
 int wgrad_launch(BwdArgs &a, hipStream_t st) {
     constexpr int kLds = Ring<BM, BN>::kBytes;
     static_assert(kLds <= 160 * 1024, "the ring does not fit a CU's LDS");
-    static QtOncePerDevice configured;
-    if (const int rc = set_lds(conv2d_wgrad_kernel<BM, BN>, kLds, configured)) return rc;
+    if (const int rc = qt_allow_lds<conv2d_wgrad_kernel<BM, BN>>(kLds)) return rc;
     conv2d_wgrad_kernel<BM, BN><<<(unsigned)(a.tiles_m * a.tiles_n * a.ksplit), kThreads, kLds, st>>>(a);
     return qt_launch_status();
 }

@@ -10,7 +10,7 @@
 #error "libqt_hip is written for gfx950 (MI355X) only"
 #endif
 
-// hipFuncSetAttribute is per DEVICE, a `static bool` is per process: the package runs models on several devices of one process
+// A kernel's dynamic-LDS attribute is per DEVICE, a `static bool` is per process: the package runs models on several devices of one process
 // (_native.note_device), and the second device would never get the large-LDS attribute.  One bit per device ordinal.  The ordinal
 // needed() looked up travels to done() in a thread_local: the object itself is a function-local static shared by every host thread
 // (ctypes releases the GIL), and a member would let thread B's device overwrite thread A's between its needed() and done().
@@ -38,6 +38,19 @@ struct QtOncePerDevice {
 inline int qt_launch_status() {
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? QT_OK : (int)e;
+}
+
+// Allow `bytes` of dynamic LDS for KERNEL on the current device (a launch above 64 KiB needs it): one flag per kernel instantiation
+// and per device.  QT_OK or the HIP error code.
+template <auto KERNEL>
+inline int qt_allow_lds(int bytes) {
+    static QtOncePerDevice once;
+    if (once.needed()) {
+        const hipError_t e = hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (e != hipSuccess) return (int)e;
+        once.done();
+    }
+    return QT_OK;
 }
 
 // Compute units of the current device, looked up once per process (256 if the query fails).

@@ -18,6 +18,7 @@
 
 #include "qt_device.h"
 #include "qt_chain.h"
+#include "qt_dispatch.h"
 
 extern "C" float qt_internal_posit_threshold(int nbits, int es);
 extern "C" int qt_internal_fp8_emin(float fp8_min);
@@ -1461,20 +1462,9 @@ __global__ __launch_bounds__(256) void posit_bits_kernel(const float *__restrict
 }
 
 // ---- launch helpers --------------------------------------------------------------------------
-int num_cus() {
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) return 256;
-        cus = p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
-    }
-    return cus;
-}
-
 inline unsigned grid_for(size_t work_items, size_t per_block, int blocks_per_cu) {
     size_t want = (work_items + per_block - 1) / per_block;
-    size_t cap = (size_t)num_cus() * blocks_per_cu;
+    size_t cap = (size_t)qt_cu_count() * blocks_per_cu;
     if (want < 1) want = 1;
     return (unsigned)(want < cap ? want : cap);
 }
@@ -1493,10 +1483,9 @@ int launch_variant(const void *x, void *y, size_t n, const qt_format &fmt, const
     constexpr int kPer = IO == kIoBf16 ? 8 : 4;
     const size_t nvec = n / kPer;
     unsigned grid = grid_for(nvec, (size_t)BLOCK * UNR, g_blocks_per_cu);
-    if (amax)
-        fq_kernel<IO, KIND, true, BLOCK, UNR, NT><<<grid, BLOCK, 0, st>>>(x, y, nvec, n, fmt, lut, scale, amax);
-    else
-        fq_kernel<IO, KIND, false, BLOCK, UNR, NT><<<grid, BLOCK, 0, st>>>(x, y, nvec, n, fmt, lut, scale, amax);
+    qt_pick_bool(amax != nullptr, [&](auto OBS) {
+        fq_kernel<IO, KIND, decltype(OBS)::value, BLOCK, UNR, NT><<<grid, BLOCK, 0, st>>>(x, y, nvec, n, fmt, lut, scale, amax);
+    });
     return qt_launch_status();
 }
 
@@ -1522,36 +1511,34 @@ int launch_fq_kind(const void *x, void *y, size_t n, const qt_format &fmt, const
                 return qt_launch_status();
             }
             unsigned grid = grid_for(nv, (size_t)kAluBlock * kUnroll, row_blocks ? row_blocks : 8);
-            if (amax)
-                fq_kernel<IO, kFmtRows, true, kAluBlock><<<grid, kAluBlock, 0, st>>>(x, y, nv, n, fmt, lut, scale, amax);
-            else
-                fq_kernel<IO, kFmtRows, false, kAluBlock><<<grid, kAluBlock, 0, st>>>(x, y, nv, n, fmt, lut, scale, amax);
+            qt_pick_bool(amax != nullptr, [&](auto OBS) {
+                fq_kernel<IO, kFmtRows, decltype(OBS)::value, kAluBlock><<<grid, kAluBlock, 0, st>>>(x, y, nv, n, fmt, lut, scale, amax);
+            });
             return qt_launch_status();
         }
         if (aligned && y != nullptr && n >= 4096 && n < kLutLdsMinElems) {
             const size_t nv = n / kPer;
             unsigned grid = grid_for(nv, 256, 8);
-            if (amax) fq_gather_vec_kernel<IO, true><<<grid, 256, 0, st>>>(x, y, nv, n, fmt, lut, scale, amax);
-            else fq_gather_vec_kernel<IO, false><<<grid, 256, 0, st>>>(x, y, nv, n, fmt, lut, scale, amax);
+            qt_pick_bool(amax != nullptr, [&](auto OBS) {
+                fq_gather_vec_kernel<IO, decltype(OBS)::value><<<grid, 256, 0, st>>>(x, y, nv, n, fmt, lut, scale, amax);
+            });
             return qt_launch_status();
         }
     }
     if (gather) {
         // observe-only never touches the table, so KIND is irrelevant there
         unsigned grid = grid_for(n, 256 * 8, 8);
-        if (amax)
-            fq_gather_kernel<IO, KIND, true><<<grid, 256, 0, st>>>(x, y, n, fmt, lut, scale, amax);
-        else
-            fq_gather_kernel<IO, KIND, false><<<grid, 256, 0, st>>>(x, y, n, fmt, lut, scale, amax);
+        qt_pick_bool(amax != nullptr, [&](auto OBS) {
+            fq_gather_kernel<IO, KIND, decltype(OBS)::value><<<grid, 256, 0, st>>>(x, y, n, fmt, lut, scale, amax);
+        });
         return qt_launch_status();
     }
     const size_t nvec = n / kPer;
     if constexpr (KIND == QT_FMT_LUT) {
         unsigned grid = grid_for(nvec, (size_t)kLutBlock * 4 * 4, 1);
-        if (amax)
-            fq_kernel<IO, KIND, true, kLutBlock, 4><<<grid, kLutBlock, 0, st>>>(x, y, nvec, n, fmt, lut, scale, amax);
-        else
-            fq_kernel<IO, KIND, false, kLutBlock, 4><<<grid, kLutBlock, 0, st>>>(x, y, nvec, n, fmt, lut, scale, amax);
+        qt_pick_bool(amax != nullptr, [&](auto OBS) {
+            fq_kernel<IO, KIND, decltype(OBS)::value, kLutBlock, 4><<<grid, kLutBlock, 0, st>>>(x, y, nvec, n, fmt, lut, scale, amax);
+        });
     } else {
 #ifdef QT_TUNING_BUILD
         if constexpr (IO == kIoBf16 && KIND == QT_FMT_FP_SAT) {
@@ -1580,10 +1567,10 @@ int launch_fq_kind(const void *x, void *y, size_t n, const qt_format &fmt, const
         unsigned grid = grid_for(nvec, (size_t)kAluBlock * kUnroll, g_blocks_per_cu);
         if (amax && nvec <= kRowsDirectMaxVecs)     // observed short pass: a quarter of the workgroups, i.e. of the same-address atomics
             fq_kernel<IO, KIND, true, 1024><<<grid_for(nvec, 1024, 2), 1024, 0, st>>>(x, y, nvec, n, fmt, lut, scale, amax);
-        else if (amax)
-            fq_kernel<IO, KIND, true, kAluBlock><<<grid, kAluBlock, 0, st>>>(x, y, nvec, n, fmt, lut, scale, amax);
         else
-            fq_kernel<IO, KIND, false, kAluBlock><<<grid, kAluBlock, 0, st>>>(x, y, nvec, n, fmt, lut, scale, amax);
+            qt_pick_bool(amax != nullptr, [&](auto OBS) {
+                fq_kernel<IO, KIND, decltype(OBS)::value, kAluBlock><<<grid, kAluBlock, 0, st>>>(x, y, nvec, n, fmt, lut, scale, amax);
+            });
     }
     return qt_launch_status();
 }
@@ -1600,15 +1587,11 @@ int launch_fq(const void *x, void *y, size_t n, const qt_format *fmt, const uint
         qt_format ident = {QT_FMT_IDENTITY, 0, 0, 0.0f, 0.0f};
         return launch_fq_kind<IO, QT_FMT_IDENTITY>(x, nullptr, n, ident, nullptr, nullptr, amax, st);
     }
-    switch (fmt->kind) {
-        case QT_FMT_LUT:
-            if (!lut && y) return QT_ERR_BAD_ARG;
-            return launch_fq_kind<IO, QT_FMT_LUT>(x, y, n, *fmt, lut, scale, amax, st);
-        case QT_FMT_FP_SAT: return launch_fq_kind<IO, QT_FMT_FP_SAT>(x, y, n, *fmt, lut, scale, amax, st);
-        case QT_FMT_INT: return launch_fq_kind<IO, QT_FMT_INT>(x, y, n, *fmt, lut, scale, amax, st);
-        case QT_FMT_IDENTITY: return launch_fq_kind<IO, QT_FMT_IDENTITY>(x, y, n, *fmt, lut, scale, amax, st);
-        default: return QT_ERR_BAD_ARG;
-    }
+    if (fmt->kind == QT_FMT_LUT && !lut) return QT_ERR_BAD_ARG;
+    int rc = QT_ERR_BAD_ARG;          // (launch_fq_kind<QT_FMT_LUT> takes the row form itself)
+    qt_pick<QT_FMT_LUT, QT_FMT_FP_SAT, QT_FMT_INT, QT_FMT_IDENTITY>(
+        fmt->kind, [&](auto K) { rc = launch_fq_kind<IO, decltype(K)::value>(x, y, n, *fmt, lut, scale, amax, st); });
+    return rc;
 }
 
 template <int IO, int KIND>
@@ -1650,16 +1633,11 @@ int launch_pc(const void *x, void *y, size_t outer, size_t C, size_t inner, cons
     if (outer * C * inner == 0) return QT_OK;
     if (!x || !fmt || (!y && !amax)) return QT_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
-    switch (fmt->kind) {
-        case QT_FMT_LUT:
-            if (!lut && y) return QT_ERR_BAD_ARG;
-            return launch_pc_kind<IO, QT_FMT_LUT>(x, y, outer, C, inner, *fmt, lut, scale, amax, st);
-        case QT_FMT_FP_SAT: return launch_pc_kind<IO, QT_FMT_FP_SAT>(x, y, outer, C, inner, *fmt, lut, scale, amax, st);
-        case QT_FMT_INT: return launch_pc_kind<IO, QT_FMT_INT>(x, y, outer, C, inner, *fmt, lut, scale, amax, st);
-        case QT_FMT_IDENTITY:
-            return launch_pc_kind<IO, QT_FMT_IDENTITY>(x, y, outer, C, inner, *fmt, lut, scale, amax, st);
-        default: return QT_ERR_BAD_ARG;
-    }
+    if (fmt->kind == QT_FMT_LUT && !lut && y) return QT_ERR_BAD_ARG;
+    int rc = QT_ERR_BAD_ARG;
+    qt_pick<QT_FMT_LUT, QT_FMT_FP_SAT, QT_FMT_INT, QT_FMT_IDENTITY>(
+        fmt->kind, [&](auto K) { rc = launch_pc_kind<IO, decltype(K)::value>(x, y, outer, C, inner, *fmt, lut, scale, amax, st); });
+    return rc;
 }
 
 template <int IO>
@@ -1686,14 +1664,35 @@ int launch_mx(const void *x, void *y, void *sf, size_t rows, size_t cols, int bs
     const uint4 *xv = (const uint4 *)x;
     uint4 *yv = (uint4 *)y;
     hipStream_t st = (hipStream_t)stream;
-    switch (fmt->kind) {
-        case QT_FMT_LUT: fq_mx_kernel<IO, QT_FMT_LUT><<<grid, 256, 0, st>>>(xv, yv, sf, nvec, group, *fmt, lut, quant_max, scale_lut); break;
-        case QT_FMT_FP_SAT: fq_mx_kernel<IO, QT_FMT_FP_SAT><<<grid, 256, 0, st>>>(xv, yv, sf, nvec, group, *fmt, lut, quant_max, scale_lut); break;
-        case QT_FMT_INT: fq_mx_kernel<IO, QT_FMT_INT><<<grid, 256, 0, st>>>(xv, yv, sf, nvec, group, *fmt, lut, quant_max, scale_lut); break;
-        case QT_FMT_IDENTITY: fq_mx_kernel<IO, QT_FMT_IDENTITY><<<grid, 256, 0, st>>>(xv, yv, sf, nvec, group, *fmt, lut, quant_max, scale_lut); break;
-        default: return QT_ERR_BAD_ARG;
-    }
+    if (!qt_pick<QT_FMT_LUT, QT_FMT_FP_SAT, QT_FMT_INT, QT_FMT_IDENTITY>(fmt->kind, [&](auto K) {
+            fq_mx_kernel<IO, decltype(K)::value><<<grid, 256, 0, st>>>(xv, yv, sf, nvec, group, *fmt, lut, quant_max, scale_lut);
+        }))
+        return QT_ERR_BAD_ARG;
     return qt_launch_status();
+}
+
+// iters calls of `call(offset into the pool)` between two events: mean milliseconds per call
+template <class F>
+int bench_calls(int iters, size_t pool_stride, int pool_count, void *stream, float *ms_out, F &&call) {
+    if (!ms_out || iters < 1 || pool_count < 1) return QT_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    hipEvent_t e0, e1;
+    hipError_t e;
+    if ((e = hipEventCreate(&e0)) != hipSuccess) return (int)e;
+    if ((e = hipEventCreate(&e1)) != hipSuccess) { (void)hipEventDestroy(e0); return (int)e; }
+    int rc = QT_OK;
+    (void)hipEventRecord(e0, st);
+    for (int i = 0; i < iters && rc == QT_OK; ++i) rc = call((size_t)(i % pool_count) * pool_stride);
+    (void)hipEventRecord(e1, st);
+    e = hipEventSynchronize(e1);
+    float ms = 0.0f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    if (rc != QT_OK) return rc;
+    if (e != hipSuccess) return (int)e;
+    *ms_out = ms / (float)iters;
+    return QT_OK;
 }
 
 }  // namespace
@@ -1753,16 +1752,13 @@ int qt_fake_quant_bf16_fp8(const uint16_t *x, uint16_t *y, uint8_t *y8, size_t n
     const uint4 *xv = (const uint4 *)x;
     uint4 *yv = (uint4 *)y;
     uint4 *y8v = (uint4 *)y8;
-#define QT_FQ8(OBS, BOTH, E5)                                                                                  \
-    fq8_kernel<OBS, BOTH, E5><<<grid, 256, 0, st>>>(xv, yv, y8v, nvec, *fmt, scale, amax)
-    if (e5m2) {
-        if (amax) { if (y) QT_FQ8(true, true, true); else QT_FQ8(true, false, true); }
-        else      { if (y) QT_FQ8(false, true, true); else QT_FQ8(false, false, true); }
-    } else {
-        if (amax) { if (y) QT_FQ8(true, true, false); else QT_FQ8(true, false, false); }
-        else      { if (y) QT_FQ8(false, true, false); else QT_FQ8(false, false, false); }
-    }
-#undef QT_FQ8
+    qt_pick_bool(e5m2, [&](auto E5) {
+        qt_pick_bool(amax != nullptr, [&](auto OBS) {
+            qt_pick_bool(y != nullptr, [&](auto BOTH) {
+                fq8_kernel<decltype(OBS)::value, decltype(BOTH)::value, decltype(E5)::value><<<grid, 256, 0, st>>>(xv, yv, y8v, nvec, *fmt, scale, amax);
+            });
+        });
+    });
     return qt_launch_status();
 }
 
@@ -1807,11 +1803,7 @@ static int chain_launch(const uint16_t *x_dev, const uint16_t *x2_dev, int pre_o
 #ifdef QT_TUNING_BUILD
     a.dbg = ew_stamp_region();
 #endif
-    for (int i = 0; i < nstage; ++i) {
-        if (stages[i].src >= i || stages[i].src < -1) return QT_ERR_BAD_ARG;
-        if ((uintptr_t)stages[i].out_dev & 15u) return QT_ERR_UNALIGNED;
-        a.st[i] = ChainStageDev{stages[i].scale_f32_dev, stages[i].amax_bits_dev, (uint4 *)stages[i].out_dev, stages[i].src};
-    }
+    if (const int rc = chain_stage_args(stages, nstage, a.st)) return rc;
     chain_geometry(rows, cols, a.strips, a.bands, a.band_rows, pre_op);
     a.colsum_stage = -1;
     if (colsum_stage >= 0) {
@@ -1824,25 +1816,10 @@ static int chain_launch(const uint16_t *x_dev, const uint16_t *x2_dev, int pre_o
     }
     const unsigned grid = (unsigned)(a.strips * a.bands);
     hipStream_t st = (hipStream_t)stream;
-#define QT_CHAIN(K, NS) fq_chain_kernel<K, NS><<<grid, kChainBlock, 0, st>>>(a, *fmt, lut_dev)
-#define QT_CHAIN_NS(K)                                                                  \
-    switch (nstage) {                                                                   \
-        case 1: QT_CHAIN(K, 1); break;                                                  \
-        case 2: QT_CHAIN(K, 2); break;                                                  \
-        case 3: QT_CHAIN(K, 3); break;                                                  \
-        default: QT_CHAIN(K, 4); break;                                                 \
-    }
-    switch (fmt->kind) {
-        case QT_FMT_LUT:
-            if (!lut_dev || !(fmt->p1 & 1)) return QT_ERR_BAD_DTYPE;             // table formats in their row form only
-            QT_CHAIN_NS(kFmtRows)
-            break;
-        case QT_FMT_FP_SAT: QT_CHAIN_NS(QT_FMT_FP_SAT) break;
-        case QT_FMT_INT: QT_CHAIN_NS(QT_FMT_INT) break;
-        default: return QT_ERR_BAD_DTYPE;
-    }
-#undef QT_CHAIN_NS
-#undef QT_CHAIN
+    if (!qt_pick_kind_rows<kFmtRows, QT_FMT_FP_SAT, QT_FMT_INT>(*fmt, lut_dev, [&](auto K) {                  // table formats in their row form only
+            qt_pick<1, 2, 3, 4>(nstage, [&](auto NS) { fq_chain_kernel<decltype(K)::value, decltype(NS)::value><<<grid, kChainBlock, 0, st>>>(a, *fmt, lut_dev); });
+        }))
+        return QT_ERR_BAD_DTYPE;
     return qt_launch_status();
 }
 
@@ -1865,46 +1842,6 @@ int qt_gelu_backward_chain_bf16(const uint16_t *grad_out_dev, const uint16_t *x_
                         ws_dev, ws_bytes, stream);
 }
 
-static int chain_stage_args(const qt_chain_stage *stages, int nstage, ChainStageDev (&st)[kChainMax]) {
-    if (nstage < 0 || nstage > kChainMax || (nstage > 0 && !stages)) return QT_ERR_BAD_ARG;
-    for (int i = 0; i < nstage; ++i) {
-        if (stages[i].src >= i || stages[i].src < -1) return QT_ERR_BAD_ARG;
-        if ((uintptr_t)stages[i].out_dev & 15u) return QT_ERR_UNALIGNED;
-        st[i] = ChainStageDev{stages[i].scale_f32_dev, stages[i].amax_bits_dev, (uint4 *)stages[i].out_dev, stages[i].src};
-    }
-    return QT_OK;
-}
-
-#define QT_LN_DISPATCH(KERNEL, ARGS, GRID)                                                                                      \
-    switch (fmt->kind) {                                                                                                        \
-        case QT_FMT_LUT:                                                                                                        \
-            if (!lut_dev || !(fmt->p1 & 1)) return QT_ERR_BAD_DTYPE;                                                            \
-            switch (nstage) {                                                                                                   \
-                case 1: KERNEL<kFmtRows, 1, 512><<<(unsigned)((GRID)(512)), 512, 0, st>>>(ARGS, *fmt, lut_dev); break;          \
-                case 2: KERNEL<kFmtRows, 2, 512><<<(unsigned)((GRID)(512)), 512, 0, st>>>(ARGS, *fmt, lut_dev); break;          \
-                case 3: KERNEL<kFmtRows, 3, 512><<<(unsigned)((GRID)(512)), 512, 0, st>>>(ARGS, *fmt, lut_dev); break;          \
-                default: KERNEL<kFmtRows, 4, 512><<<(unsigned)((GRID)(512)), 512, 0, st>>>(ARGS, *fmt, lut_dev); break;         \
-            }                                                                                                                   \
-            break;                                                                                                              \
-        case QT_FMT_FP_SAT:                                                                                                     \
-            switch (nstage) {                                                                                                   \
-                case 1: KERNEL<QT_FMT_FP_SAT, 1, 512><<<(unsigned)((GRID)(512)), 512, 0, st>>>(ARGS, *fmt, lut_dev); break;     \
-                case 2: KERNEL<QT_FMT_FP_SAT, 2, 512><<<(unsigned)((GRID)(512)), 512, 0, st>>>(ARGS, *fmt, lut_dev); break;     \
-                case 3: KERNEL<QT_FMT_FP_SAT, 3, 512><<<(unsigned)((GRID)(512)), 512, 0, st>>>(ARGS, *fmt, lut_dev); break;     \
-                default: KERNEL<QT_FMT_FP_SAT, 4, 512><<<(unsigned)((GRID)(512)), 512, 0, st>>>(ARGS, *fmt, lut_dev); break;    \
-            }                                                                                                                   \
-            break;                                                                                                              \
-        case QT_FMT_INT:                                                                                                        \
-            switch (nstage) {                                                                                                   \
-                case 1: KERNEL<QT_FMT_INT, 1, 512><<<(unsigned)((GRID)(512)), 512, 0, st>>>(ARGS, *fmt, lut_dev); break;        \
-                case 2: KERNEL<QT_FMT_INT, 2, 512><<<(unsigned)((GRID)(512)), 512, 0, st>>>(ARGS, *fmt, lut_dev); break;        \
-                case 3: KERNEL<QT_FMT_INT, 3, 512><<<(unsigned)((GRID)(512)), 512, 0, st>>>(ARGS, *fmt, lut_dev); break;        \
-                default: KERNEL<QT_FMT_INT, 4, 512><<<(unsigned)((GRID)(512)), 512, 0, st>>>(ARGS, *fmt, lut_dev); break;       \
-            }                                                                                                                   \
-            break;                                                                                                              \
-        default: return QT_ERR_BAD_DTYPE;                                                                                       \
-    }
-
 int qt_layernorm_train_bf16(const uint16_t *x_dev, const uint16_t *weight_dev, const uint16_t *bias_dev, uint16_t *y_dev, float *mean_dev,
                             float *rstd_dev, long rows, long cols, float eps, const qt_chain_stage *stages, int nstage, const qt_format *fmt,
                             const uint16_t *lut_dev, const uint16_t *residual_dev, uint16_t *sum_dev, void *stream) {
@@ -1920,8 +1857,11 @@ int qt_layernorm_train_bf16(const uint16_t *x_dev, const uint16_t *weight_dev, c
     a.mean = mean_dev; a.rstd = rstd_dev; a.rows = rows; a.nvec = (int)(cols / 8); a.inv_cols = 1.0f / (float)cols; a.eps = eps;
     if (const int rc = chain_stage_args(stages, nstage, a.st)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    auto grid = [&](int block) { return (rows + block / 64 - 1) / (block / 64); };
-    QT_LN_DISPATCH(ln_train_fwd_kernel, a, grid)
+    const unsigned grid = (unsigned)((rows + 7) / 8);                 // 512 threads = 8 waves, one row per wave
+    if (!qt_pick_kind_rows<kFmtRows, QT_FMT_FP_SAT, QT_FMT_INT>(*fmt, lut_dev, [&](auto K) {
+            qt_pick<1, 2, 3, 4>(nstage, [&](auto NS) { ln_train_fwd_kernel<decltype(K)::value, decltype(NS)::value, 512><<<grid, 512, 0, st>>>(a, *fmt, lut_dev); });
+        }))
+        return QT_ERR_BAD_DTYPE;
     return qt_launch_status();
 }
 
@@ -1955,11 +1895,15 @@ int qt_layernorm_train_backward_bf16(const uint16_t *grad_out_dev, const uint16_
                                  fan_items[i].fq ? 1 : 0};
     }
     hipStream_t st = (hipStream_t)stream;
-    auto grid = [&](int) { return groups; };
 #ifdef QT_TUNING_BUILD
     a.dbg = ew_stamp_region();
 #endif
-    QT_LN_DISPATCH(ln_train_bwd_kernel, a, grid)
+    if (!qt_pick_kind_rows<kFmtRows, QT_FMT_FP_SAT, QT_FMT_INT>(*fmt, lut_dev, [&](auto K) {
+            qt_pick<1, 2, 3, 4>(nstage, [&](auto NS) {
+                ln_train_bwd_kernel<decltype(K)::value, decltype(NS)::value, 512><<<(unsigned)groups, 512, 0, st>>>(a, *fmt, lut_dev);
+            });
+        }))
+        return QT_ERR_BAD_DTYPE;
     if (const int rc = qt_launch_status()) return rc;
     ln_train_reduce_kernel<<<dim3((unsigned)((cols + 63) / 64), colsum_stage >= 0 ? 3u : 2u), 256, 0, st>>>(part_dev, (int)groups, (int)cols, grad_weight_dev,
                                                                                                       grad_bias_dev, colsum_out_dev);
@@ -1982,24 +1926,14 @@ int qt_fake_quant_rows_bf16(const uint16_t *x, uint16_t *y, long d0, long d1, lo
     RowsArgs a{x, y, d1, d2, inner / 8, s0, s1, s2, (size_t)(d0 * d1 * d2 * (inner / 8))};
     const unsigned grid = grid_for(a.nvec, 256, 32);
     hipStream_t st = (hipStream_t)stream;
-#define QT_ROWS(K)                                                                           \
-    do {                                                                                     \
-        if (amax && a.nvec <= kRowsDirectMaxVecs)                                            \
-            fq_rows_kernel<K, true, 0, 1024><<<grid_for(a.nvec, 1024, 2), 1024, 0, st>>>(a, *fmt, lut, scale, amax);  \
-        else if (amax) fq_rows_kernel<K, true><<<grid, 256, 0, st>>>(a, *fmt, lut, scale, amax);  \
-        else fq_rows_kernel<K, false><<<grid, 256, 0, st>>>(a, *fmt, lut, scale, amax);      \
-    } while (0)
-    switch (fmt->kind) {
-        case QT_FMT_LUT:
-            if (fmt->p1 & 1) QT_ROWS(kFmtRows);          // row form behind the map
-            else QT_ROWS(QT_FMT_LUT);
-            break;
-        case QT_FMT_FP_SAT: QT_ROWS(QT_FMT_FP_SAT); break;
-        case QT_FMT_INT: QT_ROWS(QT_FMT_INT); break;
-        case QT_FMT_IDENTITY: QT_ROWS(QT_FMT_IDENTITY); break;
-        default: return QT_ERR_BAD_ARG;
-    }
-#undef QT_ROWS
+    if (!qt_pick_kind<kFmtRows, QT_FMT_LUT, QT_FMT_FP_SAT, QT_FMT_INT, QT_FMT_IDENTITY>(*fmt, [&](auto K) {
+            constexpr int KIND = decltype(K)::value;
+            if (amax && a.nvec <= kRowsDirectMaxVecs)
+                fq_rows_kernel<KIND, true, 0, 1024><<<grid_for(a.nvec, 1024, 2), 1024, 0, st>>>(a, *fmt, lut, scale, amax);
+            else
+                qt_pick_bool(amax != nullptr, [&](auto OBS) { fq_rows_kernel<KIND, decltype(OBS)::value><<<grid, 256, 0, st>>>(a, *fmt, lut, scale, amax); });
+        }))
+        return QT_ERR_BAD_ARG;
     return qt_launch_status();
 }
 
@@ -2025,8 +1959,7 @@ int qt_fake_quant_bf16_fp8_multi(const uint16_t *const *xs, const size_t *ns, in
     if ((uintptr_t)y8 & 15u) return QT_ERR_UNALIGNED;
     const unsigned grid = grid_for(run, 256, g_blocks_per_cu);
     hipStream_t st = (hipStream_t)stream;
-    if (e5m2) fq8_multi_kernel<true><<<grid, 256, 0, st>>>(a, (uint4 *)y8, *fmt);
-    else fq8_multi_kernel<false><<<grid, 256, 0, st>>>(a, (uint4 *)y8, *fmt);
+    qt_pick_bool(e5m2, [&](auto E5) { fq8_multi_kernel<decltype(E5)::value><<<grid, 256, 0, st>>>(a, (uint4 *)y8, *fmt); });
     return qt_launch_status();
 }
 
@@ -2039,8 +1972,7 @@ int qt_fake_quant_multi_bf16_fp8(const qt_fq8_item *items_dev, int count, unsign
     static_assert(sizeof(qt_fq8_item) == sizeof(qt_fq8_item_dev), "layout of qt_fq8_item");
     const qt_fq8_item_dev *it = (const qt_fq8_item_dev *)items_dev;
     hipStream_t st = (hipStream_t)stream;
-    if (e5m2) fq8_items_kernel<true><<<(unsigned)total_tiles, 256, 0, st>>>(it, count, *fmt);
-    else fq8_items_kernel<false><<<(unsigned)total_tiles, 256, 0, st>>>(it, count, *fmt);
+    qt_pick_bool(e5m2, [&](auto E5) { fq8_items_kernel<decltype(E5)::value><<<(unsigned)total_tiles, 256, 0, st>>>(it, count, *fmt); });
     return qt_launch_status();
 }
 
@@ -2053,15 +1985,9 @@ int qt_fake_quant_multi_bf16(const qt_fq_item *items_dev, int count, unsigned lo
     const qt_fq_item_dev *it = (const qt_fq_item_dev *)items_dev;
     hipStream_t st = (hipStream_t)stream;
     const unsigned grid = (unsigned)total_tiles;
-    switch (fmt->kind) {
-        case QT_FMT_LUT:
-            if (!lut_dev || !(fmt->p1 & 1)) return QT_ERR_BAD_ARG;          // table formats: the row form behind the map only
-            fq_multi_kernel<kFmtRows><<<grid, kMultiBlock, 0, st>>>(it, count, *fmt, lut_dev);
-            break;
-        case QT_FMT_FP_SAT: fq_multi_kernel<QT_FMT_FP_SAT><<<grid, kMultiBlock, 0, st>>>(it, count, *fmt, lut_dev); break;
-        case QT_FMT_INT: fq_multi_kernel<QT_FMT_INT><<<grid, kMultiBlock, 0, st>>>(it, count, *fmt, lut_dev); break;
-        default: return QT_ERR_BAD_ARG;
-    }
+    if (!qt_pick_kind_rows<kFmtRows, QT_FMT_FP_SAT, QT_FMT_INT>(             // table formats: the row form behind the map only
+            *fmt, lut_dev, [&](auto K) { fq_multi_kernel<decltype(K)::value><<<grid, kMultiBlock, 0, st>>>(it, count, *fmt, lut_dev); }))
+        return QT_ERR_BAD_ARG;
     return qt_launch_status();
 }
 
@@ -2070,13 +1996,13 @@ int qt_fake_quant_rows_bf16_fp8(const uint16_t *x, uint16_t *y, uint8_t *y8, lon
     if (d0 * d1 * d2 * inner == 0) return QT_OK;
     const int f8 = qt_fp8_code(fmt);
     if (!x || !y8 || !f8 || d0 < 0 || d1 < 0 || d2 < 0 || inner < 0) return QT_ERR_BAD_ARG;
-    const bool e5m2 = f8 == 2;
     if ((inner & 7) || ((s0 | s1 | s2) & 7) || (((uintptr_t)x | (uintptr_t)y) & 15u) || ((uintptr_t)y8 & 7u)) return QT_ERR_UNALIGNED;
     RowsArgs a{x, y, d1, d2, inner / 8, s0, s1, s2, (size_t)(d0 * d1 * d2 * (inner / 8))};          // y may be NULL: FP8 codes only
     const unsigned grid = grid_for(a.nvec, 256, 32);
     hipStream_t st = (hipStream_t)stream;
-    if (e5m2) fq_rows_kernel<QT_FMT_FP_SAT, false, 2><<<grid, 256, 0, st>>>(a, *fmt, nullptr, nullptr, nullptr, (uint2 *)y8);
-    else fq_rows_kernel<QT_FMT_FP_SAT, false, 1><<<grid, 256, 0, st>>>(a, *fmt, nullptr, nullptr, nullptr, (uint2 *)y8);
+    qt_pick<1, 2>(f8, [&](auto FP8) {                                // 1 E4M3, 2 E5M2
+        fq_rows_kernel<QT_FMT_FP_SAT, false, decltype(FP8)::value><<<grid, 256, 0, st>>>(a, *fmt, nullptr, nullptr, nullptr, (uint2 *)y8);
+    });
     return qt_launch_status();
 }
 
@@ -2159,55 +2085,15 @@ int qt_posit_quantize_f32(const float *x, float *y, int32_t *pbits, size_t n, in
 int qt_bench_fake_quant_bf16(const uint16_t *x, uint16_t *y, size_t n, const qt_format *fmt, const uint16_t *lut,
                              const float *scale, uint32_t *amax, int iters, size_t pool_stride, int pool_count,
                              void *stream, float *ms_out) {
-    if (!ms_out || iters < 1 || pool_count < 1) return QT_ERR_BAD_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    hipEvent_t e0, e1;
-    hipError_t e;
-    if ((e = hipEventCreate(&e0)) != hipSuccess) return (int)e;
-    if ((e = hipEventCreate(&e1)) != hipSuccess) { (void)hipEventDestroy(e0); return (int)e; }
-    int rc = QT_OK;
-    (void)hipEventRecord(e0, st);
-    for (int i = 0; i < iters && rc == QT_OK; ++i) {
-        const size_t off = (size_t)(i % pool_count) * pool_stride;
-        rc = launch_fq<kIoBf16>(x + off, y ? y + off : nullptr, n, fmt, lut, scale, amax, stream);
-    }
-    (void)hipEventRecord(e1, st);
-    e = hipEventSynchronize(e1);
-    float ms = 0.0f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (rc != QT_OK) return rc;
-    if (e != hipSuccess) return (int)e;
-    *ms_out = ms / (float)iters;
-    return QT_OK;
+    return bench_calls(iters, pool_stride, pool_count, stream, ms_out,
+                       [&](size_t off) { return launch_fq<kIoBf16>(x + off, y ? y + off : nullptr, n, fmt, lut, scale, amax, stream); });
 }
 
 int qt_bench_fake_quant_bf16_fp8(const uint16_t *x, uint16_t *y, uint8_t *y8, size_t n, const qt_format *fmt,
                                  const float *scale, uint32_t *amax, int iters, size_t pool_stride, int pool_count,
                                  void *stream, float *ms_out) {
-    if (!ms_out || iters < 1 || pool_count < 1) return QT_ERR_BAD_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    hipEvent_t e0, e1;
-    hipError_t e;
-    if ((e = hipEventCreate(&e0)) != hipSuccess) return (int)e;
-    if ((e = hipEventCreate(&e1)) != hipSuccess) { (void)hipEventDestroy(e0); return (int)e; }
-    int rc = QT_OK;
-    (void)hipEventRecord(e0, st);
-    for (int i = 0; i < iters && rc == QT_OK; ++i) {
-        const size_t off = (size_t)(i % pool_count) * pool_stride;
-        rc = qt_fake_quant_bf16_fp8(x + off, y ? y + off : nullptr, y8 + off, n, fmt, scale, amax, stream);
-    }
-    (void)hipEventRecord(e1, st);
-    e = hipEventSynchronize(e1);
-    float ms = 0.0f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (rc != QT_OK) return rc;
-    if (e != hipSuccess) return (int)e;
-    *ms_out = ms / (float)iters;
-    return QT_OK;
+    return bench_calls(iters, pool_stride, pool_count, stream, ms_out,
+                       [&](size_t off) { return qt_fake_quant_bf16_fp8(x + off, y ? y + off : nullptr, y8 + off, n, fmt, scale, amax, stream); });
 }
 
 }  // extern "C"

@@ -388,13 +388,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_fq_kernel(GemmArgs g) {
 
 template <int BMODE, bool OBS_B, bool B_NN>
 int launch_one(const GemmArgs &g, int batches, hipStream_t st) {
-    static bool attr_set = false;   // per instantiation; idempotent, so a race is harmless
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void *)gemm_fq_kernel<BMODE, OBS_B, B_NN>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        if (e != hipSuccess) return (int)e;
-        attr_set = true;
-    }
+    if (const int rc = qt_allow_lds<gemm_fq_kernel<BMODE, OBS_B, B_NN>>(kLdsBytes)) return rc;
     dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, batches);
     gemm_fq_kernel<BMODE, OBS_B, B_NN><<<grid, kThreads, kLdsBytes, st>>>(g);
     return qt_launch_status();

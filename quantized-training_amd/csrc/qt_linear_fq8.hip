@@ -913,12 +913,7 @@ __global__ __launch_bounds__(512, 1) void linear_fq8r_kernel(Args a) {
 template <int FX, int FW, int NB, bool PAIR = false>
 int launch_r_nb(const Args &a, hipStream_t st) {
     constexpr int kLds = LinearFq8R<FX, FW, NB, PAIR>::kLds;
-    static QtOncePerDevice configured;      
-    if (configured.needed()) {
-        const hipError_t e = hipFuncSetAttribute((const void *)linear_fq8r_kernel<FX, FW, NB, PAIR>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
-        if (e != hipSuccess) return (int)e;
-        configured.done();
-    }
+    if (const int rc = qt_allow_lds<linear_fq8r_kernel<FX, FW, NB, PAIR>>(kLds)) return rc;
     linear_fq8r_kernel<FX, FW, NB, PAIR><<<a.tiles_m * a.tiles_n, 512, kLds, st>>>(a);
     return qt_launch_status();
 }
@@ -926,12 +921,7 @@ int launch_r_nb(const Args &a, hipStream_t st) {
 template <int FX, int FW>
 int launch_r2(const Args &a, hipStream_t st) {
     constexpr int kLds = LinearFq8R2<FX, FW>::kLds;
-    static QtOncePerDevice configured;      
-    if (configured.needed()) {
-        const hipError_t e = hipFuncSetAttribute((const void *)linear_fq8r2_kernel<FX, FW>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
-        if (e != hipSuccess) return (int)e;
-        configured.done();
-    }
+    if (const int rc = qt_allow_lds<linear_fq8r2_kernel<FX, FW>>(kLds)) return rc;
     linear_fq8r2_kernel<FX, FW><<<a.tiles_m * a.tiles_n, 512, kLds, st>>>(a);
     return qt_launch_status();
 }

@@ -730,12 +730,7 @@ __global__ __launch_bounds__(512, 1) void linear_fqt_kernel(Args a) {
 template <int TM, int NB, bool SROWS, int STAMPS = 0>
 int launch_one(const Args &a, hipStream_t st) {
     constexpr int kLds = LinearFqt<TM, NB, SROWS>::kLds;
-    static QtOncePerDevice configured;      
-    if (configured.needed()) {
-        const hipError_t e = hipFuncSetAttribute((const void *)linear_fqt_kernel<TM, NB, SROWS, STAMPS>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
-        if (e != hipSuccess) return (int)e;
-        configured.done();
-    }
+    if (const int rc = qt_allow_lds<linear_fqt_kernel<TM, NB, SROWS, STAMPS>>(kLds)) return rc;
     linear_fqt_kernel<TM, NB, SROWS, STAMPS><<<a.tiles_m * a.tiles_n * a.ksplit, 512, kLds, st>>>(a);
     return qt_launch_status();
 }

@@ -11,6 +11,7 @@
 
 #include "../../include/qt_hip.h"
 #include "qt_device.h"
+#include "qt_dispatch.h"
 #include "qt_formats.h"
 #include "qt_value_codes.h"
 #include "qt_value_rows.h"
@@ -544,9 +545,7 @@ __global__ __launch_bounds__(256) void gelu_kernel(const uint4 *__restrict__ x, 
 
 template <int G, bool ADD, int NV>
 void launch_layernorm_nv(const LnArgs &a, int fq, unsigned blocks, hipStream_t st) {
-    if (fq == 2) layernorm_kernel<G, 2, ADD, NV><<<blocks, 256, 0, st>>>(a);
-    else if (fq == 1) layernorm_kernel<G, 1, ADD, NV><<<blocks, 256, 0, st>>>(a);
-    else layernorm_kernel<G, 0, ADD, NV><<<blocks, 256, 0, st>>>(a);
+    qt_pick<0, 1, 2>(fq, [&](auto FQ) { layernorm_kernel<G, decltype(FQ)::value, ADD, NV><<<blocks, 256, 0, st>>>(a); });
 }
 
 template <int G, bool ADD>
@@ -717,16 +716,13 @@ int qt_rmsnorm_fq8_bf16(const uint16_t *x, const uint16_t *weight, uint16_t *y, 
     if (rows * cols == 0) return QT_OK;
     const int f8 = qt_fp8_code(fmt);
     if (!x || !weight || !y8 || !f8 || rows < 0 || cols < 0) return QT_ERR_BAD_ARG;       // y NULL: codes only
-    const bool e5m2 = f8 == 2;
     if (cols % 8 || cols > (long)kNormThreads * kNormMaxVec * 8 || (((uintptr_t)x | (uintptr_t)weight | (uintptr_t)y) & 15u) ||
         ((uintptr_t)y8 & 7u))
         return QT_ERR_UNALIGNED;
-    if (e5m2)
-        launch_rms<2, false, 0>((unsigned)rows, (int)(cols / 8), (hipStream_t)stream, (const uint4 *)x, (const uint4 *)weight, (uint4 *)y,
-                                                                                    (int)(cols / 8), 1.0f / (float)cols, eps, (uint2 *)y8, *fmt);
-    else
-        launch_rms<1, false, 0>((unsigned)rows, (int)(cols / 8), (hipStream_t)stream, (const uint4 *)x, (const uint4 *)weight, (uint4 *)y,
-                                                                                    (int)(cols / 8), 1.0f / (float)cols, eps, (uint2 *)y8, *fmt);
+    qt_pick<1, 2>(f8, [&](auto FQ) {                                  // 1 E4M3, 2 E5M2
+        launch_rms<decltype(FQ)::value, false, 0>((unsigned)rows, (int)(cols / 8), (hipStream_t)stream, (const uint4 *)x, (const uint4 *)weight, (uint4 *)y,
+                                                  (int)(cols / 8), 1.0f / (float)cols, eps, (uint2 *)y8, *fmt);
+    });
     return qt_launch_status();
 }
 
@@ -743,9 +739,10 @@ int qt_add_rmsnorm_bf16(const uint16_t *x, const uint16_t *residual, const uint1
     const int nvec = (int)(cols / 8);
     const float inv = 1.0f / (float)cols;
     const qt_format f = fq ? *fmt : qt_format{};
-    if (fq == 2) launch_rms<2, true, 0>((unsigned)rows, nvec, st, (const uint4 *)x, (const uint4 *)weight, (uint4 *)y, nvec, inv, eps, (uint2 *)y8, f, (const uint4 *)residual, (uint4 *)sum);
-    else if (fq == 1) launch_rms<1, true, 0>((unsigned)rows, nvec, st, (const uint4 *)x, (const uint4 *)weight, (uint4 *)y, nvec, inv, eps, (uint2 *)y8, f, (const uint4 *)residual, (uint4 *)sum);
-    else launch_rms<0, true, 0>((unsigned)rows, nvec, st, (const uint4 *)x, (const uint4 *)weight, (uint4 *)y, nvec, inv, eps, nullptr, f, (const uint4 *)residual, (uint4 *)sum);
+    qt_pick<0, 1, 2>(fq, [&](auto FQ) {                               // (fq 0: y8 is NULL)
+        launch_rms<decltype(FQ)::value, true, 0>((unsigned)rows, nvec, st, (const uint4 *)x, (const uint4 *)weight, (uint4 *)y, nvec, inv, eps, (uint2 *)y8, f,
+                                                 (const uint4 *)residual, (uint4 *)sum);
+    });
     return qt_launch_status();
 }
 
@@ -763,9 +760,10 @@ int qt_add_rmsnorm_sumfq_bf16(const uint16_t *x, const uint16_t *residual, const
     const int nvec = (int)(cols / 8);
     const float inv = 1.0f / (float)cols;
     const qt_format f = fq ? *fmt : qt_format{};
-    if (fq == 2) launch_rms<2, true, 0>((unsigned)rows, nvec, st, (const uint4 *)x, (const uint4 *)weight, (uint4 *)y, nvec, inv, eps, (uint2 *)y8, f, (const uint4 *)residual, (uint4 *)sum, NormExtra{}, sfq, *sum_fmt);
-    else if (fq == 1) launch_rms<1, true, 0>((unsigned)rows, nvec, st, (const uint4 *)x, (const uint4 *)weight, (uint4 *)y, nvec, inv, eps, (uint2 *)y8, f, (const uint4 *)residual, (uint4 *)sum, NormExtra{}, sfq, *sum_fmt);
-    else launch_rms<0, true, 0>((unsigned)rows, nvec, st, (const uint4 *)x, (const uint4 *)weight, (uint4 *)y, nvec, inv, eps, nullptr, f, (const uint4 *)residual, (uint4 *)sum, NormExtra{}, sfq, *sum_fmt);
+    qt_pick<0, 1, 2>(fq, [&](auto FQ) {                               // (fq 0: y8 is NULL)
+        launch_rms<decltype(FQ)::value, true, 0>((unsigned)rows, nvec, st, (const uint4 *)x, (const uint4 *)weight, (uint4 *)y, nvec, inv, eps, (uint2 *)y8, f,
+                                                 (const uint4 *)residual, (uint4 *)sum, NormExtra{}, sfq, *sum_fmt);
+    });
     return qt_launch_status();
 }
 
@@ -792,17 +790,14 @@ int qt_rmsnorm_consumers_bf16(const uint16_t *x, const uint16_t *residual, const
     hipStream_t st = (hipStream_t)stream;
     const int nvec = (int)(cols / 8);
     const float inv = 1.0f / (float)cols;
-    const int key = (code[0] == 2 ? 4 : 0) | (residual ? 2 : 0) | (consumers == 3 ? 1 : 0);
-    switch (key) {
-        case 0: launch_norm_consumers<1, false, 1>(x, residual, weight, sum, y, y8[0], rows, nvec, inv, eps, *fmt[0], ex, st); break;
-        case 1: launch_norm_consumers<1, false, 2>(x, residual, weight, sum, y, y8[0], rows, nvec, inv, eps, *fmt[0], ex, st); break;
-        case 2: launch_norm_consumers<1, true, 1>(x, residual, weight, sum, y, y8[0], rows, nvec, inv, eps, *fmt[0], ex, st); break;
-        case 3: launch_norm_consumers<1, true, 2>(x, residual, weight, sum, y, y8[0], rows, nvec, inv, eps, *fmt[0], ex, st); break;
-        case 4: launch_norm_consumers<2, false, 1>(x, residual, weight, sum, y, y8[0], rows, nvec, inv, eps, *fmt[0], ex, st); break;
-        case 5: launch_norm_consumers<2, false, 2>(x, residual, weight, sum, y, y8[0], rows, nvec, inv, eps, *fmt[0], ex, st); break;
-        case 6: launch_norm_consumers<2, true, 1>(x, residual, weight, sum, y, y8[0], rows, nvec, inv, eps, *fmt[0], ex, st); break;
-        default: launch_norm_consumers<2, true, 2>(x, residual, weight, sum, y, y8[0], rows, nvec, inv, eps, *fmt[0], ex, st); break;
-    }
+    qt_pick<1, 2>(code[0], [&](auto FQ) {
+        qt_pick_bool(residual != nullptr, [&](auto ADD) {
+            qt_pick<1, 2>(consumers - 1, [&](auto EXTRA) {
+                launch_norm_consumers<decltype(FQ)::value, decltype(ADD)::value, decltype(EXTRA)::value>(x, residual, weight, sum, y, y8[0], rows, nvec, inv, eps,
+                                                                                                      *fmt[0], ex, st);
+            });
+        });
+    });
     return qt_launch_status();
 }
 
@@ -871,9 +866,10 @@ int qt_gelu_bf16(const uint16_t *x, uint16_t *y, uint8_t *y8, size_t n, const qt
     size_t blocks = (nvec + 255) / 256;
     if (blocks > 256 * 32) blocks = 256 * 32;
     hipStream_t st = (hipStream_t)stream;
-    if (fq == 2) gelu_kernel<2><<<(unsigned)blocks, 256, 0, st>>>((const uint4 *)x, (uint4 *)y, (uint2 *)y8, nvec, *fmt);
-    else if (fq == 1) gelu_kernel<1><<<(unsigned)blocks, 256, 0, st>>>((const uint4 *)x, (uint4 *)y, (uint2 *)y8, nvec, *fmt);
-    else gelu_kernel<0><<<(unsigned)blocks, 256, 0, st>>>((const uint4 *)x, (uint4 *)y, nullptr, nvec, qt_format{});
+    const qt_format f = fq ? *fmt : qt_format{};
+    qt_pick<0, 1, 2>(fq, [&](auto FQ) {                               // (fq 0: y8 is NULL)
+        gelu_kernel<decltype(FQ)::value><<<(unsigned)blocks, 256, 0, st>>>((const uint4 *)x, (uint4 *)y, (uint2 *)y8, nvec, f);
+    });
     return qt_launch_status();
 }
 
@@ -898,19 +894,16 @@ int qt_silu_mul_fq8_bf16(const uint16_t *gate, const uint16_t *up, uint16_t *y, 
     if (n == 0) return QT_OK;
     const int f8 = qt_fp8_code(fmt);
     if (!gate || !up || !y || !y8 || !f8 || gate_row_stride < cols || up_row_stride < cols) return QT_ERR_BAD_ARG;
-    const bool e5m2 = f8 == 2;
     if ((cols & 7) || ((gate_row_stride | up_row_stride) & 7) || (((uintptr_t)gate | (uintptr_t)up | (uintptr_t)y) & 15u) ||
         ((uintptr_t)y8 & 7u))
         return QT_ERR_UNALIGNED;
     const size_t nvec = n / 8;
     size_t blocks = (nvec + 255) / 256;
     if (blocks > 256 * 32) blocks = 256 * 32;
-    if (e5m2)
-        silu_mul_fq8_kernel<true><<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>((const uint4 *)gate, (const uint4 *)up, (uint4 *)y, (uint2 *)y8, nvec, *fmt,
-                                                                                     cols / 8, gate_row_stride / 8, up_row_stride / 8);
-    else
-        silu_mul_fq8_kernel<false><<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>((const uint4 *)gate, (const uint4 *)up, (uint4 *)y, (uint2 *)y8, nvec, *fmt,
-                                                                                      cols / 8, gate_row_stride / 8, up_row_stride / 8);
+    qt_pick_bool(f8 == 2, [&](auto E5M2) {
+        silu_mul_fq8_kernel<decltype(E5M2)::value><<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>((const uint4 *)gate, (const uint4 *)up, (uint4 *)y, (uint2 *)y8, nvec,
+                                                                                                      *fmt, cols / 8, gate_row_stride / 8, up_row_stride / 8);
+    });
     return qt_launch_status();
 }
 

@@ -19,6 +19,7 @@
 
 #include "../../include/qt_hip.h"
 #include "qt_device.h"
+#include "qt_dispatch.h"
 #include "qt_formats.h"
 #include "qt_mx.h"
 
@@ -1094,12 +1095,7 @@ template <int FA, int FB, int TM, int NBP>
 int launch_wide_nbp(const MxGemmArgs &g, const WideGeom &geo, long batch, hipStream_t st) {
     constexpr int kLds = MxWide<FA, FB, TM, NBP>::kLds;
     static_assert(kLds <= 160 * 1024, "LDS rings of the wide kernel exceed a CU's 160 KiB");
-    static QtOncePerDevice configured;      
-    if (configured.needed()) {
-        const hipError_t e = hipFuncSetAttribute((const void *)mx_gemm_wide_kernel<FA, FB, TM, NBP>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
-        if (e != hipSuccess) return (int)e;
-        configured.done();
-    }
+    if (const int rc = qt_allow_lds<mx_gemm_wide_kernel<FA, FB, TM, NBP>>(kLds)) return rc;
     mx_gemm_wide_kernel<FA, FB, TM, NBP><<<dim3((unsigned)(geo.tiles_m * geo.tiles_n), (unsigned)batch), 512, kLds, st>>>(g, geo);
     return qt_launch_status();
 }
@@ -1117,6 +1113,32 @@ int launch_wide(const MxGemmArgs &g, const WideGeom &geo, long batch, hipStream_
     if (nbp == 2) return launch_wide_nbp<FA, FB, 128, 2>(g, geo, batch, st);
     if (nbp == 3) return launch_wide_nbp<FA, FB, 128, 3>(g, geo, batch, st);
     return launch_wide_nbp<FA, FB, 128, 4>(g, geo, batch, st);
+}
+
+// The element-format pairs with a kernel, for the 256 x 256, the LDS-DMA and the plain 128 x 128 kernels alike.
+using MxPairs = qt_pairs<qt_pair<0, 0>, qt_pair<0, 1>, qt_pair<1, 0>, qt_pair<1, 1>, qt_pair<2, 2>, qt_pair<3, 3>, qt_pair<4, 4>, qt_pair<0, 4>,
+                         qt_pair<2, 4>, qt_pair<3, 4>>;
+
+template <int FA, int FB>
+int launch_big(const MxGemmArgs &g, long big_tiles, long batch, hipStream_t st) {
+    mx_gemm_big_kernel<FA, FB><<<dim3((unsigned)big_tiles, (unsigned)batch), 512, 0, st>>>(g);
+    return qt_launch_status();
+}
+
+template <int FA, int FB>
+int launch_dma(const MxGemmArgs &g, dim3 grid, bool ring, hipStream_t st) {
+    constexpr int kLds = Tile<FA>::kBytes + Tile<FB>::kBytes + 1024;
+    if (ring) mx_gemm_dma_kernel<FA, FB, 2><<<grid, 256, 0, st>>>(g);              // static LDS, one object per stage
+    else mx_gemm_dma_kernel<FA, FB, 1><<<grid, 256, kLds, st>>>(g);
+    return qt_launch_status();
+}
+
+template <int FA, int FB>
+int launch_plain(const MxGemmArgs &g, dim3 grid, hipStream_t st) {
+    constexpr int kLds = 2 * Tile<FA>::kBytes + 2 * Tile<FB>::kBytes;
+    if (const int rc = qt_allow_lds<mx_gemm_kernel<FA, FB>>(kLds)) return rc;
+    mx_gemm_kernel<FA, FB><<<grid, 256, kLds, st>>>(g);
+    return qt_launch_status();
 }
 
 // ---- packing: (values, block scales) -> element codes + E8M0 ------------------------------------------------
@@ -1231,44 +1253,12 @@ int qt_mx_gemm(const uint8_t *a_codes, const uint8_t *a_e8m0, int a_format, cons
         if (a_format == 1 && b_format == 0) return launch_wide<1, 0>(g, geo, batch, st);
         return launch_wide<1, 1>(g, geo, batch, st);
     }
-#define QT_MX_BIG(FA, FB)                                                                                          \
-    if (big && a_format == FA && b_format == FB) {                                                                 \
-        const dim3 bgrid((unsigned)big_tiles, (unsigned)batch);                                                    \
-        mx_gemm_big_kernel<FA, FB><<<bgrid, 512, 0, st>>>(g);                                                      \
-        return qt_launch_status();                                                                                 \
-    }
-    QT_MX_BIG(0, 0) QT_MX_BIG(0, 1) QT_MX_BIG(1, 0) QT_MX_BIG(1, 1) QT_MX_BIG(4, 4) QT_MX_BIG(0, 4)
-    QT_MX_BIG(2, 2) QT_MX_BIG(3, 3) QT_MX_BIG(2, 4) QT_MX_BIG(3, 4)
-#undef QT_MX_BIG
-#define QT_MX_DMA(FA, FB)                                                                                          \
-    if (dma_ok && a_format == FA && b_format == FB) {                                                              \
-        constexpr int kLds = Tile<FA>::kBytes + Tile<FB>::kBytes + 1024;                                           \
-        if (ring) {                                                                                                \
-            mx_gemm_dma_kernel<FA, FB, 2><<<grid, 256, 0, st>>>(g);              /* static LDS, one object per stage */ \
-        } else {                                                                                                   \
-            mx_gemm_dma_kernel<FA, FB, 1><<<grid, 256, kLds, st>>>(g);                                             \
-        }                                                                                                          \
-        return qt_launch_status();                                                                                 \
-    }
-    QT_MX_DMA(0, 0) QT_MX_DMA(0, 1) QT_MX_DMA(1, 0) QT_MX_DMA(1, 1) QT_MX_DMA(4, 4) QT_MX_DMA(0, 4)
-    QT_MX_DMA(2, 2) QT_MX_DMA(3, 3) QT_MX_DMA(2, 4) QT_MX_DMA(3, 4)
-#undef QT_MX_DMA
-#define QT_MX(FA, FB)                                                                                              \
-    if (a_format == FA && b_format == FB) {                                                                        \
-        constexpr int kLds = 2 * Tile<FA>::kBytes + 2 * Tile<FB>::kBytes;                                          \
-        static QtOncePerDevice configured;                                                                                  \
-        if (configured.needed()) {                                                                                         \
-            const hipError_t e = hipFuncSetAttribute((const void *)mx_gemm_kernel<FA, FB>,                         \
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, kLds);            \
-            if (e != hipSuccess) return (int)e;                                                                    \
-            configured.done();                                                                                      \
-        }                                                                                                          \
-        mx_gemm_kernel<FA, FB><<<grid, 256, kLds, st>>>(g);                                                        \
-        return qt_launch_status();                                                                                 \
-    }
-    QT_MX(0, 0) QT_MX(0, 1) QT_MX(1, 0) QT_MX(1, 1) QT_MX(2, 2) QT_MX(3, 3) QT_MX(4, 4) QT_MX(0, 4) QT_MX(2, 4) QT_MX(3, 4)
-#undef QT_MX
-    return QT_ERR_BAD_DTYPE;          // element-format pair without a kernel: caller dequantizes
+    int rc = QT_ERR_BAD_DTYPE;        // element-format pair without a kernel: caller dequantizes
+    qt_pick_pair(MxPairs{}, a_format, b_format, [&](auto P) {
+        constexpr int FA = decltype(P)::a, FB = decltype(P)::b;
+        rc = big ? launch_big<FA, FB>(g, big_tiles, batch, st) : (dma_ok ? launch_dma<FA, FB>(g, grid, ring, st) : launch_plain<FA, FB>(g, grid, st));
+    });
+    return rc;
 }
 
 
@@ -1301,12 +1291,7 @@ int qt_q8_gemm(const int8_t *a_codes, const int8_t *b_codes, void *c_dev, int c_
         return qt_launch_status();
     }
     constexpr int kLds = 4 * Tile<0>::kBytes;
-    static QtOncePerDevice configured;      
-    if (configured.needed()) {
-        const hipError_t e = hipFuncSetAttribute((const void *)mx_gemm_kernel<0, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
-        if (e != hipSuccess) return (int)e;
-        configured.done();
-    }
+    if (const int rc = qt_allow_lds<mx_gemm_kernel<0, 0, true>>(kLds)) return rc;
     mx_gemm_kernel<0, 0, true><<<grid, 256, kLds, st>>>(g);
     return qt_launch_status();
 }

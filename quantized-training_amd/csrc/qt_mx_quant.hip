@@ -15,6 +15,7 @@
 
 #include "../../include/qt_hip.h"
 #include "qt_device.h"
+#include "qt_dispatch.h"
 #include "qt_formats.h"
 #include "qt_mx.h"
 #include "qt_mx_log2_tables.h"
@@ -236,15 +237,19 @@ __global__ __launch_bounds__(LDS_TABLE ? 1024 : 256) void quantize_mx_kernel(MxQ
     }
 }
 
-int num_cus() {
-    static int n = 0;
-    if (!n) {
-        int dev = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) n = p.multiProcessorCount;
-        if (n <= 0) n = 256;
+template <int IO, int PB>
+int launch_pb(const MxQuantArgs &a, bool rowform, bool lds, hipStream_t st) {
+    const size_t want = (a.nvec + 255) / 256, cap = (size_t)qt_cu_count() * 32;
+    const unsigned grid = (unsigned)(want < cap ? want : cap);
+    if (rowform) {                               // (8 workgroups per CU measured slower: 3.6 against 4.4 TB/s)
+        quantize_mx_kernel<IO, false, PB, true><<<grid, 256, 0, st>>>(a);
+    } else if (lds) {
+        if (const int rc = qt_allow_lds<quantize_mx_kernel<IO, true, PB>>(65536 * 2)) return rc;
+        quantize_mx_kernel<IO, true, PB><<<(unsigned)qt_cu_count(), 1024, 65536 * 2, st>>>(a);
+    } else {
+        quantize_mx_kernel<IO, false, PB><<<grid, 256, 0, st>>>(a);
     }
-    return n;
+    return qt_launch_status();
 }
 
 template <int IO>
@@ -266,29 +271,9 @@ int launch(const void *x, void *q, void *sf, uint8_t *codes, uint8_t *e8m0, size
     const bool rowform = a.lut && (fmt->p1 & 1) && (((uintptr_t)a.lut) & 15u) == 0;
     const bool lds = !rowform && a.lut && rows * cols >= ((size_t)1 << 22) && (((uintptr_t)a.lut) & 15u) == 0;
     hipStream_t st = (hipStream_t)stream;
-#define QT_MXQ(PB)                                                                                                 \
-    if (pb == PB) {                                                                                                \
-        if (rowform) {                               /* (8 workgroups per CU measured slower: 3.6 against 4.4 TB/s) */     \
-            size_t want = (a.nvec + 255) / 256, cap = (size_t)num_cus() * 32;                                      \
-            quantize_mx_kernel<IO, false, PB, true><<<(unsigned)(want < cap ? want : cap), 256, 0, st>>>(a);       \
-        } else if (lds) {                                                                                              \
-            static QtOncePerDevice configured;                                                                              \
-            if (configured.needed()) {                                                                                     \
-                const hipError_t e = hipFuncSetAttribute((const void *)quantize_mx_kernel<IO, true, PB>,           \
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, 65536 * 2);   \
-                if (e != hipSuccess) return (int)e;                                                                \
-                configured.done();                                                                                  \
-            }                                                                                                      \
-            quantize_mx_kernel<IO, true, PB><<<(unsigned)num_cus(), 1024, 65536 * 2, st>>>(a);                     \
-        } else {                                                                                                   \
-            size_t want = (a.nvec + 255) / 256, cap = (size_t)num_cus() * 32;                                      \
-            quantize_mx_kernel<IO, false, PB><<<(unsigned)(want < cap ? want : cap), 256, 0, st>>>(a);             \
-        }                                                                                                          \
-        return qt_launch_status();                                                                                 \
-    }
-    QT_MXQ(0) QT_MXQ(8) QT_MXQ(6) QT_MXQ(4)
-#undef QT_MXQ
-    return QT_ERR_BAD_ARG;
+    int rc = QT_ERR_BAD_ARG;
+    qt_pick<0, 8, 6, 4>(pb, [&](auto PB) { rc = launch_pb<IO, decltype(PB)::value>(a, rowform, lds, st); });
+    return rc;
 }
 
 }  // namespace

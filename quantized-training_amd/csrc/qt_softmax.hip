@@ -20,6 +20,7 @@
 
 #include "qt_device.h"
 #include "qt_chain.h"
+#include "qt_dispatch.h"
 
 namespace {
 
@@ -302,13 +303,7 @@ template <int KIND>
 int launch_softmax(const SoftmaxArgs &a, hipStream_t st) {
     const long nvec_row = a.cols / 8;
     const int nv = (int)((nvec_row + 63) / 64);
-    static int cus = 0;      // queried once (never inside a stream capture after the first call)
-    if (cus == 0) {
-        int dev = 0;
-        hipDeviceProp_t p;
-        cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0)
-                  ? p.multiProcessorCount : 256;
-    }
+    const int cus = qt_cu_count();      // queried once (never inside a stream capture after the first call)
     long want = (a.rows + 3) / 4;
     long cap = (long)cus * (a.amax ? 3 : 16);       // observed (a training step): one amax atomic per workgroup, so fewer, longer workgroups
     unsigned grid = (unsigned)(want < cap ? want : cap);
@@ -332,6 +327,13 @@ int launch_softmax(const SoftmaxArgs &a, hipStream_t st) {
     return qt_launch_status();
 }
 
+// Rows or table, every kind of the ABI
+int launch_softmax_fmt(const SoftmaxArgs &a, hipStream_t st) {
+    int rc = QT_ERR_BAD_ARG;
+    qt_pick_kind<kFmtRows, QT_FMT_LUT, QT_FMT_FP_SAT, QT_FMT_INT, QT_FMT_IDENTITY>(a.fmt, [&](auto K) { rc = launch_softmax<decltype(K)::value>(a, st); });
+    return rc;
+}
+
 }  // namespace
 
 extern "C" int qt_softmax_fq_bf16(const uint16_t *scores, const uint16_t *mask, uint16_t *out, long batch, int heads,
@@ -347,14 +349,7 @@ extern "C" int qt_softmax_fq_bf16(const uint16_t *scores, const uint16_t *mask, 
         (mask && ((mask_sb | mask_sh | mask_sq) & 7)))
         return QT_ERR_UNALIGNED;
     SoftmaxArgs a{scores, mask, out, rows, cols, heads, q_len, mask_sb, mask_sh, mask_sq, scaling, *fmt, lut, scale, amax, nullptr, 0, nullptr};
-    hipStream_t st = (hipStream_t)stream;
-    switch (fmt->kind) {
-        case QT_FMT_LUT: return (fmt->p1 & 1) ? launch_softmax<kFmtRows>(a, st) : launch_softmax<QT_FMT_LUT>(a, st);
-        case QT_FMT_FP_SAT: return launch_softmax<QT_FMT_FP_SAT>(a, st);
-        case QT_FMT_INT: return launch_softmax<QT_FMT_INT>(a, st);
-        case QT_FMT_IDENTITY: return launch_softmax<QT_FMT_IDENTITY>(a, st);
-        default: return QT_ERR_BAD_ARG;
-    }
+    return launch_softmax_fmt(a, (hipStream_t)stream);
 }
 
 namespace {
@@ -441,14 +436,7 @@ extern "C" int qt_softmax_fq_probs_bf16(const uint16_t *scores, const uint16_t *
         (mask && ((mask_sb | mask_sh | mask_sq) & 7)))
         return QT_ERR_UNALIGNED;
     SoftmaxArgs a{scores, mask, out, rows, cols, heads, q_len, mask_sb, mask_sh, mask_sq, scaling, *fmt, lut, scale, amax, nullptr, 0, probs_dev};
-    hipStream_t st = (hipStream_t)stream;
-    switch (fmt->kind) {
-        case QT_FMT_LUT: return (fmt->p1 & 1) ? launch_softmax<kFmtRows>(a, st) : launch_softmax<QT_FMT_LUT>(a, st);
-        case QT_FMT_FP_SAT: return launch_softmax<QT_FMT_FP_SAT>(a, st);
-        case QT_FMT_INT: return launch_softmax<QT_FMT_INT>(a, st);
-        case QT_FMT_IDENTITY: return launch_softmax<QT_FMT_IDENTITY>(a, st);
-        default: return QT_ERR_BAD_ARG;
-    }
+    return launch_softmax_fmt(a, (hipStream_t)stream);
 }
 
 namespace {
@@ -479,18 +467,11 @@ extern "C" int qt_softmax_backward_chain_bf16(const uint16_t *grad_probs_dev, co
     if (((uintptr_t)grad_probs_dev | (uintptr_t)probs_dev | (uintptr_t)grad_scores_dev) & 15u) return QT_ERR_UNALIGNED;
     SoftmaxBwdArgs a{};
     a.dp = grad_probs_dev; a.p = probs_dev; a.ds = grad_scores_dev; a.rows = rows; a.cols = cols; a.scaling = scaling;
-    for (int i = 0; i < nstage; ++i) {
-        if (stages[i].src >= i || stages[i].src < -1) return QT_ERR_BAD_ARG;
-        if ((uintptr_t)stages[i].out_dev & 15u) return QT_ERR_UNALIGNED;
-        a.st[i] = ChainStageDev{stages[i].scale_f32_dev, stages[i].amax_bits_dev, (uint4 *)stages[i].out_dev, stages[i].src};
-    }
+    if (const int rc = chain_stage_args(stages, nstage, a.st)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    switch (fmt->kind) {
-        case QT_FMT_LUT:
-            if (!lut_dev || !(fmt->p1 & 1)) return QT_ERR_BAD_DTYPE;
-            return nstage == 1 ? launch_softmax_bwd<kFmtRows, 1>(a, *fmt, lut_dev, st) : launch_softmax_bwd<kFmtRows, 2>(a, *fmt, lut_dev, st);
-        case QT_FMT_FP_SAT: return nstage == 1 ? launch_softmax_bwd<QT_FMT_FP_SAT, 1>(a, *fmt, lut_dev, st) : launch_softmax_bwd<QT_FMT_FP_SAT, 2>(a, *fmt, lut_dev, st);
-        case QT_FMT_INT: return nstage == 1 ? launch_softmax_bwd<QT_FMT_INT, 1>(a, *fmt, lut_dev, st) : launch_softmax_bwd<QT_FMT_INT, 2>(a, *fmt, lut_dev, st);
-        default: return QT_ERR_BAD_DTYPE;
-    }
+    int rc = QT_ERR_BAD_DTYPE;
+    qt_pick_kind_rows<kFmtRows, QT_FMT_FP_SAT, QT_FMT_INT>(*fmt, lut_dev, [&](auto K) {
+        qt_pick<1, 2>(nstage, [&](auto NS) { rc = launch_softmax_bwd<decltype(K)::value, decltype(NS)::value>(a, *fmt, lut_dev, st); });
+    });
+    return rc;
 }

@@ -13,6 +13,7 @@
 
 #include "qt_device.h"
 #include "qt_chain.h"
+#include "qt_dispatch.h"
 
 namespace {
 
@@ -68,16 +69,6 @@ __global__ __launch_bounds__(kFanBlock) void fanin_kernel(FaninArgs a, qt_format
     chain_amax_commit<N, kFanBlock>(a.st, amax, s_amax);
 }
 
-template <int KIND>
-void launch_n(const FaninArgs &a, int n, unsigned grid, const qt_format &fmt, const uint16_t *lut, hipStream_t st) {
-    switch (n) {
-        case 1: fanin_kernel<KIND, 1><<<grid, kFanBlock, 0, st>>>(a, fmt, lut); break;
-        case 2: fanin_kernel<KIND, 2><<<grid, kFanBlock, 0, st>>>(a, fmt, lut); break;
-        case 3: fanin_kernel<KIND, 3><<<grid, kFanBlock, 0, st>>>(a, fmt, lut); break;
-        default: fanin_kernel<KIND, 4><<<grid, kFanBlock, 0, st>>>(a, fmt, lut); break;
-    }
-}
-
 }  // namespace
 
 extern "C" int qt_grad_fanin_bf16(const uint16_t *first_dev, const qt_fanin_item *items, int count, uint16_t *sum_dev, size_t n, const qt_format *fmt,
@@ -99,14 +90,9 @@ extern "C" int qt_grad_fanin_bf16(const uint16_t *first_dev, const qt_fanin_item
     const size_t want = (a.nvec + kFanBlock - 1) / kFanBlock;
     const unsigned grid = (unsigned)(want < 256 ? want : 256);
     hipStream_t st = (hipStream_t)stream;
-    switch (fmt->kind) {
-        case QT_FMT_LUT:
-            if (!lut_dev || !(fmt->p1 & 1)) return QT_ERR_BAD_DTYPE;
-            launch_n<kFmtRows>(a, count, grid, *fmt, lut_dev, st);
-            break;
-        case QT_FMT_FP_SAT: launch_n<QT_FMT_FP_SAT>(a, count, grid, *fmt, lut_dev, st); break;
-        case QT_FMT_INT: launch_n<QT_FMT_INT>(a, count, grid, *fmt, lut_dev, st); break;
-        default: return QT_ERR_BAD_DTYPE;
-    }
+    if (!qt_pick_kind_rows<kFmtRows, QT_FMT_FP_SAT, QT_FMT_INT>(*fmt, lut_dev, [&](auto K) {
+            qt_pick<1, 2, 3, 4>(count, [&](auto N) { fanin_kernel<decltype(K)::value, decltype(N)::value><<<grid, kFanBlock, 0, st>>>(a, *fmt, lut_dev); });
+        }))
+        return QT_ERR_BAD_DTYPE;
     return qt_launch_status();
 }

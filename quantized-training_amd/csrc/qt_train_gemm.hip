@@ -262,12 +262,7 @@ int launch_tile(Args &a, hipStream_t st) {
     constexpr int kLds = Ring<BM, BN>::kStage * kStages;
     static_assert(kLds <= 160 * 1024, "the ring does not fit a CU's LDS");
     if (a.K / kBK < kStages - 1) return QT_ERR_BAD_ARG;
-    static QtOncePerDevice configured;
-    if (configured.needed()) {
-        const hipError_t e = hipFuncSetAttribute((const void *)train_gemm_kernel<TA, TB, BM, BN, SS>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
-        if (e != hipSuccess) return (int)e;
-        configured.done();
-    }
+    if (const int rc = qt_allow_lds<train_gemm_kernel<TA, TB, BM, BN, SS>>(kLds)) return rc;
     a.tiles_m = (a.M + BM - 1) / BM;
     a.tiles_n = (a.N + BN - 1) / BN;
     train_gemm_kernel<TA, TB, BM, BN, SS><<<a.count * a.tiles_m * a.tiles_n, kThreads, kLds, st>>>(a);
@@ -324,12 +319,7 @@ template <int BMW, int BNW>
 int launch_backward(Args &w, Args &d, hipStream_t st) {
     constexpr int kLds = Ring<BMW, BNW>::kBytes > Ring<128, 64>::kBytes ? Ring<BMW, BNW>::kBytes : Ring<128, 64>::kBytes;
     if (w.K / kBK < Ring<BMW, BNW>::kStages - 1 || d.K / kBK < Ring<128, 64>::kStages - 1) return QT_ERR_BAD_ARG;
-    static QtOncePerDevice configured;
-    if (configured.needed()) {
-        const hipError_t e = hipFuncSetAttribute((const void *)train_gemm_backward_kernel<BMW, BNW>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
-        if (e != hipSuccess) return (int)e;
-        configured.done();
-    }
+    if (const int rc = qt_allow_lds<train_gemm_backward_kernel<BMW, BNW>>(kLds)) return rc;
     w.tiles_m = (w.M + BMW - 1) / BMW;
     w.tiles_n = (w.N + BNW - 1) / BNW;
     d.tiles_m = (d.M + 127) / 128;
