@@ -1633,7 +1633,8 @@ int launch_pc(const void *x, void *y, size_t outer, size_t C, size_t inner, cons
     if (outer * C * inner == 0) return QT_OK;
     if (!x || !fmt || (!y && !amax)) return QT_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
-    if (fmt->kind == QT_FMT_LUT && !lut && y) return QT_ERR_BAD_ARG;
+    // also when only observing (y == NULL): the vectorised kernels evaluate the rounder, and with it the map, before they look at y
+    if (fmt->kind == QT_FMT_LUT && !lut) return QT_ERR_BAD_ARG;
     int rc = QT_ERR_BAD_ARG;
     qt_pick<QT_FMT_LUT, QT_FMT_FP_SAT, QT_FMT_INT, QT_FMT_IDENTITY>(
         fmt->kind, [&](auto K) { rc = launch_pc_kind<IO, decltype(K)::value>(x, y, outer, C, inner, *fmt, lut, scale, amax, st); });

@@ -71,6 +71,10 @@ CALLS = {
     "qt_vmap_bf16": (lambda L, f, t: L.qt_vmap_bf16(P, P, 8, f, t, None), ANY_KIND, QT_ERR_BAD_ARG),
     "qt_fake_quant_pc_bf16": (lambda L, f, t: L.qt_fake_quant_pc_bf16(P, P, 1, 1, 8, f, t, None, None, None), ANY_KIND, QT_ERR_BAD_ARG),
     "qt_fake_quant_pc_f32": (lambda L, f, t: L.qt_fake_quant_pc_f32(P, P, 1, 1, 8, f, t, None, None, None), ANY_KIND, QT_ERR_BAD_ARG),
+    # observe only (y NULL, amax given): the vectorised per-channel kernels evaluate the rounder before they look at y, so a table format
+    # needs its table here too
+    "qt_fake_quant_pc_bf16, observe only": (lambda L, f, t: L.qt_fake_quant_pc_bf16(P, None, 1, 1, 8, f, t, None, P, None), ANY_KIND, QT_ERR_BAD_ARG),
+    "qt_fake_quant_pc_f32, observe only": (lambda L, f, t: L.qt_fake_quant_pc_f32(P, None, 1, 1, 8, f, t, None, P, None), ANY_KIND, QT_ERR_BAD_ARG),
     "qt_softmax_fq_bf16": (lambda L, f, t: L.qt_softmax_fq_bf16(P, None, P, 1, 1, 1, 8, 0, 0, 0, 1.0, f, t, None, None, None), ANY_KIND, QT_ERR_BAD_ARG),
     "qt_softmax_fq_probs_bf16": (lambda L, f, t: L.qt_softmax_fq_probs_bf16(P, None, P, P, 1, 1, 1, 8, 0, 0, 0, 1.0, f, t, None, None, None), ANY_KIND,
                                  QT_ERR_BAD_ARG),

@@ -1238,10 +1238,11 @@ def test_rmsnorm_within_bf16_rounding_of_the_torch_chain(nv):
 
 @pytest.mark.parametrize("dtype_name", ["int8", "e4m3", "posit8_1"])
 @pytest.mark.parametrize("tdtype", [torch.bfloat16, torch.float32])
-@pytest.mark.parametrize("shape,axis", [((96, 1024), 0), ((5, 24, 640), 1), ((64, 100), 0)])
+@pytest.mark.parametrize("shape,axis", [((96, 1024), 0), ((5, 24, 640), 1), ((64, 100), 0), ((300, 40), -1), ((6, 700, 512), 1)])
 def test_per_channel_module_device_vs_cpu(nv, dtype_name, tdtype, shape, axis):
     """per_channel_symmetric fake-quant (fake_quantize.py:218-221): rows of whole 16-byte vectors take the vectorised
-    kernel, the last shape the element-wise one; outputs, scales and amax history identical to the CPU formulas."""
+    kernel, (64, 100) the element-wise one, (300, 40) with the channel last the inner == 1 one; (6, 700, 512) has 4200 rows, more than
+    the grid takes in one pass, and six rows per channel; outputs, scales and amax history identical to the CPU formulas."""
     import quantized_training as qt
     from quantized_training.fake_quantize import FusedAmaxObsFakeQuantize
     from quantized_training.quantizer.quantizer import QuantizationSpec
