@@ -638,7 +638,11 @@ int qt_mask_row_live_checked(const uint16_t *mask_dev, long rows, long cols, lon
  * and the kernel applies that without reading the mask (x + 0 = x; bf16(x + min) = min for finite x); mask_irregular_dev (optional): the
  * device-side verdict of qt_mask_row_live_checked, 0 meaning the same.  out: [B][Sq][H][D] bf16;
  * with out8 (+ out_format, an e4m3 / e5m2 closed-form format) the consumer's stateless input fake-quantizer -- the output projection's --
- * is applied on the way out: out = fq(result), out8 its FP8 codes.  Sk % 128 == 0, Sk <= 1024. */
+ * is applied on the way out: out = fq(result), out8 its FP8 codes.  Sk % 128 == 0, Sk <= 1024.
+ * The three output modes: out alone (values, no consumer format); out and out8 (fq(result) and its codes); out8 alone, out == NULL
+ * (CODES ONLY: for a consumer that multiplies the codes -- the values are never written, and they are exactly what the codes decode
+ * to).  Both NULL is QT_ERR_BAD_ARG.  The kernel writes rows 0 .. Sq-1 of out / out8 and nothing else; both leave in 16-byte stores,
+ * so out and out8 must be 16-byte aligned (QT_ERR_UNALIGNED). */
 int qt_value_codes_t(const uint16_t *v_dev, uint8_t *vt8_dev, long B, long H, long Sk, int head_dim, long stride_b, long stride_h, long stride_k,
                      const qt_format *fmt, void *stream);
 int qt_attention_fp8(const uint8_t *q8_dev, const uint8_t *k8_dev, const uint8_t *vt8_dev, int operand_format, const uint16_t *mask_dev,

@@ -42,11 +42,11 @@ struct AttnArgs {
     long lsb, lsh, lsq;
     int mask_simple;                    // the caller vouches: every mask row is exactly 0 up to its row_live entry and the bf16 minimum from
                                         // there on (causal, right padding) -- the mask is then not read at all
-    uint16_t *out;                      // [B][Sq][H][128] bf16
+    uint16_t *out;                      // [B][Sq][H][128] bf16; optional when out8 is given (codes only)
     int H, Sq, Sk;
     float scaling;
     uint8_t *out8;                      // optional: the consumer's (output projection's input) stateless FP8 fake-quantizer applied on the way
-    qt_format out_fmt;                  // out: `out` then holds fq(result), out8 its codes, same layout
+    qt_format out_fmt;                  // out: `out` (when given) then holds fq(result), out8 its codes, same layout
     const int *mask_irregular;          // optional, device: 0 = qt_mask_row_live_checked found every row "zeros, then the minimum" (as mask_simple)
 };
 
@@ -139,6 +139,13 @@ __device__ __forceinline__ void score_half(const uint8_t *blk, int t0, const v8i
         mx = max3(mx, v[2], v[3]);
     }
 }
+
+// The epilogue's use of the block buffers: both groups' parked partial sums ([2][64 rows][D / 2 + 4] fp32), then the finished tile as
+// bf16 values and as codes, rows padded by 16 bytes.  head_dim 128: 34 + 17 + 9 KiB of 128; head_dim 64, MB = 4: 18 + 9 + 5 = all 32 KiB.
+template <int D> constexpr int kTilesAt = 2 * 64 * (D / 2 + 4) * 4;
+template <int D> constexpr int kValRow = 2 * D + 16;
+template <int D> constexpr int kCodeRow = D + 16;
+template <int D> constexpr int kEpilogueLds = kTilesAt<D> + 64 * (kValRow<D> + kCodeRow<D>);
 
 // MB: key blocks of 128 the strip is sized for (8: up to 1024 keys, one workgroup per CU; 4, head_dim 64 only: up to 512 keys -- half the
 // strip registers (113 in all) and a quarter of the LDS, so TWO workgroups share a CU and cover each other's sweeps and barriers:
@@ -330,34 +337,81 @@ __global__ __launch_bounds__(512, (MB == 4 && D == 64) ? 4 : 1) void attention_f
             }
         }
     }
-    // ---- the two partial sums meet in LDS: group 1 parks its accumulators, group 0 adds and stores
+    // ---- the two partial sums meet in LDS, and the finished 64 x D tile leaves through it.  Group 0 finishes d tiles 0 .. kDT/2 - 1,
+    // group 1 the rest: each parks the half of its accumulators the other one finishes and adds the other's half to its own (the sum
+    // of the same two fp32 terms as ever), rounds, and writes its half of the tile -- bf16 values when they are wanted, codes when
+    // they are -- next to the parked sums in the block buffers, which are dead by now.  Then all eight waves store 16 bytes a lane:
+    // a wave's store instruction covers whole 128-byte lines of `out` / `out8`.  Rows padded by 16 bytes (4 floats) spread a wave's
+    // accesses over the banks.
+    constexpr int kHalf = kDT / 2, kPartRow = 16 * kHalf + 4;
     const int prow = wq * 16 + r;
-    split_park_partials(lds, acc, grp, prow, g);
-    if (grp == 0 && qrow < a.Sq) {
+    float *part = (float *)lds;                                            // [2 groups][64 rows][kPartRow]
+    uint8_t *tile_v = lds + kTilesAt<D>, *tile_c = tile_v + 64 * kValRow<D>;
+    v4f fin[kHalf];
+    __syncthreads();                                                       // everyone is through sweep 2
+    {
+        float *mine = part + (grp * 64 + prow) * kPartRow + 4 * g;
+        if (grp == 0) {
 #pragma unroll
-        for (int dt = 0; dt < kDT; ++dt) {
-            const float4 o = split_partial_sums<kDT>(lds, prow, dt, g);
-            acc[dt][0] += o.x; acc[dt][1] += o.y; acc[dt][2] += o.z; acc[dt][3] += o.w;
-        }
-        const long o0 = (((long)b * a.Sq + qrow) * a.H + h) * D + 4 * g;
-        uint16_t *orow = a.out + o0;
-        if (a.out8) {
-            const bool oe5 = a.out_fmt.p0 == 2;
-#pragma unroll
-            for (int dt = 0; dt < kDT; dt += 2) {
-                uint32_t o[4] = {pack_bf16x2(acc[dt][0], acc[dt][1]), pack_bf16x2(acc[dt][2], acc[dt][3]),
-                                 pack_bf16x2(acc[dt + 1][0], acc[dt + 1][1]), pack_bf16x2(acc[dt + 1][2], acc[dt + 1][3])};
-                const uint2 codes = oe5 ? fq8_hw_vec8<true>(o, a.out_fmt) : fq8_hw_vec8<false>(o, a.out_fmt);
-                *(uint2 *)(orow + dt * 16) = uint2{o[0], o[1]};
-                *(uint2 *)(orow + dt * 16 + 16) = uint2{o[2], o[3]};
-                *(uint32_t *)(a.out8 + o0 + dt * 16) = codes.x;
-                *(uint32_t *)(a.out8 + o0 + dt * 16 + 16) = codes.y;
+            for (int j = 0; j < kHalf; ++j) {
+                *(float4 *)(mine + 16 * j) = float4{acc[kHalf + j][0], acc[kHalf + j][1], acc[kHalf + j][2], acc[kHalf + j][3]};
+                fin[j] = acc[j];
             }
         } else {
 #pragma unroll
-            for (int dt = 0; dt < kDT; ++dt)
-                *(uint2 *)(orow + dt * 16) = uint2{pack_bf16x2(acc[dt][0], acc[dt][1]), pack_bf16x2(acc[dt][2], acc[dt][3])};
+            for (int j = 0; j < kHalf; ++j) {
+                *(float4 *)(mine + 16 * j) = float4{acc[j][0], acc[j][1], acc[j][2], acc[j][3]};
+                fin[j] = acc[kHalf + j];
+            }
         }
+    }
+    __syncthreads();
+    {
+        const float *theirs = part + ((1 - grp) * 64 + prow) * kPartRow + 4 * g;
+#pragma unroll
+        for (int j = 0; j < kHalf; ++j) {
+            const float4 o = *(const float4 *)(theirs + 16 * j);
+            fin[j][0] += o.x; fin[j][1] += o.y; fin[j][2] += o.z; fin[j][3] += o.w;
+        }
+    }
+    {
+        const int d0 = grp * (16 * kHalf) + 4 * g;                         // this lane's first column
+        uint8_t *vrow = tile_v + prow * kValRow<D> + 2 * d0, *crow = tile_c + prow * kCodeRow<D> + d0;
+        if (a.out8) {
+            const bool oe5 = a.out_fmt.p0 == 2;
+#pragma unroll
+            for (int j = 0; j < kHalf; j += 2) {
+                uint32_t o[4] = {pack_bf16x2(fin[j][0], fin[j][1]), pack_bf16x2(fin[j][2], fin[j][3]),
+                                 pack_bf16x2(fin[j + 1][0], fin[j + 1][1]), pack_bf16x2(fin[j + 1][2], fin[j + 1][3])};
+                const uint2 codes = oe5 ? fq8_hw_vec8<true>(o, a.out_fmt) : fq8_hw_vec8<false>(o, a.out_fmt);
+                if (a.out) {
+                    *(uint2 *)(vrow + j * 32) = uint2{o[0], o[1]};
+                    *(uint2 *)(vrow + j * 32 + 32) = uint2{o[2], o[3]};
+                }
+                *(uint32_t *)(crow + j * 16) = codes.x;
+                *(uint32_t *)(crow + j * 16 + 16) = codes.y;
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < kHalf; ++j)
+                *(uint2 *)(vrow + j * 32) = uint2{pack_bf16x2(fin[j][0], fin[j][1]), pack_bf16x2(fin[j][2], fin[j][3])};
+        }
+    }
+    __syncthreads();
+    const int rows = min(64, a.Sq - q0);                                   // rows >= Sq are never stored
+    const long orow0 = ((long)b * a.Sq + q0) * a.H + h;                    // row q0 of this head, in rows of D elements; the next is H further
+    if (a.out) {
+        constexpr int kCh = D / 8;                                         // 16-byte chunks of a row of values
+#pragma unroll
+        for (int i = 0; i < 64 * kCh / 512; ++i) {
+            const int c = t + i * 512, row = c / kCh, ch = c % kCh;
+            if (row < rows) *(u32x4 *)((uint8_t *)a.out + (orow0 + (long)row * a.H) * (2 * D) + 16 * ch) = *(const u32x4 *)(tile_v + row * kValRow<D> + 16 * ch);
+        }
+    }
+    if (a.out8) {
+        constexpr int kCh = D / 16;                                        // 16-byte chunks of a row of codes
+        const int row = t / kCh, ch = t % kCh;                             // 64 kCh <= 512: at most one chunk a lane
+        if (row < rows) *(u32x4 *)(a.out8 + (orow0 + (long)row * a.H) * D + 16 * ch) = *(const u32x4 *)(tile_c + row * kCodeRow<D> + 16 * ch);
     }
 }
 
@@ -372,7 +426,7 @@ __global__ __launch_bounds__(256) void value_codes_t_kernel(const uint16_t *v, u
 template <int F, int D, int MB>
 int launch_split_mb(const AttnArgs &a, long BH, int nqb, hipStream_t st) {
     constexpr int kLds = MB * kBlock * D + 2 * 2 * 64 * 4;               // every block of a sweep + the row statistics
-    static_assert(MB * kBlock * D >= 64 * (D + 4) * 4, "the partial sums of the second wave group reuse the block buffers");
+    static_assert(MB * kBlock * D >= kEpilogueLds<D>, "the parked partial sums and the finished tile reuse the block buffers");
     if (qt_allow_lds<attention_fp8_split_kernel<F, D, MB>>(kLds)) return QT_ERR_BAD_ARG;
     attention_fp8_split_kernel<F, D, MB><<<dim3((unsigned)BH, (unsigned)nqb), 512, kLds, st>>>(a);
     return qt_launch_status();
@@ -415,13 +469,14 @@ int qt_attention_fp8(const uint8_t *q8_dev, const uint8_t *k8_dev, const uint8_t
                      int mask_is_simple, const int *mask_irregular_dev, uint16_t *out_dev, uint8_t *out8_dev, const qt_format *out_format, long B,
                      int H, int Sq, int Sk, int head_dim, float scaling, void *stream) {
     if (B * H * Sq == 0) return QT_OK;
-    if (!q8_dev || !k8_dev || !vt8_dev || !out_dev || B < 0 || H < 1 || Sq < 1 || Sk < kBlock || Sk % kBlock != 0 || Sk > kBlock * kMaxBlocks ||
+    if (!q8_dev || !k8_dev || !vt8_dev || (!out_dev && !out8_dev) || B < 0 || H < 1 || Sq < 1 || Sk < kBlock || Sk % kBlock != 0 || Sk > kBlock * kMaxBlocks ||
         B * H > 65535 || operand_format < 0 || operand_format > 1 || (head_dim != 64 && head_dim != 128))
         return QT_ERR_BAD_ARG;
-    if ((((uintptr_t)q8_dev | (uintptr_t)k8_dev | (uintptr_t)vt8_dev) & 15u) || ((uintptr_t)out_dev & 7u) ||
+    if ((((uintptr_t)q8_dev | (uintptr_t)k8_dev | (uintptr_t)vt8_dev) & 15u) || ((uintptr_t)out_dev & 15u) ||
         (mask_dev && ((((uintptr_t)mask_dev) & 7u) || ((mask_sb | mask_sh | mask_sq) & 3))))
         return QT_ERR_UNALIGNED;
-    if (out8_dev && (!qt_fp8_code(out_format) || ((uintptr_t)out8_dev & 3u))) return QT_ERR_BAD_ARG;
+    if (out8_dev && !qt_fp8_code(out_format)) return QT_ERR_BAD_ARG;
+    if ((uintptr_t)out8_dev & 15u) return QT_ERR_UNALIGNED;                 // both results leave in 16-byte stores
     AttnArgs a{q8_dev, k8_dev, vt8_dev, mask_dev, mask_sb, mask_sh, mask_sq, row_live_dev, live_sb, live_sh, live_sq, mask_is_simple ? 1 : 0,
                out_dev, H, Sq, Sk, scaling, out8_dev, out8_dev ? *out_format : qt_format{}, mask_irregular_dev};
     const int nqb = (Sq + 63) / 64;

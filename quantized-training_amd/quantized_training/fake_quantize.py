@@ -786,6 +786,15 @@ class FusedAmaxObsFakeQuantize(FakeQuantizeBase):
                     if handover.is_lazy(X) and not self.__dict__.get("_qt_lazy_ok"):
                         handover.materialize(X)
                     return handover.carry(X, x8, X)           # (lazy when the producer wrote the codes only: this consumer decodes on demand)
+        rec = precomputed.EXPECTED.peek(self) if self.__dict__.get("_qt_lazy_ok") else None
+        if rec is not None and rec.payload[1] is None and handover.lazy_owner(X) is not None:
+            # X is a reshaped view of a tensor whose producer wrote the codes only and left them for this call (the attention core in front
+            # of the output projection): the consumer multiplies the codes, so the view goes through lazy as its owner is -- not decoded.
+            # (Looked at before it is taken: a record with a replacement stays for the branch below.)
+            expect = precomputed.EXPECTED.take(self, X)
+            if expect is not precomputed.MISS:
+                _Stats.add(X.numel())
+                return handover.stamp(X, codes=expect[0].view(X.shape), lazy=True, register=False)
         handover.materialize(X)          # every path below reads X's values: a producer may have written its FP8 codes only
         if (done_by is not None and self._emit_fp8 and isinstance(done_by, FusedAmaxObsFakeQuantize)
                 and handover.codes(X) is not None and X.is_cuda and X.dtype == torch.bfloat16 and X.is_contiguous()

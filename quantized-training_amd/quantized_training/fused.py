@@ -1022,6 +1022,22 @@ def _mask_strides(attention_mask, B, H, Q, C, device, align, no_grad=False):
     return m, sb, sh, sq
 
 
+def attention_output_plan(attn):
+    """What qt_attention_fp8's epilogue does for the consumer of its result: (fq_o, codes_only).  fq_o: the output projection's
+    stateless FP8 input fake-quantizer when the kernel may apply it, else None.  codes_only (model_fusions.codes_only_ok): the projection
+    multiplies the codes and nobody else can see the result -- no hook on the attention module but the package's own context hooks
+    (which is why the module is not handed to codes_only_ok as the producer), none on the projection or its fake-quantizer -- so the
+    kernel writes ONLY the codes and the bf16 tensor stays unwritten (`_qt_lazy`; whoever asks for the values
+    after all gets them decoded: handover.materialize, through HF's reshaped view too)."""
+    from .model_fusions import codes_only_ok, consumer_fq
+    own = getattr(attn, "o_proj", None)
+    proj = own or attn.__dict__.get("_qt_out_proj")                                 # LLaMA's own / BERT's BertSelfOutput.dense
+    fq_o = consumer_fq(proj) if (proj is not None and switches.on("QT_FUSED_PRODUCER_FQ")) else None
+    # (codes only where the projection is the block's own: the result then never leaves the attention module's forward.  BERT's
+    # BertSelfAttention RETURNS it to its parent, which hands it to BertSelfOutput -- it keeps its values)
+    return fq_o, fq_o is not None and own is not None and pc.no_foreign_hooks(attn) and codes_only_ok([proj])
+
+
 def _attention_fp8_or_none(attn, query, key, value, attention_mask, scaling, fqs):
     """qt_attention_fp8: the attention core in one launch on FP8 codes (head_dim 128 or 64, keys in blocks of 128 up to 1024) when the
     four fake-quantizers around the two matmuls are stateless E4M3 / E5M2 ones of one format.  q / k either arrive with their codes (the
@@ -1111,18 +1127,19 @@ def _attention_fp8_or_none(attn, query, key, value, attention_mask, scaling, fqs
                                          ctypes.byref(fmt), st), "qt_value_codes_t")
     STATS.add(value.numel())                                 # fq_v, evaluated by that pass
     STATS.add(B * H * Q * C)                                 # fq_p, evaluated inside the kernel
-    out = torch.empty((B, Q, H, D), dtype=torch.bfloat16, device=query.device)
     # the output projection's stateless FP8 input fake-quantizer rides on the epilogue (as model_fusions.attention_output does for the
     # library-GEMM chain): HF reshapes the result before the projection's hook sees it, so the hand-over is an expectation
-    from .model_fusions import consumer_fq
-    proj = getattr(attn, "o_proj", None) or attn.__dict__.get("_qt_out_proj")       # LLaMA's own / BERT's BertSelfOutput.dense
-    fq_o = consumer_fq(proj) if (proj is not None and switches.on("QT_FUSED_PRODUCER_FQ")) else None
+    fq_o, codes_only = attention_output_plan(attn)
     out8 = torch.empty((B, Q, H, D), dtype=torch.uint8, device=query.device) if fq_o is not None else None
+    shape = (B, Q, H, D)
+    out = handover.unwritten(shape, torch.bfloat16, query.device) if codes_only else torch.empty(shape, dtype=torch.bfloat16, device=query.device)
     _native.check(L.qt_attention_fp8(q8.data_ptr(), k8.data_ptr(), vt8.data_ptr(), 1 if fmt.p0 == 2 else 0,
                                      mask.data_ptr() if mask is not None else None, msb, msh, msq, rl_ptr, lsb, lsh, lsq, 0, irregular_ptr,
-                                     out.data_ptr(), out8.data_ptr() if out8 is not None else None,
+                                     None if codes_only else out.data_ptr(), out8.data_ptr() if out8 is not None else None,
                                      ctypes.byref(fq_o._qt_format) if fq_o is not None else None, B, H, Q, C, D, float(scaling), st),
                   "qt_attention_fp8")
+    if codes_only:
+        handover.stamp(out, fq_o, handover.fp8_view(out8, fq_o), lazy=True)
     if fq_o is not None:
         fq_o.expect_prequantized(out, handover.fp8_view(out8, fq_o))
     return out

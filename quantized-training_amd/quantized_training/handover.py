@@ -132,6 +132,18 @@ def mark_lazy(t):
     return t
 
 
+def lazy_owner(t):
+    """The registered lazy tensor that `t` is a view of (same storage, same extent), or None."""
+    if not _LAZY:
+        return None
+    ref = _LAZY.get(t.data_ptr())
+    base = ref() if ref is not None else None
+    if (base is not None and base is not t and is_lazy(base) and base.device == t.device and base.dtype == t.dtype
+            and base.numel() == t.numel() and t.is_contiguous()):
+        return base
+    return None
+
+
 def materialize(t):
     """A producer that knew its consumer multiplies FP8 codes wrote ONLY the codes of fq(t).  The fake-quantized values are exactly
     what the codes decode to, so whoever asks for them after all gets them here."""
@@ -140,13 +152,10 @@ def materialize(t):
         t._qt_lazy = False
         t._qt_ver = t._version
         return
-    if _LAZY:
-        ref = _LAZY.get(t.data_ptr())
-        base = ref() if ref is not None else None
-        if (base is not None and base is not t and is_lazy(base) and base.device == t.device and base.dtype == t.dtype
-                and base.numel() == t.numel() and t.is_contiguous()):
-            # a view of a lazy tensor (same storage, same extent): decode through the owner
-            stamped = valid(t)
-            materialize(base)
-            if stamped:
-                t._qt_ver = t._version
+    base = lazy_owner(t)
+    if base is not None:
+        # a view of a lazy tensor: decode through the owner
+        stamped = valid(t)
+        materialize(base)
+        if stamped:
+            t._qt_ver = t._version

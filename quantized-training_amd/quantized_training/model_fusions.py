@@ -636,11 +636,13 @@ def apply_bert_fusions(model):
 _CURRENT_ATTN = []
 
 
+@pc.own_hook
 def _attn_enter(module, args, kwargs):
     _CURRENT_ATTN.append(module)
     module.__dict__["_qt_cacheless"] = kwargs.get("past_key_values") is None and kwargs.get("past_key_value") is None
 
 
+@pc.own_hook
 def _attn_exit(module, args, kwargs, output):
     if _CURRENT_ATTN and _CURRENT_ATTN[-1] is module:
         _CURRENT_ATTN.pop()

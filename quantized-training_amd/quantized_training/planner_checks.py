@@ -11,6 +11,18 @@ def no_hooks(mod):
     return not (mod._forward_hooks or mod._forward_pre_hooks or mod._backward_hooks or mod._backward_pre_hooks)
 
 
+def own_hook(fn):
+    """Marks a hook the package itself registers (the context hooks model_fusions and train_fusions keep on an attention block)."""
+    fn._qt_own_hook = True
+    return fn
+
+
+def no_foreign_hooks(mod):
+    """No hook of any kind but the package's own (own_hook): nobody outside the package is handed the module's inputs or its result."""
+    return all(getattr(h, "_qt_own_hook", False)
+               for hooks in (mod._forward_hooks, mod._forward_pre_hooks, mod._backward_hooks, mod._backward_pre_hooks) for h in hooks.values())
+
+
 def no_forward_hooks(mod):
     """No forward hook and no forward pre-hook (backward hooks not looked at): a fake-quantizer somebody hooked runs as the module it is."""
     return not (mod._forward_hooks or mod._forward_pre_hooks)

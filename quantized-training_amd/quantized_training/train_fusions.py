@@ -103,10 +103,12 @@ def put_colsum(g, gb):
 _ATTN_ACTIVE = []         # the self-attention modules whose forward is running (innermost last)
 
 
+@pc.own_hook
 def _attn_enter(module, args, kwargs=None):
     _ATTN_ACTIVE.append(module)
 
 
+@pc.own_hook
 def _attn_leave(module, args, output):
     from .modules.qat.linear import flush_forward
     if _ATTN_ACTIVE and _ATTN_ACTIVE[-1] is module:

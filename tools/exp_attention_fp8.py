@@ -76,6 +76,23 @@ def main():
             print("library route unavailable"); continue
         t1, tc = timeit(one_launch), timeit(chain)
         tv, ta, tn = timeit(vpass_t), timeit(core), timeit(lambda: core(False))
+        # the three output modes of the epilogue: bf16 values alone, fq(values) + their codes (a consumer fake-quantizer on the way out),
+        # codes alone (the consumer multiplies the codes: the 2-byte tensor is never written)
+        out8m = torch.empty(B, S, H, D, dtype=torch.uint8, device=DEV)
+
+        def mode(values, codes):
+            def run():
+                _native.check(L.qt_attention_fp8(q8.data_ptr(), k8.data_ptr(), vt8.data_ptr(), 0, mp, 0, 0, S if mask is not None else 0,
+                                                 live.data_ptr() if live is not None else None, 0, 0, 1, int(live is not None), None,
+                                                 out.data_ptr() if values else None, out8m.data_ptr() if codes else None,
+                                                 ctypes.byref(fmt) if codes else None, B, H, S, S, D, scaling, st()), "attn")
+            return run
+        tm = []
+        for values, codes in ((True, False), (True, True), (False, True)):
+            try:
+                tm.append(f"{timeit(mode(values, codes)):6.1f}")
+            except _native.QtError:
+                tm.append("   n/a")                       # a library from before the codes-only mode refuses out == NULL
         if mask is not None and B == 1 and S == 1024:
             # the call as the model issues it: the output projection's fake-quantizer on the epilogue, the mask's regularity as a device
             # flag; and the same call with a large GEMM-like stream of other work in between (cold caches, sustained clocks)
@@ -111,6 +128,7 @@ def main():
                   f"(GEMM alone {tb:6.1f})", flush=True)
         print(f"B{B} H{H} S{S} D{D} {'causal' if causal else 'no mask'}: one launch {t1:6.1f} us (value codes {tv:5.1f} + core {ta:6.1f}; core without row extents {tn:6.1f})"
               f" | chain {tc:6.1f} us", flush=True)
+        print(f"    core by output mode: values {tm[0]} us | values + codes {tm[1]} us | codes only {tm[2]} us", flush=True)
 
 
 if __name__ == "__main__":
