@@ -268,7 +268,7 @@ def rope_map(q, k, cos, sin, fq_q, fq_k, inner_q=False, inner_k=False, value_job
 
     value_job = (attn, value, fq_v), set when the table-format attention core is what will consume these tensors (_attention_value_plan):
     the launch then also carries that kernel's value pass (qt_rope_map_value) and leaves V^T with the attention module for the core's
-    call (fused.attention_rows_or_none, which counts fq_v's call when it takes it)."""
+    call (attention_route.attention_rows_or_none, which counts fq_v's call when it takes it)."""
     pf = fq_q.map_producer_format(q.device)
     if pf is None or fq_k.map_producer_format(q.device) is None or fq_k.dtype != fq_q.dtype:
         return None
@@ -278,7 +278,6 @@ def rope_map(q, k, cos, sin, fq_q, fq_k, inner_q=False, inner_k=False, value_job
     q_out = torch.empty((B, Hq, S, D), dtype=q.dtype, device=q.device)
     k_out = torch.empty((B, Hk, S, D), dtype=k.dtype, device=k.device)
     if value_job is not None:
-        from . import fused
         attn, value, fq_v = value_job
         vt = torch.empty((B, Hk, D, S), dtype=torch.bfloat16, device=q.device)
         wjob = _o_proj_weight_job(attn, q, fq_q, qmap)
@@ -288,7 +287,7 @@ def rope_map(q, k, cos, sin, fq_q, fq_k, inner_q=False, inner_k=False, value_job
             _row_stride(k), ctypes.byref(fmt), qmap.data_ptr(), int(bool(inner_q)), int(bool(inner_k)), value.data_ptr(), vt.data_ptr(),
             value.stride(0), value.stride(1), value.stride(2), W.data_ptr() if W is not None else None, wq.data_ptr() if wq is not None else None,
             W.numel() if W is not None else 0, _stream_ptr(q)), "qt_rope_map_value_weight")
-        attn.__dict__["_qt_vt_rows"] = (fused.value_key(value), fq_v, vt)
+        precomputed.VALUE_T_ROWS.leave(attn, value, (fq_v, vt))
         if wjob is not None:
             # the output projection's weight_fake_quant(W) call finds its result (valid for the very next call on this weight at this
             # version, counted there: precomputed.PRE, taken by fake_quantize.py's forward)
@@ -462,7 +461,6 @@ def rope_fq(q, k, cos, sin, fq_q, fq_k, value_job=None):
                                                     Hk, D, _row_stride(q), _row_stride(k), ctypes.byref(fq_q._qt_format),
                                                     ctypes.byref(fq_k._qt_format), _stream_ptr(q)), "qt_rope_fq_bf16")
     else:
-        from . import fused
         attn, value, fq_v = value_job
         vt8 = torch.empty((B, Hk, D, S), dtype=torch.uint8, device=q.device)
         _native.check(_native.lib().qt_rope_fq_value(q.data_ptr(), k.data_ptr(), cos.data_ptr(), sin.data_ptr(), None, None, q8.data_ptr(),
@@ -470,7 +468,7 @@ def rope_fq(q, k, cos, sin, fq_q, fq_k, value_job=None):
                                                      ctypes.byref(fq_q._qt_format), ctypes.byref(fq_k._qt_format), value.data_ptr(),
                                                      vt8.data_ptr(), value.stride(0), value.stride(1), value.stride(2),
                                                      ctypes.byref(fq_v._qt_format), _stream_ptr(q)), "qt_rope_fq_value")
-        attn.__dict__["_qt_vt8"] = (fused.value_key(value), fq_v, vt8)
+        precomputed.VALUE_CODES_T.leave(attn, value, (fq_v, vt8))
     # with the codes Q.K^T can run as an FP8 GEMM (functional_modules.py).  lazy: bf16 values not written, see the docstring (flag alone)
     lazy = value_job is not None
     return (handover.stamp(q_out, fq_q, handover.fp8_view(q8, fq_q), lazy=lazy, register=False),
@@ -617,7 +615,7 @@ def apply_bert_fusions(model):
             group = SiblingGroup(qkv)
             for lin in qkv:
                 lin.__dict__["_qt_sibling_group"] = group
-        inner.__dict__["_qt_out_proj"] = mod.attention.output.dense   # consumes the attention core's result (fused._attention_fp8_or_none)
+        inner.__dict__["_qt_out_proj"] = mod.attention.output.dense   # consumes the attention core's result (attention_route._attention_fp8_or_none)
         if prev_norm is not None:
             prev_norm.__dict__["_qt_consumers"] = qkv
         mod.attention.output.LayerNorm.__dict__["_qt_consumers"] = [mod.intermediate.dense]
@@ -793,7 +791,8 @@ _LAYER_PARAMS = ["self", "hidden_states", "attention_mask", "position_ids", "pas
 def _drop_layer_handovers(layer):
     """One-shot hand-overs a block's kernels leave for each other, dropped at the end of the block whichever route ran (each holds
     10 - 56 MB per layer at 13B widths): the sibling groups' [M, sum N] products once their members have taken their slices, the
-    value pass the rotary launch wrote ahead (`_qt_vt_rows`), the o projection's pre-quantized weight (precomputed.PRE)."""
+    value pass the rotary launch wrote ahead (precomputed.VALUE_CODES_T / VALUE_T_ROWS), the o projection's pre-quantized weight
+    (precomputed.PRE)."""
     attn, mlp = getattr(layer, "self_attn", None), getattr(layer, "mlp", None)
     for owner, names in ((attn, ("q_proj", "k_proj", "v_proj", "o_proj")), (mlp, ("gate_proj", "up_proj"))):
         if owner is None:
@@ -806,7 +805,8 @@ def _drop_layer_handovers(layer):
             if group is not None:
                 group.stash = None
     if attn is not None:
-        attn.__dict__.pop("_qt_vt_rows", None)
+        precomputed.VALUE_CODES_T.drop(attn)
+        precomputed.VALUE_T_ROWS.drop(attn)
         o = getattr(attn, "o_proj", None)
         fq = getattr(o, "weight_fake_quant", None) if o is not None else None
         if fq is not None and not torch.is_grad_enabled():

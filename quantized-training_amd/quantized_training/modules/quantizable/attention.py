@@ -96,7 +96,7 @@ def quantizable_attention_forward(module, query, key, value, attention_mask, sca
         causal = getattr(module, "is_causal", False)
     if attention_mask is None and query.shape[2] > 1 and causal:
         attention_mask = _causal_mask(query.shape[2], key.shape[2], query.dtype, query.device)
-    from ...fused import fused_attention_or_none, fused_scores_to_probs_or_none
+    from ...attention_route import fused_attention_or_none, fused_scores_to_probs_or_none
     core = fused_attention_or_none(module, query, key, value, attention_mask, scaling, dropout)
     if core is not None:
         return core, None                      # probabilities are never materialised on this path

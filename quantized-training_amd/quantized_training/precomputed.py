@@ -9,6 +9,8 @@ package.
   WEIGHT_CODES  the FP8 weight codes of a Linear / SiblingGroup   fused.BatchedWeightCodes
   COLSUM        column sums of a grad_output (the bias gradient)  train_fusions.put_colsum / take_colsum
   LINEAR_GRADS  (grad_input, grad_weight) of a q / k / v Linear   train_fusions.group_qkv_backward / take_linear_grads
+  VALUE_CODES_T (fq_v, V^T as FP8 codes) for qt_attention_fp8     `_qt_vt8`: model_fusions.rope_fq, pt2e_fusion / attention_route
+  VALUE_T_ROWS  (fq_v, fq_v(V)^T) for qt_attention_rows_bf16      `_qt_vt_rows`: model_fusions.rope_map / attention_route
   the amax histories whose next scale update is already done      mark_preupdated / take_preupdate / forget_preupdated
 
 Every record is ONE SHOT (looking it up removes it, hit or not) and names the tensor(s) the future call must receive by address and
@@ -19,7 +21,7 @@ Stays where it is (its lifetime is not that of a one-shot record keyed by a tens
   train_fusions._PENDING / _HOLDS          follow the autograd graph's token, not a capacity
   `_qt_deferred`                           an arm flag, not a tensor key
   modules/qat/linear.py _FWD_PENDING, `_qt_train_xw`      launches not yet issued / weak references to a node's operands
-  fused.SiblingGroup.stash, `_qt_vt_rows`  shared by several takers / keyed by fused.value_key"""
+  fused.SiblingGroup.stash                 shared by several takers"""
 from collections import namedtuple
 
 from .handover import tensor_key
@@ -36,10 +38,15 @@ def _versions_key(ts):
     return tuple((t.data_ptr(), t._version) for t in ts)
 
 
+def _strided_key(t):
+    return (*tensor_key(t), t.stride())
+
+
 # rule -> (key of the tensor(s), the layout the call's tensor must have beside an equal key)
 _RULES = {"shape": (tensor_key, lambda X, kept: X.is_contiguous() or X.stride() == kept.stride()),
           "numel": (_numel_key, lambda X, kept: X.is_contiguous()),
-          "versions": (_versions_key, lambda Xs, kept: True)}           # several tensors: one (address, version) per member
+          "versions": (_versions_key, lambda Xs, kept: True),           # several tensors: one (address, version) per member
+          "strided": (_strided_key, lambda X, kept: True)}              # a view a kernel reads in place: the same strides too
 
 
 class Slot:
@@ -70,6 +77,8 @@ PRE = Slot("_qt_pre", "shape")
 EXPECTED = Slot("_qt_expected", "numel")
 CHAIN_RESULT = Slot("_qt_chain_result", "shape")
 WEIGHT_CODES = Slot("_qt_w8_pre", "versions")
+VALUE_CODES_T = Slot("_qt_vt8", "strided")            # payload (fq_v, vt): the taker accepts it only for its own fq_v
+VALUE_T_ROWS = Slot("_qt_vt_rows", "strided")
 
 
 class Table:

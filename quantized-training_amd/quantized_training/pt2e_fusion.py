@@ -29,8 +29,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.fx import GraphModule, Node
 
-from . import _native, handover, switches
-from .fake_quantize import STATS as _FQ_STATS, FusedAmaxObsFakeQuantize, _stream_ptr
+from . import _native, handover, precomputed, switches
+from .fake_quantize import FusedAmaxObsFakeQuantize, _stream_ptr
 from .modules.qat.linear import Linear as QATLinear
 
 __all__ = ["fuse_prepared_graph", "unfuse_prepared_graph", "PreparedCausalLMLoss", "ShapeMemo", "PreparedLinear", "PreparedMLP", "PreparedRMSNorm", "PreparedAttention"]
@@ -186,7 +186,7 @@ class PreparedAttention(nn.Module):
         """Stateless TABLE formats on all four matmul inputs: the rotary kernel applies fq_q / fq_k (and the inner pair) in their row
         form, fq_v runs as its own strided pass, and the core is qt_attention_fq_bf16 (bf16 matrix instructions, the probabilities'
         fake-quantizer inside, §4.4b of DESIGN.md)."""
-        from . import fused, model_fusions as mf
+        from . import attention_route as ar, model_fusions as mf
         fq_q, fq_k, fq_p, fq_v = self.__dict__["fqs"]
         inner_q, inner_k = self.__dict__["inner"]
         if not switches.on("QT_FUSED_ATTENTION"):
@@ -204,10 +204,9 @@ class PreparedAttention(nn.Module):
             return None
         if cos.dim() != 3 or cos.shape[0] not in (1, B) or cos.shape[-1] != D or cos.shape[-2] != S or sin.shape != cos.shape:
             return None
-        mk = fused._mask_strides(mask, B, H, S, S, q.device, 4)
-        if mk is False:
+        mk = ar.AttentionMask.of(mask, B, H, S, S, q.device, 4)
+        if mk is None:
             return None
-        m, msb, msh, msq = mk
         pf = fq_p.map_producer_format(q.device)
         if pf is None:
             return None
@@ -219,30 +218,19 @@ class PreparedAttention(nn.Module):
         qq, kq = got
         for f, t in ((fq_q, q), (fq_k, k), (inner_q, q), (inner_k, k)):      # evaluated inside the rotary launch
             if f is not None:
-                f.__dict__["_qt_calls"] = f.__dict__.get("_qt_calls", 0) + 1
-                _FQ_STATS.add(t.numel())
+                ar.count_call(f, t.numel())
         fmt, qmap = pf
-        out = torch.empty((B, S, H, D), dtype=torch.bfloat16, device=q.device)
-        _FQ_STATS.add(B * H * S * S)                          # fq_p, inside the kernel
-        fq_p.__dict__["_qt_calls"] = fq_p.__dict__.get("_qt_calls", 0) + 1
+        ar.count_call(fq_p, B * H * S * S)                    # fq_p, inside the kernel
         proj = self.__dict__["_qt_out_proj"]
         fq_o = mf.consumer_fq_map(proj) if proj is not None else None
         if not (fq_o is not None and fq_o.dtype == fq_p.dtype and _table_ok(fq_o)):
             fq_o = None                                       # else: its node runs its own pass
         # (with fq_o: the output projection's input fake-quantizer, same format, on the kernel's epilogue; its node hands the result through)
-        if fused.attention_rows_or_none(_native.lib(), _stream_ptr(q), qq, kq, v, fq_v, m, mask, (msb, msh, msq), out, (B, H, S, S, D), self.scaling, fmt,
-                                        qmap.data_ptr(), fq_o is not None):
-            pass                                              # (the value pass of the launch pair was fq_v's call: counted there)
-        else:
-            vq = fq_v(v).contiguous()
-            fused.launch_attention_fq(_native.lib(), _stream_ptr(q), qq, kq, vq, m, mask, (msb, msh, msq), out, (B, H, S, S, D), self.scaling, fmt,
-                                      qmap.data_ptr(), None, None, fq_o is not None)
-        if fq_o is not None:
-            fq_o.expect_prequantized(out, None)
+        out = ar.table_format_core(self, _stream_ptr(q), qq, kq, v, fq_v, mk, (B, H, S, S, D), self.scaling, fmt, qmap.data_ptr(), fq_o)
         return out.reshape(B, S, H * D)
 
     def _fused(self, q, k, v, cos, sin, mask):
-        from . import fused, model_fusions as mf
+        from . import attention_route as ar, model_fusions as mf
         fqs = self.__dict__["fqs"]
         inner_q, inner_k = self.__dict__["inner"]
         if not switches.on("QT_FP8_ATTENTION") or not switches.on("QT_FP8_ATTENTION_KERNEL"):
@@ -258,7 +246,7 @@ class PreparedAttention(nn.Module):
             if f is not None and not _producer_ok(f):
                 return None
         rq, rk = mf._row_stride(q), mf._row_stride(k)
-        if rq is None or rk is None or v.stride(-1) != 1 or any(s % 8 for s in v.stride()[:3]) or v.data_ptr() % 16:
+        if rq is None or rk is None or not ar.readable_in_place(v):
             return None
         if cos.shape[-1] != D or cos.shape[-2] != S or sin.shape != cos.shape:
             return None
@@ -281,14 +269,13 @@ class PreparedAttention(nn.Module):
             _stream_ptr(q)), "qt_rope_fq_inner_value")
         for f, t in ((inner_q, q), (inner_k, k)):              # the two inner calls, evaluated inside that launch
             if f is not None:
-                f.__dict__["_qt_calls"] = f.__dict__.get("_qt_calls", 0) + 1
-                _FQ_STATS.add(t.numel())
+                ar.count_call(f, t.numel())
         for t, t8, f in ((q_out, q8, fq_q), (k_out, k8, fq_k)):
             handover.stamp(t, f, handover.fp8_view(t8, f), lazy=True, register=False)      # (they go straight to the core below)
-        self.__dict__["_qt_vt8"] = (fused.value_key(v), fq_v, vt8)
-        out = fused._attention_fp8_or_none(self, q_out, k_out, v, mask, self.scaling, fqs)
+        precomputed.VALUE_CODES_T.leave(self, v, (fq_v, vt8))
+        out = ar._attention_fp8_or_none(self, q_out, k_out, v, mask, self.scaling, fqs)
         if out is None:                                        # the kernel declined after all (mask layout): finish on the node sequence
-            self.__dict__.pop("_qt_vt8", None)
+            precomputed.VALUE_CODES_T.drop(self)
             handover.materialize(q_out)
             handover.materialize(k_out)
             s = torch.matmul(fq_q(q_out), fq_k(k_out.transpose(2, 3))) * self.scaling

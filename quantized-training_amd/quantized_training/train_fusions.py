@@ -832,7 +832,7 @@ class _SoftmaxTrainFn(torch.autograd.Function):
     them; the backward (qt_softmax_backward_chain_bf16) evaluates qk_matmul's backward-pre quantizer on the gradient of the scores."""
 
     @staticmethod
-    def forward(ctx, scores, mask, strides, scaling, fq_p, grad_head):
+    def forward(ctx, scores, mk, scaling, fq_p, grad_head):
         from .fake_quantize import _stream_ptr, launch_scale_update
         B, H, Q, C = scores.shape
         st = _stream_ptr(scores)
@@ -841,9 +841,8 @@ class _SoftmaxTrainFn(torch.autograd.Function):
         out = torch.empty_like(scores)
         if fq_p._observe:
             launch_scale_update(fq_p.amax_history, fq_p.scale, fq_p.quant_max, fq_p.force_scale_power_of_two, st)
-        msb, msh, msq = strides
-        _native.check(_native.lib().qt_softmax_fq_probs_bf16(scores.data_ptr(), mask.data_ptr() if mask is not None else None, out.data_ptr(),
-                                                             probs.data_ptr(), B, H, Q, C, msb, msh, msq, float(scaling), ctypes.byref(fmt),
+        _native.check(_native.lib().qt_softmax_fq_probs_bf16(scores.data_ptr(), mk.ptr, out.data_ptr(),
+                                                             probs.data_ptr(), B, H, Q, C, *mk.strides, float(scaling), ctypes.byref(fmt),
                                                              fq_p.qmap.data_ptr(), fq_p.scale.data_ptr(),
                                                              fq_p.amax_history.data_ptr() if fq_p._observe else None, st), "qt_softmax_fq_probs_bf16")
         _hand_over([(fq_p, -1)], probs, [out])
@@ -873,7 +872,7 @@ class _SoftmaxTrainFn(torch.autograd.Function):
                                                                    len(members), ctypes.byref(fmt), _lut_ptr(members[0][0], fmt), st),
                       "qt_softmax_backward_chain_bf16")
         _hand_over(members, ds, outs)
-        return ds, None, None, None, None, None
+        return ds, None, None, None, None
 
 
 def softmax_or_none(attn, scores, attention_mask, scaling, dropout):
@@ -894,12 +893,12 @@ def softmax_or_none(attn, scores, attention_mask, scaling, dropout):
     if fq_p is None or _members_format([(fq_p, -1)], scores.device) is None:
         return None
     B, H, Q, C = scores.shape
-    from .fused import _mask_strides
-    mk = _mask_strides(attention_mask, B, H, Q, C, scores.device, 8, no_grad=True)
-    if mk is False:
+    from .attention_route import AttentionMask
+    mk = AttentionMask.of(attention_mask, B, H, Q, C, scores.device, 8, no_grad=True)
+    if mk is None:
         return None
     head = pc.holder_fq(attn.qk_matmul, "error_pre_process")
-    return _SoftmaxTrainFn.apply(scores, mk[0], mk[1:], scaling, fq_p, head)
+    return _SoftmaxTrainFn.apply(scores, mk, scaling, fq_p, head)
 
 
 def _served_call(fq, x, y, numel=None):
@@ -927,7 +926,7 @@ class _AttentionTrainFn(torch.autograd.Function):
     The result and the gradients are laid out [B, S, H, D], so the permute copies of the unfused path do not exist."""
 
     @staticmethod
-    def forward(ctx, q, k, v, mask, mstrides, scaling, fqs, fq_o, efqs, lins, drop_p=0.0):
+    def forward(ctx, q, k, v, mk, scaling, fqs, fq_o, efqs, lins, drop_p=0.0):
         from .fake_quantize import _stream_ptr, _Stats, launch_scale_update
         B, H, S, D = q.shape
         dev = q.device
@@ -948,13 +947,12 @@ class _AttentionTrainFn(torch.autograd.Function):
             stages[i].amax_bits_dev = fq.amax_history.data_ptr() if fq._observe else None
             stages[i].out_dev = outs[i].data_ptr()
             stages[i].src = -1
-        msb, msh, msq = mstrides
         # attention-probability dropout (between the softmax and av_matmul): the keep mask is drawn by torch's generator (one launch;
         # seeds and stream capture behave as for nn.Dropout), the kernels apply torch's dropout arithmetic with it, forward and backward
         keep = torch.empty((B, H, S, S), dtype=torch.uint8, device=dev).bernoulli_(1.0 - drop_p) if drop_p > 0.0 else None
         ctx.drop_scale = 1.0 / (1.0 - drop_p) if drop_p > 0.0 else 1.0
         _native.check(_native.lib().qt_attention_train_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), q.stride(0), q.stride(2), q.stride(1),
-                                                            mask.data_ptr() if mask is not None else None, msb, msh, msq, stages, probs.data_ptr(),
+                                                            mk.ptr, *mk.strides, stages, probs.data_ptr(),
                                                             out.data_ptr(), keep.data_ptr() if keep is not None else None, ctx.drop_scale, B, H, S, D,
                                                             float(scaling), ctypes.byref(fmt), _lut_ptr(fqs[0], fmt), st),
                       "qt_attention_train_bf16")
@@ -988,7 +986,7 @@ class _AttentionTrainFn(torch.autograd.Function):
             if keep is not None:
                 dp = torch.ops.aten.native_dropout_backward(dp, keep.bool(), ctx.drop_scale)
             ds = eq(torch.ops.aten._softmax_backward_data(dp, probs, -1, probs.dtype) * ctx.scaling)
-            return ds @ kq, ds.transpose(2, 3) @ qq, dv, None, None, None, None, None, None, None, None
+            return ds @ kq, ds.transpose(2, 3) @ qq, dv, None, None, None, None, None, None, None
         st = _stream_ptr(qq)
         dq, dk, dv = (torch.empty((B, S, H, D), dtype=qq.dtype, device=dev) for _ in range(3))
         stages = (_native.QtChainStage * 2)()
@@ -1048,7 +1046,7 @@ class _AttentionTrainFn(torch.autograd.Function):
                 put_colsum(o, gb)
         if len(riders) == 3 and [r[1] for r in riders] == [0, 1, 2]:
             group_qkv_backward(ctx.lins, [r[2] for r in riders])       # the projections' six backward products as two launches
-        return dq.permute(0, 2, 1, 3), dk.permute(0, 2, 1, 3), dv.permute(0, 2, 1, 3), None, None, None, None, None, None, None, None
+        return dq.permute(0, 2, 1, 3), dk.permute(0, 2, 1, 3), dv.permute(0, 2, 1, 3), None, None, None, None, None, None, None
 
 
 def attention_enabled():
@@ -1096,14 +1094,13 @@ def attention_or_none(attn, query, key, value, attention_mask, scaling, dropout)
     fq_o = pc.holder_fq(proj, "activation_pre_process", exact=True)
     if fq_o is not None and (fq_o.__dict__.get("_qt_chain") is not None or _members_format([(f, -1) for f in fqs + [fq_o]], dev) is None):
         fq_o = None
-    from .fused import _mask_strides
-    mk = _mask_strides(attention_mask, B, H, S, S, dev, 8, no_grad=True)
-    if mk is False or (mk[0] is not None and mk[0].shape[3] != S):
+    from .attention_route import AttentionMask
+    mk = AttentionMask.of(attention_mask, B, H, S, S, dev, 8, no_grad=True)
+    if mk is None or (mk.view is not None and mk.view.shape[3] != S):
         return None
-    mask, strides = mk[0], mk[1:]
     lins = tuple(getattr(attn, n, None) for n in ("query", "key", "value"))
     _mark_qkv_members(attn, lins)
-    return _AttentionTrainFn.apply(query, key, value, mask, strides, scaling, fqs, fq_o, efqs, lins, drop_p)
+    return _AttentionTrainFn.apply(query, key, value, mk, scaling, fqs, fq_o, efqs, lins, drop_p)
 
 
 class _EmbeddingTrainFn(torch.autograd.Function):

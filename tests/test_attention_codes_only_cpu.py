@@ -1,10 +1,10 @@
-"""The codes-only decision of the FP8 attention core (fused.attention_output_plan): the kernel may leave the bf16 values unwritten only
+"""The codes-only decision of the FP8 attention core (attention_route.attention_output_plan): the kernel may leave the bf16 values unwritten only
 while nobody but the output projection's own code path can see them."""
 import pytest
 import torch
 
 import quantized_training as qt
-from quantized_training import fused, handover
+from quantized_training import attention_route, handover
 
 IDS = torch.randint(3, 97, (2, 16), generator=torch.Generator().manual_seed(0))
 
@@ -30,12 +30,12 @@ def test_attention_codes_only_declines_when_someone_can_see_the_values(hooked, m
     if target is not None:
         target.register_forward_hook(lambda m, a, out: None)
     with torch.no_grad():
-        got_fq, codes_only = fused.attention_output_plan(attn)
+        got_fq, codes_only = attention_route.attention_output_plan(attn)
         assert got_fq is fq_o                                                # the epilogue still applies the fake-quantizer: values AND codes
         assert codes_only is (hooked == "nothing")
         monkeypatch.setenv("QT_CODES_ONLY", "0")
-        assert fused.attention_output_plan(attn) == (fq_o, False)
-    assert fused.attention_output_plan(attn) == (fq_o, False)                # gradients on: somebody will read the values
+        assert attention_route.attention_output_plan(attn) == (fq_o, False)
+    assert attention_route.attention_output_plan(attn) == (fq_o, False)                # gradients on: somebody will read the values
 
 
 def test_view_of_a_codes_only_result_goes_through_the_consumer_undecoded(monkeypatch):

@@ -196,15 +196,15 @@ def test_codes_only_attention_leaves_the_window_nll_unchanged(monkeypatch):
     """A 2-layer LLaMA (hidden 256, 2 heads of 128): the window NLL with the attention core handing only codes to o_proj
     (QT_CODES_ONLY=1) and with every producer writing values (=0) is the same number bit for bit, eager and through GraphedWindow.  The
     suite runs with QT_LAZY_POISON=1: a read of the unwritten values would surface as NaN."""
-    from quantized_training import fused, harness
+    from quantized_training import attention_route, harness
     ids = torch.randint(0, 512, (1, 256), generator=torch.Generator().manual_seed(5)).cuda()
     res, lazy_seen = {}, {}
-    real = fused.attention_output_plan
+    real = attention_route.attention_output_plan
 
     for mode in ("1", "0"):
         monkeypatch.setenv("QT_CODES_ONLY", mode)
         seen = []
-        monkeypatch.setattr(fused, "attention_output_plan", lambda attn, seen=seen: (seen.append(real(attn)), seen[-1])[1])
+        monkeypatch.setattr(attention_route, "attention_output_plan", lambda attn, seen=seen: (seen.append(real(attn)), seen[-1])[1])
         m = _tiny_llama()
         with torch.no_grad():
             harness.window_nll(m, ids, 256)                                  # the first call creates the fake-quantizers

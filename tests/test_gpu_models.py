@@ -209,7 +209,7 @@ def test_bert_squad_style_batch_parity(monkeypatch):
     route runs the attention core as qt_attention_fp8 (head_dim 64, right-padded rows): checked to be the kernel that ran, with the
     same fake-quant call and element counts as the bf16 attention kernel it replaces."""
     from transformers import BertConfig, BertForQuestionAnswering
-    from quantized_training import fused
+    from quantized_training import attention_route
     from quantized_training.fake_quantize import STATS
     for k in ("QT_FP8_ATTENTION_KERNEL", "QT_FP8_ATTENTION"):
         monkeypatch.delenv(k, raising=False)                                   # the test asserts which kernel ran
@@ -221,13 +221,13 @@ def test_bert_squad_style_batch_parity(monkeypatch):
     att = torch.ones_like(ids); att[:, 300:] = 0
     import copy
     ran = {"n": 0}
-    real = fused._attention_fp8_or_none
+    real = attention_route._attention_fp8_or_none
 
     def counted(*a, **k):
         out = real(*a, **k)
         ran["n"] += out is not None
         return out
-    monkeypatch.setattr(fused, "_attention_fp8_or_none", counted)
+    monkeypatch.setattr(attention_route, "_attention_fp8_or_none", counted)
     counts = {}
 
     def build(dev, groups="gemm,residual,activation,layernorm,scaling"):
@@ -776,7 +776,7 @@ def test_pt2e_prepared_route_at_size(monkeypatch):
     downstream, as for the eager route); and a hipGraph replay of the fused graph is no slower than 1.15x the eager route's
     (quantize() + model_fusions) window on the same model -- whose graph has FEWER fake-quantizers (the PT2E annotator also
     quantizes the residual stream and the rotary's first product)."""
-    from quantized_training import fused
+    from quantized_training import attention_route, fused
     from quantized_training.fake_quantize import STATS
     tok = torch.randint(0, 32000, (1, 1024), generator=torch.Generator().manual_seed(11)).cuda()
     calls = {"attention": 0, "fq8": 0, "mlp": 0}
@@ -788,7 +788,7 @@ def test_pt2e_prepared_route_at_size(monkeypatch):
                 calls[name] += 1
             return out
         return wrapper
-    monkeypatch.setattr(fused, "_attention_fp8_or_none", counted("attention", fused._attention_fp8_or_none))
+    monkeypatch.setattr(attention_route, "_attention_fp8_or_none", counted("attention", attention_route._attention_fp8_or_none))
     monkeypatch.setattr(fused, "hip_fq8_linear_or_none", counted("fq8", fused.hip_fq8_linear_or_none))
     monkeypatch.setattr(fused, "hip_mlp_fq8_or_none", counted("mlp", fused.hip_mlp_fq8_or_none))
 

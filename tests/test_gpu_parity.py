@@ -1345,7 +1345,7 @@ def test_rotary_and_value_codes_in_one_launch(nv):
     """qt_rope_fq_value (rotary + qk fake-quant, codes only, and the attention kernel's value-code pass in one launch) == qt_rope_fq_bf16's
     codes and qt_value_codes_t's output, bit for bit; the bf16 tensors it leaves unwritten decode from the codes exactly when a
     fake-quantizer's hand-over is asked for them."""
-    from quantized_training import model_fusions as mf
+    from quantized_training import model_fusions as mf, precomputed
     from quantized_training.fake_quantize import FusedAmaxObsFakeQuantize
     L = nv.lib()
     g = torch.Generator(device="cuda").manual_seed(13)
@@ -1369,7 +1369,7 @@ def test_rotary_and_value_codes_in_one_launch(nv):
         want_vt = torch.empty(B, H, D, S, dtype=torch.uint8, device="cuda")
         nv.check(L.qt_value_codes_t(v.data_ptr(), want_vt.data_ptr(), B, H, S, D, v.stride(0), v.stride(1), v.stride(2),
                                     ctypes.byref(fq_v._qt_format), stream()), "qt_value_codes_t")
-        assert torch.equal(attn._qt_vt8[2], want_vt)
+        assert torch.equal(precomputed.VALUE_CODES_T.peek(attn).payload[1], want_vt)
         assert torch.equal(got_q._qt_fp8.view(torch.uint8), want_q._qt_fp8.view(torch.uint8))
         assert torch.equal(got_k._qt_fp8.view(torch.uint8), want_k._qt_fp8.view(torch.uint8))
         assert got_q._qt_lazy and got_k._qt_lazy

@@ -8,7 +8,7 @@ import torch
 from torch import nn
 
 import quantized_training as qt
-from quantized_training import fused, model_fusions as mf, planner_checks as pc
+from quantized_training import attention_route, fused, model_fusions as mf, planner_checks as pc
 
 KINDS = ["forward_pre", "forward", "backward_pre", "backward"]
 
@@ -144,5 +144,5 @@ def test_planner_answers_with_a_user_forward_hook(name, consumers, norm_fq, hook
         assert [mf.consumer_fq(lin) is lin.activation_pre_process["0"] for lin in linears] == [True] * consumers
         assert _kind(mf._norm_consumer_fq(norm, allow_all=True, allow_map=name == "llama")) == norm_fq
         assert mf._qk_fqs(attn) == (attn.qk_matmul.activation_pre_process["0"], attn.qk_matmul.activation_pre_process["1"])
-        assert fused.fused_attention_or_none(attn, q, q, q, None, 0.25, 0.0) is None
-        assert fused.fused_scores_to_probs_or_none(attn, q, None, 0.25, 0.0, q) is None
+        assert attention_route.fused_attention_or_none(attn, q, q, q, None, 0.25, 0.0) is None
+        assert attention_route.fused_scores_to_probs_or_none(attn, q, None, 0.25, 0.0, q) is None

@@ -15,6 +15,7 @@ class Owner:
 SHAPE = Slot("_test_shape", "shape")
 NUMEL = Slot("_test_numel", "numel")
 SEVERAL = Slot("_test_several", "versions")
+STRIDED = Slot("_test_strided", "strided")
 
 
 # ---- Slot ------------------------------------------------------------------------------------------------------------------------
@@ -80,6 +81,48 @@ def test_numel_slot_takes_a_contiguous_view_of_another_shape():
     base = torch.zeros(6, 4)
     NUMEL.leave(o, base.t(), "result")                                       # the shape rule would take this one; this rule wants it contiguous
     assert NUMEL.take(o, base.t()) is MISS
+
+
+def test_strided_slot_takes_the_very_view_with_the_very_strides():
+    """The rule of the value pass a rotary launch writes ahead of the attention core (VALUE_CODES_T, VALUE_T_ROWS): the kernels read the
+    [B, H, S, D] view of a projection's output in place, so another stride over the same storage is another tensor."""
+    assert precomputed.VALUE_CODES_T.name == "_qt_vt8" and precomputed.VALUE_T_ROWS.name == "_qt_vt_rows"
+    o, fq = Owner(), object()
+    buf = torch.zeros(2, 8, 3 * 4 * 16)                                      # [B, S, 3 * H * D]: q | k | v
+    value = buf[:, :, 128:].view(2, 8, 4, 16).transpose(1, 2)                # [B, H, S, D]
+    for slot in (STRIDED, precomputed.VALUE_CODES_T, precomputed.VALUE_T_ROWS):
+        assert slot.take(o, value) is None
+        slot.leave(o, value, (fq, "vt"))
+        rec = slot.peek(o)
+        assert rec.key == (*handover.tensor_key(value), value.stride()) and rec.tensors is value
+        again = buf[:, :, 128:].view(2, 8, 4, 16).transpose(1, 2)            # another view object of the same contents
+        assert slot.take(o, again) == (fq, "vt")
+        assert slot.peek(o) is None and slot.take(o, value) is None          # gone after the take
+        slot.leave(o, value, (fq, "vt"))
+        narrow = torch.as_strided(buf, value.shape, (value.stride(0), 8, value.stride(2), 1), value.storage_offset())
+        assert handover.tensor_key(narrow) == handover.tensor_key(value) and narrow.stride() != value.stride()
+        assert slot.take(o, narrow) is MISS                                  # the same storage seen through another stride
+        assert slot.peek(o) is None and slot.take(o, value) is None          # gone after a miss too
+        slot.leave(o, value, (fq, "vt"))
+        assert slot.take(o, value.contiguous()) is MISS                      # a copy: another address
+        slot.leave(o, value, (fq, "vt"))
+        buf.add_(1)                                                          # a bumped version: other contents
+        assert slot.take(o, value) is MISS and slot.peek(o) is None
+        slot.leave(o, value, (fq, "vt"))
+        slot.drop(o)
+        assert slot.peek(o) is None and slot.take(o, value) is None
+
+
+def test_strided_slot_holds_its_tensor_while_it_exists():
+    o = Owner()
+    t = torch.randn(2, 4, 8, 16)
+    STRIDED.leave(o, t, ("fq", "vt"))
+    ptr = t.data_ptr()
+    del t
+    others = [torch.randn(2, 4, 8, 16) for _ in range(32)]
+    assert all(x.data_ptr() != ptr for x in others)                          # no later tensor is placed at the recorded address ...
+    assert STRIDED.peek(o).tensors.data_ptr() == ptr
+    assert STRIDED.take(o, others[0]) is MISS                                # ... so none can match the record
 
 
 def test_slot_over_several_tensors_sits_on_its_owner():
