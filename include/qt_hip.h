@@ -243,6 +243,42 @@ int qt_fake_quant_mx_f32(const float *x_dev, float *y_dev, float *sf_dev, size_t
                          int block_size, const qt_format *fmt, const uint16_t *lut_dev, float quant_max,
                          const uint16_t *scale_lut_dev, void *stream);
 
+/* ---- group-wise affine: one scale and one zero point per block of `block_size` consecutive indices of one axis.
+ * All six entry points see the tensor as contiguous [outer][n][inner]; blocks are consecutive indices of n, and the block
+ * parameters are [outer][n / block_size][inner] in the tensor's dtype.  inner == 1 is the last-axis layout, inner > 1 the
+ * strided one (ax=-2 on [B, H, S, D]: outer = B * H, n = S, inner = D).
+ * Declined before any device call (QT_ERR_BAD_ARG / QT_ERR_UNALIGNED): NULL pointers; block_size not a power of two in
+ * 8..512 (bf16) / 4..256 (fp32) when inner == 1, or outside 1..512 when inner > 1; n % block_size != 0 (the torch ops zero-pad,
+ * and the pad takes part in min / max); inner % 8 (bf16) / % 4 (fp32) != 0 when inner > 1; a pointer that is not 16-byte
+ * aligned; quant_max <= quant_min.  Empty tensors return QT_OK.
+ *
+ * GroupWiseAffineFakeQuantFunction.forward                           fake_quantize.py:136-194
+ *   lo, hi = min, max of the block (NaN propagates)
+ *   sf = (hi - lo) / (quant_max - quant_min); sf = sf > 0 ? sf : 1;  zp = -lo / sf + quant_min
+ *   scale_lut ? (sf = vmap(sf, scale_lut), zp = vmap(zp, scale_lut))   -- after both are computed
+ *   y = (clamp(round(x / sf + zp), quant_min, quant_max) - zp) * sf   (every op in the tensor's dtype; round = half to even)
+ * scale_out_dev / zp_out_dev receive sf / zp.  scale_lut_dev may be NULL. */
+int qt_fake_quant_gwa_bf16(const uint16_t *x_dev, uint16_t *y_dev, uint16_t *scale_out_dev, uint16_t *zp_out_dev, size_t outer,
+                           size_t n, size_t inner, int block_size, float quant_min, float quant_max,
+                           const uint16_t *scale_lut_dev, void *stream);
+int qt_fake_quant_gwa_f32(const float *x_dev, float *y_dev, float *scale_out_dev, float *zp_out_dev, size_t outer, size_t n,
+                          size_t inner, int block_size, float quant_min, float quant_max, const uint16_t *scale_lut_dev,
+                          void *stream);
+/* quantized_ops::quantize with block-wise scale and zero point       decomposed.py:173-210
+ *   y = vmap(x / s_blk + z_blk, lut) */
+int qt_quantize_blocks_bf16(const uint16_t *x_dev, uint16_t *y_dev, const uint16_t *scale_dev, const uint16_t *zp_dev,
+                            size_t outer, size_t n, size_t inner, int block_size, const uint16_t *lut_dev, void *stream);
+int qt_quantize_blocks_f32(const float *x_dev, float *y_dev, const float *scale_dev, const float *zp_dev, size_t outer, size_t n,
+                           size_t inner, int block_size, const uint16_t *lut_dev, void *stream);
+/* quantized_ops::dequantize with block-wise scale and zero point     decomposed.py:220-262
+ *   y = vmap?((vmap?(x, in_lut) - z_blk) * s_blk, out_lut);  in_lut_dev / out_lut_dev may be NULL */
+int qt_dequantize_blocks_bf16(const uint16_t *x_dev, uint16_t *y_dev, const uint16_t *scale_dev, const uint16_t *zp_dev,
+                              size_t outer, size_t n, size_t inner, int block_size, const uint16_t *in_lut_dev,
+                              const uint16_t *out_lut_dev, void *stream);
+int qt_dequantize_blocks_f32(const float *x_dev, float *y_dev, const float *scale_dev, const float *zp_dev, size_t outer, size_t n,
+                             size_t inner, int block_size, const uint16_t *in_lut_dev, const uint16_t *out_lut_dev,
+                             void *stream);
+
 /* ---- A9/A10: fake-quant GEMMs (bf16 in, fp32 accumulate on MFMA, bf16 out) ---------------
  * qt_linear_fq_bf16 replaces  F.linear(fq_a(x), weight_fake_quant(W), b)
  *     modules/qat/linear.py:40-41 + the activation pre-hook quantize.py:128-140

@@ -64,6 +64,14 @@ inline int qt_cu_count() {
     return n;
 }
 
+// Grid of a grid-stride kernel: one block per `per_block` work items, at most `blocks_per_cu` blocks per compute unit.
+inline unsigned grid_for(size_t work_items, size_t per_block, int blocks_per_cu) {
+    size_t want = (work_items + per_block - 1) / per_block;
+    size_t cap = (size_t)qt_cu_count() * blocks_per_cu;
+    if (want < 1) want = 1;
+    return (unsigned)(want < cap ? want : cap);
+}
+
 namespace {
 
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
@@ -174,6 +182,7 @@ __device__ __forceinline__ uint2 fq8_hw_vec8(uint32_t (&o)[4], const qt_format &
 struct UniformDiv {
     float s, r;
     bool safe, pow2;
+    __device__ __forceinline__ UniformDiv() : s(1.0f), r(1.0f), safe(true), pow2(true) {}      // arrays of divisors (one per column)
     __device__ __forceinline__ explicit UniformDiv(float scale) : s(scale), r(1.0f / scale) {
         const uint32_t as = qt_f2u(scale) & 0x7FFFFFFFu;
         safe = as >= ((127u - 100u) << 23) && as <= ((127u + 100u) << 23);

@@ -1462,13 +1462,6 @@ __global__ __launch_bounds__(256) void posit_bits_kernel(const float *__restrict
 }
 
 // ---- launch helpers --------------------------------------------------------------------------
-inline unsigned grid_for(size_t work_items, size_t per_block, int blocks_per_cu) {
-    size_t want = (work_items + per_block - 1) / per_block;
-    size_t cap = (size_t)qt_cu_count() * blocks_per_cu;
-    if (want < 1) want = 1;
-    return (unsigned)(want < cap ? want : cap);
-}
-
 // Tensors below this many elements use the global-table gather kernel instead of staging 128 KiB per CU.
 constexpr size_t kLutLdsMinElems = (size_t)1 << 21;
 

@@ -82,6 +82,41 @@ def _lut_format():
     return _native.QtFormat(_native.QT_FMT_LUT, 0, 0, 0.0, 0.0)
 
 
+def block_param_view(shape, param_shape, block_size, dtype):
+    """(outer, n, inner) when `param_shape` is `shape` with exactly one dimension divided by `block_size` and the group-wise
+    kernels take that layout (fake_quantize.gwa_block_view), else None."""
+    if len(param_shape) != len(shape) or not isinstance(block_size, int):
+        return None
+    diff = [d for d in range(len(shape)) if param_shape[d] != shape[d]]
+    if len(diff) != 1 or param_shape[diff[0]] * block_size != shape[diff[0]]:
+        return None
+    from .fake_quantize import gwa_block_view
+    return gwa_block_view(tuple(shape), dtype, block_size, diff[0])
+
+
+def _block_param_view(input, scale, zero_point, block_size):
+    """The kernels' view of a block-wise quantize / dequantize call with zero points on a device tensor, or None.  The kernels
+    compute in the tensor's own dtype, which is what torch's type promotion does only when the parameters already have it."""
+    if (input.device.type != "cuda" or zero_point is None or scale.dtype != input.dtype or zero_point.dtype != input.dtype
+            or tuple(zero_point.shape) != tuple(scale.shape)):
+        return None
+    return block_param_view(tuple(input.shape), tuple(scale.shape), block_size, input.dtype)
+
+
+def _blocks_hip_or_none(op, input, scale, zero_point, view, block_size, maps):
+    """qt_quantize_blocks_* / qt_dequantize_blocks_*: one pass; None when the library declines (an unaligned view)."""
+    L = _native.lib()
+    x, s, z = input.contiguous(), scale.contiguous(), zero_point.contiguous()
+    y = torch.empty_like(x)
+    fn = getattr(L, f"qt_{op}_blocks_" + ("bf16" if x.dtype == torch.bfloat16 else "f32"))
+    code = fn(x.data_ptr(), y.data_ptr(), s.data_ptr(), z.data_ptr(), *view, block_size,
+              *(m.data_ptr() if m is not None else None for m in maps), _stream_ptr(x))
+    if _native.declined(code):
+        return None
+    _native.check(code, f"qt_{op}_blocks")
+    return y
+
+
 def _quantize_impl(input, scale, zero_point=None, axes=None, block_size=None, qmap=None, output_code=None):
     assert qmap is not None, "qmap must be provided for quantization"
     # the fused kernels compute in the tensor's own dtype, which is what torch's type promotion does
@@ -104,6 +139,11 @@ def _quantize_impl(input, scale, zero_point=None, axes=None, block_size=None, qm
         return y
     pow2 = getattr(scale, "_qt_pow2", False)
     if block_size is not None:
+        view = _block_param_view(input, scale, zero_point, block_size)
+        if view is not None and qmap.dtype == torch.bfloat16 and qmap.numel() == 65536:
+            out = _blocks_hip_or_none("quantize", input, scale, zero_point, view, block_size, (qmap.contiguous(),))
+            if out is not None:
+                return out
         scale = expand(scale, input.shape, block_size)
         if zero_point is not None:
             zero_point = expand(zero_point, input.shape, block_size)
@@ -136,6 +176,14 @@ def _dequantize_impl(input, scale, zero_point=None, axes=None, block_size=None, 
                              output_qmap.data_ptr() if output_qmap is not None else None, _stream_ptr(x)),
                           "qt_dequantize")
         return y
+    if block_size is not None:
+        view = _block_param_view(input, scale, zero_point, block_size)
+        if view is not None and all(m is None or (m.dtype == torch.bfloat16 and m.numel() == 65536)
+                                    for m in (input_qmap, output_qmap)):
+            maps = tuple(m.contiguous() if m is not None else None for m in (input_qmap, output_qmap))
+            out = _blocks_hip_or_none("dequantize", input, scale, zero_point, view, block_size, maps)
+            if out is not None:
+                return out
     if input_qmap is not None:
         input = torch.ops.quantized_ops.vmap(input, input_qmap)
     if block_size is not None:

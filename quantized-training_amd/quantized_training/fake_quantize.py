@@ -543,40 +543,113 @@ def _hip_mx_or_none(input, scale, qmap, axes, block_size, quant_max, pow2, scale
     return y
 
 
+def group_wise_affine_composite(input, scale, zero_point, axes, block_size, quant_min, quant_max, scale_qmap=None):
+    """GroupWiseAffineFakeQuantFunction.forward as torch ops in the tensor's dtype (upstream fake_quantize.py:160-194): every
+    layout and dtype, on any device.  Fills `scale` / `zero_point` and returns the fake-quantized tensor."""
+    from .decomposed import expand, _const_like
+    from .mx_utils import _reshape_to_blocks
+    assert block_size > 0
+    axes = [axes] if type(axes) == int else list(axes)
+    axes = [x + input.ndim if x < 0 else x for x in axes]
+    blocks, baxes, _, _ = _reshape_to_blocks(input, axes, block_size)
+    block_axes = [x + 1 for x in baxes]
+    lo = torch.amin(blocks, dim=block_axes)
+    hi = torch.amax(blocks, dim=block_axes)
+    sf = (hi - lo) / _const_like(quant_max - quant_min, hi)
+    sf = torch.where(sf > 0.0, sf, _const_like(1.0, sf))
+    zp = -lo / sf + quant_min
+    if scale_qmap is not None:
+        sf = torch.ops.quantized_ops.vmap(sf, scale_qmap)
+        zp = torch.ops.quantized_ops.vmap(zp, scale_qmap)
+    scale.resize_(sf.shape).copy_(sf)
+    zero_point.resize_(zp.shape).copy_(zp)
+    sfe = expand(sf, input.shape, block_size)
+    zpe = expand(zp, input.shape, block_size)
+    # clamp as the reference's CPU kernel does it, std::min(std::max(q, lo), hi): a q of -0 stays -0 at lo = 0 (torch.clamp on the
+    # device returns +0 there, and the sign reaches the output when the zero point is 0)
+    q = torch.round(input / sfe + zpe)
+    q = torch.where(q < quant_min, quant_min, q)
+    q = torch.where(q > quant_max, quant_max, q)
+    return (q - zpe) * sfe
+
+
 class GroupWiseAffineFakeQuantFunction(torch.autograd.Function):
     """Asymmetric block-wise integer fake-quant with per-block scale and zero point
-    (upstream fake_quantize.py:136-194); plain torch ops in the tensor's dtype."""
+    (upstream fake_quantize.py:136-194).  The fused HIP pass (qt_fake_quant_gwa_*) covers blocks along one axis of a
+    bf16 / fp32 device tensor (see gwa_block_view); other calls use the same formulas as torch ops in the tensor's dtype."""
 
     @staticmethod
     def forward(ctx, input, fake_quant_enabled, scale, zero_point, axes, block_size, quant_min, quant_max,
                 scale_qmap=None):
         if not _as_flag(fake_quant_enabled):
             return input
-        from .decomposed import expand, _const_like
-        from .mx_utils import _reshape_to_blocks
-        assert block_size > 0
-        axes = [axes] if type(axes) == int else list(axes)
-        axes = [x + input.ndim if x < 0 else x for x in axes]
-        blocks, baxes, _, _ = _reshape_to_blocks(input, axes, block_size)
-        block_axes = [x + 1 for x in baxes]
-        lo = torch.amin(blocks, dim=block_axes)
-        hi = torch.amax(blocks, dim=block_axes)
-        sf = (hi - lo) / _const_like(quant_max - quant_min, hi)
-        sf = torch.where(sf > 0.0, sf, _const_like(1.0, sf))
-        zp = -lo / sf + quant_min
-        if scale_qmap is not None:
-            sf = torch.ops.quantized_ops.vmap(sf, scale_qmap)
-            zp = torch.ops.quantized_ops.vmap(zp, scale_qmap)
-        scale.resize_(sf.shape).copy_(sf)
-        zero_point.resize_(zp.shape).copy_(zp)
-        sfe = expand(sf, input.shape, block_size)
-        zpe = expand(zp, input.shape, block_size)
-        q = torch.clamp(torch.round(input / sfe + zpe), quant_min, quant_max)
-        return (q - zpe) * sfe
+        out = _hip_gwa_or_none(input, scale, zero_point, axes, block_size, quant_min, quant_max, scale_qmap)
+        if out is not None:
+            return out
+        return group_wise_affine_composite(input, scale, zero_point, axes, block_size, quant_min, quant_max, scale_qmap)
 
     @staticmethod
     def backward(ctx, grad_output):
         return (grad_output,) + (None,) * 8
+
+
+def gwa_block_view(shape, dtype, block_size, axes):
+    """(outer, n, inner) when the group-wise kernels take blocks of `block_size` along `axes` of a contiguous tensor of this shape
+    and dtype, else None: one block axis (int or one-element sequence, negative or not), an int block size that divides the
+    axis, bf16 / fp32; along the last axis the block is a power of two of 8..512 (bf16) / 4..256 (fp32) elements, along any
+    other axis it is 1..512 rows of a row length that is a multiple of 8 (bf16) / 4 (fp32)."""
+    if dtype not in (torch.bfloat16, torch.float32) or len(shape) < 1:
+        return None
+    if isinstance(block_size, bool) or not isinstance(block_size, int):
+        return None
+    if isinstance(axes, int):
+        ax = axes
+    else:
+        axes = tuple(axes)
+        if len(axes) != 1 or not isinstance(axes[0], int):
+            return None
+        ax = axes[0]
+    if not -len(shape) <= ax < len(shape):
+        return None
+    outer, n, inner = _channel_view(tuple(shape), ax % len(shape))
+    if outer * n * inner == 0 or block_size < 1 or n % block_size:
+        return None
+    per = 8 if dtype == torch.bfloat16 else 4
+    if inner == 1:
+        if block_size < per or block_size & (block_size - 1) or block_size > 64 * per:
+            return None
+    elif block_size > 512 or inner % per:
+        return None
+    return outer, n, inner
+
+
+def _hip_gwa_or_none(input, scale, zero_point, axes, block_size, quant_min, quant_max, scale_qmap):
+    """Fused device pass for blocks along one axis; None when it does not apply."""
+    if not _is_device(input):
+        return None
+    view = gwa_block_view(tuple(input.shape), input.dtype, block_size, axes)
+    if view is None or not quant_max > quant_min:
+        return None
+    if scale_qmap is not None and (scale_qmap.dtype != torch.bfloat16 or scale_qmap.numel() != 65536
+                                   or not scale_qmap.is_contiguous()):
+        return None
+    outer, n, inner = view
+    L = _native.lib()
+    x = input.contiguous()
+    y = torch.empty_like(x)
+    ax = (axes if isinstance(axes, int) else tuple(axes)[0]) % x.dim()
+    pshape = x.shape[:ax] + (n // block_size,) + x.shape[ax + 1:]
+    sf = torch.empty(pshape, dtype=x.dtype, device=x.device)
+    zp = torch.empty(pshape, dtype=x.dtype, device=x.device)
+    fn = L.qt_fake_quant_gwa_bf16 if x.dtype == torch.bfloat16 else L.qt_fake_quant_gwa_f32
+    code = fn(x.data_ptr(), y.data_ptr(), sf.data_ptr(), zp.data_ptr(), outer, n, inner, block_size, float(quant_min),
+              float(quant_max), scale_qmap.data_ptr() if scale_qmap is not None else None, _stream_ptr(x))
+    if _native.declined(code):                      # a view that starts off a 16-byte boundary
+        return None
+    _native.check(code, "qt_fake_quant_gwa")
+    scale.resize_(sf.shape).copy_(sf)
+    zero_point.resize_(zp.shape).copy_(zp)
+    return y
 
 
 def _forward_cpu(input, observe, quantize, qmap, amax_history, scale, quant_max, ch_axis, per_channel, pow2):
