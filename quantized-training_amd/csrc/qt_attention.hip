@@ -100,18 +100,10 @@ __global__ __launch_bounds__(256) void attention_fq_kernel(AttnArgs a) {
     const bool simple = a.mask && a.row_live && a.mask_irregular && *a.mask_irregular == 0;      // uniform over the launch
     const int lv = simple ? a.row_live[b * a.lsb + h * a.lsh + (long)qload * a.lsq] : 0;          // this lane's query row
 
-    Rounder<KIND> rnd{a.fmt, a.lut};
-    if constexpr (KIND == kFmtRows) {
-        // table format with the row words behind the map (qt_format.p1 bit 0, csrc/qt_device.h): the probabilities' fake-quantizer is
-        // arithmetic on a 4 / 8 KiB row table in LDS instead of one gather per element from the 128 KiB map in global memory
-        __shared__ uint4 s_rows[512];
-        const uint4 *gr = (const uint4 *)(a.lut + QT_MAP_ENTRIES);
-        const int nrows = (a.fmt.p1 & 2) ? 512 : 256;
-        for (int i = threadIdx.x; i < nrows; i += 256) s_rows[i] = gr[i];
-        rnd.lds = (const uint16_t *)s_rows;
-        rnd.glut = a.lut;
-        __syncthreads();
-    }
+    // table format with the row words behind the map (qt_format.p1 bit 0, csrc/qt_device.h): the probabilities' fake-quantizer is
+    // arithmetic on a 4 / 8 KiB row table in LDS instead of one gather per element from the 128 KiB map in global memory
+    __shared__ uint4 s_rows[KIND == kFmtRows ? 512 : 1];
+    const Rounder<KIND> rnd = make_rounder<KIND>(a.fmt, a.lut, s_rows, 256);
     const float s = UNIT ? 1.0f : qt_bf2f(qt_f2bf(*a.scale));
     const UniformDiv dv(s);
 

@@ -131,15 +131,8 @@ __global__ __launch_bounds__(512, 1) void attention_rows_split_kernel(Args a) {
     const int q0 = qb * 64;
     const int qrow = q0 + wq * 16 + r, qc = min(qrow, a.Sq - 1);
     // ---- the row table of the probabilities' (and the output's) fake-quantizer
-    Rounder<kFmtRows> rnd{a.fmt, nullptr, nullptr};
-    {
-        uint4 *s_rows = (uint4 *)(lds + kRing);
-        const uint4 *gr = (const uint4 *)(a.lut + QT_MAP_ENTRIES);
-        const int nrows = (a.fmt.p1 & 2) ? 512 : 256;
-        if (t < nrows) s_rows[t] = gr[t];
-        rnd.lds = (const uint16_t *)s_rows;
-        rnd.glut = a.lut;
-    }
+    stage_row_words(a.fmt, a.lut, (uint4 *)(lds + kRing), 512);           // (no barrier here: the first one below comes before any use)
+    const Rounder<kFmtRows> rnd{a.fmt, (const uint16_t *)(lds + kRing), a.lut};
     int nlive, wmax, wmin, my_live;                                        // the row extents: split_row_extents
     split_row_extents(a, b, h, q0, qc, l, nkb, nlive, wmax, wmin, my_live);
     const int niter = (nlive + 1) / 2;                                     // iteration i: blocks 2 i and 2 i + 1
@@ -360,15 +353,7 @@ __global__ __launch_bounds__(256) void value_t_rows_kernel(const uint16_t *v, ui
                                                            const uint16_t *lut) {
     __shared__ __attribute__((aligned(16))) uint16_t tile[value_rows_tile_elems<kBlock>()];
     __shared__ uint4 s_rows[512];
-    Rounder<kFmtRows> rnd{fmt, nullptr, nullptr};
-    {
-        const uint4 *gr = (const uint4 *)(lut + QT_MAP_ENTRIES);
-        const int nrows = (fmt.p1 & 2) ? 512 : 256;
-        for (int i = threadIdx.x; i < nrows; i += 256) s_rows[i] = gr[i];
-        rnd.lds = (const uint16_t *)s_rows;
-        rnd.glut = lut;
-    }
-    __syncthreads();
+    const Rounder<kFmtRows> rnd = make_rounder<kFmtRows>(fmt, lut, s_rows, 256);
     value_t_rows_block<kBlock>(tile, rnd, v, vt, H, Sk, sb, sh, sk, (long)blockIdx.y, (int)blockIdx.x, (int)threadIdx.x);
 }
 

@@ -156,7 +156,7 @@ __global__ __launch_bounds__(kThreads) void attn_train_fwd_kernel(AttnTrainFwdAr
     const uint16_t *mrow = a.mask ? a.mask + (long)b * a.msb + (long)h * a.msh : nullptr;
     uint4 m0 = {0u, 0u, 0u, 0u};
     if (mrow && a.msq == 0 && li < nvec_row) m0 = ((const uint4 *)mrow)[li];      // one mask row for the whole (batch, head): the usual padding mask
-    const Rounder<KIND> rnd = chain_rounder<KIND>(fmt, lut, s_rows, kThreads);
+    const Rounder<KIND> rnd = make_rounder<KIND>(fmt, lut, s_rows, kThreads);
     float sc[5];
     uint32_t amax[5];
 #pragma unroll
@@ -406,7 +406,7 @@ __global__ __launch_bounds__(kThreads) void attn_train_bwd_kernel(AttnTrainBwdAr
     row_load(1, xp1, pr1, mk1);
     row_load(2, xp2, pr2, mk2);
     row_load(3, xp3, pr3, mk3);
-    const Rounder<KIND> rnd = chain_rounder<KIND>(fmt, lut, s_rows, kThreads);
+    const Rounder<KIND> rnd = make_rounder<KIND>(fmt, lut, s_rows, kThreads);
     float sc[2], gsc[3];
     uint32_t amax[2];
 #pragma unroll

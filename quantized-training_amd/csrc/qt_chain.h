@@ -5,9 +5,6 @@
 
 namespace {
 
-constexpr int kIoBf16 = 0;
-constexpr int kIoF32 = 1;
-
 // ---- cross-workgroup column sums in 64-bit fixed point (bias gradients: the chain kernel's bands, the attention backward's batch) -----
 // `arrivals` workgroups each add one partial sum per column to a zeroed accumulator; the one that draws the last ticket reads it.
 // One unit = 2^(E - shift), E = exponent of the largest value an element can take.  A partial sum that is NaN / Inf adds `poison`
@@ -131,22 +128,6 @@ __device__ __forceinline__ uint4 chain_apply(uint4 v, float s, const UniformDiv 
 #pragma unroll
     for (int i = 0; i < 4; ++i) r[i] = pack_bf16x2(bf_lo(r[i]) * dv.s, bf_hi(r[i]) * dv.s);
     return uint4{r[0], r[1], r[2], r[3]};
-}
-
-// A table format's row words (4 - 8 KiB behind the map's 65 536 entries) into LDS: a chain applies several fake-quantizers per vector, and
-// eight row gathers per stage from global memory made its kernels latency-bound (an LDS gather returns in ~100 cycles, an L1 hit in ~500).
-// s_rows: __shared__ uint4[512].  Other kinds: nothing to stage.
-template <int KIND>
-__device__ __forceinline__ Rounder<KIND> chain_rounder(const qt_format &fmt, const uint16_t *lut, uint4 *s_rows, int block) {
-    Rounder<KIND> rnd{fmt, nullptr, lut};
-    if constexpr (KIND == kFmtRows) {
-        const uint4 *g = (const uint4 *)(lut + QT_MAP_ENTRIES);
-        const int nrows = (fmt.p1 & 2) ? 512 : 256;
-        for (int i = threadIdx.x; i < nrows; i += block) s_rows[i] = g[i];
-        rnd.lds = (const uint16_t *)s_rows;
-        __syncthreads();
-    }
-    return rnd;
 }
 
 // All stages of a chain on one vector `v` (the producer's bf16 values): results written where a stage has an output, amax of every

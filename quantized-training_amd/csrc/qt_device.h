@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 // Written for gfx950 only: the scaled matrix instructions (v_mfma_scale_f32_16x16x128_f8f6f4), v_mfma_f32_16x16x32_bf16, the
 // v_cvt_scalef32_pk_* conversions, 16-byte LDS-DMA and the 160 KiB LDS budgets do not exist on any other target.  ARCH is a Makefile
 // variable, so say so at compile time.
@@ -202,6 +204,9 @@ struct UniformDiv {
     __device__ __forceinline__ float operator()(float x) const { return x / s; }
 };
 
+constexpr int kIoBf16 = 0;      // the tensor's element type: bf16 | fp32
+constexpr int kIoF32 = 1;
+
 constexpr int kFmtRows = 5;      // QT_FMT_LUT with the row words behind the map (qt_format.p1 bit 0): the row form, table of rows in LDS
 
 template <int KIND>
@@ -361,6 +366,98 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
         v = v > o ? v : o;
     }
     return v;
+}
+
+// ---- what every fake-quant pass starts with: the table where the kernel reads it, the scale, the divisor class ------------------------
+// A table format's row words (256 or 512 of them behind the map's 65 536 entries: qt_format.p1 bit 0, bit 1 = 512; 4 - 8 KiB) into
+// s_rows (__shared__ uint4[512]): an LDS gather returns in ~100 cycles, an L1 hit in ~500.  The copy ALONE: the barrier that publishes
+// it is make_rounder's, or a later one of the caller's own.
+__device__ __forceinline__ void stage_row_words(const qt_format &fmt, const uint16_t *lut, uint4 *s_rows, int block) {
+    const uint4 *g = (const uint4 *)(lut + QT_MAP_ENTRIES);
+    const int nrows = (fmt.p1 & 2) ? 512 : 256;
+    for (int i = threadIdx.x; i < nrows; i += block) s_rows[i] = g[i];
+}
+
+// The Rounder of a kernel of `block` threads.  kFmtRows: the row words staged in s_rows, a barrier, the map in global memory for the
+// flagged rows.  QT_FMT_LUT: the map where it lies, in global memory.  Closed forms: nothing to stage (s_rows: a dummy of one element).
+template <int KIND>
+__device__ __forceinline__ Rounder<KIND> make_rounder(const qt_format &fmt, const uint16_t *lut, uint4 *s_rows, int block) {
+    Rounder<KIND> rnd{fmt, lut, lut};
+    if constexpr (KIND == kFmtRows) {
+        stage_row_words(fmt, lut, s_rows, block);
+        rnd.lds = (const uint16_t *)s_rows;
+        __syncthreads();
+    }
+    return rnd;
+}
+
+// The whole 128 KiB map into s_lut (__shared__ uint4[kMapVecs]) by a workgroup of BLOCK threads; no barrier.
+constexpr int kMapVecs = QT_MAP_ENTRIES * 2 / 16;
+template <int BLOCK>
+__device__ __forceinline__ void stage_map(const uint16_t *lut, uint4 *s_lut) {
+    const uint4 *g = (const uint4 *)lut;
+#pragma unroll
+    for (int i = 0; i < kMapVecs / BLOCK; ++i) s_lut[i * BLOCK + threadIdx.x] = g[i * BLOCK + threadIdx.x];
+}
+
+// scale[c] (NULL = 1) cast to the tensor's dtype like scale.to(X.dtype), and what the pass derives from it
+struct PassScale {
+    float s;
+    bool unit;        // s == 1: x / 1 and r * 1 are exact, both are skipped
+    UniformDiv dv;
+};
+template <int IO>
+__device__ __forceinline__ PassScale pass_scale(const float *scale, size_t c = 0) {
+    float s = scale ? scale[c] : 1.0f;
+    if constexpr (IO == kIoBf16) s = qt_bf2f(qt_f2bf(s));
+    return PassScale{s, s == 1.0f, UniformDiv(s)};
+}
+
+// f(std::integral_constant<int, DIV>) for the scale's divisor class [, std::bool_constant<OBS>]: a uniform branch around code compiled
+// per class.  f is a generic lambda marked __attribute__((always_inline)).
+template <class F>
+__device__ __forceinline__ void with_div(const PassScale &ps, F &&f) {
+    if (ps.unit) f(std::integral_constant<int, kDivUnit>{});
+    else if (ps.dv.safe) f(std::integral_constant<int, kDivFast>{});
+    else f(std::integral_constant<int, kDivExact>{});
+}
+template <class F>
+__device__ __forceinline__ void with_div_obs(const PassScale &ps, bool obs, F &&f) {
+    if (obs) with_div(ps, [&](auto div) __attribute__((always_inline)) { f(div, std::true_type{}); });
+    else with_div(ps, [&](auto div) __attribute__((always_inline)) { f(div, std::false_type{}); });
+}
+
+// amax of one row of a per-channel pass (256 threads) into the channel's slot.  Unlike the per-tensor commit (block_amax_commit,
+// qt_elementwise.hip) it does not read the slot before the atomic: a channel's slot meets the few workgroups that hold its rows, not
+// thousands that queue on one address.  s_part is reused by the workgroup's next row, hence the second barrier.
+__device__ __forceinline__ void row_amax_commit(uint32_t amax, uint32_t *slot, uint32_t (&s_part)[4]) {
+    amax = wave_max_u32(amax);
+    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = amax;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t m = s_part[0];
+        for (int i = 1; i < 4; ++i) m = m > s_part[i] ? m : s_part[i];
+        if (m) atomicMax(slot, m);
+    }
+    __syncthreads();
+}
+
+// The item that workgroup blockIdx.x's tile belongs to in a many-tensor launch: the last one whose first tile is <= blockIdx.x (`first`
+// ascends).  Wave 0 looks at all items at once (lane l at items l, l + 64, ...: independent loads, one round trip) -- a binary search
+// is log2(count) DEPENDENT loads, 3-5 us in front of a tile that takes 3.  Ends in a barrier.
+template <class ITEM>
+__device__ __forceinline__ int tile_item(const ITEM *__restrict__ items, int count) {
+    __shared__ int s_item;
+    if (threadIdx.x < 64) {
+        int best = 0;
+        for (int j = (int)threadIdx.x; j < count; j += 64)
+            if (items[j].first <= (unsigned long long)blockIdx.x) best = j;
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) best = max(best, __shfl_xor(best, off, 64));
+        if (threadIdx.x == 0) s_item = best;
+    }
+    __syncthreads();
+    return s_item;
 }
 
 // ---- 16-byte LDS-DMA (global_load_lds_dwordx4): each of the wave's 64 lanes brings 16 bytes from global memory, and they land

@@ -125,48 +125,43 @@ __device__ __forceinline__ void fq_stream(const uint4 *__restrict__ x, uint4 *__
 //   x, y      : 16-B aligned base; nvec 16-B vectors followed by `ntail` scalar elements
 //   scale     : fp32 scale on device (NULL = 1); cast to the input dtype like scale.to(X.dtype)
 //   amax_out  : uint32 view of amax_history[0] (NULL when OBS is false)
-template <int IO, int KIND, bool OBS, int BLOCK, int kUnroll = 1, int NT = 0>
+// TABLE: where a table format's table is read (closed forms have none).
+//   kTableLds     the map (QT_FMT_LUT: 128 KiB, one 1024-thread workgroup per CU) or its row words (kFmtRows: 4 - 8 KiB, many
+//                 workgroups per CU) staged in LDS, a barrier in front of the first load: the long passes.
+//   kTableGlobal  read where it lies (L1 / L2 hits), eight gathers in flight per vector -- no staging and no barrier in front of the
+//                 first load.  The row form for SHORT passes (a lane has one or two vectors: the [2048, 768 .. 3072] activations and
+//                 gradients of a training step), and the plain map for aligned tensors too small to amortise a 128 KiB LDS fill per
+//                 workgroup (a [2048, 768] gradient is 1.5 M elements; the element-granular kernel below moves 2 B per lane per
+//                 access -- 12.4 us for such a gradient; this one is bandwidth-shaped again).
+// An OBSERVED short pass runs 1024-thread workgroups: every workgroup that can raise the running maximum issues an atomicMax on ONE
+// address, the slot starts each step at zero, and same-address atomics serialise at ~12 ns each -- 768 workgroups of 256 threads spent
+// most of a [2048, 768] launch's 10.9 us queueing there.
+constexpr int kTableLds = 0, kTableGlobal = 1;
+
+template <int IO, int KIND, bool OBS, int BLOCK, int kUnroll = 1, int NT = 0, int TABLE = kTableLds>
 __global__ __launch_bounds__(BLOCK) void fq_kernel(const void *__restrict__ xv, void *__restrict__ yv, size_t nvec,
                                                   size_t n, qt_format fmt, const uint16_t *__restrict__ lut,
                                                   const float *__restrict__ scale, uint32_t *amax_out) {
-    Rounder<KIND> rnd{fmt, nullptr};
-    if constexpr (KIND == QT_FMT_LUT) {
-        constexpr int kVecs = QT_MAP_ENTRIES * 2 / 16;
-        __shared__ uint4 s_lut[kVecs];
-        if (yv) {
-            const uint4 *g = (const uint4 *)lut;
-#pragma unroll
-            for (int i = 0; i < kVecs / BLOCK; ++i) s_lut[i * BLOCK + threadIdx.x] = g[i * BLOCK + threadIdx.x];
-        }
-        rnd.lds = (const uint16_t *)s_lut;
+    constexpr bool kMapInLds = KIND == QT_FMT_LUT && TABLE == kTableLds, kRowsInLds = KIND == kFmtRows && TABLE == kTableLds;
+    __shared__ uint4 s_table[kMapInLds ? kMapVecs : (kRowsInLds ? 512 : 1)];
+    Rounder<KIND> rnd{fmt, lut, lut};
+    if constexpr (kMapInLds) {
+        if (yv) stage_map<BLOCK>(lut, s_table);
+        rnd.lds = (const uint16_t *)s_table;
         __syncthreads();
+    } else if constexpr (kRowsInLds) {
+        rnd = make_rounder<kFmtRows>(fmt, lut, s_table, BLOCK);
+    } else if constexpr (KIND == kFmtRows) {
+        rnd = Rounder<kFmtRows>{fmt, lut + QT_MAP_ENTRIES, lut};
     }
-    if constexpr (KIND == kFmtRows) {
-        // the row words sit behind the 65 536 map entries: 4 KiB (rows by exponent) or 8 KiB in LDS, many workgroups per CU
-        __shared__ uint4 s_rows[512];
-        const uint4 *g = (const uint4 *)(lut + QT_MAP_ENTRIES);
-        const int nrows = (fmt.p1 & 2) ? 512 : 256;
-        for (int i = threadIdx.x; i < nrows; i += BLOCK) s_rows[i] = g[i];
-        rnd.lds = (const uint16_t *)s_rows;
-        rnd.glut = lut;
-        __syncthreads();
-    }
-    float s = scale ? *scale : 1.0f;
-    if constexpr (IO == kIoBf16) s = qt_bf2f(qt_f2bf(s));
-    const bool unit = (s == 1.0f);
+    const PassScale ps = pass_scale<IO>(scale);
     uint32_t amax = 0;
-    const uint4 *x = (const uint4 *)xv;
-    uint4 *y = (uint4 *)yv;
-    const UniformDiv dv(s);
-    if (unit)
-        fq_stream<IO, KIND, kDivUnit, OBS, BLOCK, kUnroll, NT>(x, y, nvec, dv, rnd, amax);
-    else if (dv.safe)
-        fq_stream<IO, KIND, kDivFast, OBS, BLOCK, kUnroll, NT>(x, y, nvec, dv, rnd, amax);
-    else
-        fq_stream<IO, KIND, kDivExact, OBS, BLOCK, kUnroll, NT>(x, y, nvec, dv, rnd, amax);
+    with_div(ps, [&](auto div) __attribute__((always_inline)) {
+        fq_stream<IO, KIND, decltype(div)::value, OBS, BLOCK, kUnroll, NT>((const uint4 *)xv, (uint4 *)yv, nvec, ps.dv, rnd, amax);
+    });
     constexpr int kPer = IO == kIoBf16 ? 8 : 4;
     if (blockIdx.x == gridDim.x - 1) {
-        for (size_t i = nvec * kPer + threadIdx.x; i < n; i += BLOCK) fq_one<IO, KIND, OBS>(xv, yv, i, s, unit, rnd, amax);
+        for (size_t i = nvec * kPer + threadIdx.x; i < n; i += BLOCK) fq_one<IO, KIND, OBS>(xv, yv, i, ps.s, ps.unit, rnd, amax);
     }
     if constexpr (OBS) block_amax_commit<BLOCK>(amax, amax_out);
 }
@@ -178,70 +173,10 @@ __global__ __launch_bounds__(256) void fq_gather_kernel(const void *__restrict__
                                                        qt_format fmt, const uint16_t *__restrict__ lut,
                                                        const float *__restrict__ scale, uint32_t *amax_out) {
     Rounder<KIND> rnd{fmt, lut};
-    float s = scale ? *scale : 1.0f;
-    if constexpr (IO == kIoBf16) s = qt_bf2f(qt_f2bf(s));
-    const bool unit = (s == 1.0f);
+    const PassScale ps = pass_scale<IO>(scale);
     uint32_t amax = 0;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
-        fq_one<IO, KIND, OBS>(xv, yv, i, s, unit, rnd, amax);
-    if constexpr (OBS) block_amax_commit<256>(amax, amax_out);
-}
-
-// The row form for SHORT passes (a lane has one or two vectors: the [2048, 768 .. 3072] activations and gradients of a training step):
-// the 4 - 8 KiB row table is read where it lies, in global memory behind the map (L1 / L2 hits), eight gathers in flight per vector --
-// no staging into LDS and no barrier in front of the first load.  An OBSERVED short pass runs 1024-thread workgroups: every workgroup
-// that can raise the running maximum issues an atomicMax on ONE address, the slot starts each step at zero, and same-address atomics
-// serialise at ~12 ns each -- 768 workgroups of 256 threads spent most of a [2048, 768] launch's 10.9 us queueing there.
-template <int IO, bool OBS, int BLOCK, int UNR = 1>
-__global__ __launch_bounds__(BLOCK) void fq_rows_direct_kernel(const void *__restrict__ xv, void *__restrict__ yv, size_t nvec, size_t n,
-                                                            qt_format fmt, const uint16_t *__restrict__ lut, const float *__restrict__ scale,
-                                                            uint32_t *amax_out) {
-    Rounder<kFmtRows> rnd{fmt, lut + QT_MAP_ENTRIES, lut};
-    float s = scale ? *scale : 1.0f;
-    if constexpr (IO == kIoBf16) s = qt_bf2f(qt_f2bf(s));
-    const bool unit = (s == 1.0f);
-    uint32_t amax = 0;
-    const uint4 *x = (const uint4 *)xv;
-    uint4 *y = (uint4 *)yv;
-    const UniformDiv dv(s);
-    if (unit)
-        fq_stream<IO, kFmtRows, kDivUnit, OBS, BLOCK, UNR, 0>(x, y, nvec, dv, rnd, amax);
-    else if (dv.safe)
-        fq_stream<IO, kFmtRows, kDivFast, OBS, BLOCK, UNR, 0>(x, y, nvec, dv, rnd, amax);
-    else
-        fq_stream<IO, kFmtRows, kDivExact, OBS, BLOCK, UNR, 0>(x, y, nvec, dv, rnd, amax);
-    constexpr int kPer = IO == kIoBf16 ? 8 : 4;
-    if (blockIdx.x == gridDim.x - 1) {
-        for (size_t i = nvec * kPer + threadIdx.x; i < n; i += BLOCK) fq_one<IO, kFmtRows, OBS>(xv, yv, i, s, unit, rnd, amax);
-    }
-    if constexpr (OBS) block_amax_commit<BLOCK>(amax, amax_out);
-}
-
-// Vector-granular variant of the same (aligned tensors too small for the LDS table: a [2048, 768] gradient is 1.5 M
-// elements): 16-B loads and stores, eight gathers per lane from the L2-resident table.  The element-granular kernel
-// above moves 2 B per lane per access -- 12.4 us for such a gradient; this one is bandwidth-shaped again.
-template <int IO, bool OBS>
-__global__ __launch_bounds__(256) void fq_gather_vec_kernel(const void *__restrict__ xv, void *__restrict__ yv, size_t nvec,
-                                                           size_t n, qt_format fmt, const uint16_t *__restrict__ lut,
-                                                           const float *__restrict__ scale, uint32_t *amax_out) {
-    Rounder<QT_FMT_LUT> rnd{fmt, lut};
-    float s = scale ? *scale : 1.0f;
-    if constexpr (IO == kIoBf16) s = qt_bf2f(qt_f2bf(s));
-    const bool unit = (s == 1.0f);
-    uint32_t amax = 0;
-    const uint4 *x = (const uint4 *)xv;
-    uint4 *y = (uint4 *)yv;
-    const UniformDiv dv(s);
-    if (unit)
-        fq_stream<IO, QT_FMT_LUT, kDivUnit, OBS, 256, 1, 0>(x, y, nvec, dv, rnd, amax);
-    else if (dv.safe)
-        fq_stream<IO, QT_FMT_LUT, kDivFast, OBS, 256, 1, 0>(x, y, nvec, dv, rnd, amax);
-    else
-        fq_stream<IO, QT_FMT_LUT, kDivExact, OBS, 256, 1, 0>(x, y, nvec, dv, rnd, amax);
-    constexpr int kPer = IO == kIoBf16 ? 8 : 4;
-    if (blockIdx.x == gridDim.x - 1) {
-        for (size_t i = nvec * kPer + threadIdx.x; i < n; i += 256) fq_one<IO, QT_FMT_LUT, OBS>(xv, yv, i, s, unit, rnd, amax);
-    }
+        fq_one<IO, KIND, OBS>(xv, yv, i, ps.s, ps.unit, rnd, amax);
     if constexpr (OBS) block_amax_commit<256>(amax, amax_out);
 }
 
@@ -331,7 +266,7 @@ __global__ __launch_bounds__(kChainBlock) void fq_chain_kernel(ChainArgs a, qt_f
     __shared__ uint4 s_rows[KIND == kFmtRows ? 512 : 1];
     QT_EW_STAMP(a, 0);
     QT_EW_STAMP_HEAD(a, 0x100 + NS * 16 + (a.colsum_stage >= 0 ? 1 : 0) + (a.pre_op << 1));
-    const Rounder<KIND> rnd = chain_rounder<KIND>(fmt, lut, s_rows, kChainBlock);
+    const Rounder<KIND> rnd = make_rounder<KIND>(fmt, lut, s_rows, kChainBlock);
     QT_EW_STAMP(a, 1);
     const int t = threadIdx.x;
     const int v = t % kChainStripV, rl = t / kChainStripV;
@@ -476,7 +411,7 @@ struct LnTrainArgs {
 template <int KIND, int NS, int BLOCK>
 __global__ __launch_bounds__(BLOCK) void ln_train_fwd_kernel(LnTrainArgs a, qt_format fmt, const uint16_t *__restrict__ lut) {
     __shared__ uint4 s_rows[KIND == kFmtRows ? 512 : 1];
-    const Rounder<KIND> rnd = chain_rounder<KIND>(fmt, lut, s_rows, BLOCK);
+    const Rounder<KIND> rnd = make_rounder<KIND>(fmt, lut, s_rows, BLOCK);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long row = (long)blockIdx.x * (BLOCK / 64) + wave;
     float sc[NS];
@@ -574,7 +509,7 @@ __global__ __launch_bounds__(BLOCK) void ln_train_bwd_kernel(LnBwdArgs a, qt_for
     __shared__ uint4 s_rows[KIND == kFmtRows ? 512 : 1];
     QT_EW_STAMP(a, 0);
     QT_EW_STAMP_HEAD(a, 0x200 + NS * 16 + a.nfan * 2 + (a.colsum_stage >= 0 ? 1 : 0));
-    const Rounder<KIND> rnd = chain_rounder<KIND>(fmt, lut, s_rows, BLOCK);
+    const Rounder<KIND> rnd = make_rounder<KIND>(fmt, lut, s_rows, BLOCK);
     QT_EW_STAMP(a, 1);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float sc[NS];
@@ -942,41 +877,20 @@ constexpr int kMultiBlock = 256, kMultiUnroll = 4, kMultiTile = kMultiBlock * kM
 template <int KIND>
 __global__ __launch_bounds__(kMultiBlock) void fq_multi_kernel(const qt_fq_item_dev *__restrict__ items, int count, qt_format fmt,
                                                               const uint16_t *__restrict__ lut) {
-    Rounder<KIND> rnd{fmt, nullptr};
-    if constexpr (KIND == kFmtRows) {
-        __shared__ uint4 s_rows[512];
-        const uint4 *g = (const uint4 *)(lut + QT_MAP_ENTRIES);
-        const int nrows = (fmt.p1 & 2) ? 512 : 256;
-        for (int i = threadIdx.x; i < nrows; i += kMultiBlock) s_rows[i] = g[i];
-        rnd.lds = (const uint16_t *)s_rows;
-        rnd.glut = lut;
-        __syncthreads();
-    }
-    // the tensor this tile belongs to: the last item whose first tile is <= blockIdx.x.  Wave 0 looks at all items at once (lane l at
-    // items l, l + 64, ...: independent loads, one round trip) -- a binary search is log2(count) DEPENDENT loads, 3-5 us in front of a
-    // tile that takes 3
-    __shared__ int s_item;
-    if (threadIdx.x < 64) {
-        int best = 0;
-        for (int j = (int)threadIdx.x; j < count; j += 64)
-            if (items[j].first <= (unsigned long long)blockIdx.x) best = j;          // (`first` ascends with j)
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) best = max(best, __shfl_xor(best, off, 64));
-        if (threadIdx.x == 0) s_item = best;
-    }
-    __syncthreads();
-    const qt_fq_item_dev it = items[s_item];
+    __shared__ uint4 s_rows[KIND == kFmtRows ? 512 : 1];
+    const Rounder<KIND> rnd = make_rounder<KIND>(fmt, lut, s_rows, kMultiBlock);
+    const qt_fq_item_dev it = items[tile_item(items, count)];
     const size_t v0 = ((size_t)blockIdx.x - it.first) * kMultiTile;
-    const float s = qt_bf2f(qt_f2bf(*it.scale));
+    const PassScale ps = pass_scale<kIoBf16>(it.scale);
     // (pointers that come out of memory are generic to the compiler: say that they are global, or every access is a flat_ instruction)
     typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
     typedef const __attribute__((address_space(1))) u32x4_t *gload_t;
     typedef __attribute__((address_space(1))) u32x4_t *gstore_t;
     const gload_t gx = (gload_t)(const void *)it.x;
     const gstore_t gy = (gstore_t)(void *)it.y;
-    const UniformDiv dv(s);
     uint32_t amax = 0;
-    auto run = [&](auto divc, auto obsc) __attribute__((always_inline)) {
+    const bool obs = it.amax != nullptr;                      // uniform
+    with_div_obs(ps, obs, [&](auto divc, auto obsc) __attribute__((always_inline)) {
         constexpr int DIV = decltype(divc)::value;
         constexpr bool OBS = decltype(obsc)::value;
         uint4 v[kMultiUnroll];
@@ -992,21 +906,10 @@ __global__ __launch_bounds__(kMultiBlock) void fq_multi_kernel(const qt_fq_item_
 #pragma unroll
         for (int u = 0; u < kMultiUnroll; ++u) {
             const size_t i = v0 + (size_t)u * kMultiBlock + threadIdx.x;
-            const uint4 r = fq_vec<kIoBf16, KIND, DIV, OBS>(v[u], dv, rnd, amax);
+            const uint4 r = fq_vec<kIoBf16, KIND, DIV, OBS>(v[u], ps.dv, rnd, amax);
             if (i < it.nvec) gy[i] = u32x4_t{r.x, r.y, r.z, r.w};
         }
-    };
-    const bool obs = it.amax != nullptr;                      // uniform
-    if (s == 1.0f) {
-        if (obs) run(std::integral_constant<int, kDivUnit>{}, std::true_type{});
-        else run(std::integral_constant<int, kDivUnit>{}, std::false_type{});
-    } else if (dv.safe) {
-        if (obs) run(std::integral_constant<int, kDivFast>{}, std::true_type{});
-        else run(std::integral_constant<int, kDivFast>{}, std::false_type{});
-    } else {
-        if (obs) run(std::integral_constant<int, kDivExact>{}, std::true_type{});
-        else run(std::integral_constant<int, kDivExact>{}, std::false_type{});
-    }
+    });
     if (obs) block_amax_commit<kMultiBlock>(amax, it.amax);
 }
 
@@ -1025,17 +928,7 @@ constexpr int kMulti8Tile = 256 * 4;
 template <bool E5M2>
 __global__ __launch_bounds__(256) void fq8_items_kernel(const qt_fq8_item_dev *__restrict__ items, int count, qt_format fmt) {
     // (the tile's tensor by one round of independent loads, its pointers declared global: see fq_multi_kernel)
-    __shared__ int s_item;
-    if (threadIdx.x < 64) {
-        int best = 0;
-        for (int j = (int)threadIdx.x; j < count; j += 64)
-            if (items[j].first <= (unsigned long long)blockIdx.x) best = j;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) best = max(best, __shfl_xor(best, off, 64));
-        if (threadIdx.x == 0) s_item = best;
-    }
-    __syncthreads();
-    const qt_fq8_item_dev it = items[s_item];
+    const qt_fq8_item_dev it = items[tile_item(items, count)];
     const size_t p0 = ((size_t)blockIdx.x - it.first) * kMulti8Tile;
     typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
     const __attribute__((address_space(1))) u32x4_t *const gx = (const __attribute__((address_space(1))) u32x4_t *)(const void *)it.x;
@@ -1187,24 +1080,14 @@ __global__ __launch_bounds__(256) void fq_pc_kernel(const void *__restrict__ xv,
     __shared__ uint32_t s_part[4];
     for (size_t row = blockIdx.x; row < rows; row += gridDim.x) {
         const size_t c = row % C;
-        float s = scale ? scale[c] : 1.0f;
-        if constexpr (IO == kIoBf16) s = qt_bf2f(qt_f2bf(s));
-        const bool unit = (s == 1.0f);
+        const PassScale ps = pass_scale<IO>(scale, c);
         uint32_t amax = 0;
         const size_t base = row * inner;
         if (amax_out) {
-            for (size_t i = threadIdx.x; i < inner; i += 256) fq_one<IO, KIND, true>(xv, yv, base + i, s, unit, rnd, amax);
-            amax = wave_max_u32(amax);
-            if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = amax;
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                uint32_t m = s_part[0];
-                for (int i = 1; i < 4; ++i) m = m > s_part[i] ? m : s_part[i];
-                if (m) atomicMax(amax_out + c, m);
-            }
-            __syncthreads();
+            for (size_t i = threadIdx.x; i < inner; i += 256) fq_one<IO, KIND, true>(xv, yv, base + i, ps.s, ps.unit, rnd, amax);
+            row_amax_commit(amax, amax_out + c, s_part);
         } else {
-            for (size_t i = threadIdx.x; i < inner; i += 256) fq_one<IO, KIND, false>(xv, yv, base + i, s, unit, rnd, amax);
+            for (size_t i = threadIdx.x; i < inner; i += 256) fq_one<IO, KIND, false>(xv, yv, base + i, ps.s, ps.unit, rnd, amax);
         }
     }
 }
@@ -1270,38 +1153,24 @@ template <int IO, int KINDL>
 __global__ __launch_bounds__(1024) void fq_pc_vec_lds_kernel(const uint4 *__restrict__ x, uint4 *__restrict__ y, size_t rows,
                                                              size_t C, size_t vpr, qt_format fmt, const uint16_t *__restrict__ lut,
                                                              const float *__restrict__ scale, uint32_t *amax_out) {
-    constexpr int kVecs = QT_MAP_ENTRIES * 2 / 16;
-    __shared__ uint4 s_lut[kVecs];
-    {
-        const uint4 *g = (const uint4 *)lut;
-#pragma unroll
-        for (int i = 0; i < kVecs / 1024; ++i) s_lut[i * 1024 + threadIdx.x] = g[i * 1024 + threadIdx.x];
-    }
+    __shared__ uint4 s_lut[kMapVecs];
+    stage_map<1024>(lut, s_lut);
     __syncthreads();
     Rounder<KINDL> rnd{fmt, (const uint16_t *)s_lut};
     const int lane = threadIdx.x & 63;
     const size_t wave = (size_t)blockIdx.x * 16 + (threadIdx.x >> 6), nwaves = (size_t)gridDim.x * 16;
     for (size_t row = wave; row < rows; row += nwaves) {
         const size_t c = row % C;
-        float s = scale ? scale[c] : 1.0f;
-        if constexpr (IO == kIoBf16) s = qt_bf2f(qt_f2bf(s));
-        const bool unit = (s == 1.0f);
-        const UniformDiv dv(s);
+        const PassScale ps = pass_scale<IO>(scale, c);
         uint32_t amax = 0;
         const uint4 *xr = x + row * vpr;
         uint4 *yr = y + row * vpr;
         for (size_t i = lane; i < vpr; i += 64) {
             const uint4 in = xr[i];
             uint4 r;
-            if (amax_out) {
-                if (unit) r = fq_vec<IO, KINDL, kDivUnit, true>(in, dv, rnd, amax);
-                else if (dv.safe) r = fq_vec<IO, KINDL, kDivFast, true>(in, dv, rnd, amax);
-                else r = fq_vec<IO, KINDL, kDivExact, true>(in, dv, rnd, amax);
-            } else {
-                if (unit) r = fq_vec<IO, KINDL, kDivUnit, false>(in, dv, rnd, amax);
-                else if (dv.safe) r = fq_vec<IO, KINDL, kDivFast, false>(in, dv, rnd, amax);
-                else r = fq_vec<IO, KINDL, kDivExact, false>(in, dv, rnd, amax);
-            }
+            with_div_obs(ps, amax_out != nullptr, [&](auto div, auto obs) __attribute__((always_inline)) {
+                r = fq_vec<IO, KINDL, decltype(div)::value, decltype(obs)::value>(in, ps.dv, rnd, amax);
+            });
             yr[i] = r;
         }
         if (amax_out) {
@@ -1319,14 +1188,13 @@ __global__ __launch_bounds__(256) void fq_pc_last_kernel(const void *__restrict_
     Rounder<KIND> rnd{fmt, lut};
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
         const size_t c = i % C;
-        float s = scale ? scale[c] : 1.0f;
-        if constexpr (IO == kIoBf16) s = qt_bf2f(qt_f2bf(s));
+        const PassScale ps = pass_scale<IO>(scale, c);
         uint32_t amax = 0;
         if (amax_out) {
-            fq_one<IO, KIND, true>(xv, yv, i, s, s == 1.0f, rnd, amax);
+            fq_one<IO, KIND, true>(xv, yv, i, ps.s, ps.unit, rnd, amax);
             if (amax) atomicMax(amax_out + c, amax);
         } else {
-            fq_one<IO, KIND, false>(xv, yv, i, s, s == 1.0f, rnd, amax);
+            fq_one<IO, KIND, false>(xv, yv, i, ps.s, ps.unit, rnd, amax);
         }
     }
 }
@@ -1498,10 +1366,12 @@ int launch_fq_kind(const void *x, void *y, size_t n, const qt_format &fmt, const
             static const int e_row_blocks = getenv("QT_ROW_BLOCKS") ? atoi(getenv("QT_ROW_BLOCKS")) : 0;   // tools/ only: workgroups per CU
             row_blocks = e_row_blocks;
 #endif
-            if (IO == kIoBf16 && nv <= kRowsDirectMaxVecs) {           // short pass: the table where it lies (fq_rows_direct_kernel)
-                if (amax) fq_rows_direct_kernel<IO, true, 1024><<<grid_for(nv, 1024, 2), 1024, 0, st>>>(x, y, nv, n, fmt, lut, scale, amax);
-                else fq_rows_direct_kernel<IO, false, 256><<<grid_for(nv, 256, 8), 256, 0, st>>>(x, y, nv, n, fmt, lut, scale, amax);
-                return qt_launch_status();
+            if constexpr (IO == kIoBf16) {
+                if (nv <= kRowsDirectMaxVecs) {                        // short pass: the row words where they lie (kTableGlobal)
+                    if (amax) fq_kernel<IO, kFmtRows, true, 1024, 1, 0, kTableGlobal><<<grid_for(nv, 1024, 2), 1024, 0, st>>>(x, y, nv, n, fmt, lut, scale, amax);
+                    else fq_kernel<IO, kFmtRows, false, 256, 1, 0, kTableGlobal><<<grid_for(nv, 256, 8), 256, 0, st>>>(x, y, nv, n, fmt, lut, scale, amax);
+                    return qt_launch_status();
+                }
             }
             unsigned grid = grid_for(nv, (size_t)kAluBlock * kUnroll, row_blocks ? row_blocks : 8);
             qt_pick_bool(amax != nullptr, [&](auto OBS) {
@@ -1513,7 +1383,7 @@ int launch_fq_kind(const void *x, void *y, size_t n, const qt_format &fmt, const
             const size_t nv = n / kPer;
             unsigned grid = grid_for(nv, 256, 8);
             qt_pick_bool(amax != nullptr, [&](auto OBS) {
-                fq_gather_vec_kernel<IO, decltype(OBS)::value><<<grid, 256, 0, st>>>(x, y, nv, n, fmt, lut, scale, amax);
+                fq_kernel<IO, QT_FMT_LUT, decltype(OBS)::value, 256, 1, 0, kTableGlobal><<<grid, 256, 0, st>>>(x, y, nv, n, fmt, lut, scale, amax);
             });
             return qt_launch_status();
         }

@@ -151,13 +151,7 @@ __global__ __launch_bounds__(256) void silu_mul_map_kernel(const uint4 *__restri
                                                            size_t nvec, qt_format fmt, const uint16_t *__restrict__ map, size_t cv, size_t rs_g,
                                                            size_t rs_u) {
     __shared__ uint4 s_rows[512];
-    {
-        const uint4 *gr = (const uint4 *)(map + QT_MAP_ENTRIES);
-        const int nrows = (fmt.p1 & 2) ? 512 : 256;
-        for (int i = threadIdx.x; i < nrows; i += 256) s_rows[i] = gr[i];
-        __syncthreads();
-    }
-    const Rounder<kFmtRows> rnd{fmt, (const uint16_t *)s_rows, map};
+    const Rounder<kFmtRows> rnd = make_rounder<kFmtRows>(fmt, map, s_rows, 256);
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (size_t)gridDim.x * 256) {
         const size_t row = i / cv, col = i - row * cv;
         const uint4 a = g[row * rs_g + col], b = u[row * rs_u + col];
@@ -324,9 +318,7 @@ __device__ __forceinline__ void rope_fq_token(const RopeFqArgs &a, size_t bs0, u
 __global__ __launch_bounds__(256) void rope_fq_kernel(RopeFqArgs q, RopeFqArgs k, unsigned tpb) {
     __shared__ uint4 s_rope_rows[512];
     if (q.map) {                                             // one table format for q and k (checked on the host)
-        const uint4 *gr = (const uint4 *)(q.map + QT_MAP_ENTRIES);
-        const int nrows = (q.fmt.p1 & 2) ? 512 : 256;
-        for (int i = threadIdx.x; i < nrows; i += 256) s_rope_rows[i] = gr[i];
+        stage_row_words(q.fmt, q.map, s_rope_rows, 256);
         __syncthreads();
         q.rows_lds = k.rows_lds = (const uint16_t *)s_rope_rows;
     }
@@ -386,13 +378,9 @@ __global__ __launch_bounds__(256) void rope_map_value_kernel(RopeFqArgs q, RopeF
                                                              unsigned tpb) {
     __shared__ __attribute__((aligned(16))) uint16_t tile[value_rows_tile_elems<64>()];
     __shared__ uint4 s_rows[512];
-    {
-        const uint4 *gr = (const uint4 *)(q.map + QT_MAP_ENTRIES);
-        const int nrows = (q.fmt.p1 & 2) ? 512 : 256;
-        for (int i = threadIdx.x; i < nrows; i += 256) s_rows[i] = gr[i];
-        __syncthreads();
-        q.rows_lds = k.rows_lds = (const uint16_t *)s_rows;
-    }
+    stage_row_words(q.fmt, q.map, s_rows, 256);
+    __syncthreads();
+    q.rows_lds = k.rows_lds = (const uint16_t *)s_rows;
     if (blockIdx.x < wp.blocks) {
         const Rounder<kFmtRows> rnd{q.fmt, (const uint16_t *)s_rows, q.map};
         // two workgroups per CU with four loads in flight per lane: the bytes in flight of the stand-alone pass (eight workgroups of one

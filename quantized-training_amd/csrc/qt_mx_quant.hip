@@ -22,8 +22,6 @@
 
 namespace {
 
-constexpr int kIoBf16 = 0, kIoF32 = 1;
-
 struct MxQuantArgs {
     const uint4 *x;
     uint4 *q;                 // element values, tensor dtype (NULL = not wanted)
@@ -74,11 +72,7 @@ __global__ __launch_bounds__(LDS_TABLE ? 1024 : 256) void quantize_mx_kernel(MxQ
     Rounder<kFmtRows> rnd{a.fmt, nullptr, a.lut};
     if constexpr (ROWS) {
         __shared__ uint4 s_rows[512];
-        const uint4 *gr = (const uint4 *)(a.lut + QT_MAP_ENTRIES);
-        const int nrows = (a.fmt.p1 & 2) ? 512 : 256;
-        for (int i = threadIdx.x; i < nrows; i += kThreads) s_rows[i] = gr[i];
-        rnd.lds = (const uint16_t *)s_rows;
-        __syncthreads();
+        rnd = make_rounder<kFmtRows>(a.fmt, a.lut, s_rows, kThreads);
     }
     auto look = [&](uint32_t img) __attribute__((always_inline)) -> uint32_t {      // image of map[x]
         if constexpr (ROWS) return rnd(img);

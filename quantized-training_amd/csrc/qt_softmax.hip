@@ -64,21 +64,11 @@ __global__ __launch_bounds__(256) void softmax_fq_kernel(SoftmaxArgs a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int li = lane % G, sub = lane / G;
     constexpr int RPW = 64 / G;
-    Rounder<KIND> rnd{a.fmt, a.lut};
-    if constexpr (KIND == kFmtRows) {
-        // table formats whose map came with its row form (qt_format.p1 bit 0): the row words in LDS instead of a gather from the
-        // 128 KiB map in L2 per probability (csrc/qt_device.h, Rounder<kFmtRows>)
-        __shared__ uint4 s_rows[512];
-        const uint4 *g = (const uint4 *)(a.lut + QT_MAP_ENTRIES);
-        const int nrows = (a.fmt.p1 & 2) ? 512 : 256;
-        for (int i = threadIdx.x; i < nrows; i += 256) s_rows[i] = g[i];
-        rnd.lds = (const uint16_t *)s_rows;
-        rnd.glut = a.lut;
-        __syncthreads();
-    }
-    const float s = a.scale ? qt_bf2f(qt_f2bf(*a.scale)) : 1.0f;
-    const bool unit = s == 1.0f;
-    const UniformDiv dv(s);
+    // table formats whose map came with its row form (qt_format.p1 bit 0): the row words in LDS instead of a gather from the
+    // 128 KiB map in L2 per probability (csrc/qt_device.h, Rounder<kFmtRows>)
+    __shared__ uint4 s_rows[KIND == kFmtRows ? 512 : 1];
+    const Rounder<KIND> rnd = make_rounder<KIND>(a.fmt, a.lut, s_rows, 256);
+    const PassScale ps = pass_scale<kIoBf16>(a.scale);
     const int nvec_row = (int)(a.cols / 8);
     uint32_t amax = 0;
     for (long row0 = ((long)blockIdx.x * 4 + wave) * RPW; row0 < a.rows; row0 += (long)gridDim.x * 4 * RPW) {
@@ -189,13 +179,13 @@ __global__ __launch_bounds__(256) void softmax_fq_kernel(SoftmaxArgs a) {
                             continue;
                         }
                     }
-                    if (!unit) {
-                        uint32_t qd = pack_bf16x2(dv.exact(qt_u2f(lo)), dv.exact(qt_u2f(hi)));
+                    if (!ps.unit) {
+                        uint32_t qd = pack_bf16x2(ps.dv.exact(qt_u2f(lo)), ps.dv.exact(qt_u2f(hi)));
                         lo = qd << 16;
                         hi = qd & 0xFFFF0000u;
                     }
                     const uint32_t r0 = rnd(lo), r1 = rnd(hi);
-                    w[j] = unit ? ((r0 >> 16) | (r1 & 0xFFFF0000u)) : pack_bf16x2(qt_u2f(r0) * s, qt_u2f(r1) * s);
+                    w[j] = ps.unit ? ((r0 >> 16) | (r1 & 0xFFFF0000u)) : pack_bf16x2(qt_u2f(r0) * ps.s, qt_u2f(r1) * ps.s);
                     f8[2 * j] = qt_u2f(r0);
                     f8[2 * j + 1] = qt_u2f(r1);
                 }
@@ -241,7 +231,7 @@ struct SoftmaxBwdArgs {
 template <int KIND, int NS, int NV, int G>
 __global__ __launch_bounds__(256) void softmax_bwd_kernel(SoftmaxBwdArgs a, qt_format fmt, const uint16_t *__restrict__ lut) {
     __shared__ uint4 s_rows[KIND == kFmtRows ? 512 : 1];
-    const Rounder<KIND> rnd = chain_rounder<KIND>(fmt, lut, s_rows, 256);
+    const Rounder<KIND> rnd = make_rounder<KIND>(fmt, lut, s_rows, 256);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int sub = lane / G, li = lane % G;
     constexpr int RPW = 64 / G;                                  // rows per wave

@@ -40,7 +40,7 @@ __device__ __forceinline__ uint4 add_bf16x8(const uint4 &a, const uint4 &b) {
 template <int KIND, int N>
 __global__ __launch_bounds__(kFanBlock) void fanin_kernel(FaninArgs a, qt_format fmt, const uint16_t *__restrict__ lut) {
     __shared__ uint4 s_rows[KIND == kFmtRows ? 512 : 1];
-    const Rounder<KIND> rnd = chain_rounder<KIND>(fmt, lut, s_rows, kFanBlock);
+    const Rounder<KIND> rnd = make_rounder<KIND>(fmt, lut, s_rows, kFanBlock);
     float sc[N];
     uint32_t amax[N];
 #pragma unroll
