@@ -17,6 +17,7 @@ uint16 arrays, fp32 tensors are float32 arrays (or their uint32 view).
 """
 import math
 import re
+from typing import NamedTuple, Optional
 
 import numpy as np
 
@@ -586,16 +587,18 @@ def scale_and_mask(scores_bits, mask_bits, scaling):
     return t
 
 
-def softmax_fq(scores_bits, mask_bits, scaling, qmap):
+def softmax_fq(scores_bits, mask_bits, scaling, qmap, with_interval=False):
     """scores_bits: uint16 [..., rows, cols] bf16 patterns; mask_bits: broadcastable uint16 array or None; scaling: python
-    float (multiplied as fp32, like torch's bf16-tensor x scalar); qmap: uint16[65536] or None.  Returns (p_bits, pq_bits).
+    float (multiplied as fp32, like torch's bf16-tensor x scalar); qmap: uint16[65536] or None.  Returns (p_bits, pq_bits); with
+    `with_interval` also the probabilities' admissible interval (softmax_interval, below) as a third element.
     Pinned to upstream's BertSelfAttention twin by tests/test_oracle_golden.py::test_attention_chain (tests/golden/attn_chain.*)."""
     t = scale_and_mask(scores_bits, mask_bits, scaling)
     mx = t.max(axis=-1, keepdims=True)
     e = np.exp(t - mx)
     p = e / e.sum(axis=-1, keepdims=True)
     p_bits = f32_to_bf16(p.astype(np.float32))
-    return p_bits, (vmap_bf16(p_bits, qmap) if qmap is not None else p_bits)
+    out = p_bits, (vmap_bf16(p_bits, qmap) if qmap is not None else p_bits)
+    return out + (softmax_interval(scores_bits, mask_bits, scaling),) if with_interval else out
 
 
 def softmax_fq_f32(scores, mask, scaling, qmap):
@@ -624,3 +627,340 @@ def attention_fq(q_bits, k_bits, v_bits, mask_bits, scaling, qmap):
     pq = bf16_to_f32(pq_bits).astype(np.float64)
     out = np.einsum("bhqk,bhkd->bhqd", pq, v)
     return f32_to_bf16(out.astype(np.float32)), pq_bits
+
+
+# ---- row reductions: norms, softmax backward, causal-LM loss -- fp64 restatements with an error interval ---------------------------------
+# Each function below restates one row-reduction kernel's documented chain (csrc/qt_model_ops.hip, qt_softmax.hip, qt_elementwise.hip) on
+# bf16 bit patterns.  Every bf16 rounding point of the chain is explicit; every sum and transcendental is evaluated in float64.  A result
+# is a RowInterval per output tensor:
+#     v        the float64 value in front of the chain's FIRST INEXACT rounding
+#     rho      a radius any correct fp32 evaluation of that value stays within (derived in each docstring, never measured)
+#     lo, hi   bf16 patterns: the images of v - rho and v + rho under the rest of the chain, which is exact and monotone once the first
+#              rounding is fixed.  An element is DECIDED when lo == hi: every correct implementation writes that pattern.
+# The error model (u = 2^-24, the unit roundoff of fp32):
+#     sums         an fp32 sum whose terms pass through chains of at most d = 128 additions: |error| <= d u sum|t_i|.  d is a contract of
+#                  these kernels: at most 64 serial additions per lane, then the lane tree and the LDS stage, with margin.  A sum with at
+#                  most one non-zero term is exact (adding zeros does not round).
+#     * + -        one u (relative) each; a fused multiply-add only removes a rounding
+#     rsqrtf logf  4 u relative (the documented 1 ulp, doubled); 1 / x is given the same 4 u
+#     __expf(a)    (2 + 1.4427 |a|) 2^-23 relative: the argument's scaling by log2(e) plus v_exp_f32
+#     subnormals   softmax probabilities get an absolute 2^-126: a result in the fp32 subnormal range may be flushed to zero.  Whether the
+#                  hardware path does flush there is NOT verified on hardware; the radius admits both.
+#     overflow     modelled explicitly: a sum of squares with a term above the fp32 maximum is inf, its rsqrt 0.  Zeros compare without
+#                  regard to sign (bf16_order maps both to 0).
+U_F32 = 2.0 ** -24
+SUM_DEPTH = 128
+F32_MAX = float(np.finfo(np.float32).max)
+
+
+class RowInterval:
+    """v, rho: float64 arrays; lo, hi: uint16 bf16 patterns (NaN: 0x7FC0 in both)."""
+
+    def __init__(self, v, rho, lo, hi):
+        self.v, self.rho = np.asarray(v, np.float64), np.asarray(rho, np.float64)
+        lo, hi = canon_nan16(lo), canon_nan16(hi)
+        swap = bf16_order(lo) > bf16_order(hi)
+        self.lo, self.hi = np.where(swap, hi, lo).astype(U16), np.where(swap, lo, hi).astype(U16)
+
+    def rows(self, sel):
+        return RowInterval(self.v[sel], self.rho[sel], self.lo[sel], self.hi[sel])
+
+    @property
+    def nan(self):
+        return (self.lo == 0x7FC0) | (self.hi == 0x7FC0)
+
+    @property
+    def decided(self):
+        return (bf16_order(self.lo) == bf16_order(self.hi)) & ~self.nan
+
+    def decided_share(self):
+        """Share of the finite elements whose pattern the oracle fixes."""
+        fin = ~self.nan
+        return float(self.decided[fin].mean()) if fin.any() else 1.0
+
+    def distance(self, got_bits):
+        """Per element: 0 inside [lo, hi] (in bf16 value order, -0 == +0), else the number of bf16 steps outside; NaN must meet NaN
+        (a mismatch counts as 65536)."""
+        got = canon_nan16(got_bits)
+        k, klo, khi = bf16_order(got), bf16_order(self.lo), bf16_order(self.hi)
+        d = np.maximum(np.maximum(klo - k, k - khi), 0)
+        gnan = got == 0x7FC0
+        return np.where(gnan | self.nan, np.where(gnan & self.nan, 0, 65536), d)
+
+    def report(self, got_bits):
+        d = self.distance(got_bits)
+        return f"decided share {self.decided_share():.4f}, worst distance from the interval {int(d.max())} bf16 steps, {int((d > 0).sum())} of {d.size} outside"
+
+
+def bf16_order(bits):
+    """bf16 patterns -> int32 keys in value order; -0 and +0 share key 0.  (NaN patterns get keys beyond the infinities.)"""
+    b = np.asarray(bits, dtype=U16).astype(np.int32)
+    return np.where(b < 0x8000, b, -(b & 0x7FFF))
+
+
+def _b64(bits):
+    return bf16_to_f32(bits).astype(np.float64)
+
+
+def _bf16_of(x64):
+    """float64 -> bf16 pattern, ONE rounding to nearest even.  (Through fp32 would round twice; for an interval end point the difference
+    could only move the end by a pattern where v +- rho sits within 2^-29 relative of a bf16 tie, so round once, from the fp64 value:
+    RNE on the fp64 image truncated to sticky.)"""
+    x64 = np.asarray(x64, np.float64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        f = x64.astype(F32)                                       # RNE to fp32 ...
+        # ... made sticky: where fp32 rounding was inexact and landed exactly on a bf16 tie, nudge toward the true value
+        tie = (f.view(U32) & U32(0xFFFF)) == U32(0x8000)
+        f64 = f.astype(np.float64)
+        adj = np.where(tie & np.isfinite(f64) & (f64 != x64), np.where((np.abs(x64) > np.abs(f64)), 1, -1), 0)
+        f = (f.view(U32).astype(np.int64) + adj).astype(U32).view(F32)
+    return f32_to_bf16(f)
+
+
+def _sum_radius(abs_terms, axis=-1, keepdims=True):
+    """d u sum|t_i| -- and 0 where at most one term is non-zero."""
+    a = np.asarray(abs_terms, np.float64)
+    r = SUM_DEPTH * U_F32 * a.sum(axis=axis, keepdims=keepdims)
+    return np.where((a != 0).sum(axis=axis, keepdims=keepdims) <= 1, 0.0, r)
+
+
+def _interval(v, rho, then=None):
+    """RowInterval of bf16(v +- rho); `then` maps a bf16 pattern array through the (exact, monotone) rest of the chain."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        lo, hi = _bf16_of(v - rho), _bf16_of(v + rho)
+    if then is not None:
+        lo, hi = then(lo), then(hi)
+    return RowInterval(v, rho, lo, hi)
+
+
+def bf16_add(a_bits, b_bits):
+    """torch's bf16 + bf16: the fp32 sum (correctly rounded), then ONE rounding to bf16 -- what the residual variants write to `sum`."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        return f32_to_bf16(bf16_to_f32(a_bits) + bf16_to_f32(b_bits))
+
+
+def _bf16_mul(a_bits, b_bits):
+    """bf16(a * b): the product of two bf16 values is exact in fp32 (16 significant bits), so this is one rounding."""
+    with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+        return f32_to_bf16(bf16_to_f32(a_bits) * bf16_to_f32(b_bits))
+
+
+def _sq_sum_f32(sq_terms):
+    """The fp32 fate of a sum of non-negative fp64 terms: (value, certain_inf, maybe_inf).  A term or a total beyond the fp32 maximum
+    (with the sum's own error margin) is certainly inf; a total within that margin of the maximum may be either."""
+    s = sq_terms.sum(axis=-1, keepdims=True)
+    margin = SUM_DEPTH * U_F32
+    with np.errstate(invalid="ignore"):
+        certain = (sq_terms.max(axis=-1, keepdims=True) > F32_MAX) | (s * (1 - margin) > F32_MAX)
+        maybe = ~certain & (s * (1 + margin) > F32_MAX)
+    return np.where(certain, np.inf, s), certain, maybe
+
+
+def rmsnorm(x_bits, w_bits, eps, res_bits=None):
+    """LlamaRMSNorm on bf16 rows [rows, cols] (csrc/qt_model_ops.hip):  s = bf16(x + res) (optional);  r = rsqrt(mean(s^2) + eps) in
+    fp32;  h = bf16(s * r);  y = bf16(w * h).  Returns (y: RowInterval, sum_bits or None).
+
+    First inexact rounding: h.  v = s * r.  Radius: the squares s_i^2 are exact in fp32; their sum has relative error d u (all terms are
+    non-negative); 1 / cols, the product with it and the addition of eps add one u each, so the rsqrt's argument is within (d + 3) u
+    relative and its result within (d + 3) u / 2 + 4 u; the product s * r adds u.  rho = |v| ((d + 3) / 2 + 5 + 1) u -- one further u for
+    the second-order terms -- plus 2^-149 (an fp32 product in the subnormal range rounds absolutely; the same 2^-149 per square
+    below 2^-126 moves the mean square by at most that much, r by r^3 2^-150).  After h the chain is
+    y = bf16(w * h): an exact product, one rounding, monotone in h for the sign of w.
+    Overflow: a square beyond the fp32 maximum makes the sum inf, r = 0 and h = s * 0 = +-0 (NaN where s is inf); a row whose sum of
+    squares lies within d u of the maximum admits both fates."""
+    s_bits = np.asarray(x_bits, U16) if res_bits is None else bf16_add(x_bits, res_bits)
+    s = _b64(s_bits)
+    cols = s.shape[-1]
+    with np.errstate(all="ignore"):
+        ss, _, maybe = _sq_sum_f32(s * s)
+        r = 1.0 / np.sqrt(ss / cols + float(F32(eps)))
+        v = s * r
+        rho = np.abs(v) * (((SUM_DEPTH + 3) / 2 + 6) * U_F32 + 0.5 * 2.0 ** -149 * r * r) + 2.0 ** -149
+        rho = np.where(np.isnan(v), np.nan, np.where(r == 0, 0.0, rho))
+    w = np.broadcast_to(np.asarray(w_bits, U16), s.shape)
+    y = _interval(v, rho, then=lambda h: _bf16_mul(w, h))
+    if maybe.any():                                                # the sum may or may not have overflowed: admit y = +-0 as well
+        zero = np.zeros_like(y.lo)
+        m = np.broadcast_to(maybe, s.shape) & ~y.nan
+        y = RowInterval(y.v, y.rho, np.where(m & (bf16_order(y.lo) > 0), zero, y.lo), np.where(m & (bf16_order(y.hi) < 0), zero, y.hi))
+    return y, (None if res_bits is None else s_bits)
+
+
+class LayerNormResult(NamedTuple):
+    """What layernorm() returns; the statistics are float64, one per row."""
+    y: RowInterval
+    mean: np.ndarray            # the fp64 mean, admissible within +- rho_mean
+    rho_mean: np.ndarray
+    rstd: np.ndarray            # the fp64 rstd, admissible within [rstd_lo, rstd_hi]
+    rstd_lo: np.ndarray
+    rstd_hi: np.ndarray
+    sum_bits: Optional[np.ndarray]      # bf16(x + res), None without a residual
+
+
+def layernorm(x_bits, w_bits, b_bits, eps, res_bits=None):
+    """torch's native_layer_norm on bf16 rows (csrc/qt_model_ops.hip layernorm_kernel, csrc/qt_elementwise.hip ln_train_fwd_kernel):
+    s = bf16(x + res) (optional);  mean = sum(s) / cols;  rstd = rsqrt(sum((s - mean)^2) / cols + eps);  y = bf16(w * (rstd * (s - mean))
+    + b), everything in front of that one rounding in fp32.  Returns a LayerNormResult.
+
+    First inexact rounding: y itself (v = w rstd (s - mean) + b).  Radius, step by step:
+      mean   the sum of the row: d u sum|s_i|; the division by cols (exact in fp32) one u:  rho_mean = d u mean|s_i| + 2 u |mean|
+      var    with the computed mean m^, sum (s_i - m^)^2 = sum (s_i - mean)^2 + cols (m^ - mean)^2 exactly, so the sum the kernel forms is
+             cols (var + delta^2), 0 <= delta <= rho_mean; each term carries 2 u (the subtraction, squared) + u (the square), the sum
+             d u, the product with the rounded 1 / cols two u, the addition of eps one:  the rsqrt's argument lies in
+             [(var + eps) (1 - (d + 6) u), (var + rho_mean^2 + eps) (1 + (d + 6) u)]  -+ 2^-149 (squares in the subnormal range)
+      rstd   4 u relative around the rsqrt of that:  [rstd_lo, rstd_hi]  (rows with |mean| >> std, constant rows above all, get a wide
+             interval here: rho_mean^2 is not small against var + eps.  They are the ill-conditioned rows.)
+      y      |s - mean| =: A is known to rho_mean; the difference, the two products carry 3 u (4 with margin):  the product rstd (s - m^)
+             lies in [P_lo, P_hi] = [rstd_lo (A - rho_mean), rstd_hi (A + rho_mean)] (1 -+ 4 u) (P_lo with rstd_hi where A < rho_mean);
+             rho = |w| max(P_hi - P, P - P_lo) + u (|w| P_hi + |b|), the last term for the final addition.
+    Overflow: a squared difference beyond the fp32 maximum makes the variance inf and rstd = 0, so y = bf16(w * 0 + b) = b exactly."""
+    s_bits = np.asarray(x_bits, U16) if res_bits is None else bf16_add(x_bits, res_bits)
+    s = _b64(s_bits)
+    cols = s.shape[-1]
+    w, b = _b64(np.broadcast_to(np.asarray(w_bits, U16), s.shape)), _b64(np.broadcast_to(np.asarray(b_bits, U16), s.shape))
+    u, d = U_F32, SUM_DEPTH
+    with np.errstate(all="ignore"):
+        mean = s.sum(-1, keepdims=True) / cols
+        rho_mean = _sum_radius(np.abs(s)) / cols + 2 * u * np.abs(mean)
+        diff = s - mean
+        _, certain, maybe = _sq_sum_f32((np.abs(diff) + rho_mean) ** 2)         # (the overflow question is asked of the largest admissible terms)
+        var = (diff * diff).sum(-1, keepdims=True) / cols
+        e = float(F32(eps))
+        tiny = 2.0 ** -149                                         # a square below 2^-126 rounds absolutely: 2^-149 per term, so per mean
+        m_lo, m_hi = (var + e) * (1 - (d + 6) * u) - tiny, (var + rho_mean ** 2 + e) * (1 + (d + 6) * u) + tiny
+        rstd = 1.0 / np.sqrt(var + e)
+        rstd_lo, rstd_hi = (1 - 4 * u) / np.sqrt(m_hi), (1 + 4 * u) / np.sqrt(m_lo)
+        rstd, rstd_lo, rstd_hi = (np.where(certain, 0.0, t) for t in (rstd, rstd_lo, rstd_hi))
+        rstd_lo = np.where(maybe, 0.0, rstd_lo)
+        A = np.abs(diff)
+        P = rstd * A
+        P_hi = rstd_hi * (A + rho_mean) * (1 + 4 * u)
+        P_lo = np.where(A >= rho_mean, rstd_lo * (A - rho_mean) * (1 - 4 * u), rstd_hi * (A - rho_mean) * (1 + 4 * u))
+        v = w * (rstd * diff) + b
+        rho = np.abs(w) * np.maximum(P_hi - P, P - P_lo) + u * (np.abs(w) * P_hi + np.abs(b))
+        rho = np.where(np.isnan(v), np.nan, np.where(np.broadcast_to(certain, s.shape), 0.0, rho))
+    return LayerNormResult(_interval(v, rho), mean[..., 0], rho_mean[..., 0], rstd[..., 0], rstd_lo[..., 0], rstd_hi[..., 0],
+                           None if res_bits is None else s_bits)
+
+
+def layernorm_backward(dy_bits, x_bits, w_bits, mean, rstd):
+    """torch's native_layer_norm_backward on bf16 rows [rows, cols] from GIVEN fp32 statistics (csrc/qt_elementwise.hip
+    ln_train_bwd_kernel):  xh = (x - mean) rstd;  g = dy w;  c1 = mean(g);  c2 = mean(g xh);  dx = bf16(rstd (g - c1 - xh c2));
+    dgamma = bf16(sum_rows dy xh);  dbeta = bf16(sum_rows dy).  Returns (dx, dgamma, dbeta) as RowIntervals.
+
+    First inexact rounding: each output's own.  Radii: xh carries 2 u; g is an exact product.  s1 = sum g: d u sum|g|.  s2 = sum g xh:
+    3 u per term and d u for the sum: (d + 3) u sum|g xh|.  c1, c2: two u each for 1 / cols and the product:
+    rho_c = rho_s / cols + 2 u |c|.  The bracket g - c1 - xh c2 then errs by rho_c1 + |xh| rho_c2 + 4 u (|g| + |c1| + |xh c2|) (the product
+    xh c2 with xh's two u, both subtractions), the product with rstd adds u:
+        rho_dx = rstd (rho_c1 + |xh| rho_c2 + 4 u (|g| + |c1| + |xh c2|)) + u |dx|.
+    dgamma: terms dy xh with 3 u each, sum over the rows d u: (d + 3) u sum|dy xh|;  dbeta: exact terms, d u sum|dy|."""
+    dy, x = _b64(dy_bits), _b64(x_bits)
+    w = _b64(np.broadcast_to(np.asarray(w_bits, U16), x.shape))
+    mean = np.asarray(mean, F32).astype(np.float64).reshape(-1, 1)
+    rstd = np.asarray(rstd, F32).astype(np.float64).reshape(-1, 1)
+    cols = x.shape[-1]
+    u, d = U_F32, SUM_DEPTH
+    with np.errstate(all="ignore"):
+        xh = (x - mean) * rstd
+        g = dy * w
+        c1, c2 = g.sum(-1, keepdims=True) / cols, (g * xh).sum(-1, keepdims=True) / cols
+        rho_c1 = _sum_radius(np.abs(g)) / cols + 2 * u * np.abs(c1)
+        rho_c2 = (d + 3) * u * np.abs(g * xh).sum(-1, keepdims=True) / cols + 2 * u * np.abs(c2)
+        v = rstd * (g - c1 - xh * c2)
+        rho = rstd * (rho_c1 + np.abs(xh) * rho_c2 + 4 * u * (np.abs(g) + np.abs(c1) + np.abs(xh * c2))) + u * np.abs(v) + 2.0 ** -149
+        t = dy * xh
+        vg, rg = t.sum(0), (d + 3) * u * np.abs(t).sum(0) + 2.0 ** -149
+        vb, rb = dy.sum(0), _sum_radius(np.abs(dy), axis=0, keepdims=False)
+    return _interval(v, rho), _interval(vg, rg), _interval(vb, rb)
+
+
+def softmax_backward(dp_bits, p_bits, scaling):
+    """torch's _softmax_backward_data on bf16 rows, then the scaling's backward (csrc/qt_softmax.hip softmax_bwd_kernel):
+    d1 = bf16((dP - sum(dP P)) P) in fp32;  ds = bf16(d1 * scaling), the product rounded to fp32 first (scaling is an fp32 number).
+    Returns ds as a RowInterval.
+
+    First inexact rounding: d1.  v = (dP - dot) P.  The products dP_i P_i are exact in fp32, the dot product errs by
+    rho_dot = d u sum|dP_i P_i| (0 for a one-hot row: one non-zero term).  The subtraction and the product add one u each:
+        rho = |P| rho_dot + 2 u |v|  (times 1 + 2^-20 for the second-order terms) + 2^-149.
+    After d1 the chain is the deterministic pair of roundings fp32(d1 * scaling) -> bf16, monotone in d1 (for scaling > 0)."""
+    dp, p = _b64(dp_bits), _b64(p_bits)
+    sc = F32(scaling)
+    with np.errstate(all="ignore"):
+        t = dp * p
+        dot = t.sum(-1, keepdims=True)
+        v = (dp - dot) * p
+        rho = (np.abs(p) * _sum_radius(np.abs(t)) + 2 * U_F32 * np.abs(v)) * (1 + 2.0 ** -20)
+        rho = np.where(rho == 0, 0.0, rho + 2.0 ** -149)
+
+    def then(d1):
+        with np.errstate(all="ignore"):
+            return f32_to_bf16(bf16_to_f32(d1) * sc)
+    return _interval(v, rho, then=then)
+
+
+def softmax_interval(scores_bits, mask_bits, scaling):
+    """The probabilities of softmax_fq with their admissible interval (csrc/qt_softmax.hip softmax_fq_kernel):
+    t = bf16(bf16(score x scaling) + mask) is bit-defined, so is the row maximum;  a = t - max;  e = __expf(a);  p = bf16(e * (1 / sum e)).
+
+    First inexact rounding: p.  v = exp(a) / sum exp(a).  Per term, rel_i = (2 + 1.4427 |a_i|) 2^-23 + u |a_i| (the subtraction t - max
+    of two bf16 values can round).  The sum errs by its terms' errors, sum_j e_j rel_j, and by d u; relative to the sum that is the
+    p-weighted mean of rel_j, plus d u.  The reciprocal 4 u, the product u:
+        rho = v (rel_i + sum_j v_j rel_j + (d + 5) u) + 2^-126,
+    the absolute term for a flush of a subnormal exponential or product (not verified on hardware, see above).  Vectors the kernel skips
+    (all eight logits more than 110 below the maximum) hold values below 2^-158: zero in bf16 either way.
+    Where a < -104.5 the exponential with its relative error lies below 2^-150, half the smallest fp32 subnormal: every fp32 evaluation,
+    flushing or not, returns 0, the sum is at least 1 (the maximum's own term), so p = 0 exactly: v = 0, rho = 0 there."""
+    t = scale_and_mask(scores_bits, mask_bits, scaling)
+    with np.errstate(all="ignore"):
+        a = t - t.max(axis=-1, keepdims=True)
+        e = np.exp(a)
+        v = e / e.sum(axis=-1, keepdims=True)
+        rel = np.where(np.isfinite(a), (2 + 1.4427 * np.abs(a)) * 2.0 ** -23 + U_F32 * np.abs(a), 0.0)
+        rho = v * (rel + (v * rel).sum(axis=-1, keepdims=True) + (SUM_DEPTH + 5) * U_F32) + 2.0 ** -126
+        gone = a < -104.5                                          # (false for NaN)
+        v = np.where(gone, 0.0, v)
+        rho = np.where(np.isnan(v), np.nan, np.where(gone, 0.0, rho))
+        iv = _interval(v, rho)
+        neg = bf16_order(iv.lo) < 0                      # a probability is never negative: e >= 0 and 1 / sum > 0
+    return RowInterval(iv.v, iv.rho, np.where(neg & ~iv.nan, U16(0), iv.lo), iv.hi)
+
+
+def causal_lm_nll(logits_bits, labels, ignore_index=-100):
+    """transformers' ForCausalLMLoss on bf16 logits [B, S, V] (csrc/qt_model_ops.hip nll_rows_kernel / nll_mean_kernel): position s is
+    scored against labels[s + 1] (the last position of a sequence, an ignored or out-of-range label: not scored);
+    loss = (max + log sum exp(x - max)) - x[label] in fp32;  the result is the mean over the scored positions (NaN when there are none).
+    Returns (loss [B, S] float64, rho [B, S], scored [B, S] bool, mean, rho_mean); unscored positions hold NaN.
+
+    Radius: the kernel keeps a running maximum, so a term exp(x_j - max) is a product of up to K exponentials whose (non-positive)
+    arguments add up to x_j - max: K <= ceil(V / 2048) + 8 (a lane's maximum updates, six lane-tree steps, the LDS stage).
+    rel_j = (2 K + 1.4427 |a_j|) 2^-23 + (K + |a_j|) u.  The sum S: p-weighted mean of rel_j plus d u =: rel_S.  logf: 4 u |log S|, and
+    log(S (1 + rel_S)) - log S <= 2 rel_S.  The two additions one u each:
+        rho = 2 rel_S + 4 u |log S| + u |max + log S| + u |loss| + 2^-149.
+    The mean: rho_mean = (sum rho_i + d u sum|loss_i|) / n + u |mean|."""
+    x = _b64(logits_bits)
+    B, S, V = x.shape
+    labels = np.asarray(labels, np.int64)
+    lab = np.full((B, S), ignore_index, np.int64)
+    lab[:, :-1] = labels[:, 1:]
+    scored = (lab != ignore_index) & (lab >= 0) & (lab < V)
+    K = -(-V // 2048) + 8
+    u = U_F32
+    with np.errstate(all="ignore"):
+        mx = x.max(-1, keepdims=True)
+        a = x - mx
+        e = np.exp(a)
+        Ssum = e.sum(-1, keepdims=True)
+        p = e / Ssum
+        rel = np.where(np.isfinite(a), (2 * K + 1.4427 * np.abs(a)) * 2.0 ** -23 + (K + np.abs(a)) * u, 0.0)
+        rel_S = ((p * rel).sum(-1, keepdims=True) + SUM_DEPTH * u)[..., 0]
+        logS, mx = np.log(Ssum)[..., 0], mx[..., 0]
+        xl = np.take_along_axis(x, np.where(scored, lab, 0)[..., None], -1)[..., 0]
+        loss = (mx + logS) - xl
+        rho = 2 * rel_S + 4 * u * np.abs(logS) + u * np.abs(mx + logS) + u * np.abs(loss) + 2.0 ** -149
+        loss, rho = np.where(scored, loss, np.nan), np.where(scored, rho, np.nan)
+        n = int(scored.sum())
+        if n == 0:
+            return loss, rho, scored, float("nan"), float("nan")
+        mean = loss[scored].sum() / n
+        rho_mean = (rho[scored].sum() + SUM_DEPTH * u * np.abs(loss[scored]).sum()) / n + u * abs(mean)
+    return loss, rho, scored, float(mean), float(rho_mean)

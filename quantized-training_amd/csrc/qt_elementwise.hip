@@ -441,7 +441,7 @@ __global__ __launch_bounds__(BLOCK) void ln_train_fwd_kernel(LnTrainArgs a, qt_f
         }
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off, 64);
-        const float mean = sum * a.inv_cols;
+        const float mean = sum / (float)(a.nvec * 8);               // a division: exact for a constant row (as layernorm_kernel, csrc/qt_model_ops.hip)
         float sq = 0.0f;
 #pragma unroll
         for (int i = 0; i < kLnMaxVec; ++i) {

@@ -474,7 +474,9 @@ __global__ __launch_bounds__(256) void layernorm_kernel(LnArgs a) {
         }
         return t;
     };
-    const float mean = reduce(sum, 0) * a.inv_cols;
+    // (a division, not a product with 1 / cols: at 449 of the 2048 row lengths -- 56, 120, 1000, ... -- the product of an exact sum c * cols
+    // with the rounded reciprocal is not c, and a constant row came out as w * (+-0.2 .. +-1) + b at a small eps instead of b)
+    const float mean = reduce(sum, 0) / (float)(a.nvec * 8);
     float sq = 0.0f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {

@@ -14,7 +14,9 @@
 //                                                       amax(p) max-accumulated for the observer
 // One wavefront owns one row: 16-B loads, lane-local + __shfl_xor reductions, no LDS.
 // Numerics: every step except exp, the row-sum order and e * (1/sum) vs e / sum is bit-defined; p can differ
-// from torch's by at most one bf16 ULP on a small fraction of elements (tests/test_gpu_parity.py::test_softmax_fq states the tolerance).
+// from torch's by at most one bf16 ULP on a small fraction of elements (tests/test_gpu_parity.py::test_softmax_fq states the tolerance;
+// tests/test_gpu_row_kernels.py holds every row-length instantiation to the fp64 oracle's interval).  A NaN anywhere in a row makes the
+// whole row NaN, masked columns included, as torch's softmax does.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -146,13 +148,16 @@ __global__ __launch_bounds__(256) void softmax_fq_kernel(SoftmaxArgs a) {
 #pragma unroll
         for (int off = G / 2; off >= 1; off >>= 1) sum += __shfl_xor(sum, off, 64);
         const float inv = 1.0f / sum;                 // one division per row; p = e * inv (<= 1 fp32 ULP from e / sum)
+        // A NaN (or +inf) logit anywhere in the row makes the sum NaN and with it EVERY probability of the row, as torch's softmax
+        // does: the skipped vectors too, which then take the full path below (their t[] still holds the logits; logit * NaN = NaN).
+        const bool row_nan = sum != sum;
         uint4 *dst = (a.out && row_ok) ? (uint4 *)(a.out + row * a.cols) : nullptr;
         uint2 *dst8 = (a.out8 && row_ok) ? (uint2 *)(a.out8 + row * a.cols) : nullptr;
         uint4 *dstp = (a.probs && row_ok) ? (uint4 *)(a.probs + row * a.cols) : nullptr;
 #pragma unroll
         for (int v = 0; v < NV; ++v) {
             const int iv = v * G + li;
-            if (iv < nvec_row && dead[v]) {                  // fq(0) = +0, FP8 code 0; amax unaffected
+            if (iv < nvec_row && dead[v] && !row_nan) {      // fq(0) = +0, FP8 code 0; amax unaffected
                 if (dst) dst[iv] = uint4{0u, 0u, 0u, 0u};
                 if (dst8) dst8[iv] = uint2{0u, 0u};
                 if (dstp) dstp[iv] = uint4{0u, 0u, 0u, 0u};
