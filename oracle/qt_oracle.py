@@ -964,3 +964,122 @@ def causal_lm_nll(logits_bits, labels, ignore_index=-100):
         mean = loss[scored].sum() / n
         rho_mean = (rho[scored].sum() + SUM_DEPTH * u * np.abs(loss[scored]).sum()) / n + u * abs(mean)
     return loss, rho, scored, float(mean), float(rho_mean)
+
+
+# ---- elementwise launches: rotary, SiLU * up, GELU (csrc/qt_model_ops.hip) -----------------------------------------------------------------
+def rope(x_bits, cos_bits, sin_bits, inner_qmap=None, out_qmap=None):
+    """The rotary embedding on bf16 patterns x [B, S, H, D] with tables cos / sin [B, S, D] (HF's apply_rotary_pos_emb on bf16 tensors;
+    rope_one / rope_fq_token of csrc/qt_model_ops.hip):
+
+        y = bf16( fq_inner(bf16(x * cos)) + bf16(rotate_half(x) * sin) ),   rotate_half(x) = cat(-x[D/2:], x[:D/2]),
+
+    then out_qmap (a value map, uint16[65536]) applied to y.  inner_qmap is the value map PT2E graphs put on the earlier operand of the
+    add.  cos_bits None: no rotation, y = x.
+
+    Bit for bit, no interval: the product of two bf16 values has 16 significant bits and is exact in fp32 (in the subnormal range too:
+    it is a multiple of 2^-149 wherever it is at least that large, and below that one correctly rounded fp32 product), the fp32 sum of
+    two bf16 values is correctly rounded, and each is rounded once more to bf16 -- numpy float32 arithmetic performs exactly these
+    roundings, keeps subnormals and follows IEEE for inf * 0 and inf - inf.  Returns bf16 patterns in the order of x, NaN canonical."""
+    x_bits = np.asarray(x_bits, U16)
+    if cos_bits is None:
+        y = canon_nan16(x_bits)
+    else:
+        half = x_bits.shape[-1] // 2
+        x = bf16_to_f32(x_bits)
+        c, s = bf16_to_f32(cos_bits)[:, :, None, :], bf16_to_f32(sin_bits)[:, :, None, :]
+        with np.errstate(all="ignore"):
+            a = f32_to_bf16(x * c)
+            if inner_qmap is not None:
+                a = vmap_bf16(a, inner_qmap)
+            rot = np.concatenate([-x[..., half:], x[..., :half]], axis=-1)
+            b = f32_to_bf16(rot * s)
+            y = f32_to_bf16(bf16_to_f32(a) + bf16_to_f32(b))
+    if out_qmap is not None:
+        y = vmap_bf16(y, out_qmap)
+    return canon_nan16(y)
+
+
+LN_F32_MAX = math.log(F32_MAX)              # 88.7228...: expf of anything above is +inf in fp32
+SILU_U = 12                                 # radius of the SiLU quotient in units of u (derived in silu_mul's docstring)
+ERFF_U = 8                                  # absolute error of erff in units of u |erf| (gelu's docstring)
+
+_ELEMENTWISE_TABLES = {}
+
+
+def _silu_table():
+    """Per gate pattern: (v, rho, lo, hi) of s = bf16(g / (1 + expf(-g)))."""
+    if "silu" not in _ELEMENTWISE_TABLES:
+        with np.errstate(all="ignore"):
+            g = _b64(all_bf16_patterns())
+            v = g / (1.0 + np.exp(-g))
+            rho = SILU_U * U_F32 * np.abs(v) + 2.0 ** -149
+            over = -g > LN_F32_MAX                                 # expf(-g) = +inf: the quotient is g / inf
+            v = np.where(over, np.where(np.isinf(g), np.nan, -0.0), v)
+            rho = np.where(over | (v == 0) | np.isinf(v), 0.0, rho)
+            rho = np.where(np.isnan(v), np.nan, rho)
+        iv = _interval(v, rho)
+        _ELEMENTWISE_TABLES["silu"] = (v, rho, iv.lo, iv.hi)
+    return _ELEMENTWISE_TABLES["silu"]
+
+
+def silu_mul(gate_bits, up_bits):
+    """SiLU(gate) * up on bf16 patterns (silu_mul_kernel; HF's LlamaMLP act_fn(gate) * up on bf16 tensors):
+
+        s = bf16(g / (1 + expf(-g)));   y = bf16(s * up).
+
+    First (and only) inexact rounding: s.  v = g / (1 + e^-g) in fp64.  Radius, with the conventions of the error model above U_F32
+    (u = 2^-24; a documented bound in ulp counts 2 u per ulp):
+        expf      documented 1 ulp, doubled as for rsqrtf and logf: 4 u relative.  Its argument -g is exact.
+        1 + e     e's error enters the sum with weight e / (1 + e) <= 1: at most 4 u; the addition rounds once: u.
+        g / (.)   the documented bound of fp32 division without the correctly-rounded option is 2.5 ulp = 5 u; one more u as margin.
+        second-order terms: u.
+    rho = 12 u |v| + 2^-149 (a quotient in the fp32 subnormal range rounds absolutely).  A flush of such a quotient to zero is NOT
+    admitted: the torch chain this restates keeps it.
+    Overflow: for -g > ln(F32_MAX) = 88.72 expf returns +inf, 1 + inf = inf and g / inf is exactly -0 (fp64 alone says -2.4e-37 at
+    g = -89); g = -inf gives -inf / inf = NaN.  No bf16 value lies between 88.5 and 89, and e^88.5 = 2.7e38 is a factor 1.25 below the
+    fp32 maximum, so which side a gate falls on does not depend on expf's error.  g = +inf: e = 0, s = inf.  v == 0 is exact (rho 0).
+    After s the chain is y = bf16(s * up): an exact product, one rounding, monotone in s for the sign of up.
+    Returns the RowInterval of y (v, rho: those of s)."""
+    gate_bits, up_bits = np.asarray(gate_bits, U16), np.asarray(up_bits, U16)
+    v, rho, lo, hi = _silu_table()
+    return RowInterval(v[gate_bits], rho[gate_bits], _bf16_mul(lo[gate_bits], up_bits), _bf16_mul(hi[gate_bits], up_bits))
+
+
+def _gelu_table():
+    if "gelu" not in _ELEMENTWISE_TABLES:
+        with np.errstate(invalid="ignore"):
+            x = _b64(all_bf16_patterns())
+        fin = np.isfinite(x)
+        c = float(F32(math.sqrt(0.5)))                             # the kernel's constant, rounded to fp32
+        t = np.where(fin, x, 0.0) * c
+        erf = np.array([math.erf(a) for a in t])
+        with np.errstate(all="ignore"):
+            erf = np.where(fin, erf, np.where(np.isnan(x), np.nan, np.sign(x)))
+            derf = np.where(fin, 2.0 / math.sqrt(math.pi) * np.exp(-t * t), 0.0)
+            v = (x * 0.5) * (1.0 + erf)
+            e_abs = U_F32 * (ERFF_U * np.abs(erf) + np.abs(t) * derf + np.abs(1.0 + erf))
+            rho = np.where(fin, np.abs(x * 0.5) * e_abs + 2 * U_F32 * np.abs(v) + 2.0 ** -149, 0.0)
+            rho = np.where(np.isnan(v), np.nan, np.where(x == 0, 0.0, rho))
+        iv = _interval(v, rho)
+        _ELEMENTWISE_TABLES["gelu"] = (v, rho, iv.lo, iv.hi)
+    return _ELEMENTWISE_TABLES["gelu"]
+
+
+def gelu(x_bits):
+    """The erf GELU on bf16 patterns (gelu_kernel; torch's GELU on a bf16 tensor):  y = bf16((x * 0.5) * (1 + erff(x * sqrt(1/2)))),
+    one rounding to bf16 at the end.  v = (x / 2)(1 + erf(x c)) in fp64 with c the fp32 value of sqrt(1/2), as the kernel has it.
+
+    Radius.  1 + erff cancels for negative x (erf -> -1), so the error of erff enters ABSOLUTELY, times |x / 2|:
+        t = x * c           one rounding: u relative; it moves erf by |t| erf'(t) u, erf'(t) = 2 / sqrt(pi) e^(-t^2)
+        erff(t)             a bound of 4 ulp (twice the 2 ulp commonly documented for erff, the doubling of the error model above):
+                            8 u |erf(t)|
+        1 + erf             one rounding: u |1 + erf|
+      so |error of (1 + erff)| <= u (8 |erf| + |t| erf'(t) + |1 + erf|) =: E, and
+        rho = |x / 2| E + 2 u |v| + 2^-149
+    (x * 0.5 is exact; the last product rounds once, one further u for the second-order terms; a product in the fp32 subnormal range
+    rounds absolutely).  x = 0: exactly 0.  x = +inf: inf * 2 = inf.  x = -inf: -inf * 0 = NaN (torch's GELU gives the same).  For
+    x <= -5.6 or so the interval contains both signs of zero and the kernel's -0 (erff = -1 exactly) is inside it.
+    The elements the radius cannot decide are the negative tail, where 8 u is not small against 1 + erf."""
+    x_bits = np.asarray(x_bits, U16)
+    v, rho, lo, hi = _gelu_table()
+    return RowInterval(v[x_bits], rho[x_bits], lo[x_bits], hi[x_bits])
