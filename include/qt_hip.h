@@ -779,6 +779,36 @@ int qt_quantize_mx_f32(const float *x_dev, float *q_dev, float *scales_dev, uint
                        size_t rows, size_t cols, int block_size, const qt_format *fmt, const uint16_t *lut_dev,
                        float quant_max, int force_pow2, const uint16_t *scale_lut_dev, int pack_format, void *stream);
 
+/* Fused quantize_mx / MXFakeQuantFunction for blocks along an axis that is NOT the last (decomposed.py:365-448 with
+ * axes != [-1]; the value operand of P.V and the [K, N] operand of any matmul_mx are quantized along axis -2).  The tensor is
+ * contiguous [outer][n][inner] (the view of the qt_fake_quant_gwa_* family: ax = -2 on [B, H, S, D] is outer = B H, n = S,
+ * inner = D); a block is block_size consecutive indices of n; scales are [outer][n / block_size][inner] in the tensor's
+ * dtype; q / y have the tensor's layout.  The arithmetic is qt_quantize_mx_*'s, operation for operation, with one scale per
+ * column; x is read once.
+ *   qt_quantize_mx_strided_*:   q = map[x / scale] (nullable: scales only, or scales + pack), scales, and, when codes / e8m0 are
+ *     given (both or neither), the packed operand TRANSPOSED: codes [outer][inner][n bits / 8], e8m0 [outer][inner][n / 32] --
+ *     for b [B, K, N] with outer = B, n = K, inner = N exactly the second operand qt_mx_gemm reads (decomposed.py:304-363:
+ *     matmul_mx multiplies `other` by its scales expanded along axis -2).  The pack requires force_pow2, block_size % 32 == 0,
+ *     pack_format 0..4 and (n bits / 8) % 16 == 0.
+ *   qt_fake_quant_mx_strided_*: y = rd(q * scale), rd = rounding to the tensor's dtype; takes force_pow2, unlike qt_fake_quant_mx_*.
+ * Declines, all answered before the first HIP call: QT_ERR_BAD_ARG for NULL x / scales / fmt (or y), a table format without
+ * its table, block_size outside 1..512 (32..512 in steps of 32 with a pack), quant_max <= 0, only one of codes / e8m0, a pack
+ * without force_pow2 or with a pack_format outside 0..4, inner == 1 (the last-axis layout: qt_quantize_mx_* / qt_fake_quant_mx_*),
+ * inner / (elements of 16 bytes) > 2^32 - 1; QT_ERR_UNALIGNED for n % block_size != 0, inner % 8 != 0 (bf16) / inner % 4 != 0
+ * (fp32), a tensor pointer off a 16-byte boundary, (n bits / 8) % 16 != 0 with a pack.  QT_OK without a launch for an empty tensor. */
+int qt_quantize_mx_strided_bf16(const uint16_t *x_dev, uint16_t *q_dev, uint16_t *scales_dev, uint8_t *codes_dev, uint8_t *e8m0_dev,
+                                size_t outer, size_t n, size_t inner, int block_size, const qt_format *fmt, const uint16_t *lut_dev,
+                                float quant_max, int force_pow2, const uint16_t *scale_lut_dev, int pack_format, void *stream);
+int qt_quantize_mx_strided_f32(const float *x_dev, float *q_dev, float *scales_dev, uint8_t *codes_dev, uint8_t *e8m0_dev,
+                               size_t outer, size_t n, size_t inner, int block_size, const qt_format *fmt, const uint16_t *lut_dev,
+                               float quant_max, int force_pow2, const uint16_t *scale_lut_dev, int pack_format, void *stream);
+int qt_fake_quant_mx_strided_bf16(const uint16_t *x_dev, uint16_t *y_dev, uint16_t *sf_dev, size_t outer, size_t n, size_t inner,
+                                  int block_size, const qt_format *fmt, const uint16_t *lut_dev, float quant_max, int force_pow2,
+                                  const uint16_t *scale_lut_dev, void *stream);
+int qt_fake_quant_mx_strided_f32(const float *x_dev, float *y_dev, float *sf_dev, size_t outer, size_t n, size_t inner,
+                                 int block_size, const qt_format *fmt, const uint16_t *lut_dev, float quant_max, int force_pow2,
+                                 const uint16_t *scale_lut_dev, void *stream);
+
 /* ---- the model's own elementwise chains between the fake-quantized GEMMs (Hugging Face LLaMA block) -----------
  * Not part of the reference package: its examples run HF's modeling_llama as is, where each of these is 3-8 torch
  * kernels.  Same operation order and bf16 rounding points as those chains (transformers modeling_llama.py:

@@ -231,6 +231,11 @@ def _calculate_mx_qparam_impl(input, axes, block_size, quant_max, force_scale_po
     import math
     assert block_size > 0
     axes = [axes] if type(axes) == int else list(axes)
+    if input.device.type == "cuda":                    # one non-last block axis: a scales-only launch of the strided kernel
+        out = _quantize_mx_strided_hip_or_none(input, None, axes, block_size, quant_max, force_scale_power_of_two, scale_qmap,
+                                               want_q=False)
+        if out is not None:
+            return out[0]
     axes = [x + input.ndim if x < 0 else x for x in axes]
     blocks, axes, _, _ = _reshape_to_blocks(input, axes, block_size)
     block_axes = [x + 1 for x in axes]
@@ -251,14 +256,82 @@ def _calculate_mx_qparam_impl(input, axes, block_size, quant_max, force_scale_po
     return scale
 
 
+def _mx_table_ok(m):
+    return m.dtype == torch.bfloat16 and m.numel() == 65536 and m.is_contiguous()
+
+
+def _quantize_mx_strided_hip_or_none(input, qmap, axes, block_size, quant_max, pow2, scale_qmap, want_q=True):
+    """One device pass (qt_quantize_mx_strided_*) for blocks along an axis that is not the last: scales, values (`want_q`) and --
+    with power-of-two scales, a format the matrix instruction takes and the block axis at position dim - 2 -- the packed
+    [batch N, K] operand matmul_mx reads, left on q as `_qt_mx_packed_b`.  (scale, q or None), or None when the kernel does not
+    take the call."""
+    from .fake_quantize import _launch_format, mx_block_view
+    if input.device.type != "cuda" or not quant_max > 0:
+        return None
+    view = mx_block_view(tuple(input.shape), input.dtype, block_size, axes)
+    if view is None or (want_q and not _mx_table_ok(qmap)) or (scale_qmap is not None and not _mx_table_ok(scale_qmap)):
+        return None
+    from . import mx_gemm
+    outer, n, inner = view
+    L = _native.lib()
+    x = input.contiguous()
+    ax = (axes if isinstance(axes, int) else list(axes)[0]) % x.dim()
+    q = torch.empty_like(x) if want_q else None
+    sf = torch.empty(x.shape[:ax] + (n // block_size,) + x.shape[ax + 1:], dtype=x.dtype, device=x.device)
+    fmt_name = mx_gemm.format_of_qmap(qmap) if want_q and pow2 and block_size % 32 == 0 else None
+    codes = e8 = None
+    fid = -1
+    if fmt_name is not None and ax == x.dim() - 2 and (n * mx_gemm._BITS[mx_gemm.FMT_ID[fmt_name]] // 8) % 16 == 0:
+        fid = mx_gemm.FMT_ID[fmt_name]
+        codes = torch.empty((outer * inner, n * mx_gemm._BITS[fid] // 8), dtype=torch.uint8, device=x.device)
+        e8 = torch.empty((outer * inner, n // 32), dtype=torch.uint8, device=x.device)
+    if want_q:
+        fmt = _launch_format(_lut_format(), qmap)            # the row form behind the map, when this is a map from _device_map
+    else:
+        fmt = _native.QtFormat(_native.QT_FMT_IDENTITY, 0, 0, 0.0, 0.0)      # scales only: no element is mapped
+    fn = L.qt_quantize_mx_strided_bf16 if x.dtype == torch.bfloat16 else L.qt_quantize_mx_strided_f32
+    code = fn(x.data_ptr(), q.data_ptr() if want_q else None, sf.data_ptr(), codes.data_ptr() if codes is not None else None,
+              e8.data_ptr() if e8 is not None else None, outer, n, inner, block_size, ctypes.byref(fmt),
+              qmap.data_ptr() if want_q else None, float(quant_max), int(bool(pow2)),
+              scale_qmap.data_ptr() if scale_qmap is not None else None, fid, _stream_ptr(x))
+    if _native.declined(code):                               # a view that starts off a 16-byte boundary
+        return None
+    _native.check(code, "qt_quantize_mx_strided")
+    if pow2:
+        sf._qt_pow2 = True
+        if fmt_name is not None:
+            q._qt_mx_fmt = fmt_name
+        if codes is not None:
+            q._qt_mx_packed_b = (fid, block_size, codes, e8)
+    return sf, q
+
+
 def _quantize_mx_hip_or_none(input, qmap, axes, block_size, quant_max, pow2, scale_qmap):
-    """One fused device pass (qt_quantize_mx_*) for blocks along the last axis: values, scales and, for a format the
-    matrix instruction takes with power-of-two scales, the packed operand that linear_mx / matmul_mx consume."""
+    """One fused device pass: values, scales and, for a format the matrix instruction takes with power-of-two scales, the packed
+    operand that linear_mx / matmul_mx consume.  Blocks along the last axis: qt_quantize_mx_*; along another axis:
+    qt_quantize_mx_strided_*; along axis -2 of a transpose(-1, -2) view of a contiguous tensor: the last-axis pass on the stored
+    tensor, whose packed codes ARE the [N, K] operand of matmul_mx (the y . y^T / Q . K^T case), returned as transposed views."""
     if input.device.type != "cuda" or input.dtype not in (torch.bfloat16, torch.float32) or input.dim() < 1:
         return None
     axes = [axes] if isinstance(axes, int) else list(axes)
-    if len(axes) != 1 or axes[0] % input.dim() != input.dim() - 1:
+    if len(axes) != 1 or not isinstance(axes[0], int) or not -input.dim() <= axes[0] < input.dim():
         return None
+    if axes[0] % input.dim() != input.dim() - 1:
+        from .fake_quantize import transposed_storage
+        stored = transposed_storage(input) if axes[0] % input.dim() == input.dim() - 2 else None
+        if stored is not None:
+            out = _quantize_mx_hip_or_none(stored, qmap, [-1], block_size, quant_max, pow2, scale_qmap)
+            if out is not None:
+                sf, q = out
+                sf_t, q_t = sf.transpose(-1, -2), q.transpose(-1, -2)
+                if hasattr(sf, "_qt_pow2"):
+                    sf_t._qt_pow2 = sf._qt_pow2
+                if hasattr(q, "_qt_mx_fmt"):
+                    q_t._qt_mx_fmt = q._qt_mx_fmt
+                if hasattr(q, "_qt_mx_packed_act"):                 # [batch N, K]: rows of the stored tensor
+                    q_t._qt_mx_packed_b = q._qt_mx_packed_act
+                return sf_t, q_t
+        return _quantize_mx_strided_hip_or_none(input, qmap, axes, block_size, quant_max, pow2, scale_qmap)
     per = 8 if input.dtype == torch.bfloat16 else 4
     cols = input.shape[-1]
     if (not isinstance(block_size, int) or block_size < per or block_size & (block_size - 1) or block_size > 64 * per

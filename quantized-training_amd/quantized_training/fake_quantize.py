@@ -495,8 +495,9 @@ class FusedAmaxObsFakeQuantFunction(torch.autograd.Function):
 class MXFakeQuantFunction(torch.autograd.Function):
     """Microscaling fake-quant: one scale per block of `block_size` elements along `axes`, from the block's
     amax (or its shared exponent), then `qmap[x / s] * s` (upstream fake_quantize.py:98-133).  The fused HIP
-    pass (qt_fake_quant_mx_*) covers blocks along the last axis of a contiguous bf16 / fp32 device tensor;
-    other layouts use the same formulas as torch ops with the table lookup on the HIP vmap kernel."""
+    pass covers blocks along one axis of a bf16 / fp32 device tensor: the last (qt_fake_quant_mx_*) or any other
+    (qt_fake_quant_mx_strided_*, see mx_block_view; power-of-two scales included); other layouts use the same
+    formulas as torch ops with the table lookup on the HIP vmap kernel."""
 
     @staticmethod
     def forward(ctx, input, fake_quant_enabled, scale, qmap, axes, block_size, quant_max,
@@ -517,13 +518,80 @@ class MXFakeQuantFunction(torch.autograd.Function):
         return (grad_output,) + (None,) * 9
 
 
+def mx_block_view(shape, dtype, block_size, axes):
+    """(outer, n, inner) when the strided microscaling kernels (qt_quantize_mx_strided_* / qt_fake_quant_mx_strided_*) take blocks of
+    `block_size` along `axes` of a contiguous tensor of this shape and dtype, else None: bf16 / fp32, one block axis (int or
+    one-element sequence, negative or not) that is not the last, an int block size of 1..512 that divides the axis, and a row length
+    behind the axis that is a multiple of 8 (bf16) / 4 (fp32) and more than one element.  The single source of that rule for the
+    fake-quant function, quantize_mx and calculate_mx_qparam."""
+    if dtype not in (torch.bfloat16, torch.float32) or len(shape) < 2:
+        return None
+    if isinstance(block_size, bool) or not isinstance(block_size, int):
+        return None
+    if isinstance(axes, int):
+        ax = axes
+    else:
+        axes = tuple(axes)
+        if len(axes) != 1 or isinstance(axes[0], bool) or not isinstance(axes[0], int):
+            return None
+        ax = axes[0]
+    if not -len(shape) <= ax < len(shape) or ax % len(shape) == len(shape) - 1:
+        return None
+    outer, n, inner = _channel_view(tuple(shape), ax % len(shape))
+    if outer * n * inner == 0 or block_size < 1 or block_size > 512 or n % block_size:
+        return None
+    if inner == 1 or inner % (8 if dtype == torch.bfloat16 else 4):
+        return None
+    return outer, n, inner
+
+
+def transposed_storage(t):
+    """The contiguous tensor `t` is a transpose(-1, -2) view of, else None (a contiguous tensor, a slice, fewer than two dimensions)."""
+    if t.dim() < 2 or t.is_contiguous():
+        return None
+    s = t.transpose(-1, -2)
+    return s if s.is_contiguous() else None
+
+
+def _table_ok(m):
+    return m is None or (m.dtype == torch.bfloat16 and m.numel() == 65536 and m.is_contiguous())
+
+
+def _hip_mx_strided_or_none(input, scale, qmap, axes, block_size, quant_max, pow2, scale_qmap, fmt):
+    """qt_fake_quant_mx_strided_*: blocks along an axis that is not the last, power-of-two scales included."""
+    view = mx_block_view(tuple(input.shape), input.dtype, block_size, axes)
+    if view is None or not quant_max > 0 or not _table_ok(scale_qmap) or (qmap is not None and not _table_ok(qmap)):
+        return None
+    fmt = fmt if fmt is not None else _native.QtFormat(_native.QT_FMT_LUT, 0, 0, 0.0, 0.0)
+    if fmt.kind == _native.QT_FMT_LUT and qmap is None:
+        return None
+    outer, n, inner = view
+    L = _native.lib()
+    x = input.contiguous()
+    y = torch.empty_like(x)
+    ax = (axes if isinstance(axes, int) else tuple(axes)[0]) % x.dim()
+    sf = torch.empty(x.shape[:ax] + (n // block_size,) + x.shape[ax + 1:], dtype=x.dtype, device=x.device)
+    fmt = _launch_format(fmt, qmap)
+    fn = L.qt_fake_quant_mx_strided_bf16 if x.dtype == torch.bfloat16 else L.qt_fake_quant_mx_strided_f32
+    code = fn(x.data_ptr(), y.data_ptr(), sf.data_ptr(), outer, n, inner, block_size, ctypes.byref(fmt),
+              qmap.data_ptr() if qmap is not None else None, float(quant_max), int(bool(pow2)),
+              scale_qmap.data_ptr() if scale_qmap is not None else None, _stream_ptr(x))
+    if _native.declined(code):                      # a view that starts off a 16-byte boundary
+        return None
+    _native.check(code, "qt_fake_quant_mx_strided")
+    scale.resize_(sf.shape).copy_(sf)
+    return y
+
+
 def _hip_mx_or_none(input, scale, qmap, axes, block_size, quant_max, pow2, scale_qmap, fmt):
-    """Fused device pass for the common layout; None when it does not apply."""
+    """Fused device pass for the common layouts; None when it does not apply."""
     if not _is_device(input) or input.dtype not in (torch.bfloat16, torch.float32) or input.dim() < 1:
         return None
     ax = axes if isinstance(axes, int) else (axes[0] if len(axes) == 1 else None)
-    if ax is None or (ax % input.dim()) != input.dim() - 1:
+    if ax is None:
         return None
+    if (ax % input.dim()) != input.dim() - 1:       # mx_block_view decides, an axis out of range included
+        return _hip_mx_strided_or_none(input, scale, qmap, axes, block_size, quant_max, pow2, scale_qmap, fmt)
     if not isinstance(block_size, int) or block_size not in (8, 16, 32, 64, 128) or pow2:
         return None
     cols = input.shape[-1]

@@ -176,15 +176,19 @@ def mx_matmul_or_none(a, b, a_scale, b_scale, block_size, a_code, b_code):
         batch *= d
     if batch > 65535:
         return _fallback("batch > 65535")
-    a3, sa3 = a.contiguous().view(batch, M, K), a_scale.contiguous().view(batch, M, K // block_size)
-    b3, sb3 = b.contiguous().view(batch, K, N), b_scale.contiguous().view(batch, K // block_size, N)
     pre = getattr(a, "_qt_mx_packed_act", None)
     if pre is not None and pre[0] == fia and pre[1] == block_size and pre[2].shape == (batch * M, K * _BITS[fia] // 8):
         pa = (pre[2], pre[3])
     else:
+        a3, sa3 = a.contiguous().view(batch, M, K), a_scale.contiguous().view(batch, M, K // block_size)
         pa = _pack(a3, sa3, fia, block_size, batch, M, K, (M * K, K, 1), (sa3.stride(0), sa3.stride(1), 1), check=False)
-    # second operand: logical rows are b's columns (stride 1), k walks b's rows (stride N)
-    pb = _pack(b3, sb3, fib, block_size, batch, N, K, (K * N, 1, N), (sb3.stride(0), 1, sb3.stride(1)), check=False)
+    pre = getattr(b, "_qt_mx_packed_b", None)                # quantize_mx along axis -2 already emitted the [batch N, K] operand
+    if pre is not None and pre[0] == fib and pre[1] == block_size and pre[2].shape == (batch * N, K * _BITS[fib] // 8):
+        pb = (pre[2], pre[3])
+    else:
+        b3, sb3 = b.contiguous().view(batch, K, N), b_scale.contiguous().view(batch, K // block_size, N)
+        # second operand: logical rows are b's columns (stride 1), k walks b's rows (stride N)
+        pb = _pack(b3, sb3, fib, block_size, batch, N, K, (K * N, 1, N), (sb3.stride(0), 1, sb3.stride(1)), check=False)
     out = torch.empty(a.shape[:-1] + (N,), dtype=a.dtype, device=a.device)
     L = _native.lib()
     _native.check(L.qt_mx_gemm(pa[0].data_ptr(), pa[1].data_ptr(), fia, pb[0].data_ptr(), pb[1].data_ptr(), fib,

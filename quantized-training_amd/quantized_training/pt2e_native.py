@@ -20,6 +20,9 @@ The graph `convert_pt2e` returns is untouched on the CPU (it is pinned node for 
 idempotent pass that convert_pt2e applies to device models (`native=None` -> automatic, `QT_PT2E_NATIVE=0` turns it off).
 Accumulation is exact (int32) where upstream's fp32 / bf16 `aten.linear` rounds, so results agree within the accumulation
 bound, not bit for bit.  STATS counts the native launches (tests assert the route was taken).
+
+`fuse_mx_pairs` is the same kind of pass for microscaling graphs: an activation's `calculate_mx_qparam` + `quantize` pair becomes
+one `quantize_mx` node (one device pass, bit-identical results).
 """
 import ctypes
 
@@ -29,7 +32,7 @@ from torch.fx import GraphModule
 from . import _native, switches
 from .fake_quantize import _stream_ptr
 
-__all__ = ["fuse_native_gemms", "STATS"]
+__all__ = ["fuse_native_gemms", "fuse_mx_pairs", "STATS"]
 
 STATS = {"linear_int8": 0, "matmul_int8": 0, "linear_fp8": 0, "matmul_fp8": 0}
 _IDENTITY_DTYPES = (None, "None", "bfloat16", "float32", "float16")
@@ -261,6 +264,70 @@ def fuse_native_gemms(model: GraphModule) -> int:
             fused += 1
     if fused:
         graph.eliminate_dead_code(is_impure_node=lambda n: n.op in {"placeholder", "output"})
+        graph.lint()
+        model.recompile()
+    return fused
+
+
+def _is_mx_consumer(node):
+    ops = torch.ops.quantized_ops
+    return getattr(node, "op", None) == "call_function" and node.target in (ops.linear_mx.default, ops.matmul_mx.default,
+                                                                            ops.conv2d_mx.default)
+
+
+def _axes_list(axes):
+    """The `axes` argument of a graph node as a list of ints (a hand-built graph may carry a bare int), else None."""
+    if isinstance(axes, int) and not isinstance(axes, bool):
+        return [axes]
+    if isinstance(axes, (list, tuple)) and all(isinstance(a, int) and not isinstance(a, bool) for a in axes):
+        return list(axes)
+    return None
+
+
+def fuse_mx_pairs(model: GraphModule) -> int:
+    """Folds `s = calculate_mx_qparam(x, axes, bs, qmax, pow2[, smap])` + `quantize(x, s, None, axes, bs, qmap, None)` -- what
+    convert_pt2e emits for an activation whose blocks do not run along the last axis (the second operand of every block-scaled
+    matmul, quantize_pt2e.py: `_with_axis(activation, -2)`) -- into one `quantize_mx(x, qmap, axes, bs, qmax, pow2, smap, None)`
+    node with two getitems, so that the device runs one pass over x (and gets the packed matmul operand with it).  quantize_mx's
+    fallback is literally those two ops, so the fold changes no result on any device or dtype.  Returns the number of folds."""
+    import operator
+    ops = torch.ops.quantized_ops
+    graph = model.graph
+    order = {n: i for i, n in enumerate(graph.nodes)}
+    fused = 0
+    for q in list(graph.nodes):
+        if not _is(q, ops.quantize.default) or q.kwargs or len(q.args) < 6:
+            continue
+        a = list(q.args) + [None] * (7 - len(q.args))
+        src, s, zp, axes, bs, qmap, code = a[:7]
+        if not _is(s, ops.calculate_mx_qparam.default) or s.kwargs or zp is not None or code is not None or qmap is None:
+            continue
+        if not 4 <= len(s.args) <= 6:
+            continue
+        sa = list(s.args) + [False, None][len(s.args) - 4:]        # (x, axes, bs, qmax, pow2, smap)
+        if sa[0] is not src or getattr(src, "op", "get_attr") == "get_attr":
+            continue
+        s_axes, q_axes = _axes_list(sa[1]), _axes_list(axes)
+        if s_axes is None or s_axes != q_axes or sa[2] != bs:      # axes that are no int or sequence of ints: leave the pair
+            continue
+        if any(u is not q and (not _is_mx_consumer(u) or order[u] < order[q]) for u in s.users):
+            continue
+        with graph.inserting_before(q):                             # behind the map's get_attr; every user of s comes after q
+            mx = graph.call_function(ops.quantize_mx.default, (src, qmap, s_axes if isinstance(sa[1], int) else sa[1], bs, sa[3], sa[4], sa[5], None))
+            s_new = graph.call_function(operator.getitem, (mx, 0))
+            q_new = graph.call_function(operator.getitem, (mx, 1))
+        # the fused branch of quantize_pt2e._lower_mx_fake_quant: (scale dtype, element dtype) on the node, each on its getitem
+        mx.meta["dtype"] = (s.meta.get("dtype"), q.meta.get("dtype"))
+        if "source_fn_stack" in q.meta:
+            mx.meta["source_fn_stack"] = [(mx.name, mx.target)]
+        s_new.meta, q_new.meta = dict(s.meta), dict(q.meta)
+        q_new.meta.pop("source_fn_stack", None)
+        q.replace_all_uses_with(q_new)
+        s.replace_all_uses_with(s_new)
+        graph.erase_node(q)
+        graph.erase_node(s)
+        fused += 1
+    if fused:
         graph.lint()
         model.recompile()
     return fused

@@ -491,4 +491,5 @@ def convert_pt2e(model: GraphModule, output_dtype: str = None, eliminate_no_effe
     from . import pt2e_native
     if native or (native is None and pt2e_native.enabled_for(model)):
         pt2e_native.fuse_native_gemms(model)
+        pt2e_native.fuse_mx_pairs(model)                         # calculate_mx_qparam + quantize of an activation -> one quantize_mx
     return model
