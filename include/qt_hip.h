@@ -754,6 +754,23 @@ int qt_mx_gemm(const uint8_t *a_codes, const uint8_t *a_e8m0, int a_format, cons
                int b_format, void *c_dev, int c_is_f32, const void *bias_dev, long batch, int M, int N, int K,
                long a_batch_stride_rows, long b_batch_stride_rows, void *stream);
 
+/* conv2d_mx (decomposed.py:265-301: both operands times their expanded block scales, then F.conv2d) as an implicit GEMM on the same
+ * instruction, from packed operands whose blocks run along the channel axis:
+ *     y[n, ho, wo, co] = sum_{r, s, c} x[n, ho sh - ph + r dh, wo sw - pw + s dw, c] 2^(ex - 127) . w[co, r, s, c] 2^(ew - 127) (+ bias[co])
+ * x_codes: NHWC [N][H][W][Cin bits / 8], x_e8m0 [N][H][W][Cin / 32]; w_codes [Cout][kh][kw][Cin bits / 8], w_e8m0
+ * [Cout][kh][kw][Cin / 32] (the packed operand above with the contraction ordered (r, s, c), as in qt_conv2d_bf16); y NHWC
+ * [N][Ho][Wo][Cout], bf16 or fp32; bias [Cout] in y's dtype, nullable.  Zero padding, groups = 1; fp32 accumulation in a fixed
+ * order, bias added in fp32, one rounding.  Takes the format pairs of qt_mx_gemm (any other pair: QT_ERR_BAD_DTYPE), Cin % 32 == 0
+ * with (Cin bits / 8) % 16 == 0 for each operand (the 6-bit formats need Cin % 64 == 0: QT_ERR_UNALIGNED otherwise), every pointer
+ * 16-byte aligned (QT_ERR_UNALIGNED), any Cout, filter, stride, padding and dilation; N Ho Wo, kh kw Cin and the byte sizes of both
+ * code arrays below 2^31, kh dh, kw dw, strides and paddings below 2^20 (QT_ERR_BAD_ARG, like every NULL or non-positive argument).
+ * All of that is answered before the first HIP call; an empty output is QT_OK without a launch.  No address outside the operands
+ * is read: taps in the padding are zero chunks multiplied by the scale 1.  No allocation, no synchronisation: safe under stream
+ * capture; the same bits on every launch. */
+int qt_conv2d_mx(const uint8_t *x_codes, const uint8_t *x_e8m0, int x_format, const uint8_t *w_codes, const uint8_t *w_e8m0, int w_format,
+                 void *y, int y_is_f32, const void *bias, int N, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw, int ph,
+                 int pw, int dh, int dw, void *stream);
+
 /* ---- section 8(f).1: converted per-tensor graphs, quantize -> GEMM -> dequantize(s_x * s_w)     quantize_pt2e.py:323-446
  * The int8 GEMM of such a graph on v_mfma_i32_16x16x64_i8 with the dequantize node in its epilogue:
  *     C[b][M][N] = round_C( round_C( A[b][M][K] . B[b][N][K]^T + bias[N] ) * out_scale )

@@ -1141,6 +1141,219 @@ int launch_plain(const MxGemmArgs &g, dim3 grid, hipStream_t st) {
     return qt_launch_status();
 }
 
+// ---- conv2d_mx as an implicit GEMM (decomposed.py:265-301) --------------------------------------------------
+// The register-staged 128 x 128 x 128 kernel above with a gathered A side.  Rows = output pixels (n, ho, wo), columns = Cout,
+// K = kh kw Cin ordered (r, s, c).  The B operand is the packed [Cout][kh kw Cin] weight as it stands.  The A operand has no
+// matrix in memory: x codes are NHWC with P = Cin bits / 8 bytes per pixel (a multiple of 16), so the 16-byte chunk at byte b
+// of the virtual kh kw P-byte row of an output pixel is bytes [b % P, b % P + 16) of input pixel
+// (ho sh - ph + r dh, wo sw - pw + s dw) with (r, s) = tap b / P -- a chunk never straddles a tap -- and the scale byte of
+// 32-block kb is block kb % (Cin / 32) of tap kb / (Cin / 32).  A tap in the zero padding, a row past M and the K tail store
+// zero chunks (code 0 is +0 in all five formats) and multiply them by the scale 1; their loads are redirected to byte 0 of the
+// operand, so no address outside x_codes / x_e8m0 is ever formed into a load.
+// A k tile starts at 32-block u_blk of tap (u_tr, u_ts): wave-uniform, moved on by additions.  A lane's chunk or scale byte
+// lies at most four taps further (128 k over Cin >= 32), found by comparisons; a lane's pixel never changes over the k loop.
+struct MxConvGeom {
+    int H, W, kh, kw, sh, sw, ph, pw, dh, dw, Ho, Wo;
+    int cpb;                      // 32-blocks per input pixel, Cin / 32
+};
+
+// position v (< 5 per) counted from the start of tap (tr0, ts0 < kw) -> offset inside its tap, and that tap
+__device__ __forceinline__ void conv_tap_of(int v, int per, int ts0, int tr0, int kw, int &off, int &ts, int &tr) {
+    const int q = (v >= per) + (v >= 2 * per) + (v >= 3 * per) + (v >= 4 * per);
+    const int s = ts0 + q;                                            // < kw + 4 <= 5 kw
+    const int wrap = (s >= kw) + (s >= 2 * kw) + (s >= 3 * kw) + (s >= 4 * kw);
+    off = v - q * per;
+    ts = s - wrap * kw;
+    tr = tr0 + wrap;
+}
+
+template <int FA, int FB>
+__global__ __launch_bounds__(256) void mx_conv_kernel(MxGemmArgs a, MxConvGeom c) {
+    using M_ = Mma<FA, FB, false>;
+    using TA = Tile<FA>;
+    using TB = Tile<FB>;
+    constexpr int RA = TA::kRow, RB = TB::kRow;
+    constexpr int CA = TA::kChunks, CB = TB::kChunks;
+    constexpr int NA = kBM * CA / 256, NB = kBN * CB / 256;
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    auto s_a = [&](int buf) __attribute__((always_inline)) { return lds + buf * TA::kBytes; };
+    auto s_b = [&](int buf) __attribute__((always_inline)) { return lds + 2 * TA::kBytes + buf * TB::kBytes; };
+
+    const int t = threadIdx.x, l = t & 63, w = t >> 6;
+    const int r = l & 15, g = l >> 4;
+    const int wm = w >> 1, wn = w & 1;
+    const int tiles_m = (a.M + kBM - 1) / kBM, tiles_n = (a.N + kBN - 1) / kBN;
+    const int ntiles = tiles_m * tiles_n;
+    int id = blockIdx.x;
+    {
+        const int per = ntiles / 8, rem = ntiles % 8, x = id % 8, q = id / 8;
+        id = x * per + (x < rem ? x : rem) + q;                  // XCD x owns a contiguous run of tiles, as in mx_gemm_kernel
+    }
+    constexpr int kGroup = 8;
+    const int width = kGroup * tiles_n, grp = id / width, first_m = grp * kGroup;
+    const int gsize = min(tiles_m - first_m, kGroup);
+    const int m0 = (first_m + (id % width) % gsize) * kBM, n0 = ((id % width) / gsize) * kBN;
+    const long kbB = (long)a.K * elem_bits(FB) / 8;
+    const int nblk = a.K / 32;
+    const int nk = (a.K + kBK - 1) / kBK;
+    const int pbytes = c.cpb * (RA / 4);                             // P: code bytes of one input pixel
+
+    // an output pixel's input corner: the pixel index it would have (modulo 2^32: only taps inside the plane are fetched) and its
+    // row / column; rows past M get a corner that no tap brings back into the plane
+    auto corner = [&](int m, uint32_t &pix, int &hi0, int &wi0) __attribute__((always_inline)) {
+        const bool live = m < a.M;
+        const int mm = live ? m : 0;
+        const int n = mm / (c.Ho * c.Wo), rem = mm - n * (c.Ho * c.Wo), ho = rem / c.Wo, wo = rem - ho * c.Wo;
+        hi0 = live ? ho * c.sh - c.ph : -(1 << 28);
+        wi0 = wo * c.sw - c.pw;
+        pix = (uint32_t)n * (uint32_t)(c.H * c.W) + (uint32_t)hi0 * (uint32_t)c.W + (uint32_t)wi0;
+    };
+    uint32_t ga[NA], gs[4];          // byte offsets of the corners into x_codes (+ the chunk) / x_e8m0
+    int hia[NA], wia[NA], his[4], wis[4];
+    int la[NA], ca[NA];
+    const uint8_t *gb[NB];
+    int lb[NB], cb[NB];
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+        const int ch = t + 256 * i, row = ch / CA, cc = ch % CA;
+        uint32_t pix;
+        corner(m0 + row, pix, hia[i], wia[i]);
+        ga[i] = pix * (uint32_t)pbytes;
+        la[i] = TA::chunk_off(row, cc);
+        ca[i] = cc * 16;
+    }
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+        const int ch = t + 256 * i, row = ch / CB, cc = ch % CB;
+        gb[i] = a.B + (long)min(n0 + row, a.N - 1) * kbB + cc * 16;
+        lb[i] = TB::chunk_off(row, cc);
+        cb[i] = cc * 16;
+    }
+    const uint8_t *psb[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        uint32_t pix;
+        corner(m0 + wm * 64 + i * 16 + r, pix, his[i], wis[i]);
+        gs[i] = pix * (uint32_t)c.cpb;
+        psb[i] = a.sB + (long)min(n0 + wn * 64 + i * 16 + r, a.N - 1) * nblk;
+    }
+
+    uint4 ra[NA], rb[NB];
+    bool oka[NA];
+    int sca[4], scb[4];
+    int u_blk = 0, u_ts = 0, u_tr = 0;                               // where the next k tile to load starts
+    auto load_tile = [&](int kt) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < NA; ++i) {
+            int off, ts, tr;
+            conv_tap_of(u_blk * (RA / 4) + ca[i], pbytes, u_ts, u_tr, c.kw, off, ts, tr);
+            const int hi = hia[i] + tr * c.dh, wi = wia[i] + ts * c.dw;
+            oka[i] = (tr < c.kh) & ((unsigned)hi < (unsigned)c.H) & ((unsigned)wi < (unsigned)c.W);    // tr >= kh: the K tail
+            const uint32_t src = ga[i] + ((uint32_t)(tr * c.dh) * (uint32_t)c.W + (uint32_t)(ts * c.dw)) * (uint32_t)pbytes + (uint32_t)off;
+            ra[i] = *(const uint4 *)(a.A + (oka[i] ? src : 0u));
+        }
+#pragma unroll
+        for (int i = 0; i < NB; ++i) {
+            const long off = (long)kt * RB + cb[i];
+            rb[i] = *(const uint4 *)(gb[i] + (off < kbB ? (long)kt * RB : -(long)cb[i]));
+        }
+        int blk, ts, tr;
+        conv_tap_of(u_blk + g, c.cpb, u_ts, u_tr, c.kw, blk, ts, tr);
+        const uint32_t sdelta = ((uint32_t)(tr * c.dh) * (uint32_t)c.W + (uint32_t)(ts * c.dw)) * (uint32_t)c.cpb + (uint32_t)blk;
+        const int kb = min(kt * 4 + g, nblk - 1);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int hi = his[i] + tr * c.dh, wi = wis[i] + ts * c.dw;
+            const bool ok = (tr < c.kh) & ((unsigned)hi < (unsigned)c.H) & ((unsigned)wi < (unsigned)c.W);
+            const int sv = a.sA[ok ? gs[i] + sdelta : 0u];
+            sca[i] = ok ? sv : 127;
+            scb[i] = psb[i][kb];
+        }
+        int nb, ns, nr;
+        conv_tap_of(u_blk + 4, c.cpb, u_ts, u_tr, c.kw, nb, ns, nr);
+        u_blk = nb; u_ts = ns; u_tr = nr;
+    };
+    auto store_tile = [&](int buf, int kt) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < NA; ++i) {
+            const bool live = oka[i];
+            uint4 v = ra[i];
+            v.x = live ? v.x : 0u; v.y = live ? v.y : 0u; v.z = live ? v.z : 0u; v.w = live ? v.w : 0u;
+            *(uint4 *)(s_a(buf) + la[i]) = v;
+        }
+#pragma unroll
+        for (int i = 0; i < NB; ++i) {
+            const bool live = (long)kt * RB + cb[i] < kbB;
+            uint4 v = rb[i];
+            v.x = live ? v.x : 0u; v.y = live ? v.y : 0u; v.z = live ? v.z : 0u; v.w = live ? v.w : 0u;
+            *(uint4 *)(s_b(buf) + lb[i]) = v;
+        }
+    };
+
+    v4f acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = M_::zero();
+
+    load_tile(0);
+    store_tile(0, 0);
+    int cs_a[4], cs_b[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { cs_a[i] = sca[i]; cs_b[i] = scb[i]; }
+    __syncthreads();
+    auto compute = [&](int cur) __attribute__((always_inline)) {
+        v8i fa[4], fb[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) fa[i] = read_frag<FA>(s_a(cur), wm * 64 + i * 16 + r, g);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) fb[j] = read_frag<FB>(s_b(cur), wn * 64 + j * 16 + r, g);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                acc[i][j] = M_::run(fa[i], fb[j], acc[i][j], cs_a[i], cs_b[j]);
+    };
+    for (int kt = 0; kt + 1 < nk; ++kt) {
+        const int cur = kt & 1;
+        load_tile(kt + 1);                                // in flight during this tile's MFMAs
+        __builtin_amdgcn_sched_barrier(0);
+        compute(cur);
+        __builtin_amdgcn_sched_barrier(0);
+        store_tile(cur ^ 1, kt + 1);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { cs_a[i] = sca[i]; cs_b[i] = scb[i]; }
+        __syncthreads();
+    }
+    compute((nk - 1) & 1);
+
+    // epilogue: D col = l & 15, row = 4 g + e; y is [M][Cout] = NHWC
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int col = n0 + wn * 64 + j * 16 + r;
+        if (col >= a.N) continue;
+        float bv = 0.f;
+        if (a.bias) bv = a.out_f32 ? ((const float *)a.bias)[col] : qt_bf2f(((const uint16_t *)a.bias)[col]);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int row = m0 + wm * 64 + i * 16 + 4 * g + e;
+                if (row >= a.M) continue;
+                emit_out(a, acc[i][j][e], bv, 1.0f, (long)row * a.N + col);
+            }
+        }
+    }
+}
+
+template <int FA, int FB>
+int launch_conv(const MxGemmArgs &g, const MxConvGeom &c, unsigned grid, hipStream_t st) {
+    constexpr int kLds = 2 * Tile<FA>::kBytes + 2 * Tile<FB>::kBytes;
+    if (const int rc = qt_allow_lds<mx_conv_kernel<FA, FB>>(kLds)) return rc;
+    mx_conv_kernel<FA, FB><<<grid, 256, kLds, st>>>(g, c);
+    return qt_launch_status();
+}
+
 // ---- packing: (values, block scales) -> element codes + E8M0 ------------------------------------------------
 // A value that the format holds exactly converts exactly; anything else (and a scale that is not a power of
 // two) raises the `bad` flag so the caller can fall back to the dequantize + GEMM path.
@@ -1261,6 +1474,39 @@ int qt_mx_gemm(const uint8_t *a_codes, const uint8_t *a_e8m0, int a_format, cons
     return rc;
 }
 
+int qt_conv2d_mx(const uint8_t *x_codes, const uint8_t *x_e8m0, int x_format, const uint8_t *w_codes, const uint8_t *w_e8m0, int w_format,
+                 void *y, int y_is_f32, const void *bias, int N, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw, int ph,
+                 int pw, int dh, int dw, void *stream) {
+    if (!x_codes || !x_e8m0 || !w_codes || !w_e8m0 || !y) return QT_ERR_BAD_ARG;
+    if (x_format < 0 || x_format > 4 || w_format < 0 || w_format > 4) return QT_ERR_BAD_ARG;
+    if (N < 0 || H < 1 || W < 1 || Cout < 0 || Cin < 32 || Cin % 32 != 0 || Cin > (1 << 24)) return QT_ERR_BAD_ARG;
+    if (kh < 1 || kw < 1 || sh < 1 || sw < 1 || dh < 1 || dw < 1 || ph < 0 || pw < 0) return QT_ERR_BAD_ARG;
+    if (!qt_pick_pair(MxPairs{}, x_format, w_format, [](auto) {})) return QT_ERR_BAD_DTYPE;       // caller dequantizes
+    const long pbx = (long)Cin * elem_bits(x_format) / 8, pbw = (long)Cin * elem_bits(w_format) / 8;      // code bytes per pixel / tap
+    if ((pbx & 15) || (pbw & 15)) return QT_ERR_UNALIGNED;
+    const long eh = (long)H + 2L * ph - (long)dh * (kh - 1) - 1, ew = (long)W + 2L * pw - (long)dw * (kw - 1) - 1;
+    if (N == 0 || Cout == 0 || eh < 0 || ew < 0) return QT_OK;                                  // empty output: nothing to launch
+    if ((((uintptr_t)x_codes | (uintptr_t)x_e8m0 | (uintptr_t)w_codes | (uintptr_t)w_e8m0 | (uintptr_t)y | (uintptr_t)bias) & 15u))
+        return QT_ERR_UNALIGNED;
+    // 32-bit row and pixel indices, 32-bit byte offsets into the code arrays; the output is indexed in 64 bits
+    // (a product that reaches 2^31 saturates there, so that no argument can overflow the 64-bit arithmetic of the checks)
+    constexpr long kLim = 1L << 31;
+    auto mul = [](long a, long b) { return a >= kLim || b >= kLim ? kLim : (a * b >= kLim ? kLim : a * b); };
+    const long ho = eh / sh + 1, wo = ew / sw + 1, m = mul(N, mul(ho, wo)), taps = mul(kh, kw);
+    if (m >= kLim || mul(taps, Cin) >= kLim || mul(N, mul(mul(H, W), pbx)) >= kLim || mul(Cout, mul(taps, pbw)) >= kLim ||
+        (long)kh * dh >= (1 << 20) || (long)kw * dw >= (1 << 20) || ph >= (1 << 20) || pw >= (1 << 20) || sh >= (1 << 20) || sw >= (1 << 20))
+        return QT_ERR_BAD_ARG;
+    const int K = (int)(taps * Cin);
+    MxGemmArgs g{x_codes, w_codes, x_e8m0, w_e8m0, y, bias, (int)m, Cout, K, 0, 0, 0, 0, 0, y_is_f32, nullptr, 0, 0};
+    const MxConvGeom c{H, W, kh, kw, sh, sw, ph, pw, dh, dw, (int)ho, (int)wo, Cin / 32};
+    const long tiles = ((m + kBM - 1) / kBM) * ((Cout + kBN - 1) / kBN);
+    if (tiles >= kLim) return QT_ERR_BAD_ARG;
+    int rc = QT_ERR_BAD_DTYPE;
+    qt_pick_pair(MxPairs{}, x_format, w_format, [&](auto P) {
+        rc = launch_conv<decltype(P)::a, decltype(P)::b>(g, c, (unsigned)tiles, (hipStream_t)stream);
+    });
+    return rc;
+}
 
 int qt_q8_gemm(const int8_t *a_codes, const int8_t *b_codes, void *c_dev, int c_is_f32, const void *bias_dev, const void *out_scale_dev,
                int out_scale_per_col, int fold_f32, long batch, int M, int N, int K, long a_batch_stride_rows, long b_batch_stride_rows, void *stream) {

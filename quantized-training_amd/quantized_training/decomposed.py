@@ -281,7 +281,8 @@ def _quantize_mx_strided_hip_or_none(input, qmap, axes, block_size, quant_max, p
     fmt_name = mx_gemm.format_of_qmap(qmap) if want_q and pow2 and block_size % 32 == 0 else None
     codes = e8 = None
     fid = -1
-    if fmt_name is not None and ax == x.dim() - 2 and (n * mx_gemm._BITS[mx_gemm.FMT_ID[fmt_name]] // 8) % 16 == 0:
+    nhwc = x.dim() == 4 and ax == 1                          # [N, C, H, W] along C: the codes come out NHWC, conv2d_mx's operand
+    if fmt_name is not None and (ax == x.dim() - 2 or nhwc) and (n * mx_gemm._BITS[mx_gemm.FMT_ID[fmt_name]] // 8) % 16 == 0:
         fid = mx_gemm.FMT_ID[fmt_name]
         codes = torch.empty((outer * inner, n * mx_gemm._BITS[fid] // 8), dtype=torch.uint8, device=x.device)
         e8 = torch.empty((outer * inner, n // 32), dtype=torch.uint8, device=x.device)
@@ -301,7 +302,9 @@ def _quantize_mx_strided_hip_or_none(input, qmap, axes, block_size, quant_max, p
         sf._qt_pow2 = True
         if fmt_name is not None:
             q._qt_mx_fmt = fmt_name
-        if codes is not None:
+        if codes is not None and nhwc:
+            q._qt_mx_packed_nhwc = (fid, block_size, codes, e8)
+        elif codes is not None:
             q._qt_mx_packed_b = (fid, block_size, codes, e8)
     return sf, q
 
@@ -331,6 +334,20 @@ def _quantize_mx_hip_or_none(input, qmap, axes, block_size, quant_max, pow2, sca
                 if hasattr(q, "_qt_mx_packed_act"):                 # [batch N, K]: rows of the stored tensor
                     q_t._qt_mx_packed_b = q._qt_mx_packed_act
                 return sf_t, q_t
+        if input.dim() == 4 and axes[0] % 4 == 1 and not input.is_contiguous() and input.permute(0, 2, 3, 1).is_contiguous():
+            # channels_last-dense along C (what a layer behind an in-tree convolution receives): the last-axis pass on the stored
+            # [N, H, W, C] tensor, whose packed codes ARE the NHWC operand of conv2d_mx, returned as permuted views
+            out = _quantize_mx_hip_or_none(input.permute(0, 2, 3, 1), qmap, [-1], block_size, quant_max, pow2, scale_qmap)
+            if out is not None:
+                sf, q = out
+                sf_p, q_p = sf.permute(0, 3, 1, 2), q.permute(0, 3, 1, 2)
+                if hasattr(sf, "_qt_pow2"):
+                    sf_p._qt_pow2 = sf._qt_pow2
+                if hasattr(q, "_qt_mx_fmt"):
+                    q_p._qt_mx_fmt = q._qt_mx_fmt
+                if hasattr(q, "_qt_mx_packed_act"):
+                    q_p._qt_mx_packed_nhwc = q._qt_mx_packed_act
+                return sf_p, q_p
         return _quantize_mx_strided_hip_or_none(input, qmap, axes, block_size, quant_max, pow2, scale_qmap)
     per = 8 if input.dtype == torch.bfloat16 else 4
     cols = input.shape[-1]
@@ -420,6 +437,12 @@ def _mx_operand(x, scale, code, block_size):
 
 def _conv2d_mx_impl(input, weight, bias=None, stride=1, padding=0, dilation=1, groups=1, *, input_scale=None,
                     weight_scale=None, block_size=None, input_code=None, weight_code=None):
+    if input.device.type == "cuda":
+        from .mx_conv import mx_conv2d_or_none
+        out = mx_conv2d_or_none(input, weight, bias, stride, padding, dilation, groups, input_scale, weight_scale, block_size,
+                                input_code, weight_code)
+        if out is not None:
+            return out
     return F.conv2d(_mx_operand(input, input_scale, input_code, block_size),
                     _mx_operand(weight, weight_scale, weight_code, block_size), bias, stride, padding, dilation, groups)
 

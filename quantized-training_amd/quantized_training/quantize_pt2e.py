@@ -288,7 +288,8 @@ def _lower_mx_fake_quant(model: GraphModule, node: Node, fq):
     fuse = False
     if len(fq.ch_axis) == 1:
         axis = fq.ch_axis[0]
-        if any(u.target == torch.ops.aten.conv2d.default for u in node.users):
+        # (a consumer whose weight was lowered first already is its conv2d_mx twin: upstream's is_conv2d counts both)
+        if any(u.target in (torch.ops.aten.conv2d.default, torch.ops.quantized_ops.conv2d_mx.default) for u in node.users):
             fuse = axis in (1, -3)
         else:
             fuse = axis == -1 or ("val" in src.meta and axis == src.meta["val"].ndim - 1)
