@@ -771,6 +771,48 @@ int qt_conv2d_mx(const uint8_t *x_codes, const uint8_t *x_e8m0, int x_format, co
                  void *y, int y_is_f32, const void *bias, int N, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw, int ph,
                  int pw, int dh, int dw, void *stream);
 
+/* ---- the outlier side path of a block-scaled linear layer: filter_outlier / spmm_csr            decomposed.py:450-566
+ * qt_filter_outlier_*: replaces filter_outlier (decomposed.py:450-507, the nested Python loops over .item()).  x is the [rows][cols]
+ * view of a contiguous tensor (cols = its last axis).  threshold is the operator's threshold ALREADY ROUNDED to the tensor's dtype,
+ * which is what torch's `abs(x) > threshold` compares with.
+ *   inlier[rows][cols]    +0 where |x| > threshold, else x bit for bit (a NaN compares false and stays, like -0.0 and an inf that
+ *                         does not exceed the threshold)
+ *   data / indices        the CSR entries -- elements with |x| > threshold and x != 0, row-major -- of which the first
+ *   [max_nnz]             min(nnz, max_nnz) are stored (the cut may fall inside a row); zero from there to max_nnz
+ *   indptr[rows + 1]      int32 prefix counts of ALL entries, also of those behind max_nnz: indptr[rows] > max_nnz says "truncated"
+ * Three launches (inlier + row counts, a one-workgroup scan of indptr in place, compaction that reads the rows again), ordered by
+ * the stream alone: no workgroup waits for another, no atomics, no host read, no allocation -- safe under stream capture, the same
+ * bits on every launch.  16-byte vector accesses between the 16-byte boundaries of each row, single elements in front and behind.
+ * QT_ERR_BAD_ARG: a NULL tensor (data / indices may be NULL when max_nnz == 0), rows < 1, cols < 1, rows, cols or rows cols
+ * >= 2^31 - 1, max_nnz < 0 or > rows cols; QT_ERR_UNALIGNED: a pointer off its element size.  All answered before the first launch. */
+int qt_filter_outlier_bf16(const uint16_t *x_dev, uint16_t *inlier_dev, uint16_t *data_dev, int32_t *indices_dev, int32_t *indptr_dev, long rows,
+                           long cols, float threshold, long max_nnz, void *stream);
+int qt_filter_outlier_f32(const float *x_dev, float *inlier_dev, float *data_dev, int32_t *indices_dev, int32_t *indptr_dev, long rows, long cols,
+                          float threshold, long max_nnz, void *stream);
+
+/* qt_spmm_csr_*: replaces spmm_csr (decomposed.py:510-566: dequantize the whole weight, then a Python loop over rows and entries):
+ *     y[r][n] = sum over i in [indptr[r], indptr[r + 1]) of data[i] . Bd[n][indices[i]],      r < rows, n < N
+ * b_is_kn = 0: b is stored [N][K] (the Linear weight as the graph passes it); 1: [K][N] (weight_transposed).  Bd is the operand as
+ * the reference forms it, element (i0, i1) of the STORED b:  v = code ? code[(long)b] : b;  Bd = scale ? rd(v . scale[i0 / div0][i1 / div1]) : v
+ * with rd the rounding to the tensor's dtype, scale [scale_rows][scale_cols], div = 1 along an axis the scale has in full and the
+ * block size along a blocked one (what expand() does, a partial last block included).  code: n_code <= 256 values; an index is
+ * truncated toward zero, a negative one counts from the end as in torch, and one outside the codebook (or a NaN) gives 0.
+ * The weight is taken in place: a workgroup stages the operand rows of its output features into LDS, nothing dequantized, gathered
+ * or transposed is written to memory.  fp32 accumulation in a fixed order (the row's entries in order, in groups of 16 whose sums are
+ * added in order: a long row's error grows with 16 + m / 16 roundings, not m), fused multiply-adds, one rounding to the output dtype;
+ * every element of y is written (rows without entries: zeros); no atomics: the same bits on every launch.  No host read, no allocation.
+ * capacity = the element count of data / indices.  A truncated CSR (indptr counts entries the arrays do not hold) is memory-safe:
+ * every row's range is clamped to [0, capacity], entries behind it are skipped, and so is an entry whose index is outside [0, K).
+ * QT_ERR_BAD_ARG: NULL indptr / b / y (data / indices may be NULL when capacity == 0), K < 1, a dimension or the capacity
+ * >= 2^31 - 1, a scale that does not cover b, n_code outside 1..256, K too long for one operand row in LDS (K bytes > 159 KiB);
+ * QT_ERR_UNALIGNED: a pointer off its element size.  QT_OK without a launch when rows == 0 or N == 0. */
+int qt_spmm_csr_bf16(const uint16_t *data_dev, const int32_t *indices_dev, const int32_t *indptr_dev, long capacity, long rows, const uint16_t *b_dev,
+                     long N, long K, int b_is_kn, const uint16_t *scale_dev, long scale_rows, long scale_cols, int scale_div0, int scale_div1,
+                     const uint16_t *code_dev, int n_code, uint16_t *y_dev, void *stream);
+int qt_spmm_csr_f32(const float *data_dev, const int32_t *indices_dev, const int32_t *indptr_dev, long capacity, long rows, const float *b_dev, long N,
+                    long K, int b_is_kn, const float *scale_dev, long scale_rows, long scale_cols, int scale_div0, int scale_div1, const float *code_dev,
+                    int n_code, float *y_dev, void *stream);
+
 /* ---- section 8(f).1: converted per-tensor graphs, quantize -> GEMM -> dequantize(s_x * s_w)     quantize_pt2e.py:323-446
  * The int8 GEMM of such a graph on v_mfma_i32_16x16x64_i8 with the dequantize node in its epilogue:
  *     C[b][M][N] = round_C( round_C( A[b][M][K] . B[b][N][K]^T + bias[N] ) * out_scale )

@@ -226,6 +226,10 @@ SIGNATURES = {
                           c_int, _P, _P]),
     "qt_mx_gemm": (c_int, [_P, _P, c_int, _P, _P, c_int, _P, c_int, _P, c_long, c_int, c_int, c_int, c_long, c_long, _P]),
     "qt_conv2d_mx": (c_int, [_P, _P, c_int, _P, _P, c_int, _P, c_int, _P] + [c_int] * 13 + [_P]),
+    "qt_filter_outlier_bf16": (c_int, [_P, _P, _P, _P, _P, c_long, c_long, c_float, c_long, _P]),
+    "qt_filter_outlier_f32": (c_int, [_P, _P, _P, _P, _P, c_long, c_long, c_float, c_long, _P]),
+    "qt_spmm_csr_bf16": (c_int, [_P, _P, _P, c_long, c_long, _P, c_long, c_long, c_int, _P, c_long, c_long, c_int, c_int, _P, c_int, _P, _P]),
+    "qt_spmm_csr_f32": (c_int, [_P, _P, _P, c_long, c_long, _P, c_long, c_long, c_int, _P, c_long, c_long, c_int, c_int, _P, c_int, _P, _P]),
     "qt_q8_gemm": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, c_int, c_long, c_int, c_int, c_int, c_long, c_long, _P]),
     "qt_bench_fake_quant_bf16": (c_int, [_P, _P, c_size_t, _FMT, _P, _P, _P, c_int, c_size_t, c_int, _P,
                                         POINTER(c_float)]),

@@ -478,13 +478,19 @@ _lib.impl("matmul_mx", _matmul_mx_impl, "CompositeExplicitAutograd")
 # filter_outlier splits an activation into its inliers (|x| <= threshold, outliers zeroed) and the outliers as a CSR
 # matrix of the [rows, C] view, padded to int(numel * max_pct) entries; spmm_csr multiplies that sparse matrix by the
 # (dequantized) weight.  Upstream walks both with Python loops over .item(); here they are index arithmetic on the
-# tensor's own device, entries in the same row-major order and, on CPU, accumulated in the same order.
+# tensor's own device, entries in the same row-major order and, on CPU, accumulated in the same order.  Device tensors go to
+# the kernels of csrc/qt_outlier.hip first (outlier.py); what they do not take runs the index arithmetic below.
 _lib.define("filter_outlier(Tensor input, float threshold, float max_pct=0.05) -> (Tensor, Tensor, Tensor, Tensor)")
 _lib.define("spmm_csr(Tensor data, Tensor indices, Tensor indptr, Tensor B, Tensor? B_scale=None, "
             "Tensor? B_code=None, int? block_size=None, bool weight_transposed=False) -> Tensor")
 
 
 def _filter_outlier_impl(input, threshold, max_pct=0.05):
+    if input.device.type == "cuda":
+        from .outlier import filter_outlier_or_none
+        out = filter_outlier_or_none(input, threshold, max_pct)
+        if out is not None:
+            return out
     is_outlier = torch.abs(input) > threshold
     inlier = torch.where(is_outlier, 0, input)
     outliers = torch.where(is_outlier, input, 0).reshape(-1, input.shape[-1])
@@ -507,6 +513,11 @@ def _filter_outlier_impl(input, threshold, max_pct=0.05):
 
 
 def _spmm_csr_impl(data, indices, indptr, B, B_scale=None, B_code=None, block_size=None, weight_transposed=False):
+    if data.device.type == "cuda":
+        from .outlier import spmm_csr_or_none
+        out = spmm_csr_or_none(data, indices, indptr, B, B_scale, B_code, block_size, weight_transposed)
+        if out is not None:
+            return out
     M = indptr.numel() - 1
     K = B.shape[1] if weight_transposed else B.shape[0]
     if B_code is not None:

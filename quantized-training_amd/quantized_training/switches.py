@@ -31,7 +31,7 @@ SWITCHES = {
     "QT_LAZY_POISON": ("0", OFF, "product", "fill the tensors a codes-only producer leaves unwritten with NaN (the tests set it)"),
     "QT_PT2E_FUSE": ("1", ON, "product", "launch fusions on prepared PT2E graphs of device models"),
     "QT_PT2E_NATIVE": ("1", ON, "product", "converted PT2E per-tensor graphs run the native int8 / FP8 GEMM ops"),
-    "QT_MX_GEMM": ("1", ON, "product", "block-scaled GEMMs on the in-tree kernel (else the reference formulation)"),
+    "QT_MX_GEMM": ("1", ON, "product", "block-scaled GEMMs, conv2d_mx and the outlier side path on the in-tree kernels (else the reference formulation)"),
     "QT_TRAIN_DEBUG": ("0", MASK, "product", "training step: bits that switch a fusion OFF (train_fusions.DEBUG_BITS)"),
     "QT_CONV_GEMM": ("auto", TRI, "product", "in-tree implicit-GEMM Conv2d: by the committed rule / never / wherever it applies"),
     "QT_TRAIN_GEMM": ("1", ON, "product", "training step: a QAT Linear's three products on qt_train_gemm_bf16 (else torch's GEMMs)"),
