@@ -15,7 +15,7 @@ import torch
 import torch.nn.functional as F
 from torch.library import Library
 
-from . import _native
+from . import _native, mx_operand
 from .fake_quantize import _cpu_vmap, _stream_ptr, hip_vmap
 
 __all__ = ["vmap", "quantize", "dequantize", "expand", "calculate_mx_qparam", "quantize_mx", "linear_mx", "matmul_mx",
@@ -137,7 +137,7 @@ def _quantize_impl(input, scale, zero_point=None, axes=None, block_size=None, qm
             _native.check(fn(x.data_ptr(), y.data_ptr(), x.numel(), ctypes.byref(fmt), qmap.data_ptr(),
                              s.data_ptr(), z.data_ptr() if z is not None else None, _stream_ptr(x)), "qt_quantize")
         return y
-    pow2 = getattr(scale, "_qt_pow2", False)
+    pow2 = mx_operand.is_pow2(scale)
     if block_size is not None:
         view = _block_param_view(input, scale, zero_point, block_size)
         if view is not None and qmap.dtype == torch.bfloat16 and qmap.numel() == 65536:
@@ -150,8 +150,9 @@ def _quantize_impl(input, scale, zero_point=None, axes=None, block_size=None, qm
     input = input / scale if zero_point is None else input / scale + zero_point
     out = torch.ops.quantized_ops.vmap(input, qmap)
     if pow2 and zero_point is None and out.device.type == "cuda":
-        from .mx_gemm import remember_format
-        remember_format(out, qmap)                     # lets linear_mx / matmul_mx take the element codes directly
+        fmt = mx_operand.format_of_qmap(qmap)
+        if fmt is not None:
+            mx_operand.set_format(out, fmt)            # lets linear_mx / matmul_mx take the element codes directly
     return out
 
 
@@ -252,7 +253,7 @@ def _calculate_mx_qparam_impl(input, axes, block_size, quant_max, force_scale_po
             scale = torch.ops.quantized_ops.vmap(scale, scale_qmap)
     scale = torch.where(scale > 0.0, scale, _const_like(1.0, scale))
     if force_scale_power_of_two:
-        scale._qt_pow2 = True                          # an E8M0-representable scale, by construction
+        mx_operand.set_pow2(scale)                     # an E8M0-representable scale, by construction
     return scale
 
 
@@ -263,7 +264,7 @@ def _mx_table_ok(m):
 def _quantize_mx_strided_hip_or_none(input, qmap, axes, block_size, quant_max, pow2, scale_qmap, want_q=True):
     """One device pass (qt_quantize_mx_strided_*) for blocks along an axis that is not the last: scales, values (`want_q`) and --
     with power-of-two scales, a format the matrix instruction takes and the block axis at position dim - 2 -- the packed
-    [batch N, K] operand matmul_mx reads, left on q as `_qt_mx_packed_b`.  (scale, q or None), or None when the kernel does not
+    [batch N, K] operand matmul_mx reads, left on q (mx_operand.SECOND).  (scale, q or None), or None when the kernel does not
     take the call."""
     from .fake_quantize import _launch_format, mx_block_view
     if input.device.type != "cuda" or not quant_max > 0:
@@ -271,20 +272,19 @@ def _quantize_mx_strided_hip_or_none(input, qmap, axes, block_size, quant_max, p
     view = mx_block_view(tuple(input.shape), input.dtype, block_size, axes)
     if view is None or (want_q and not _mx_table_ok(qmap)) or (scale_qmap is not None and not _mx_table_ok(scale_qmap)):
         return None
-    from . import mx_gemm
     outer, n, inner = view
     L = _native.lib()
     x = input.contiguous()
     ax = (axes if isinstance(axes, int) else list(axes)[0]) % x.dim()
     q = torch.empty_like(x) if want_q else None
     sf = torch.empty(x.shape[:ax] + (n // block_size,) + x.shape[ax + 1:], dtype=x.dtype, device=x.device)
-    fmt_name = mx_gemm.format_of_qmap(qmap) if want_q and pow2 and block_size % 32 == 0 else None
+    fmt_name = mx_operand.format_of_qmap(qmap) if want_q and pow2 and block_size % 32 == 0 else None
     codes = e8 = None
     fid = -1
     nhwc = x.dim() == 4 and ax == 1                          # [N, C, H, W] along C: the codes come out NHWC, conv2d_mx's operand
-    if fmt_name is not None and (ax == x.dim() - 2 or nhwc) and (n * mx_gemm._BITS[mx_gemm.FMT_ID[fmt_name]] // 8) % 16 == 0:
-        fid = mx_gemm.FMT_ID[fmt_name]
-        codes = torch.empty((outer * inner, n * mx_gemm._BITS[fid] // 8), dtype=torch.uint8, device=x.device)
+    if fmt_name is not None and (ax == x.dim() - 2 or nhwc) and mx_operand.row_is_whole_chunks(n, mx_operand.FMT_ID[fmt_name]):
+        fid = mx_operand.FMT_ID[fmt_name]
+        codes = torch.empty((outer * inner, mx_operand.row_bytes(n, fid)), dtype=torch.uint8, device=x.device)
         e8 = torch.empty((outer * inner, n // 32), dtype=torch.uint8, device=x.device)
     if want_q:
         fmt = _launch_format(_lut_format(), qmap)            # the row form behind the map, when this is a map from _device_map
@@ -299,13 +299,7 @@ def _quantize_mx_strided_hip_or_none(input, qmap, axes, block_size, quant_max, p
         return None
     _native.check(code, "qt_quantize_mx_strided")
     if pow2:
-        sf._qt_pow2 = True
-        if fmt_name is not None:
-            q._qt_mx_fmt = fmt_name
-        if codes is not None and nhwc:
-            q._qt_mx_packed_nhwc = (fid, block_size, codes, e8)
-        elif codes is not None:
-            q._qt_mx_packed_b = (fid, block_size, codes, e8)
+        mx_operand.quantized(q, sf, fmt_name, mx_operand.NHWC if nhwc else mx_operand.SECOND, fid, block_size, codes, e8)
     return sf, q
 
 
@@ -327,12 +321,7 @@ def _quantize_mx_hip_or_none(input, qmap, axes, block_size, quant_max, pow2, sca
             if out is not None:
                 sf, q = out
                 sf_t, q_t = sf.transpose(-1, -2), q.transpose(-1, -2)
-                if hasattr(sf, "_qt_pow2"):
-                    sf_t._qt_pow2 = sf._qt_pow2
-                if hasattr(q, "_qt_mx_fmt"):
-                    q_t._qt_mx_fmt = q._qt_mx_fmt
-                if hasattr(q, "_qt_mx_packed_act"):                 # [batch N, K]: rows of the stored tensor
-                    q_t._qt_mx_packed_b = q._qt_mx_packed_act
+                mx_operand.carry(q, sf, q_t, sf_t)                  # [batch N, K]: rows of the stored tensor
                 return sf_t, q_t
         if input.dim() == 4 and axes[0] % 4 == 1 and not input.is_contiguous() and input.permute(0, 2, 3, 1).is_contiguous():
             # channels_last-dense along C (what a layer behind an in-tree convolution receives): the last-axis pass on the stored
@@ -341,12 +330,7 @@ def _quantize_mx_hip_or_none(input, qmap, axes, block_size, quant_max, pow2, sca
             if out is not None:
                 sf, q = out
                 sf_p, q_p = sf.permute(0, 3, 1, 2), q.permute(0, 3, 1, 2)
-                if hasattr(sf, "_qt_pow2"):
-                    sf_p._qt_pow2 = sf._qt_pow2
-                if hasattr(q, "_qt_mx_fmt"):
-                    q_p._qt_mx_fmt = q._qt_mx_fmt
-                if hasattr(q, "_qt_mx_packed_act"):
-                    q_p._qt_mx_packed_nhwc = q._qt_mx_packed_act
+                mx_operand.carry(q, sf, q_p, sf_p)
                 return sf_p, q_p
         return _quantize_mx_strided_hip_or_none(input, qmap, axes, block_size, quant_max, pow2, scale_qmap)
     per = 8 if input.dtype == torch.bfloat16 else 4
@@ -357,18 +341,17 @@ def _quantize_mx_hip_or_none(input, qmap, axes, block_size, quant_max, pow2, sca
     if qmap.dtype != torch.bfloat16 or qmap.numel() != 65536 or \
             (scale_qmap is not None and (scale_qmap.dtype != torch.bfloat16 or scale_qmap.numel() != 65536)):
         return None
-    from . import mx_gemm
     L = _native.lib()
     x = input.contiguous()
     rows = x.numel() // cols
     q = torch.empty_like(x)
     sf = torch.empty(x.shape[:-1] + (cols // block_size,), dtype=x.dtype, device=x.device)
-    fmt_name = mx_gemm.format_of_qmap(qmap) if pow2 and block_size % 32 == 0 else None
+    fmt_name = mx_operand.format_of_qmap(qmap) if pow2 and block_size % 32 == 0 else None
     codes = e8 = None
     fid = -1
-    if fmt_name is not None and (cols * mx_gemm._BITS[mx_gemm.FMT_ID[fmt_name]] // 8) % 16 == 0:
-        fid = mx_gemm.FMT_ID[fmt_name]
-        codes = torch.empty((rows, cols * mx_gemm._BITS[fid] // 8), dtype=torch.uint8, device=x.device)
+    if fmt_name is not None and mx_operand.row_is_whole_chunks(cols, mx_operand.FMT_ID[fmt_name]):
+        fid = mx_operand.FMT_ID[fmt_name]
+        codes = torch.empty((rows, mx_operand.row_bytes(cols, fid)), dtype=torch.uint8, device=x.device)
         e8 = torch.empty((rows, cols // 32), dtype=torch.uint8, device=x.device)
     from .fake_quantize import _launch_format
     fmt = _launch_format(_lut_format(), qmap)                # the row form behind the map, when this is a map from _device_map
@@ -378,11 +361,7 @@ def _quantize_mx_hip_or_none(input, qmap, axes, block_size, quant_max, pow2, sca
                      float(quant_max), int(bool(pow2)), scale_qmap.data_ptr() if scale_qmap is not None else None, fid,
                      _stream_ptr(x)), "qt_quantize_mx")
     if pow2:
-        sf._qt_pow2 = True
-        if fmt_name is not None:
-            q._qt_mx_fmt = fmt_name
-        if codes is not None:
-            q._qt_mx_packed_act = (fid, block_size, codes, e8)
+        mx_operand.quantized(q, sf, fmt_name, mx_operand.ROWS, fid, block_size, codes, e8)
     return sf, q
 
 

@@ -24,7 +24,7 @@ from typing import Optional
 import torch
 from torch.ao.quantization import FakeQuantizeBase
 
-from . import _native, handover, precomputed
+from . import _native, handover, mx_operand, precomputed
 from .quantizer.quantizer import QScheme
 
 # (forward() tests its own __dict__ for these before it calls into precomputed: a call nothing was left for pays one lookup per slot)
@@ -85,7 +85,7 @@ def _table_for(dtype, device):
         if flat is None:
             idx, vals = m
             flat = vals[idx].contiguous()
-            flat._qt_dtype = dtype
+            mx_operand.tag_map(flat, dtype)
             _MAP_CACHE[key] = flat
         return flat
     return m
@@ -116,10 +116,10 @@ def get_quantization_map(dtype, device=None):
         if host is None:
             table = _native.build_map_u16(dtype)          # raises ValueError on unknown dtype
             host = torch.from_numpy(table.view("int16")).view(torch.bfloat16)
-            host._qt_dtype = dtype
+            mx_operand.tag_map(host, dtype)
             _MAP_CACHE[(dtype, torch.device("cpu"))] = host
         hit = host if dev.type == "cpu" else _device_map(host, dev)
-        hit._qt_dtype = dtype    # lets the block-scaled GEMMs recognise the element format of values rounded with this map
+        mx_operand.tag_map(hit, dtype)    # lets the block-scaled GEMMs recognise the element format of values rounded with this map
         _MAP_CACHE[key] = hit
     return hit
 
@@ -870,8 +870,8 @@ class FusedAmaxObsFakeQuantize(FakeQuantizeBase):
         if self.scale.device != device or self.amax_history.device != device:
             self.to(device)
         # `model.to(device)` leaves a plain copy of the host map in the buffer: take the cached device map instead, which carries the
-        # row form behind its entries (_device_map) and the `_qt_dtype` tag the block-scaled GEMMs look for
-        if self.qmap.device != device or (device.type == "cuda" and getattr(self.qmap, "_qt_dtype", None) is None):
+        # row form behind its entries (_device_map) and the name tag the block-scaled GEMMs look for (mx_operand.tag_map)
+        if self.qmap.device != device or (device.type == "cuda" and mx_operand.map_name(self.qmap) is None):
             self.qmap = _table_for(self.dtype, device)
             if self.scale_qmap is not None:
                 self.scale_qmap = _table_for(self.scale_dtype, device)

@@ -9,7 +9,8 @@ fake-quantizer's own pass) tells the consumer of its result what it already did.
   _qt_lazy              only the codes were written; the bf16 storage is unwritten (NaN under QT_LAZY_POISON=1)
   _qt_origin            tensor_key of the tensor this one is fq(.) of (sibling GEMMs)
 
-This module is the only code that reads or writes them.  It imports nothing from the package."""
+This module is the only code that reads or writes them.  It imports nothing from the package.  (mx_operand.py is the same protocol
+for the block-scaled operands of linear_mx / matmul_mx / conv2d_mx.)"""
 import weakref
 
 import torch

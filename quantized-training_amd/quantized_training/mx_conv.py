@@ -7,7 +7,7 @@ the element codes and E8M0 bytes of each filter tap from NHWC operands: no dequa
 
 Weight [Cout, Cin, kh, kw]: packed once as [Cout][kh kw Cin] with the packer's check on, cached on the tensor object.
 Activation, in this order:
-  1. the NHWC operand quantize_mx left on its result (`_qt_mx_packed_nhwc`: the strided pass over a contiguous NCHW tensor, or the
+  1. the NHWC operand quantize_mx left on its result (mx_operand.NHWC: the strided pass over a contiguous NCHW tensor, or the
      last-axis pass over the stored tensor of a channels_last one);
   2. qt_mx_pack addressed through strides (batch N, rows H W, k = C) for NCHW-contiguous or channels_last-dense values and scales,
      after a .contiguous() for any other layout.  One measured shape class does not pay for that pack and stays with the composite
@@ -16,9 +16,9 @@ Governed by QT_MX_GEMM like linear_mx / matmul_mx and counted in the same STATS;
 the caller runs the reference formulation."""
 import torch
 
-from . import _native
+from . import _native, mx_operand
 from .fake_quantize import _stream_ptr
-from .mx_gemm import _BITS, _NARROW_FIRST, _PAIRS, FMT_ID, STATS, _common_ok, _enabled, _fallback, _pack
+from .mx_gemm import _PAIRS, FMT_ID, STATS, _common_ok, _enabled, _fallback, _pack, _pack_rows
 
 __all__ = ["mx_conv2d_or_none", "STATS"]
 
@@ -33,26 +33,10 @@ def _pair(v):
 def _conv_weight_operand(weight, scale, block_size):
     """Constant operand [Cout, Cin, kh, kw] (+ scale [Cout, Cin / bs, kh, kw]) as [Cout][kh kw Cin]: packed once, cached on the tensor
     object -> (format id, codes, e8m0) or None when the packer refuses it in every format."""
-    key = (weight._version, scale.data_ptr(), scale._version, block_size)
-    hit = getattr(weight, "_qt_mx_packed_conv", None)
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    cout, cin, kh, kw = weight.shape
-    K = kh * kw * cin
-    w = weight.permute(0, 2, 3, 1).contiguous().view(cout, K)
-    s = scale.permute(0, 2, 3, 1).contiguous().view(cout, K // block_size)
-    known = getattr(weight, "_qt_mx_fmt", None)
-    result = None
-    for name in ((known,) if known in FMT_ID else _NARROW_FIRST):
-        fid = FMT_ID[name]
-        if (cin * _BITS[fid] // 8) % 16:
-            continue
-        packed = _pack(w, s, fid, block_size, 1, cout, K, (0, K, 1), (0, s.shape[-1], 1), check=True)
-        if packed is not None:
-            result = (fid, packed[0], packed[1])
-            break
-    weight._qt_mx_packed_conv = (key, result)
-    return result
+    cout, cin = weight.shape[:2]
+    return mx_operand.weight_operand(weight, scale, block_size, mx_operand.CONV_SLOT,
+                                     lambda: (weight.permute(0, 2, 3, 1).contiguous().view(cout, -1),
+                                              scale.permute(0, 2, 3, 1).contiguous().view(cout, -1)), cin, _pack_rows)
 
 
 def _nhwc_strides(t):
@@ -68,10 +52,7 @@ def _nhwc_strides(t):
 def _left_operand(x, fid, block_size):
     """The NHWC operand quantize_mx left on `x`, (codes, e8m0), when format, block size and shape match; else None."""
     n, c, h, w = x.shape
-    pre = getattr(x, "_qt_mx_packed_nhwc", None)
-    if pre is not None and pre[0] == fid and pre[1] == block_size and pre[2].shape == (n * h * w, c * _BITS[fid] // 8):
-        return pre[2], pre[3]
-    return None
+    return mx_operand.operand(x, mx_operand.NHWC, fid, block_size, n * h * w, c)
 
 
 _APPLY_PACK_RULE = True       # tools/exp_conv2d_mx.py clears it to time the route the rule below declines
@@ -113,10 +94,9 @@ def mx_conv2d_or_none(input, weight, bias, stride, padding, dilation, groups, in
         return None
     if groups != 1 or input.dim() != 4 or weight.dim() != 4 or isinstance(padding, str):
         return _fallback(f"groups {groups}, input {tuple(input.shape)}, weight {tuple(weight.shape)}, padding {padding}")
-    fa = getattr(input, "_qt_mx_fmt", None)
-    if fa not in FMT_ID or not getattr(input_scale, "_qt_pow2", False) or not getattr(weight_scale, "_qt_pow2", False):
-        return _fallback(f"input format {fa}, power-of-two scales {getattr(input_scale, '_qt_pow2', False)} "
-                         f"{getattr(weight_scale, '_qt_pow2', False)}")
+    fa, pow2 = mx_operand.format_of(input), (mx_operand.is_pow2(input_scale), mx_operand.is_pow2(weight_scale))
+    if fa not in FMT_ID or not all(pow2):
+        return _fallback(f"input format {fa}, power-of-two scales {pow2[0]} {pow2[1]}")
     n, cin, h, w = input.shape
     cout, wcin, kh, kw = weight.shape
     if wcin != cin or cin % 32 or cin % block_size or input.numel() == 0 or weight.numel() == 0:
@@ -131,7 +111,7 @@ def mx_conv2d_or_none(input, weight, bias, stride, padding, dilation, groups, in
         return _fallback(f"empty output {ho} x {wo}")
     fid = FMT_ID[fa]
     wop = _conv_weight_operand(weight, weight_scale, block_size)
-    if wop is None or (fid, wop[0]) not in _PAIRS or (cin * _BITS[fid] // 8) % 16:
+    if wop is None or (fid, wop[0]) not in _PAIRS or not mx_operand.row_is_whole_chunks(cin, fid):
         return _fallback(f"weight operand {None if wop is None else wop[0]} with input format {fid}, Cin = {cin}")
     if _APPLY_PACK_RULE and _left_operand(input, fid, block_size) is None and not _pack_route_takes(kh * kw * cin):
         return _fallback(f"no packed operand on the input and kh kw Cin = {kh * kw * cin} < 128: profiles/conv2d_mx.txt")

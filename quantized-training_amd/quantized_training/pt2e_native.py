@@ -29,7 +29,7 @@ import ctypes
 import torch
 from torch.fx import GraphModule
 
-from . import _native, switches
+from . import _native, mx_operand, switches
 from .fake_quantize import _stream_ptr
 
 __all__ = ["fuse_native_gemms", "fuse_mx_pairs", "STATS"]
@@ -189,10 +189,10 @@ def _sole_dequantize(model, node, dtype):
         return None
     if a[5] is not None:
         try:
-            tag = getattr(model.get_buffer(a[5].target), "_qt_dtype", "?")
+            tag = mx_operand.map_name(model.get_buffer(a[5].target))
         except AttributeError:
             return None
-        if not (tag in (None, "None", "float32") or (tag == "bfloat16" and dtype == torch.bfloat16)):
+        if not (tag in ("None", "float32") or (tag == "bfloat16" and dtype == torch.bfloat16)):
             return None
     return dq, a[1], a[5]
 

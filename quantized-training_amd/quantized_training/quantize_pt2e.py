@@ -25,6 +25,7 @@ import torch
 from torch import Tensor
 from torch.fx import GraphModule, Node
 
+from . import mx_operand
 from .fake_quantize import FusedAmaxObsFakeQuantize, _DerivedObserverOrFakeQuantize, _table_for, get_quantization_map
 from .quantizer.quantizer import DerivedQuantizationSpec, QScheme, QuantizationSpec
 from .quantizer.xnnpack_quantizer import XNNPACKQuantizer
@@ -190,9 +191,8 @@ def _fresh_attr(module, prefix):
 def _buffer_node(model, graph, prefix, value):
     name = _fresh_attr(model, prefix)
     buf = value.clone().detach() if isinstance(value, Tensor) else torch.tensor(value)
-    for tag in ("_qt_dtype", "_qt_pow2", "_qt_mx_fmt"):        # hints for the block-scaled GEMMs (mx_gemm.py)
-        if hasattr(value, tag):
-            setattr(buf, tag, getattr(value, tag))
+    if isinstance(value, Tensor):
+        mx_operand.copy_hints(value, buf)                      # for the block-scaled GEMMs (mx_gemm.py)
     model.register_buffer(name, buf)
     return graph.create_node("get_attr", name)
 

@@ -9,7 +9,7 @@ import types
 import pytest
 import torch
 
-from quantized_training import _native, mx_conv, mx_gemm
+from quantized_training import _native, mx_conv, mx_gemm, mx_operand
 from quantized_training._native import QT_ERR_BAD_ARG, QT_ERR_BAD_DTYPE, QT_ERR_UNALIGNED
 
 _BUF = ctypes.create_string_buffer(4096 + 64)
@@ -93,8 +93,10 @@ def _problem(n=2, cin=64, h=6, w=5, cout=8, kh=3, kw=3, bs=32, dtype=torch.bfloa
     x = torch.randint(-2, 3, (n, cin, h, w), generator=g).to(dtype)
     wt = torch.randint(-2, 3, (cout, cin, kh, kw), generator=g).to(dtype)
     xs, ws = torch.ones(n, cin // bs, h, w, dtype=dtype), torch.ones(cout, cin // bs, kh, kw, dtype=dtype)
-    x._qt_mx_fmt = wt._qt_mx_fmt = "fp8_e4m3"
-    xs._qt_pow2 = ws._qt_pow2 = True
+    for t in (x, wt):
+        mx_operand.set_format(t, "fp8_e4m3")
+    for s in (xs, ws):
+        mx_operand.set_pow2(s)
     return dict(input=x, weight=wt, bias=None, stride=(1, 1), padding=(1, 1), dilation=(1, 1), groups=1, input_scale=xs, weight_scale=ws,
                 block_size=bs, input_code=None, weight_code=None)
 
@@ -143,24 +145,23 @@ def _with(**kw):
 
 
 def _no_format(p, state):
-    del p["input"]._qt_mx_fmt
+    mx_operand.forget(p["input"])
 
 
 def _int_format(p, state):
-    p["input"]._qt_mx_fmt = "int8"
+    mx_operand.set_format(p["input"], "int8")
 
 
 def _not_pow2(which):
     def change(p, state):
-        del p[which]._qt_pow2
+        mx_operand.forget(p[which])
     return change
 
 
 def _scale_shape(which):
     def change(p, state):
         s = p[which][:, :, :-1].contiguous()
-        s._qt_pow2 = True
-        p[which] = s
+        p[which] = mx_operand.set_pow2(s)
     return change
 
 
@@ -174,7 +175,7 @@ def _pair_without_kernel(p, state):
 
 def _six_bit_cin_32(p, state):
     q = _problem(cin=32)
-    q["input"]._qt_mx_fmt = "fp6_e2m3"
+    mx_operand.set_format(q["input"], "fp6_e2m3")
     state["weight"] = (2,) + state["weight"][1:]
     p.clear()
     p.update(q)
@@ -218,10 +219,10 @@ def test_rule_declines_only_without_a_packed_operand(lifted):
     assert mx_conv.mx_conv2d_or_none(**p) is None
     assert rec.calls == [] and (mx_gemm.STATS.native, mx_gemm.STATS.fallback) == (0, 1)
     x = p["input"]
-    x._qt_mx_packed_nhwc = (0, 32, torch.zeros(2 * 6 * 5, 64, dtype=torch.uint8), torch.zeros(2 * 6 * 5, 2, dtype=torch.uint8))
+    mx_operand.set_operand(x, mx_operand.NHWC, 0, 32, torch.zeros(2 * 6 * 5, 64, dtype=torch.uint8), torch.zeros(2 * 6 * 5, 2, dtype=torch.uint8))
     assert mx_conv.mx_conv2d_or_none(**p) is not None
     assert len(rec.calls) == 1 and (mx_gemm.STATS.native, mx_gemm.STATS.fallback) == (1, 1)
-    x._qt_mx_packed_nhwc = (4,) + x._qt_mx_packed_nhwc[1:]           # an operand of another format is no operand
+    mx_operand.set_operand(x, mx_operand.NHWC, 4, *mx_operand.operand_record(x, mx_operand.NHWC)[1:])     # an operand of another format is no operand
     assert mx_conv.mx_conv2d_or_none(**p) is None and len(rec.calls) == 1
 
 

@@ -156,18 +156,20 @@ def device_operands(case, fmt, dtype, layout="nchw"):
     x, xs, w, ws = (ops[k].to(dtype).cuda() for k in ("xv", "xs", "wv", "ws"))
     if layout == "nhwc":
         x, xs = x.contiguous(memory_format=torch.channels_last), xs.contiguous(memory_format=torch.channels_last)
-    x._qt_mx_fmt = w._qt_mx_fmt = fmt
-    xs._qt_pow2 = ws._qt_pow2 = True
+    from quantized_training import mx_operand
+    for t in (x, w):
+        mx_operand.set_format(t, fmt)
+    for s in (xs, ws):
+        mx_operand.set_pow2(s)
     return ops, x, xs, w, ws
 
 
 def test_exact_block_size_64(nv):
     """Blocks of 64 channels: the packer repeats each scale byte; case C (Cin = 128) with scales that are constant over 64 channels."""
-    from quantized_training import mx_gemm
+    from quantized_training import mx_gemm, mx_operand
     n, h, w, cin, cout, (kh, kw), stride, padding, dilation = CASES["C"]
     ops, x, xs, wt, ws = device_operands("C", "fp8_e4m3", F32)
-    xs64, ws64 = xs[:, ::2].contiguous(), ws[:, ::2].contiguous()
-    xs64._qt_pow2 = ws64._qt_pow2 = True
+    xs64, ws64 = mx_operand.set_pow2(xs[:, ::2].contiguous()), mx_operand.set_pow2(ws[:, ::2].contiguous())
     ref = conv64("C", ops["xv"].double() * ops["xs"][:, ::2].double().repeat_interleave(64, 1),
                  ops["wv"].double() * ops["ws"][:, ::2].double().repeat_interleave(64, 1))
     mx_gemm.STATS.reset()
@@ -201,14 +203,14 @@ def within_bound(y, want, mag, dtype, what):
 @pytest.mark.parametrize("fmt", ["fp8_e4m3", "fp4_e2m1"])
 @pytest.mark.parametrize("case", sorted(CASES))
 def test_tolerance_whole_grid(nv, case, fmt):
-    from quantized_training import mx_gemm
+    from quantized_training import mx_gemm, mx_operand
     n, h, w, cin, cout, (kh, kw), stride, padding, dilation = CASES[case]
     g = torch.Generator().manual_seed(7)
     x0, w0, b0 = torch.randn(n, cin, h, w, generator=g) * 2, torch.randn(cout, cin, kh, kw, generator=g) * 0.5, torch.randn(cout, generator=g)
     for dtype in (BF16, F32):
         xs, xq = quantized(x0.to(dtype).cuda().contiguous(memory_format=torch.channels_last), fmt)     # what a layer inside a network receives
         ws, wq = quantized(w0.to(dtype).cuda(), fmt)
-        assert hasattr(xq, "_qt_mx_packed_nhwc")
+        assert mx_operand.operand_record(xq, mx_operand.NHWC) is not None
         dx, dw_ = dequantized64(xq, xs), dequantized64(wq, ws)
         ref, mag = conv64(case, dx, dw_), conv64(case, dx.abs(), dw_.abs())
         for bias in (None, b0.to(dtype).cuda()):
@@ -262,7 +264,7 @@ def test_activation_operand_sources_agree(nv, case):
     """quantize_mx of an NCHW-contiguous tensor (the strided pass: takes the pack only where H W is a multiple of 8), of a
     channels_last one (the last-axis pass on the stored tensor) and qt_mx_pack through the strides of either layout: the same codes
     and E8M0 bytes as the host packer makes of the CPU composite's values and scales, and the same conv2d_mx bits."""
-    from quantized_training import mx_conv, mx_gemm
+    from quantized_training import mx_conv, mx_gemm, mx_operand
     from quantized_training.fake_quantize import get_quantization_map, mx_block_view
     fmt = "fp8_e4m3"
     n, h, w, cin, cout, (kh, kw), stride, padding, dilation = CASES[case]
@@ -277,21 +279,21 @@ def test_activation_operand_sources_agree(nv, case):
     s2, q2 = quantized(x0.cuda().contiguous(memory_format=torch.channels_last), fmt)       # channels_last-dense
     for s, q in ((s1, q1), (s2, q2)):
         assert torch.equal(bits_of(q), bits_of(q_ref)) and torch.equal(bits_of(s), bits_of(s_ref))
-        assert q._qt_mx_fmt == fmt and s._qt_pow2
+        assert mx_operand.format_of(q) == fmt and mx_operand.is_pow2(s)
     assert q1.is_contiguous() and q2.permute(0, 2, 3, 1).is_contiguous() and s2.permute(0, 2, 3, 1).is_contiguous()
     taken = mx_block_view(tuple(x0.shape), BF16, 32, [1]) is not None
     assert taken == ((h * w) % 8 == 0) == (case == "C")
-    assert hasattr(q1, "_qt_mx_packed_nhwc") == taken                                        # declined by the kernel: nothing is set
-    assert hasattr(q2, "_qt_mx_packed_nhwc") and not hasattr(q2, "_qt_mx_packed_act")
+    assert (mx_operand.operand_record(q1, mx_operand.NHWC) is not None) == taken             # declined by the kernel: nothing is set
+    assert mx_operand.operand_record(q2, mx_operand.NHWC) is not None and mx_operand.operand_record(q2, mx_operand.ROWS) is None
 
     ws, wq = quantized(w0.cuda(), fmt)
     results = {}
     for name, s, q, strip in (("nchw as left by quantize_mx", s1, q1, False), ("channels_last producer", s2, q2, False),
                               ("nchw through qt_mx_pack", s1, q1, True), ("channels_last through qt_mx_pack", s2, q2, True)):
-        if strip and hasattr(q, "_qt_mx_packed_nhwc"):
-            del q._qt_mx_packed_nhwc
+        if strip:
+            mx_operand.drop_operand(q)
         codes, e8 = mx_conv._activation_operand(q, s, 0, 32)
-        pre = getattr(q, "_qt_mx_packed_nhwc", None)
+        pre = mx_operand.operand_record(q, mx_operand.NHWC)
         assert (pre is not None and codes is pre[2]) == (not strip and (taken or q is q2)), name
         assert np.array_equal(codes.cpu().numpy(), want_codes), f"{name}: codes"
         assert np.array_equal(e8.cpu().numpy(), want_e8), f"{name}: E8M0 bytes"
@@ -314,7 +316,7 @@ def composite_operands(x, w, xs, ws, bs, x_code=None, w_code=None):
 
 
 def test_operator_goes_native_and_every_reachable_reason_falls_back(nv, monkeypatch):
-    from quantized_training import mx_gemm
+    from quantized_training import mx_gemm, mx_operand
     case = "B"
     n, h, w, cin, cout, (kh, kw), stride, padding, dilation = CASES[case]
     g = torch.Generator().manual_seed(13)
@@ -345,7 +347,7 @@ def test_operator_goes_native_and_every_reachable_reason_falls_back(nv, monkeypa
 
     check(fresh(), (1, 0), "device operands from quantize_mx")
     p = fresh(); p["groups"] = 2; p["w"], p["ws"] = p["w"][:, :32].contiguous(), p["ws"][:, :1].contiguous()
-    p["w"]._qt_mx_fmt, p["ws"]._qt_pow2 = "fp8_e4m3", True
+    mx_operand.set_format(p["w"], "fp8_e4m3"), mx_operand.set_pow2(p["ws"])
     check(p, (0, 1), "groups = 2")
     p = fresh()
     p["x"] = torch.randint(0, 16, p["x"].shape, device="cuda").to(BF16); p["x_code"] = torch.linspace(-4, 4, 16, device="cuda").to(BF16)
@@ -357,7 +359,7 @@ def test_operator_goes_native_and_every_reachable_reason_falls_back(nv, monkeypa
     check(p, (0, 1), "an input scale not flagged power-of-two")
     p = fresh(); p["ws"] = p["ws"].clone()
     check(p, (0, 1), "a weight scale not flagged power-of-two")
-    p = fresh(); p["w"] = (p["w"] * 0 + 0.3).to(BF16); p["ws"] = p["ws"].clone(); p["ws"]._qt_pow2 = True
+    p = fresh(); p["w"] = (p["w"] * 0 + 0.3).to(BF16); p["ws"] = mx_operand.set_pow2(p["ws"].clone())
     check(p, (0, 1), "a weight the packer refuses in every format")
     check(fresh(fx="fp4_e2m1", fw="fp8_e4m3"), (0, 1), "fp4 x fp8: a pair without a kernel")
     check(fresh(), (0, 0), "fp16", cast=lambda t: t.half())
@@ -365,10 +367,10 @@ def test_operator_goes_native_and_every_reachable_reason_falls_back(nv, monkeypa
     # stays with the composite where qt_mx_pack would have to run first (9 x 7 planes: the strided pass leaves nothing)
     w1 = (torch.randn(cout, cin, 1, 1, generator=g) * 0.5).to(BF16).cuda()
     p = fresh(wsrc=w1)
-    assert not hasattr(p["x"], "_qt_mx_packed_nhwc")
+    assert mx_operand.operand_record(p["x"], mx_operand.NHWC) is None
     check(p, (0, 1), "1 x 1, 64 -> 136 without a packed operand")
     p = fresh(wsrc=w1, xsrc=x0.contiguous(memory_format=torch.channels_last))
-    assert hasattr(p["x"], "_qt_mx_packed_nhwc")
+    assert mx_operand.operand_record(p["x"], mx_operand.NHWC) is not None
     check(p, (1, 0), "1 x 1, 64 -> 136 on the operand quantize_mx left")
     monkeypatch.setenv("QT_MX_GEMM", "0")
     check(fresh(), (0, 0), "QT_MX_GEMM=0")
@@ -387,7 +389,7 @@ class ToyCNN(torch.nn.Module):
 
 
 def test_converted_cnn_runs_its_eligible_layers_natively(nv):
-    from quantized_training import mx_gemm, quantize_pt2e as qp
+    from quantized_training import mx_gemm, mx_operand, quantize_pt2e as qp
     torch.manual_seed(0)
     m = ToyCNN().eval().to(BF16).cuda()
     xs = [torch.randn(2, 3, 18, 18, device="cuda").to(BF16) for _ in range(3)]
@@ -405,7 +407,7 @@ def test_converted_cnn_runs_its_eligible_layers_natively(nv):
             args, kwargs = self.fetch_args_kwargs_from_env(node)
             if node.op == "call_function" and node.target == target:
                 before = mx_gemm.STATS.native
-                had = hasattr(args[0], "_qt_mx_packed_nhwc")
+                had = mx_operand.operand_record(args[0], mx_operand.NHWC) is not None
                 out = super().run_node(node)
                 seen.append(dict(args=args, kwargs=kwargs, out=out, native=mx_gemm.STATS.native == before + 1, had=had))
                 return out

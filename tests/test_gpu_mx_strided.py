@@ -309,6 +309,7 @@ def test_a_non_finite_element_stays_in_its_own_bits(nv, name, dtype):
     """A code row that holds an Inf or a NaN: every FINITE element of it still carries exactly its own code -- in the strided kernel,
     where the neighbouring code belongs to another operand row, and in the last-axis kernel, which packs through the same helper
     (qt_mx::vec_codes masks each code to its width; the 6-bit formats and every fp32 tensor take the path that needs it)."""
+    from quantized_training import mx_operand
     from quantized_training.fake_quantize import get_quantization_map
     host, qmap = get_quantization_map(name, "cpu"), get_quantization_map(name, "cuda")
     qmax, bits = qmax_of(name), BITS[name]
@@ -316,14 +317,14 @@ def test_a_non_finite_element_stays_in_its_own_bits(nv, name, dtype):
     b[0, 5, 3], b[1, 40, 7], b[0, 63, 31] = float("inf"), float("nan"), -float("inf")
     b = b.to(dtype)
     a = b.transpose(1, 2).contiguous()                            # the same blocks along the last axis
-    for what, x, ax, attr in (("strided", b, -2, "_qt_mx_packed_b"), ("last axis", a, -1, "_qt_mx_packed_act")):
+    for what, x, ax, layout in (("strided", b, -2, mx_operand.SECOND), ("last axis", a, -1, mx_operand.ROWS)):
         s_ref, q_ref = cpu_pair(x, ax, 32, host, qmax, True)
         s, q = torch.ops.quantized_ops.quantize_mx(x.cuda(), qmap, [ax], 32, qmax, True, None, None)
         assert_same(bits_of(q), bits_of(q_ref), f"{what}: q")
         rows = (q_ref.transpose(1, 2) if ax == -2 else q_ref).reshape(64, 64).float().numpy()
         finite = np.isfinite(rows)
         assert int((~finite.all(axis=1)).sum()) == 3, f"{what}: three code rows hold a non-finite value"
-        got = unpack_codes(getattr(q, attr)[2].cpu().numpy(), bits)
+        got = unpack_codes(mx_operand.operand_record(q, layout)[2].cpu().numpy(), bits)
         assert got.shape == (64, 64)
         assert_same(got[finite], o.mx_encode(rows[finite], name), f"{what}: codes of the finite elements")
         assert int(got.max()) < (1 << bits)
@@ -404,7 +405,7 @@ def test_module_equals_its_cpu_twin(nv, pow2):
 
 # ---- 5. the operators ---------------------------------------------------------------------------------------------------------------------
 def test_quantize_mx_operator_and_the_matmul_operand(nv):
-    from quantized_training import mx_gemm
+    from quantized_training import mx_gemm, mx_operand
     from quantized_training.fake_quantize import get_quantization_map
     host, qmap = get_quantization_map("fp8_e4m3", "cpu"), get_quantization_map("fp8_e4m3", "cuda")
     g = torch.Generator().manual_seed(5)
@@ -414,30 +415,31 @@ def test_quantize_mx_operator_and_the_matmul_operand(nv):
     sb, qb = torch.ops.quantized_ops.quantize_mx(b.cuda(), qmap, [-2], 32, 448.0, True, None, None)
     assert_same(bits_of(sb), bits_of(s_ref), "scale")
     assert_same(bits_of(qb), bits_of(q_ref), "q")
-    fid, bs, codes, e8 = qb._qt_mx_packed_b
+    fid, bs, codes, e8 = mx_operand.operand_record(qb, mx_operand.SECOND)
     assert (fid, bs, tuple(codes.shape), tuple(e8.shape)) == (0, 32, (3 * 80, 64), (3 * 80, 2))
     want_codes, want_e8, rows, _ = expected_pack(s_ref, q_ref, "fp8_e4m3", 32)
     assert len(rows) == 3 * 80
     assert_same(codes.cpu().numpy(), want_codes, "codes")
     assert_same(e8.cpu().numpy(), want_e8, "e8m0")
-    assert getattr(sb, "_qt_pow2", False) and qb._qt_mx_fmt == "fp8_e4m3"
+    assert mx_operand.is_pow2(sb) and mx_operand.format_of(qb) == "fp8_e4m3"
 
     sa, qa = torch.ops.quantized_ops.quantize_mx(a, qmap, [-1], 32, 448.0, True, None, None)
     mx_gemm.STATS.reset()
     y1 = torch.ops.quantized_ops.matmul_mx(qa, qb, input_scale=sa, weight_scale=sb, block_size=32)
-    del qb._qt_mx_packed_b                                      # the qt_mx_pack route
+    mx_operand.drop_operand(qb)                                 # the qt_mx_pack route
     y2 = torch.ops.quantized_ops.matmul_mx(qa, qb, input_scale=sa, weight_scale=sb, block_size=32)
     assert (mx_gemm.STATS.native, mx_gemm.STATS.fallback) == (2, 0)
     assert_same(bits_of(y1), bits_of(y2), "matmul_mx with the operand of quantize_mx against the strided pack")
 
     s_only = torch.ops.quantized_ops.calculate_mx_qparam(b.cuda(), [-2], 32, 448.0, True)
     assert_same(bits_of(s_only), bits_of(s_ref), "calculate_mx_qparam")
-    assert getattr(s_only, "_qt_pow2", False)
+    assert mx_operand.is_pow2(s_only)
     s_amax = torch.ops.quantized_ops.calculate_mx_qparam(b.cuda(), [-2], 32, 448.0, False)
     assert_same(bits_of(s_amax), bits_of(torch.ops.quantized_ops.calculate_mx_qparam(b, [-2], 32, 448.0, False)), "calculate_mx_qparam, amax")
 
 
 def test_transposed_view_runs_the_last_axis_pass(nv):
+    from quantized_training import mx_operand
     from quantized_training.fake_quantize import get_quantization_map
     host, qmap = get_quantization_map("fp8_e4m3", "cpu"), get_quantization_map("fp8_e4m3", "cuda")
     k = torch.randn(2, 4, 96, 64, generator=torch.Generator().manual_seed(9)).bfloat16()
@@ -448,9 +450,9 @@ def test_transposed_view_runs_the_last_axis_pass(nv):
     assert_same(bits_of(s), bits_of(s_ref), "scale")
     assert_same(bits_of(q), bits_of(q_ref), "q")
     s1, q1 = torch.ops.quantized_ops.quantize_mx(k.cuda(), qmap, [-1], 32, 448.0, True, None, None)
-    for got, want in zip(q._qt_mx_packed_b, q1._qt_mx_packed_act):
+    for got, want in zip(mx_operand.operand_record(q, mx_operand.SECOND), mx_operand.operand_record(q1, mx_operand.ROWS)):
         assert torch.equal(got, want) if isinstance(got, torch.Tensor) else got == want
-    assert q._qt_mx_packed_b[2].shape == (2 * 4 * 96, 64)
+    assert mx_operand.operand_record(q, mx_operand.SECOND)[2].shape == (2 * 4 * 96, 64)
 
 
 # ---- 6. PT2E ------------------------------------------------------------------------------------------------------------------------------

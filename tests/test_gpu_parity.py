@@ -1148,6 +1148,7 @@ def _same_bits(a, b):
 @pytest.mark.parametrize("tdtype", [torch.bfloat16, torch.float32])
 @pytest.mark.parametrize("pow2", [True, False])
 def test_quantize_mx_fused_matches_composite(nv, dtype_name, tdtype, pow2):
+    from quantized_training import mx_operand
     from quantized_training.fake_quantize import get_quantization_map
     from quantized_training.quantizer.quantizer import get_quant_min_max
     qmax = float(get_quant_min_max(dtype_name)[1])
@@ -1164,7 +1165,7 @@ def test_quantize_mx_fused_matches_composite(nv, dtype_name, tdtype, pow2):
         assert _same_bits(s, s_ref), (dtype_name, block)
         assert _same_bits(q, q_ref), (dtype_name, block)
         if pow2 and block % 32 == 0 and dtype_name in MX_FMT_ID:
-            fid, bs, codes, e8 = q._qt_mx_packed_act
+            fid, bs, codes, e8 = mx_operand.operand_record(q, mx_operand.ROWS)
             finite = torch.isfinite(q_ref).all(dim=-1) & torch.isfinite(s_ref).all(dim=-1) & (s_ref.float() >= 2.0 ** -127).all(dim=-1)
             rows = torch.nonzero(finite).flatten().numpy()
             want_codes, want_e8 = o.mx_pack(q_ref.float().numpy()[rows], s_ref.float().numpy()[rows], dtype_name, block)

@@ -21,7 +21,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "quantized-training_amd"))
-from quantized_training import mx_conv, mx_gemm  # noqa: E402
+from quantized_training import mx_conv, mx_gemm, mx_operand  # noqa: E402
 from quantized_training.fake_quantize import get_quantization_map  # noqa: E402
 from quantized_training.quantizer.quantizer import get_quant_min_max  # noqa: E402
 
@@ -65,9 +65,9 @@ def bench(fmt, hw, cin, cout, k, iters, repeats):
         w = (torch.randn((cout, cin, k, k), generator=g, device=DEV) * 0.05).bfloat16()
         xs, xq = torch.ops.quantized_ops.quantize_mx(x, qmap, [1], 32, qmax, True, None, None)
         ws, wq = torch.ops.quantized_ops.quantize_mx(w, qmap, [1], 32, qmax, True, None, None)
-        assert hasattr(xq, "_qt_mx_packed_nhwc")
+        assert mx_operand.operand_record(xq, mx_operand.NHWC) is not None
         bare = xq.detach()                                            # the same memory without the packed operand
-        bare._qt_mx_fmt = xq._qt_mx_fmt
+        mx_operand.set_format(bare, mx_operand.format_of(xq))
         acts.append((xq, xs)); stripped.append((bare, xs)); weights.append((wq, ws))
 
     def call(src, i):

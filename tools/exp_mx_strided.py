@@ -91,13 +91,13 @@ def make_pool(shape, dtype, view=None):
 
 def matmul_operand(q, s, bs):
     """The second operand of matmul_mx for q [..., K, N] with scales [..., K / bs, N], the way mx_gemm.mx_matmul_or_none gets it."""
-    from quantized_training import mx_gemm
-    fid = mx_gemm.FMT_ID[q._qt_mx_fmt]
+    from quantized_training import mx_gemm, mx_operand
+    fid = mx_gemm.FMT_ID[mx_operand.format_of(q)]
     K, N = q.shape[-2:]
     batch = q.numel() // (K * N)
-    pre = getattr(q, "_qt_mx_packed_b", None)
-    if pre is not None and pre[0] == fid and pre[1] == bs and pre[2].shape == (batch * N, K * mx_gemm._BITS[fid] // 8):
-        return pre[2], pre[3]
+    pre = mx_operand.operand(q, mx_operand.SECOND, fid, bs, batch * N, K)
+    if pre is not None:
+        return pre
     b3, sb3 = q.contiguous().view(batch, K, N), s.contiguous().view(batch, K // bs, N)
     return mx_gemm._pack(b3, sb3, fid, bs, batch, N, K, (K * N, 1, N), (sb3.stride(0), 1, sb3.stride(1)), check=False)
 
