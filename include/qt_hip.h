@@ -754,6 +754,33 @@ int qt_mx_gemm(const uint8_t *a_codes, const uint8_t *a_e8m0, int a_format, cons
                int b_format, void *c_dev, int c_is_f32, const void *bias_dev, long batch, int M, int N, int K,
                long a_batch_stride_rows, long b_batch_stride_rows, void *stream);
 
+/* The same two operators (decomposed.py:304-363) for operands the scaled float instruction cannot read: integer elements (intN,
+ * N <= 8), integer codebooks of up to 256 entries, block scales of any finite positive value, over blocks of 32, 64 or 128 k.
+ * Operand: int8 codes[rows][K] and fp32 scales[rows][K / block_size].
+ *
+ * qt_mxi_pack (decomposed.py:304-363: `code[x.to(torch.long)]`, then `* expand(scale)`): values (bf16 or fp32, addressed with element
+ * strides as qt_mx_pack's) that are integers, or -- with code_dev, n_code entries in the values' dtype -- indices into that codebook,
+ * truncated toward zero; block scales in the same dtype -> codes and fp32 scales.  *bad_dev (nullable, caller-zeroed) is set to 1
+ * for a value (or codebook entry) that is no integer in [-128, 127], an index outside [0, n_code), a scale that is not finite and
+ * positive: the caller then keeps the dequantize + GEMM path.  Without the flag the same inputs are memory-safe: indices are
+ * clamped into the codebook, values saturate (NaN -> 0).
+ * qt_mxi_gemm (decomposed.py:304-363):
+ *     C[b][m][n] = rd( bias[n] + sum_kb (sA[b][m][kb] * sB[b][n][kb]) * (sum over block kb of a[b][m][k] * b[b][n][k]) )
+ * the block sums exact in int32 on the integer matrix cores, each multiplied by the fp32 product of its two scales and added by
+ * one fma into an fp32 accumulator, blocks in increasing kb; bias (nullable, C's dtype) added in fp32; one rounding to C's dtype
+ * (bf16 or fp32).  M and N are free, K % block_size == 0.  Fixed order, no atomics: the same bits on every launch.  Batch strides
+ * in rows (0 = operand shared by every batch).
+ * Both decline before their first HIP call: QT_ERR_BAD_ARG for a NULL operand or output, a negative extent, batch > 65535, a
+ * block size other than 32 / 64 / 128, K % block_size != 0, n_code outside 1..256 with a codebook (or non-zero without one);
+ * QT_ERR_UNALIGNED for codes off a 16-byte boundary or any other pointer off its element size.  QT_OK without a launch for an
+ * empty problem. */
+int qt_mxi_pack(const void *x_dev, const void *scale_dev, int is_f32, const void *code_dev, int n_code, int8_t *codes_dev, float *scales_dev,
+                long batch, long rows, long K, long x_batch_stride, long x_row_stride, long x_k_stride, long s_batch_stride,
+                long s_row_stride, long s_k_stride, int block_size, int *bad_dev, void *stream);
+int qt_mxi_gemm(const int8_t *a_codes, const float *a_scales, const int8_t *b_codes, const float *b_scales, int block_size, void *c_dev,
+                int c_is_f32, const void *bias_dev, long batch, int M, int N, int K, long a_batch_stride_rows, long b_batch_stride_rows,
+                void *stream);
+
 /* conv2d_mx (decomposed.py:265-301: both operands times their expanded block scales, then F.conv2d) as an implicit GEMM on the same
  * instruction, from packed operands whose blocks run along the channel axis:
  *     y[n, ho, wo, co] = sum_{r, s, c} x[n, ho sh - ph + r dh, wo sw - pw + s dw, c] 2^(ex - 127) . w[co, r, s, c] 2^(ew - 127) (+ bias[co])

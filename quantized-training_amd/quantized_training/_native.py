@@ -225,6 +225,8 @@ SIGNATURES = {
     "qt_mx_pack": (c_int, [_P, _P, c_int, _P, _P, c_long, c_long, c_long, c_long, c_long, c_long, c_long, c_long, c_long, c_int,
                           c_int, _P, _P]),
     "qt_mx_gemm": (c_int, [_P, _P, c_int, _P, _P, c_int, _P, c_int, _P, c_long, c_int, c_int, c_int, c_long, c_long, _P]),
+    "qt_mxi_pack": (c_int, [_P, _P, c_int, _P, c_int, _P, _P] + [c_long] * 9 + [c_int, _P, _P]),
+    "qt_mxi_gemm": (c_int, [_P, _P, _P, _P, c_int, _P, c_int, _P, c_long, c_int, c_int, c_int, c_long, c_long, _P]),
     "qt_conv2d_mx": (c_int, [_P, _P, c_int, _P, _P, c_int, _P, c_int, _P] + [c_int] * 13 + [_P]),
     "qt_filter_outlier_bf16": (c_int, [_P, _P, _P, _P, _P, c_long, c_long, c_float, c_long, _P]),
     "qt_filter_outlier_f32": (c_int, [_P, _P, _P, _P, _P, c_long, c_long, c_float, c_long, _P]),

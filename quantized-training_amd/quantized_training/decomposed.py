@@ -153,6 +153,8 @@ def _quantize_impl(input, scale, zero_point=None, axes=None, block_size=None, qm
         fmt = mx_operand.format_of_qmap(qmap)
         if fmt is not None:
             mx_operand.set_format(out, fmt)            # lets linear_mx / matmul_mx take the element codes directly
+    if block_size is not None and zero_point is None:
+        mx_operand.quantized_int(out, qmap)            # an integer map: the same record quantize_mx leaves, whatever the scales are
     return out
 
 
@@ -300,6 +302,8 @@ def _quantize_mx_strided_hip_or_none(input, qmap, axes, block_size, quant_max, p
     _native.check(code, "qt_quantize_mx_strided")
     if pow2:
         mx_operand.quantized(q, sf, fmt_name, mx_operand.NHWC if nhwc else mx_operand.SECOND, fid, block_size, codes, e8)
+    if want_q:
+        mx_operand.quantized_int(q, qmap)
     return sf, q
 
 
@@ -362,6 +366,7 @@ def _quantize_mx_hip_or_none(input, qmap, axes, block_size, quant_max, pow2, sca
                      _stream_ptr(x)), "qt_quantize_mx")
     if pow2:
         mx_operand.quantized(q, sf, fmt_name, mx_operand.ROWS, fid, block_size, codes, e8)
+    mx_operand.quantized_int(q, qmap)
     return sf, q
 
 

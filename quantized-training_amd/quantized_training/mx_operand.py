@@ -12,6 +12,12 @@ the per-tensor FP8 path):
   _qt_mx_packed, _qt_mx_packed_conv
                         on a weight: (key, (format id, codes, e8m0) or None), the packed constant operand of the GEMM / the
                         convolution.  The key carries both version counters, so these two need no stamp.
+  _qt_mxi_packed        on a weight: (key, (codes int8, scales fp32) or None), its operand in the integer family (qt_mxi_gemm); the
+                        key carries the version counters of weight, scale and codebook
+  _qt_mxi_code          on a codebook: (version, whether the integer GEMM takes it): one host read per codebook
+
+`_qt_mx_fmt` also names the integer formats (INT_BITS): `quantize` with a block size and `quantize_mx` write it for an integer map
+whatever the scales are (quantized_int), and the integer route of mx_gemm.py reads it (int_format_of).
 
 This module is the only code that reads or writes them.  A stale record reads as no record at all -- the format too, not only the
 operand: a consumer that still believed the format would pack the modified values without the packer's check.  Inference tensors
@@ -34,6 +40,12 @@ def row_bytes(k, fid):
 def row_is_whole_chunks(k, fid):
     """The kernels fetch code rows in 16-byte chunks: a row has to be a whole number of them."""
     return row_bytes(k, fid) % 16 == 0
+
+
+# ---- the integer family (qt_mxi_pack / qt_mxi_gemm): int8 codes, fp32 block scales of any value ----------------------------------
+INT_BITS = {f"int{n}": n for n in range(2, 9)}       # format name -> N: every value is an integer in [-2^(N-1), 2^(N-1) - 1]
+INT_BLOCKS = (32, 64, 128)
+INT_CODEBOOK_MAX = 256
 
 
 # ---- the layouts of a packed operand, and the stamp --------------------------------------------------------------------------------
@@ -100,6 +112,13 @@ def format_of_qmap(qmap):
     return name if name in FMT_ID else None
 
 
+def int_format_of_qmap(qmap):
+    """Name of the integer format (INT_BITS) a value map was tagged with, or None.  By tag alone: a map without one is not compared
+    by content against the integer tables."""
+    name = map_name(qmap)
+    return name if name in INT_BITS else None
+
+
 # ---- values and scales -------------------------------------------------------------------------------------------------------------
 def set_format(values, name):
     return _write(values, "_qt_mx_fmt", name)
@@ -107,6 +126,36 @@ def set_format(values, name):
 
 def format_of(values):
     return _read(values, "_qt_mx_fmt")
+
+
+def quantized_int(values, qmap):
+    """The tail of every quantize / quantize_mx route without zero points, kernel or composite, on any device and whatever the
+    scales are: values rounded with an integer map remember its name.  Returns whether they do."""
+    name = int_format_of_qmap(qmap) if values is not None else None
+    if name is not None:
+        set_format(values, name)
+    return name is not None
+
+
+def int_format_of(values):
+    """The integer format `values` remember, or None."""
+    name = format_of(values)
+    return name if name in INT_BITS else None
+
+
+def int_codebook_ok(code):
+    """Whether a codebook is one the integer GEMM takes: at most 256 entries, all integers in [-128, 127].  One host read per
+    codebook, kept on the tensor object with its version (a codebook written in place is read again)."""
+    stamp = _version(code)
+    hit = code.__dict__.get("_qt_mxi_code")
+    if hit is not None and hit[0] == stamp:
+        return hit[1]
+    ok = code.dim() == 1 and 1 <= code.numel() <= INT_CODEBOOK_MAX and code.is_floating_point()
+    if ok:
+        c = code.detach().double()
+        ok = bool(((c == c.trunc()) & (c >= -128) & (c <= 127)).all())           # host sync on a device codebook
+    code._qt_mxi_code = (stamp, ok)
+    return ok
 
 
 def set_pow2(scale):
@@ -209,5 +258,22 @@ def weight_operand(weight, scale, block_size, slot, as_rows, extent, pack):
             result = (fid, packed[0], packed[1])
             break
     setattr(weight, slot, (key, result))
+    return result
+
+
+INT_SLOT = "_qt_mxi_packed"
+
+
+def int_weight_operand(weight, scale, code, block_size, pack):
+    """A weight's operand in the integer family, (codes int8, scales fp32) or None when the packer's check refuses it: packed once,
+    cached on the tensor object under its own slot (the float family's GEMM_SLOT is another cache).  pack() -> (codes, scales) or
+    None, with the check on.  The key carries the version counters of weight, scale and codebook."""
+    key = (weight._version, scale.data_ptr(), scale._version, block_size,
+           None if code is None else (code.data_ptr(), code._version))
+    hit = getattr(weight, INT_SLOT, None)
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    result = pack()
+    setattr(weight, INT_SLOT, (key, result))
     return result
 
