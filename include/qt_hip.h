@@ -279,6 +279,40 @@ int qt_dequantize_blocks_f32(const float *x_dev, float *y_dev, const float *scal
                              size_t inner, int block_size, const uint16_t *in_lut_dev, const uint16_t *out_lut_dev,
                              void *stream);
 
+/* ---- packed group-wise affine weights and the Linear that reads them (csrc/qt_gwa_gemm.hip).
+ * A converted weight-only graph stores, per Linear, bf16 codes [N, K] (integers in [quant_min, quant_max]) and one bf16 scale and
+ * zero point per block of block_size consecutive k ([N, K / block_size]).  qt_gwa_pack turns the codes into the kernels' own
+ * layout, q - quant_min in `bits` = 4 (quant_max - quant_min <= 15) or 8 bits: one 16-byte piece per lane of a wave, per
+ * 16-column group and "super step" of 128 (4 bits) / 64 (8 bits) k, at byte ((group * nss + ss) * 64 + lane) * 16 with
+ * nss = ceil(K / super step); the piece of lane 16 g + r holds column 16 group + r, k = super step base + 32 j + 8 g + e
+ * (e = 0..7; j = 0..3 | 0..1) with code e of k step j in nibble e of word j (4 bits) or byte e of word pair j (8 bits).
+ * Columns >= N and k >= K hold code 0.  qt_gwa_packed_bytes is the size of that buffer (0 for a shape the family declines).
+ * bad_dev (may be NULL) points at an int32 the caller has zeroed: the packer writes 1 there when a code is not an integer in
+ * [quant_min, quant_max] (NaN included); the host reads it once, at convert time.
+ *
+ * qt_gwa_dequantize_bf16: y[N, K] = rd(rd(q - z_blk) * s_blk), rd = round to bf16 -- bit for bit qt_dequantize_blocks_bf16 on
+ * the unpacked codes (the two share the device function), reading 0.5 / 1 byte and writing 2 bytes per weight.
+ *
+ * qt_linear_gwa_bf16: y[M, N] = x[M, K] . Wd[N, K]^T + bias, Wd = that dequantized weight formed in registers, on
+ * v_mfma_f32_16x16x32_bf16; fp32 accumulation in a fixed order (no atomics), bias added in fp32, one rounding to bf16.
+ * A workgroup is one 16-column group x tile_m rows, K split over its 8 waves and summed in split order.  tile_m: 0 = by M
+ * (qt_linear_gwa_tile: 16 / 32 rows for M <= 16 / 32, else 64), or one of 16, 32, 64 to force a variant (tests, tools).
+ * bias_dev may be NULL.
+ *
+ * Declined before any device call: QT_ERR_BAD_ARG for a NULL pointer, bits not 4 or 8, N, K < 1 (M < 0), block_size outside
+ * {32, 64, 128, 256, 512}, a quant range that does not fit `bits` or is not integral, an unknown tile_m;
+ * QT_ERR_UNALIGNED for K % 32 != 0, K % block_size != 0, N % 8 != 0, x / packed / y / codes off a 16-byte boundary, bias off an
+ * 8-byte one, scale / zero point off their element size.  M == 0 returns QT_OK without a launch. */
+size_t qt_gwa_packed_bytes(int N, int K, int bits);
+int qt_gwa_pack(const uint16_t *codes_dev, uint8_t *packed_dev, int N, int K, int bits, float quant_min, float quant_max,
+                int *bad_dev, void *stream);
+int qt_gwa_dequantize_bf16(const uint8_t *packed_dev, const uint16_t *scale_dev, const uint16_t *zp_dev, uint16_t *y_dev, int N,
+                           int K, int block_size, int bits, float quant_min, void *stream);
+int qt_linear_gwa_tile(int M);
+int qt_linear_gwa_bf16(const uint16_t *x_dev, const uint8_t *packed_dev, const uint16_t *scale_dev, const uint16_t *zp_dev,
+                       const uint16_t *bias_dev, uint16_t *y_dev, int M, int N, int K, int block_size, int bits, float quant_min,
+                       int tile_m, void *stream);
+
 /* ---- A9/A10: fake-quant GEMMs (bf16 in, fp32 accumulate on MFMA, bf16 out) ---------------
  * qt_linear_fq_bf16 replaces  F.linear(fq_a(x), weight_fake_quant(W), b)
  *     modules/qat/linear.py:40-41 + the activation pre-hook quantize.py:128-140

@@ -17,6 +17,7 @@
 
 #include "qt_device.h"
 #include "qt_chain.h"
+#include "qt_gwa.h"
 
 namespace {
 
@@ -29,12 +30,6 @@ constexpr int kPerVec = IO == kIoBf16 ? 8 : 4;               // elements of one 
 // torch.amin / amax: NaN on either side wins
 __device__ __forceinline__ float nan_min(float a, float b) { return ((b < a) | (b != b)) ? b : a; }
 __device__ __forceinline__ float nan_max(float a, float b) { return ((b > a) | (b != b)) ? b : a; }
-
-template <int IO>
-__device__ __forceinline__ float rd_io(float f) {            // the result of one torch op in the tensor's dtype
-    if constexpr (IO == kIoBf16) return bf16_round(f);
-    else return f;
-}
 
 template <int IO>
 __device__ __forceinline__ float map_io(const uint16_t *__restrict__ t, float f) {      // quantized_ops::vmap, table in global memory
@@ -295,7 +290,7 @@ __global__ __launch_bounds__(256) void qdq_blocks_kernel(const uint4 *__restrict
                 f[e] = map_io<IO>(out_lut, rd_io<IO>(rd_io<IO>(f[e] / s[e]) + z[e]));
             } else {
                 if (in_lut) f[e] = map_io<IO>(in_lut, f[e]);
-                f[e] = rd_io<IO>(rd_io<IO>(f[e] - z[e]) * s[e]);
+                f[e] = gwa_dequant<IO>(f[e], z[e], s[e]);
                 if (out_lut) f[e] = map_io<IO>(out_lut, f[e]);
             }
         }

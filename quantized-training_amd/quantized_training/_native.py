@@ -121,6 +121,11 @@ SIGNATURES = {
     "qt_quantize_blocks_f32": (c_int, [_P, _P, _P, _P, c_size_t, c_size_t, c_size_t, c_int, _P, _P]),
     "qt_dequantize_blocks_bf16": (c_int, [_P, _P, _P, _P, c_size_t, c_size_t, c_size_t, c_int, _P, _P, _P]),
     "qt_dequantize_blocks_f32": (c_int, [_P, _P, _P, _P, c_size_t, c_size_t, c_size_t, c_int, _P, _P, _P]),
+    "qt_gwa_packed_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "qt_gwa_pack": (c_int, [_P, _P, c_int, c_int, c_int, c_float, c_float, _P, _P]),
+    "qt_gwa_dequantize_bf16": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P]),
+    "qt_linear_gwa_tile": (c_int, [c_int]),
+    "qt_linear_gwa_bf16": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, c_int, _P]),
     "qt_fake_quant_pc_bf16": (c_int, [_P, _P, c_size_t, c_size_t, c_size_t, _FMT, _P, _P, _P, _P]),
     "qt_fake_quant_pc_f32": (c_int, [_P, _P, c_size_t, c_size_t, c_size_t, _FMT, _P, _P, _P, _P]),
     "qt_linear_fq_bf16": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _OPQ, _OPQ, _P]),

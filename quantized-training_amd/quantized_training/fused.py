@@ -82,6 +82,8 @@ def routes_report():
     out.update(sorted(OPT_ROUTES.items()))
     from .conv_route import CONV_ROUTES                        # QAT convolutions (csrc/qt_conv.hip or the library's convolution)
     out.update(sorted(CONV_ROUTES.items()))
+    from .pt2e_native import GWA_ROUTES                        # packed group-wise affine Linears (csrc/qt_gwa_gemm.hip or dequantize + library GEMM)
+    out.update(sorted(GWA_ROUTES.items()))
     return out
 
 

@@ -32,7 +32,7 @@ from torch.fx import GraphModule
 from . import _native, mx_operand, switches
 from .fake_quantize import _stream_ptr
 
-__all__ = ["fuse_native_gemms", "fuse_mx_pairs", "STATS"]
+__all__ = ["fuse_native_gemms", "fuse_mx_pairs", "fuse_gwa_linears", "STATS", "GWA_STATS"]
 
 STATS = {"linear_int8": 0, "matmul_int8": 0, "linear_fp8": 0, "matmul_fp8": 0}
 _IDENTITY_DTYPES = (None, "None", "bfloat16", "float32", "float16")
@@ -340,3 +340,259 @@ def enabled_for(model) -> bool:
         return next(iter(model.parameters())).device.type == "cuda"
     except StopIteration:
         return False
+
+
+# ---- packed group-wise affine weights: dequantize + aten.linear -> linear_gwa (csrc/qt_gwa_gemm.hip) ----------------------------------
+# convert_pt2e leaves, for a `uintN,qs=group_wise_affine,bs=..,ax=-1` Linear weight, three bf16 buffers (codes, scales, zero points)
+# and `dequantize(codes, scale, zero_point, (-1,), bs)` in front of aten.linear.  fuse_gwa_linears stores the codes packed (4 or 8
+# bits each instead of 16) and rewrites the pair into one linear_gwa node; on the device that node runs the fused
+# dequantize-GEMM where the committed rule takes the shape and the one-pass dequantize kernel + the library GEMM elsewhere.
+GWA_BLOCKS = (32, 64, 128, 256, 512)
+GWA_TILES = (16, 32, 64)                  # row-tile heights of qt_linear_gwa_bf16 (tile_m; 0 = by M)
+GWA_ROUTES = {}                           # "gwa:MxNxK" -> route of the first call with that shape (fused.routes_report)
+
+
+class _GwaStats:
+    """Calls of linear_gwa per route, and why a device call did not take the fused kernel."""
+    def __init__(self):
+        self.reset()
+
+    def reset(self):
+        self.fused = self.dequant = self.reference = 0
+        self.reasons = {}
+
+    def note(self, why):
+        self.reasons[why] = self.reasons.get(why, 0) + 1
+
+
+GWA_STATS = _GwaStats()
+
+_lib.define("linear_gwa(Tensor input, Tensor packed, Tensor scale, Tensor zero_point, Tensor? bias, int block_size, int quant_min, "
+            "int bits, int K) -> Tensor")
+
+
+def gwa_dtype_range(dtype):
+    """(quant_min, quant_max, bits) of an integer element dtype of at most 8 bits ("uint4", "int4", "uint2", "uint8", ...), else None."""
+    import re
+    m = re.fullmatch(r"(u?)int(\d+)", str(dtype).split(",")[0].strip())
+    if m is None or not 1 <= int(m.group(2)) <= 8:
+        return None
+    n = int(m.group(2))
+    lo, hi = (0, 2 ** n - 1) if m.group(1) else (-(2 ** (n - 1)), 2 ** (n - 1) - 1)
+    return lo, hi, 4 if hi - lo <= 15 else 8
+
+
+def _gwa_geometry(N, K, bits):
+    j = 4 if bits == 4 else 2              # k steps of 32 per super step
+    return (N + 15) // 16, (K + 32 * j - 1) // (32 * j), j
+
+
+def gwa_pack_torch(codes, quant_min, quant_max, bits):
+    """The packed layout of qt_gwa_pack in torch ops (include/qt_hip.h): uint8 [bytes], or None when a code is not an integer in
+    [quant_min, quant_max]."""
+    N, K = codes.shape
+    c = codes.detach().to(torch.float32)
+    if not bool(((c == c.round()) & (c >= quant_min) & (c <= quant_max)).all()):
+        return None
+    n16, nss, j = _gwa_geometry(N, K, bits)
+    q = torch.zeros((n16 * 16, nss * 32 * j), dtype=torch.uint8, device=codes.device)
+    q[:N, :K] = (c - quant_min).to(torch.uint8)
+    q = q.view(n16, 16, nss, j, 4, 8).permute(0, 2, 4, 1, 3, 5)           # [group, super step, g, r, k step, e]
+    if bits == 4:
+        q = q[..., 0::2] | (q[..., 1::2] << 4)
+    return q.contiguous().view(-1)
+
+
+def gwa_unpack_torch(packed, N, K, bits):
+    """Inverse of the packers: uint8 codes - quant_min, [N, K]."""
+    n16, nss, j = _gwa_geometry(N, K, bits)
+    p = packed.view(n16, nss, 4, 16, j, 4 if bits == 4 else 8)
+    if bits == 4:
+        p = torch.stack((p & 15, p >> 4), dim=-1).view(n16, nss, 4, 16, j, 8)
+    return p.permute(0, 3, 1, 4, 2, 5).reshape(n16 * 16, nss * 32 * j)[:N, :K]
+
+
+def _gwa_shape_ok(N, K, block_size):
+    return (isinstance(block_size, int) and not isinstance(block_size, bool) and block_size in GWA_BLOCKS and K % block_size == 0
+            and K % 32 == 0 and N % 8 == 0 and N > 0)
+
+
+def gwa_pack(codes, quant_min, quant_max, bits):
+    """Packed operand of a [N, K] codes tensor, or None when the check fails (or the shape is not the kernels').  Device bf16 codes go
+    through qt_gwa_pack and its flag -- read by the host here, once, at convert time -- everything else through the torch ops."""
+    N, K = codes.shape
+    if codes.device.type == "cuda" and codes.dtype == torch.bfloat16 and K % 32 == 0 and N % 8 == 0:
+        L = _native.lib()
+        c = codes.detach().contiguous()
+        nbytes = L.qt_gwa_packed_bytes(N, K, bits)
+        if nbytes:
+            packed = torch.empty(nbytes, dtype=torch.uint8, device=c.device)
+            bad = torch.zeros(1, dtype=torch.int32, device=c.device)
+            rc = L.qt_gwa_pack(c.data_ptr(), packed.data_ptr(), N, K, bits, float(quant_min), float(quant_max), bad.data_ptr(),
+                               _stream_ptr(c))
+            if not _native.declined(rc):
+                _native.check(rc, "qt_gwa_pack")
+                return None if int(bad.item()) != 0 else packed
+    return gwa_pack_torch(codes, quant_min, quant_max, bits)
+
+
+def _gwa_reference(input, packed, scale, zero_point, bias, block_size, quant_min, bits, K):
+    """The unfused graph on the unpacked codes: bit for bit what dequantize + aten.linear computed."""
+    codes = gwa_unpack_torch(packed, scale.shape[0], K, bits).to(scale.dtype) + quant_min
+    w = torch.ops.quantized_ops.dequantize(codes, scale, zero_point, (-1,), block_size)
+    return torch.nn.functional.linear(input, w, bias)
+
+
+_GWA_FUSED_MAX_M = 32
+
+
+def _gwa_route_takes(M, N, K):
+    """The committed rule, a fixed function of the problem (never a timing).  From profiles/gwa_linear.txt (uint4, bs = 128, LLaMA-2-7B's
+    three projection shapes, weights rotating beyond the Infinity Cache): at M = 1, 16 and 32 the fused kernel's slowest round beats the
+    fastest round of qt_gwa_dequantize_bf16 + the library GEMM on every weight (1.6 - 2.8 x at the medians); at M = 64 it does so on
+    two weights of three (it ties on 11008 x 4096), at M = 128 on one, at M = 1024 on none (0.2 x: every 64-row tile converts the
+    weight again).  A shape class goes to the fused kernel only where it won every row: M <= 32."""
+    return M <= _GWA_FUSED_MAX_M
+
+
+def gwa_dequantize(packed, scale, zero_point, block_size, quant_min, bits, K):
+    """qt_gwa_dequantize_bf16: the bf16 weight [N, K] in one pass, or None when the kernel declines."""
+    N = scale.shape[0]
+    w = torch.empty((N, K), dtype=torch.bfloat16, device=packed.device)
+    rc = _native.lib().qt_gwa_dequantize_bf16(packed.data_ptr(), scale.data_ptr(), zero_point.data_ptr(), w.data_ptr(), N, K,
+                                              block_size, bits, float(quant_min), _stream_ptr(packed))
+    if _native.declined(rc):
+        return None
+    _native.check(rc, "qt_gwa_dequantize_bf16")
+    return w
+
+
+def linear_gwa_route(input, packed, scale, zero_point, bias, block_size, quant_min, bits, K, route=None, tile_m=0):
+    """linear_gwa with the route in the caller's hands: None = the committed rule, "fused" / "dequant" / "reference" = that route
+    (a forced route the kernels decline falls through to the next one, as the rule's does), tile_m = the fused kernel's variant."""
+    N = scale.shape[0]
+    device_ok = (input.device.type == "cuda" and input.dtype == torch.bfloat16 and scale.dtype == torch.bfloat16
+                 and zero_point.dtype == torch.bfloat16 and packed.dtype == torch.uint8 and input.shape[-1] == K
+                 and _gwa_shape_ok(N, K, block_size) and bits in (4, 8) and input.numel() > 0
+                 and (bias is None or bias.dtype == torch.bfloat16))
+    M = input.numel() // K if K else 0
+    key = f"gwa:{M}x{N}x{K}"
+    if route == "reference" or not device_ok:
+        if route != "reference":
+            GWA_STATS.note("not a bf16 device call the kernels take")
+        GWA_STATS.reference += 1
+        GWA_ROUTES.setdefault(key, "unpack+dequantize+linear")
+        return _gwa_reference(input, packed, scale, zero_point, bias, block_size, quant_min, bits, K)
+    L = _native.lib()
+    s, z = scale.contiguous(), zero_point.contiguous()
+    if route == "fused" or (route is None and _gwa_route_takes(M, N, K)):
+        x = input.reshape(M, K).contiguous()
+        b = bias.contiguous() if bias is not None else None
+        y = torch.empty((M, N), dtype=torch.bfloat16, device=input.device)
+        rc = L.qt_linear_gwa_bf16(x.data_ptr(), packed.data_ptr(), s.data_ptr(), z.data_ptr(), b.data_ptr() if b is not None else None,
+                                  y.data_ptr(), M, N, K, block_size, bits, float(quant_min), tile_m, _stream_ptr(x))
+        if not _native.declined(rc):
+            _native.check(rc, "qt_linear_gwa_bf16")
+            GWA_STATS.fused += 1
+            GWA_ROUTES.setdefault(key, "fused_gwa_gemm")
+            return y.view(*input.shape[:-1], N)
+        GWA_STATS.note("qt_linear_gwa_bf16 declined")
+    elif route is None:
+        GWA_STATS.note("route rule")
+    w = gwa_dequantize(packed, s, z, block_size, quant_min, bits, K)
+    if w is None:
+        GWA_STATS.note("qt_gwa_dequantize_bf16 declined")
+        GWA_STATS.reference += 1
+        GWA_ROUTES.setdefault(key, "unpack+dequantize+linear")
+        return _gwa_reference(input, packed, scale, zero_point, bias, block_size, quant_min, bits, K)
+    GWA_STATS.dequant += 1
+    GWA_ROUTES.setdefault(key, "gwa_dequantize+library_gemm")
+    return torch.nn.functional.linear(input, w, bias)
+
+
+def _linear_gwa(input, packed, scale, zero_point, bias, block_size, quant_min, bits, K):
+    return linear_gwa_route(input, packed, scale, zero_point, bias, block_size, quant_min, bits, K)
+
+
+def _linear_gwa_meta(input, packed, scale, zero_point, bias, block_size, quant_min, bits, K):
+    return input.new_empty((*input.shape[:-1], scale.shape[0]))
+
+
+_lib.impl("linear_gwa", _linear_gwa, "CompositeExplicitAutograd")
+_lib.impl("linear_gwa", _linear_gwa_meta, "Meta")
+
+
+def _owner_and_name(model, target):
+    mod, _, name = str(target).rpartition(".")
+    return (model.get_submodule(mod) if mod else model), name
+
+
+def fuse_gwa_linears(model: GraphModule) -> int:
+    """Rewrites `dequantize(codes, scale, zero_point, (last axis,), bs)` + `aten.linear` of a bf16 model into one `linear_gwa` node on
+    the packed codes (buffer `<codes>_packed`; the bf16 codes buffer is deleted when nothing else reads it).  Fused only when the
+    three operands are bf16 get_attr buffers, there are no maps, the blocks run along the weight's last axis with an int block
+    size the kernels take, the dequantize's sole user is an aten.linear that uses it as the weight, and every code passes the
+    packer's check; everything else keeps its two nodes.  Returns the number of fused Linears."""
+    DQ = torch.ops.quantized_ops.dequantize.default
+    graph = model.graph
+    fused = 0
+    for dq in list(graph.nodes):
+        if not _is(dq, DQ) or dq.kwargs or not 5 <= len(dq.args) <= 7:
+            continue
+        a = list(dq.args) + [None] * (7 - len(dq.args))
+        q, s, z, axes, bs = a[:5]
+        if a[5] is not None or a[6] is not None or z is None:
+            continue
+        if any(getattr(n, "op", None) != "get_attr" for n in (q, s, z)):
+            continue
+        users = list(dq.users.keys())
+        if len(users) != 1 or not _is(users[0], torch.ops.aten.linear.default):
+            continue
+        lin = users[0]
+        if lin.kwargs or len(lin.args) < 2 or lin.args[1] is not dq or lin.args[0] is dq or (len(lin.args) > 2 and lin.args[2] is dq):
+            continue
+        try:
+            codes, scale, zero = (model.get_buffer(n.target) for n in (q, s, z))
+        except AttributeError:
+            continue
+        if any(t.dtype != torch.bfloat16 for t in (codes, scale, zero)) or codes.dim() != 2:
+            continue
+        ax = _axes_list(axes)
+        if ax is None or len(ax) != 1 or ax[0] % codes.dim() != codes.dim() - 1:
+            continue
+        N, K = codes.shape
+        if not _gwa_shape_ok(N, K, bs) or tuple(scale.shape) != (N, K // bs) or tuple(zero.shape) != (N, K // bs):
+            continue
+        rng = gwa_dtype_range(q.meta.get("dtype"))
+        if rng is None:
+            continue
+        qmin, qmax, bits = rng
+        packed = gwa_pack(codes, qmin, qmax, bits)
+        if packed is None:
+            continue                                         # a code the packed form cannot hold: keep the value tensor
+        owner, leaf = _owner_and_name(model, q.target)
+        name, i = leaf + "_packed", 0
+        while hasattr(owner, name):
+            i += 1
+            name = f"{leaf}_packed_{i}"
+        owner.register_buffer(name, packed)
+        prefix = str(q.target).rpartition(".")[0]
+        bias = lin.args[2] if len(lin.args) > 2 else None
+        with graph.inserting_before(lin):
+            p_node = graph.create_node("get_attr", (prefix + "." if prefix else "") + name)
+            new = graph.call_function(torch.ops.quantized_ops.linear_gwa.default,
+                                      (lin.args[0], p_node, s, z, bias, bs, int(qmin), bits, K))
+        p_node.meta["dtype"] = q.meta.get("dtype")
+        new.meta = dict(lin.meta)
+        lin.replace_all_uses_with(new)
+        graph.erase_node(lin)
+        graph.erase_node(dq)
+        if len(q.users) == 0:
+            graph.erase_node(q)
+            if not any(n.op == "get_attr" and n.target == q.target for n in graph.nodes):
+                delattr(owner, leaf)                         # 2 bytes per weight -> 0.5 (or 1)
+        fused += 1
+    if fused:
+        graph.lint()
+        model.recompile()
+    return fused

@@ -493,4 +493,5 @@ def convert_pt2e(model: GraphModule, output_dtype: str = None, eliminate_no_effe
     if native or (native is None and pt2e_native.enabled_for(model)):
         pt2e_native.fuse_native_gemms(model)
         pt2e_native.fuse_mx_pairs(model)                         # calculate_mx_qparam + quantize of an activation -> one quantize_mx
+        pt2e_native.fuse_gwa_linears(model)                      # group-wise affine weight: dequantize + linear -> linear_gwa on packed codes
     return model
