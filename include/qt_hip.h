@@ -886,6 +886,40 @@ int qt_spmm_csr_f32(const float *data_dev, const int32_t *indices_dev, const int
 int qt_q8_gemm(const int8_t *a_codes, const int8_t *b_codes, void *c_dev, int c_is_f32, const void *bias_dev, const void *out_scale_dev,
                int out_scale_per_col, int fold_f32, long batch, int M, int N, int K, long a_batch_stride_rows, long b_batch_stride_rows, void *stream);
 
+/* The convolution of such a graph (quantize -> aten.conv2d -> dequantize(s_x * s_w)) as an implicit GEMM on the same instruction:
+ * qt_conv2d_mx's gather (rows = output pixels, K = kh kw Cin in (r, s, c) order, zero chunks for padding taps, rows past M and the K
+ * tail; no address outside the operands is formed into a load) with int8 codes on both sides, no scale bytes, exact int32
+ * accumulation, and qt_q8_gemm's epilogue:
+ *     y[n, ho, wo, co] = round_y( round_y( float(sum_{r, s, c} x[n, hi, wi, c] w[co, r, s, c]) + bias[co] ) * out_scale )
+ * float(): the one round-to-nearest-even conversion of the exact int32 sum; the other two roundings are those of the graph's
+ * aten.conv2d output and of its dequantize multiply; fold_f32 as in qt_q8_gemm.
+ * x_codes int8 NHWC [N][H][W][Cin], w_codes int8 [Cout][kh][kw][Cin], y NHWC [N][Ho][Wo][Cout] bf16 or fp32, bias [Cout] (nullable)
+ * and out_scale (nullable; one element, or Cout with out_scale_per_col) in y's dtype.  Zero padding, groups = 1.
+ * QT_ERR_BAD_ARG: a NULL operand or output; Cin < 32 or Cin % 32 != 0 (a 16-byte chunk must not straddle a tap and a 128-byte k
+ * tile may reach at most four taps past its first: Cin = 16 is NOT taken); kh kw Cin >= 2^17 (below it no sum of products of int8
+ * codes, -128 included, leaves int32); a non-positive extent, stride or dilation, a negative padding; N Ho Wo or the byte size of
+ * either code array >= 2^31, kh dh, kw dw, strides or paddings >= 2^20.  QT_ERR_UNALIGNED: any pointer off a 16-byte boundary.
+ * All answered before the first HIP call; an empty output (N == 0, Cout == 0, no output pixel) is QT_OK without a launch.  Every
+ * element of y is written and nothing else; no atomics, no allocation, no synchronisation: the same bits on every launch, safe
+ * under stream capture. */
+int qt_q8_conv2d(const int8_t *x_codes, const int8_t *w_codes, void *y, int y_is_f32, const void *bias, const void *out_scale,
+                 int out_scale_per_col, int fold_f32, int N, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw, int ph, int pw,
+                 int dh, int dw, void *stream);
+
+/* The activation operand of qt_q8_conv2d in one pass: codes[n][p][c] = narrow(map[index(x[n, c, p] / scale)]), the arithmetic of
+ * qt_quantize_* (the same device function) with a per-tensor scale in the tensor's dtype and no zero point, narrowed to int8.
+ * x is the [N][HW][C] view of a 4-D tensor given by element strides (batch, row, channel): NCHW-contiguous (C HW, 1, HW) -- a
+ * transposition through a padded LDS tile: reads run along HW, code rows leave in 16-byte runs -- or channels_last-dense
+ * (HW C, C, 1) -- a straight vector pass.  One read of x, one byte written per element.
+ * Narrowing rule: a mapped value that is an integer in [-128, 127] (everything a well-formed int8 map holds for a finite input) is
+ * that integer; any other value is truncated toward zero and saturated to [-128, 127]; NaN gives 0.
+ * QT_ERR_BAD_ARG: NULL x / codes / scale / fmt, a table format without its table, C % 16 != 0, N > 65535, any other stride
+ * triple; QT_ERR_UNALIGNED: x or codes off a 16-byte boundary.  QT_OK without a launch for an empty tensor. */
+int qt_quantize_codes_nhwc_bf16(const uint16_t *x_dev, int8_t *codes_dev, long N, long HW, long C, long batch_stride, long row_stride,
+                                long channel_stride, const qt_format *fmt, const uint16_t *lut_dev, const uint16_t *scale_dev, void *stream);
+int qt_quantize_codes_nhwc_f32(const float *x_dev, int8_t *codes_dev, long N, long HW, long C, long batch_stride, long row_stride,
+                               long channel_stride, const qt_format *fmt, const uint16_t *lut_dev, const float *scale_dev, void *stream);
+
 /* Fused quantize_mx for blocks along the last axis (decomposed.py:365-448 with axes = [-1]): x [rows][cols] in the
  * tensor dtype -> q (element values map[x / scale], nullable), scales [rows][cols / block_size] (same dtype), and, when
  * codes / e8m0 are given (requires force_pow2, block_size % 32 == 0, pack_format = the QT_MX_* format the map rounds

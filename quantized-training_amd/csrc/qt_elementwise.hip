@@ -1254,6 +1254,35 @@ struct QdqArgs {
     int mode;                  // 0 = x / s [+ zp], 1 = (x [- zp]) * s
 };
 
+// one element of quantize / dequantize: value `v` is kept in the tensor dtype after every op (bf16 ops round to bf16)
+template <int IO>
+__device__ __forceinline__ float qdq_value(float v, const QdqArgs &a, float s, float z, bool has_zp) {
+    auto round_io = [](float f) -> float {
+        if constexpr (IO == kIoBf16) return qt_u2f(pack_bf16x2(f, 0.0f) << 16);
+        else return f;
+    };
+    auto lookup = [&](const uint16_t *t, float f) -> float {
+        uint32_t img = (IO == kIoBf16) ? qt_f2u(f) : qt_fold_img(qt_f2u(f));
+        return qt_bf2f(t[img >> 16]);
+    };
+    if (a.in_lut) v = lookup(a.in_lut, v);
+    if (a.mode == 0) {
+        v = round_io(v / s);
+        if (has_zp) v = round_io(v + z);
+    } else {
+        if (has_zp) v = round_io(v - z);
+        v = round_io(v * s);
+    }
+    if (a.use_out) {
+        if (a.out_lut) v = lookup(a.out_lut, v);
+        else {
+            uint32_t img = (IO == kIoBf16) ? qt_f2u(v) : qt_fold_img(qt_f2u(v));
+            v = qt_u2f(qt_apply_format_img(a.out_fmt, img));
+        }
+    }
+    return v;
+}
+
 template <int IO>
 __global__ __launch_bounds__(256) void qdq_kernel(const void *__restrict__ xv, void *__restrict__ yv, size_t n, QdqArgs a,
                                                  const void *__restrict__ scale, const void *__restrict__ zp) {
@@ -1266,35 +1295,93 @@ __global__ __launch_bounds__(256) void qdq_kernel(const void *__restrict__ xv, v
         if (zp) z = *(const float *)zp;
     }
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        // value `v` is kept in the tensor dtype after every op (bf16 ops round to bf16)
         float v;
         if constexpr (IO == kIoBf16) v = qt_bf2f(((const uint16_t *)xv)[i]);
         else v = ((const float *)xv)[i];
-        auto round_io = [](float f) -> float {
-            if constexpr (IO == kIoBf16) return qt_u2f(pack_bf16x2(f, 0.0f) << 16);
-            else return f;
-        };
-        auto lookup = [&](const uint16_t *t, float f) -> float {
-            uint32_t img = (IO == kIoBf16) ? qt_f2u(f) : qt_fold_img(qt_f2u(f));
-            return qt_bf2f(t[img >> 16]);
-        };
-        if (a.in_lut) v = lookup(a.in_lut, v);
-        if (a.mode == 0) {
-            v = round_io(v / s);
-            if (zp) v = round_io(v + z);
-        } else {
-            if (zp) v = round_io(v - z);
-            v = round_io(v * s);
-        }
-        if (a.use_out) {
-            if (a.out_lut) v = lookup(a.out_lut, v);
-            else {
-                uint32_t img = (IO == kIoBf16) ? qt_f2u(v) : qt_fold_img(qt_f2u(v));
-                v = qt_u2f(qt_apply_format_img(a.out_fmt, img));
-            }
-        }
+        v = qdq_value<IO>(v, a, s, z, zp != nullptr);
         if constexpr (IO == kIoBf16) ((uint16_t *)yv)[i] = (uint16_t)(qt_f2u(v) >> 16);
         else ((float *)yv)[i] = v;
+    }
+}
+
+// ---- quantize -> int8 NHWC codes (qt_quantize_codes_nhwc_*): the activation operand of qt_q8_conv2d in one pass ----------------
+// code = narrow(qdq_value(x)) with the quantize arguments (mode 0, no zero point, the map from global memory): the value the
+// quantize kernel above would store, narrowed as torch's .to(int8) narrows an integer in [-128, 127].  Anything else a map could
+// hold: truncated toward zero, saturated to [-128, 127], NaN -> 0.
+__device__ __forceinline__ uint32_t code_of(float v) {
+    if (v != v) return 0u;
+    v = fminf(fmaxf(v, -128.0f), 127.0f);
+    return (uint32_t)(int)v & 0xFFu;
+}
+
+constexpr int kCodeTP = 64, kCodeTC = 64;            // pixels x channels of one transposition tile
+constexpr int kCodeRow = kCodeTC + 4;                // LDS bytes per pixel row: 17 words, odd, so 64 pixels of one channel hit 64 words mod 32 evenly
+
+// NCHW-contiguous input: x [N][C][HW] -> codes [N][HW][C].  grid (pixel tiles, channel tiles, N).  Reads run along HW (64
+// consecutive elements per wave instruction), each lane narrows its elements into the byte tile, then every lane writes one
+// 16-byte run of a pixel's code row.  C % 16 == 0.
+template <int IO>
+__global__ __launch_bounds__(256) void codes_nchw_kernel(const void *__restrict__ xv, uint8_t *__restrict__ codes, int C, int HW, QdqArgs a,
+                                                        const void *__restrict__ scale) {
+    __shared__ __attribute__((aligned(16))) uint8_t tile[kCodeTP * kCodeRow];
+    float s;
+    if constexpr (IO == kIoBf16) s = qt_bf2f(*(const uint16_t *)scale);
+    else s = *(const float *)scale;
+    const int t = threadIdx.x;
+    const int p0 = blockIdx.x * kCodeTP, c0 = blockIdx.y * kCodeTC;
+    const size_t n = blockIdx.z;
+    const int p = t & (kCodeTP - 1), p_g = p0 + p;
+    const size_t xbase = n * (size_t)C * (size_t)HW;
+#pragma unroll 4
+    for (int j = 0; j < kCodeTC / 4; ++j) {
+        const int c = (t >> 6) + 4 * j, c_g = c0 + c;
+        uint32_t code = 0u;
+        if (p_g < HW && c_g < C) {
+            const size_t i = xbase + (size_t)c_g * (size_t)HW + (size_t)p_g;
+            float v;
+            if constexpr (IO == kIoBf16) v = qt_bf2f(((const uint16_t *)xv)[i]);
+            else v = ((const float *)xv)[i];
+            code = code_of(qdq_value<IO>(v, a, s, 0.0f, false));
+        }
+        tile[p * kCodeRow + c] = (uint8_t)code;
+    }
+    __syncthreads();
+    const int wp = t >> 2, wc = (t & 3) * 16;          // pixel of the tile, first channel of the 16-byte run
+    if (p0 + wp < HW && c0 + wc < C) {
+        const uint32_t *src = (const uint32_t *)(tile + wp * kCodeRow + wc);
+        const uint4 v = {src[0], src[1], src[2], src[3]};
+        *(uint4 *)(codes + (n * (size_t)HW + (size_t)(p0 + wp)) * (size_t)C + (size_t)(c0 + wc)) = v;
+    }
+}
+
+// channels_last-dense input: the stored tensor is [N HW][C] already; 16 elements per lane, one 16-byte store.  n16 = elements / 16.
+template <int IO>
+__global__ __launch_bounds__(256) void codes_flat_kernel(const void *__restrict__ xv, uint4 *__restrict__ codes, size_t n16, QdqArgs a,
+                                                        const void *__restrict__ scale) {
+    float s;
+    if constexpr (IO == kIoBf16) s = qt_bf2f(*(const uint16_t *)scale);
+    else s = *(const float *)scale;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) {
+        uint32_t w[4] = {0u, 0u, 0u, 0u};
+        if constexpr (IO == kIoBf16) {
+            const uint4 lo = ((const uint4 *)xv)[2 * i], hi = ((const uint4 *)xv)[2 * i + 1];
+            const uint32_t in[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const uint32_t c0 = code_of(qdq_value<IO>(qt_u2f(in[e] << 16), a, s, 0.0f, false));
+                const uint32_t c1 = code_of(qdq_value<IO>(qt_u2f(in[e] & 0xFFFF0000u), a, s, 0.0f, false));
+                w[e >> 1] |= (c0 | (c1 << 8)) << ((e & 1) * 16);
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const uint4 in = ((const uint4 *)xv)[4 * i + q];
+                const uint32_t u[4] = {in.x, in.y, in.z, in.w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) w[q] |= code_of(qdq_value<IO>(qt_u2f(u[e]), a, s, 0.0f, false)) << (8 * e);
+            }
+        }
+        codes[i] = uint4{w[0], w[1], w[2], w[3]};
     }
 }
 
@@ -1511,6 +1598,31 @@ int launch_qdq(const void *x, void *y, size_t n, const QdqArgs &a, const void *s
     unsigned grid = grid_for(n, 256 * 4, 8);
     qdq_kernel<IO><<<grid, 256, 0, (hipStream_t)stream>>>(x, y, n, a, scale, zp);
     return qt_launch_status();
+}
+
+template <int IO>
+int launch_codes_nhwc(const void *x, int8_t *codes, long N, long HW, long C, long bs, long rs, long cs, const qt_format *fmt,
+                      const uint16_t *lut, const void *scale, void *stream) {
+    if (!fmt || (fmt->kind == QT_FMT_LUT && !lut)) return QT_ERR_BAD_ARG;
+    if (N < 0 || HW < 0 || C < 0) return QT_ERR_BAD_ARG;
+    if (N == 0 || HW == 0 || C == 0) return QT_OK;
+    if (!x || !codes || !scale) return QT_ERR_BAD_ARG;
+    if (C % 16 != 0 || N > 65535 || HW >= (1L << 31) || C >= (1L << 31) || N * HW >= (1L << 40) / C) return QT_ERR_BAD_ARG;
+    if ((((uintptr_t)x | (uintptr_t)codes) & 15u)) return QT_ERR_UNALIGNED;
+    const QdqArgs a{nullptr, fmt->kind == QT_FMT_LUT ? lut : nullptr, *fmt, 1, 0};
+    hipStream_t st = (hipStream_t)stream;
+    if (cs == 1 && rs == C && bs == HW * C) {                       // channels_last-dense: already [N HW][C]
+        const size_t n16 = (size_t)(N * HW * C) / 16;
+        codes_flat_kernel<IO><<<grid_for(n16, 256, 8), 256, 0, st>>>(x, (uint4 *)codes, n16, a, scale);
+        return qt_launch_status();
+    }
+    if (rs == 1 && cs == HW && bs == C * HW) {                      // NCHW-contiguous: transposition through LDS
+        const dim3 grid((unsigned)((HW + kCodeTP - 1) / kCodeTP), (unsigned)((C + kCodeTC - 1) / kCodeTC), (unsigned)N);
+        if (grid.y > 65535u) return QT_ERR_BAD_ARG;
+        codes_nchw_kernel<IO><<<grid, 256, 0, st>>>(x, (uint8_t *)codes, (int)C, (int)HW, a, scale);
+        return qt_launch_status();
+    }
+    return QT_ERR_BAD_ARG;                                          // any other layout: the caller makes it one of the two
 }
 
 
@@ -1910,6 +2022,14 @@ int qt_quantize_f32(const float *x, float *y, size_t n, const qt_format *fmt, co
     if (!fmt || (fmt->kind == QT_FMT_LUT && !lut)) return QT_ERR_BAD_ARG;
     QdqArgs a{nullptr, fmt->kind == QT_FMT_LUT ? lut : nullptr, *fmt, 1, 0};
     return launch_qdq<kIoF32>(x, y, n, a, scale, zp, stream);
+}
+int qt_quantize_codes_nhwc_bf16(const uint16_t *x, int8_t *codes, long N, long HW, long C, long batch_stride, long row_stride,
+                                long channel_stride, const qt_format *fmt, const uint16_t *lut, const uint16_t *scale, void *stream) {
+    return launch_codes_nhwc<kIoBf16>(x, codes, N, HW, C, batch_stride, row_stride, channel_stride, fmt, lut, scale, stream);
+}
+int qt_quantize_codes_nhwc_f32(const float *x, int8_t *codes, long N, long HW, long C, long batch_stride, long row_stride,
+                               long channel_stride, const qt_format *fmt, const uint16_t *lut, const float *scale, void *stream) {
+    return launch_codes_nhwc<kIoF32>(x, codes, N, HW, C, batch_stride, row_stride, channel_stride, fmt, lut, scale, stream);
 }
 int qt_dequantize_bf16(const uint16_t *x, uint16_t *y, size_t n, const uint16_t *scale, const uint16_t *zp,
                        const uint16_t *in_lut, const uint16_t *out_lut, void *stream) {

@@ -1167,9 +1167,11 @@ __device__ __forceinline__ void conv_tap_of(int v, int per, int ts0, int tr0, in
     tr = tr0 + wrap;
 }
 
-template <int FA, int FB>
+// I8 (qt_q8_conv2d): int8 codes on both sides, int32 accumulators, no scale bytes -- every scale load below is compiled out --
+// and the dequantize factor of emit_out in the epilogue.
+template <int FA, int FB, bool I8 = false>
 __global__ __launch_bounds__(256) void mx_conv_kernel(MxGemmArgs a, MxConvGeom c) {
-    using M_ = Mma<FA, FB, false>;
+    using M_ = Mma<FA, FB, I8>;
     using TA = Tile<FA>;
     using TB = Tile<FB>;
     constexpr int RA = TA::kRow, RB = TB::kRow;
@@ -1230,17 +1232,23 @@ __global__ __launch_bounds__(256) void mx_conv_kernel(MxGemmArgs a, MxConvGeom c
         cb[i] = cc * 16;
     }
     const uint8_t *psb[4];
+    if constexpr (!I8) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        uint32_t pix;
-        corner(m0 + wm * 64 + i * 16 + r, pix, his[i], wis[i]);
-        gs[i] = pix * (uint32_t)c.cpb;
-        psb[i] = a.sB + (long)min(n0 + wn * 64 + i * 16 + r, a.N - 1) * nblk;
+        for (int i = 0; i < 4; ++i) {
+            uint32_t pix;
+            corner(m0 + wm * 64 + i * 16 + r, pix, his[i], wis[i]);
+            gs[i] = pix * (uint32_t)c.cpb;
+            psb[i] = a.sB + (long)min(n0 + wn * 64 + i * 16 + r, a.N - 1) * nblk;
+        }
     }
 
     uint4 ra[NA], rb[NB];
     bool oka[NA];
     int sca[4], scb[4];
+    if constexpr (I8) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) sca[i] = scb[i] = 0;
+    }
     int u_blk = 0, u_ts = 0, u_tr = 0;                               // where the next k tile to load starts
     auto load_tile = [&](int kt) __attribute__((always_inline)) {
 #pragma unroll
@@ -1257,17 +1265,19 @@ __global__ __launch_bounds__(256) void mx_conv_kernel(MxGemmArgs a, MxConvGeom c
             const long off = (long)kt * RB + cb[i];
             rb[i] = *(const uint4 *)(gb[i] + (off < kbB ? (long)kt * RB : -(long)cb[i]));
         }
-        int blk, ts, tr;
-        conv_tap_of(u_blk + g, c.cpb, u_ts, u_tr, c.kw, blk, ts, tr);
-        const uint32_t sdelta = ((uint32_t)(tr * c.dh) * (uint32_t)c.W + (uint32_t)(ts * c.dw)) * (uint32_t)c.cpb + (uint32_t)blk;
-        const int kb = min(kt * 4 + g, nblk - 1);
+        if constexpr (!I8) {
+            int blk, ts, tr;
+            conv_tap_of(u_blk + g, c.cpb, u_ts, u_tr, c.kw, blk, ts, tr);
+            const uint32_t sdelta = ((uint32_t)(tr * c.dh) * (uint32_t)c.W + (uint32_t)(ts * c.dw)) * (uint32_t)c.cpb + (uint32_t)blk;
+            const int kb = min(kt * 4 + g, nblk - 1);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int hi = his[i] + tr * c.dh, wi = wis[i] + ts * c.dw;
-            const bool ok = (tr < c.kh) & ((unsigned)hi < (unsigned)c.H) & ((unsigned)wi < (unsigned)c.W);
-            const int sv = a.sA[ok ? gs[i] + sdelta : 0u];
-            sca[i] = ok ? sv : 127;
-            scb[i] = psb[i][kb];
+            for (int i = 0; i < 4; ++i) {
+                const int hi = his[i] + tr * c.dh, wi = wis[i] + ts * c.dw;
+                const bool ok = (tr < c.kh) & ((unsigned)hi < (unsigned)c.H) & ((unsigned)wi < (unsigned)c.W);
+                const int sv = a.sA[ok ? gs[i] + sdelta : 0u];
+                sca[i] = ok ? sv : 127;
+                scb[i] = psb[i][kb];
+            }
         }
         int nb, ns, nr;
         conv_tap_of(u_blk + 4, c.cpb, u_ts, u_tr, c.kw, nb, ns, nr);
@@ -1290,7 +1300,7 @@ __global__ __launch_bounds__(256) void mx_conv_kernel(MxGemmArgs a, MxConvGeom c
         }
     };
 
-    v4f acc[4][4];
+    typename M_::acc_t acc[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -1334,23 +1344,25 @@ __global__ __launch_bounds__(256) void mx_conv_kernel(MxGemmArgs a, MxConvGeom c
         if (col >= a.N) continue;
         float bv = 0.f;
         if (a.bias) bv = a.out_f32 ? ((const float *)a.bias)[col] : qt_bf2f(((const uint16_t *)a.bias)[col]);
+        float sv = 1.0f;
+        if constexpr (I8) sv = out_scale_of(a, col);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int row = m0 + wm * 64 + i * 16 + 4 * g + e;
                 if (row >= a.M) continue;
-                emit_out(a, acc[i][j][e], bv, 1.0f, (long)row * a.N + col);
+                emit_out(a, (float)acc[i][j][e], bv, sv, (long)row * a.N + col);
             }
         }
     }
 }
 
-template <int FA, int FB>
+template <int FA, int FB, bool I8 = false>
 int launch_conv(const MxGemmArgs &g, const MxConvGeom &c, unsigned grid, hipStream_t st) {
     constexpr int kLds = 2 * Tile<FA>::kBytes + 2 * Tile<FB>::kBytes;
-    if (const int rc = qt_allow_lds<mx_conv_kernel<FA, FB>>(kLds)) return rc;
-    mx_conv_kernel<FA, FB><<<grid, 256, kLds, st>>>(g, c);
+    if (const int rc = qt_allow_lds<mx_conv_kernel<FA, FB, I8>>(kLds)) return rc;
+    mx_conv_kernel<FA, FB, I8><<<grid, 256, kLds, st>>>(g, c);
     return qt_launch_status();
 }
 
@@ -1797,6 +1809,35 @@ int qt_q8_gemm(const int8_t *a_codes, const int8_t *b_codes, void *c_dev, int c_
     if (const int rc = qt_allow_lds<mx_gemm_kernel<0, 0, true>>(kLds)) return rc;
     mx_gemm_kernel<0, 0, true><<<grid, 256, kLds, st>>>(g);
     return qt_launch_status();
+}
+
+int qt_q8_conv2d(const int8_t *x_codes, const int8_t *w_codes, void *y, int y_is_f32, const void *bias, const void *out_scale,
+                 int out_scale_per_col, int fold_f32, int N, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw, int ph, int pw,
+                 int dh, int dw, void *stream) {
+    if (!x_codes || !w_codes || !y) return QT_ERR_BAD_ARG;
+    // Cin % 32: a 16-byte chunk never straddles a tap and a 128-byte k tile spans at most four taps beyond its first (conv_tap_of)
+    if (N < 0 || H < 1 || W < 1 || Cout < 0 || Cin < 32 || Cin % 32 != 0 || Cin > (1 << 24)) return QT_ERR_BAD_ARG;
+    if (kh < 1 || kw < 1 || sh < 1 || sw < 1 || dh < 1 || dw < 1 || ph < 0 || pw < 0) return QT_ERR_BAD_ARG;
+    constexpr long kLim = 1L << 31;
+    auto mul = [](long a, long b) { return a >= kLim || b >= kLim ? kLim : (a * b >= kLim ? kLim : a * b); };
+    const long taps = mul(kh, kw);
+    // kh kw Cin < 2^17: |sum| <= (2^17 - 1) * 128 * 128 < 2^31, the int32 accumulator never wraps
+    if (mul(taps, Cin) >= (1L << 17)) return QT_ERR_BAD_ARG;
+    const long eh = (long)H + 2L * ph - (long)dh * (kh - 1) - 1, ew = (long)W + 2L * pw - (long)dw * (kw - 1) - 1;
+    if (N == 0 || Cout == 0 || eh < 0 || ew < 0) return QT_OK;                                  // empty output: nothing to launch
+    if ((((uintptr_t)x_codes | (uintptr_t)w_codes | (uintptr_t)y | (uintptr_t)bias | (uintptr_t)out_scale) & 15u)) return QT_ERR_UNALIGNED;
+    // the index limits of qt_conv2d_mx: 32-bit row and pixel indices, 32-bit byte offsets into the code arrays
+    const long ho = eh / sh + 1, wo = ew / sw + 1, m = mul(N, mul(ho, wo));
+    if (m >= kLim || mul(N, mul(mul(H, W), Cin)) >= kLim || mul(Cout, mul(taps, Cin)) >= kLim ||
+        (long)kh * dh >= (1 << 20) || (long)kw * dw >= (1 << 20) || ph >= (1 << 20) || pw >= (1 << 20) || sh >= (1 << 20) || sw >= (1 << 20))
+        return QT_ERR_BAD_ARG;
+    const int K = (int)(taps * Cin);
+    const uint8_t *A = (const uint8_t *)x_codes, *B = (const uint8_t *)w_codes;
+    MxGemmArgs g{A, B, nullptr, nullptr, y, bias, (int)m, Cout, K, 0, 0, 0, 0, 0, y_is_f32, out_scale, out_scale_per_col, fold_f32};
+    const MxConvGeom c{H, W, kh, kw, sh, sw, ph, pw, dh, dw, (int)ho, (int)wo, Cin / 32};
+    const long tiles = ((m + kBM - 1) / kBM) * ((Cout + kBN - 1) / kBN);
+    if (tiles >= kLim) return QT_ERR_BAD_ARG;
+    return launch_conv<0, 0, true>(g, c, (unsigned)tiles, (hipStream_t)stream);
 }
 
 int qt_mxi_pack(const void *x_dev, const void *scale_dev, int is_f32, const void *code_dev, int n_code, int8_t *codes_dev, float *scales_dev,

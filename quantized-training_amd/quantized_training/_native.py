@@ -238,6 +238,9 @@ SIGNATURES = {
     "qt_spmm_csr_bf16": (c_int, [_P, _P, _P, c_long, c_long, _P, c_long, c_long, c_int, _P, c_long, c_long, c_int, c_int, _P, c_int, _P, _P]),
     "qt_spmm_csr_f32": (c_int, [_P, _P, _P, c_long, c_long, _P, c_long, c_long, c_int, _P, c_long, c_long, c_int, c_int, _P, c_int, _P, _P]),
     "qt_q8_gemm": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, c_int, c_long, c_int, c_int, c_int, c_long, c_long, _P]),
+    "qt_q8_conv2d": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, c_int] + [c_int] * 13 + [_P]),
+    "qt_quantize_codes_nhwc_bf16": (c_int, [_P, _P] + [c_long] * 6 + [_FMT, _P, _P, _P]),
+    "qt_quantize_codes_nhwc_f32": (c_int, [_P, _P] + [c_long] * 6 + [_FMT, _P, _P, _P]),
     "qt_bench_fake_quant_bf16": (c_int, [_P, _P, c_size_t, _FMT, _P, _P, _P, c_int, c_size_t, c_int, _P,
                                         POINTER(c_float)]),
     "qt_bench_fake_quant_bf16_fp8": (c_int, [_P, _P, _P, c_size_t, _FMT, _P, _P, c_int, c_size_t, c_int, _P,

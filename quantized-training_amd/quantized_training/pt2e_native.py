@@ -14,7 +14,10 @@ cores:
     exact int32 accumulation -- with bias, the rounding of the GEMM output to the model dtype, the dequantize multiply and its
     rounding in the epilogue (the rounding points of the three-node sequence are kept);
   * fp8_e4m3 / fp8_e5m2 (per-tensor scaled): operands narrowed to OCP FP8 codes, the in-tree scaled-MFMA GEMM at unit block
-    scales (`qt_mx_gemm`; the library GEMM `qt_fp8_gemm` only where that kernel does not take the shape), then the dequantize kernel.
+    scales (`qt_mx_gemm`; the library GEMM `qt_fp8_gemm` only where that kernel does not take the shape), then the dequantize kernel;
+  * int8 convolutions (`quantize -> aten.conv2d -> dequantize`, the ImageNet recipe): one `conv2d_q` node -- the activation to int8
+    NHWC codes in one pass (`qt_quantize_codes_nhwc_*`), then `qt_q8_conv2d`, an implicit GEMM on the same instruction with the same
+    epilogue, into a channels_last result.
 
 The graph `convert_pt2e` returns is untouched on the CPU (it is pinned node for node to upstream's); fusion is a separate,
 idempotent pass that convert_pt2e applies to device models (`native=None` -> automatic, `QT_PT2E_NATIVE=0` turns it off).
@@ -34,7 +37,7 @@ from .fake_quantize import _stream_ptr
 
 __all__ = ["fuse_native_gemms", "fuse_mx_pairs", "fuse_gwa_linears", "STATS", "GWA_STATS"]
 
-STATS = {"linear_int8": 0, "matmul_int8": 0, "linear_fp8": 0, "matmul_fp8": 0}
+STATS = {"linear_int8": 0, "matmul_int8": 0, "linear_fp8": 0, "matmul_fp8": 0, "conv2d_int8": 0}
 _IDENTITY_DTYPES = (None, "None", "bfloat16", "float32", "float16")
 _FP8 = {"fp8_e4m3": torch.float8_e4m3fn, "fp8_e5m2": torch.float8_e5m2}
 
@@ -159,6 +162,166 @@ _lib.impl("linear_q", _linear_q, "CompositeExplicitAutograd")
 _lib.impl("matmul_q", _matmul_q, "CompositeExplicitAutograd")
 
 
+# ---- quantize -> aten.conv2d -> dequantize: conv2d_q (csrc/qt_mx_gemm.hip qt_q8_conv2d, csrc/qt_elementwise.hip qt_quantize_codes_nhwc_*) ----
+# weight_codes is int8 [Cout, kh, kw, Cin]: its shape carries the filter geometry and, flattened, it is the kernel's [Cout][kh kw Cin]
+# operand.  The activation becomes int8 NHWC codes in one pass (no value tensor), the implicit GEMM accumulates in int32 and its
+# epilogue keeps the rounding points of the three nodes.  Everything the kernels do not take runs those three nodes verbatim.
+_lib.define("conv2d_q(Tensor input, Tensor scale, Tensor qmap, Tensor weight_codes, Tensor? bias, int[2] stride, int[2] padding, "
+            "int[2] dilation, int groups, Tensor out_scale, Tensor? out_map, str kind) -> Tensor")
+
+CONV_Q_REASONS = {}            # why a device call of conv2d_q ran the three-node sequence -> count
+_APPLY_CONV_Q_RULE = True      # tools/exp_conv_q.py clears it to time the route the rule below declines
+_CONV_Q_MAX_K = 1 << 17
+
+
+def _conv_q_route_takes(m, cout, cin, kh, kw):
+    """The committed rule, a fixed function of the shape (never a timing): m = N Ho Wo output pixels, cout and cin channels, the
+    filter.  From profiles/conv2d_q.txt (ResNet-50's thirteen body layers at batch 32 and five smaller problems, bf16; the graph's
+    quantize + aten.conv2d + dequantize against conv2d_q with the codes pass inside the call, NCHW-contiguous and channels_last
+    input, eager calls and hipGraph replays).  A class is listed only where the native median beat the graph's median by more than
+    the graph's own min-max spread on every row, layout and mode; t = the kernel's 128 x 128 output tiles:
+      * filters larger than 1 x 1 with t >= 52: all five rows clear (3 x 3 at 64 - 512 channels, 7 x 7 over 32; 1.24 - 3.4 x);
+      * 1 x 1 with Cout >= Cin and t >= 208: all five rows clear (1.14 - 2.1 x);
+      * 1 x 1 with Cout < Cin: two of the four rows clear (256 -> 64 at 56 x 56: 1.44 - 3.0 x; 512 -> 128 at 28 x 28: 1.05 x from
+        NCHW input) and two lose -- a long contraction over few column tiles, no split of K: replayed from NCHW input 0.70 x
+        (2048 -> 512), 0.87 x (1024 -> 256) -- so the class is not listed;
+      * a few tiles (batch 4: t <= 8): none of the four rows clears (0.64 - 1.00 x replayed from NCHW input)."""
+    tiles = -(-m // 128) * -(-cout // 128)
+    if kh * kw > 1:
+        return tiles >= 52
+    return cout >= cin and tiles >= 208
+
+
+def _conv_out_hw(h, w, kh, kw, stride, padding, dilation):
+    ho = (h + 2 * padding[0] - dilation[0] * (kh - 1) - 1) // stride[0] + 1 if stride[0] > 0 else 0
+    wo = (w + 2 * padding[1] - dilation[1] * (kw - 1) - 1) // stride[1] + 1 if stride[1] > 0 else 0
+    return ho, wo
+
+
+def _conv_q_decline(input, scale, qmap, weight_codes, bias, stride, padding, dilation, groups, out_scale, kind, on_device=None):
+    """Why the kernels do not take this call (a string), or None when they do.  `on_device` overrides the device test, so that the
+    rest of the predicate can be exercised with host tensors."""
+    if not (input.device.type == "cuda" if on_device is None else on_device):
+        return "not a device tensor"
+    if kind != "int8" or weight_codes.dtype != torch.int8:
+        return f"kind {kind}, weight codes {weight_codes.dtype}"
+    if input.dtype not in (torch.bfloat16, torch.float32):
+        return f"model dtype {input.dtype}"
+    if input.dim() != 4 or weight_codes.dim() != 4 or input.numel() == 0 or weight_codes.numel() == 0:
+        return f"input {tuple(input.shape)}, weight codes {tuple(weight_codes.shape)}"
+    if groups != 1:
+        return f"groups {groups}"
+    n, cin, h, w = input.shape
+    cout, kh, kw, wcin = weight_codes.shape
+    if wcin != cin or cin < 32 or cin % 32:
+        return f"Cin = {cin} / {wcin}: not a multiple of 32"
+    if kh * kw * cin >= _CONV_Q_MAX_K:
+        return f"kh kw Cin = {kh * kw * cin} >= 2^17: the int32 sum could wrap"
+    if qmap.dtype != torch.bfloat16 or qmap.numel() != 65536:
+        return f"value map of {qmap.numel()} {qmap.dtype} entries"
+    if scale.numel() != 1 or scale.dtype != input.dtype:
+        return f"activation scale of {scale.numel()} elements, {scale.dtype}"
+    if out_scale.numel() not in (1, cout):
+        return f"dequantize scale of {out_scale.numel()} elements behind {cout} output channels"
+    if bias is not None and bias.numel() != cout:
+        return f"bias of {bias.numel()} elements"
+    ho, wo = _conv_out_hw(h, w, kh, kw, stride, padding, dilation)
+    if ho < 1 or wo < 1:
+        return f"empty output {ho} x {wo}"
+    if input.data_ptr() % 16 or weight_codes.data_ptr() % 16 or not weight_codes.is_contiguous() or qmap.data_ptr() % 2 \
+            or not qmap.is_contiguous():
+        return "misaligned operand"
+    if _APPLY_CONV_Q_RULE and not _conv_q_route_takes(n * ho * wo, cout, cin, kh, kw):
+        return "route rule: profiles/conv2d_q.txt"
+    return None
+
+
+def _aligned16(t):
+    return t.clone() if t.data_ptr() % 16 else t
+
+
+def _conv_weight_values(weight_codes, dtype):
+    """[Cout, Cin, kh, kw] values of the codes in the model dtype, as the unfused graph stored them.  The pass leaves the layer's own
+    parameter here (no copy: a fused layer holds its parameter as before plus 1 B per weight of codes); a codes tensor that lost it
+    (moved or copied since, or built by hand) gets the values rebuilt once and kept, unless the stream is capturing (a tensor
+    allocated during a capture belongs to that graph's pool)."""
+    cache = getattr(weight_codes, "_qt_conv_values", None)
+    if cache is not None and cache.dtype == dtype and cache.device == weight_codes.device:
+        return cache
+    w = weight_codes.permute(0, 3, 1, 2).to(dtype).contiguous()
+    if not (weight_codes.device.type == "cuda" and torch.cuda.is_current_stream_capturing()):
+        weight_codes._qt_conv_values = w
+    return w
+
+
+def _conv2d_q_unfused(input, scale, qmap, weight_codes, bias, stride, padding, dilation, groups, out_scale, out_map):
+    xq = torch.ops.quantized_ops.quantize(input, scale, None, None, None, qmap)
+    y = torch.nn.functional.conv2d(xq, _conv_weight_values(weight_codes, input.dtype), bias, tuple(stride), tuple(padding),
+                                   tuple(dilation), groups)
+    return torch.ops.quantized_ops.dequantize(y, out_scale, None, None, None, out_map)
+
+
+def conv_codes_nhwc(input, scale, qmap):
+    """int8 codes [N H W, C] of quantize(input, scale, qmap) in one pass (qt_quantize_codes_nhwc_*), or None when declined."""
+    from .decomposed import _lut_format, _scalar_like
+    from .mx_conv import _nhwc_strides
+    n, c, h, w = input.shape
+    xs = _nhwc_strides(input)
+    if xs is None:
+        input, xs = input.contiguous(), (c * h * w, 1, h * w)
+    codes = torch.empty((n * h * w, c), dtype=torch.int8, device=input.device)
+    s = _scalar_like(scale, input)
+    fmt = _lut_format()
+    L = _native.lib()
+    fn = L.qt_quantize_codes_nhwc_bf16 if input.dtype == torch.bfloat16 else L.qt_quantize_codes_nhwc_f32
+    rc = fn(input.data_ptr(), codes.data_ptr(), n, h * w, c, *xs, ctypes.byref(fmt), qmap.data_ptr(), s.data_ptr(), _stream_ptr(input))
+    if _native.declined(rc):
+        return None
+    _native.check(rc, "qt_quantize_codes_nhwc")
+    return codes
+
+
+def _conv2d_q(input, scale, qmap, weight_codes, bias, stride, padding, dilation, groups, out_scale, out_map, kind):
+    stride, padding, dilation = [int(v) for v in stride], [int(v) for v in padding], [int(v) for v in dilation]
+    why = _conv_q_decline(input, scale, qmap, weight_codes, bias, stride, padding, dilation, groups, out_scale, kind)
+    if why is None:
+        n, cin, h, w = input.shape
+        cout, kh, kw, _ = weight_codes.shape
+        ho, wo = _conv_out_hw(h, w, kh, kw, stride, padding, dilation)
+        dtype = input.dtype
+        codes = conv_codes_nhwc(input, scale, qmap)
+        if codes is None:
+            why = "qt_quantize_codes_nhwc declined"
+        else:
+            out = torch.empty((n, cout, ho, wo), dtype=dtype, device=input.device, memory_format=torch.channels_last)
+            s, per_col = _scale_arg(out_scale, cout, dtype)
+            s = _aligned16(s)
+            b = _aligned16(bias.to(dtype).contiguous()) if bias is not None else None
+            fold = int(out_map is not None and dtype == torch.float32)
+            rc = _native.lib().qt_q8_conv2d(codes.data_ptr(), weight_codes.data_ptr(), out.data_ptr(), int(dtype == torch.float32),
+                                            b.data_ptr() if b is not None else None, s.data_ptr(), per_col, fold, n, h, w, cin, cout,
+                                            kh, kw, stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1],
+                                            _stream_ptr(input))
+            if not _native.declined(rc):
+                _native.check(rc, "qt_q8_conv2d")
+                STATS["conv2d_int8"] += 1
+                return out
+            why = f"qt_q8_conv2d declined the shape (code {rc})"
+    if input.device.type == "cuda":
+        CONV_Q_REASONS[why] = CONV_Q_REASONS.get(why, 0) + 1
+    return _conv2d_q_unfused(input, scale, qmap, weight_codes, bias, stride, padding, dilation, groups, out_scale, out_map)
+
+
+def _conv2d_q_meta(input, scale, qmap, weight_codes, bias, stride, padding, dilation, groups, out_scale, out_map, kind):
+    ho, wo = _conv_out_hw(input.shape[2], input.shape[3], weight_codes.shape[1], weight_codes.shape[2], list(stride), list(padding),
+                          list(dilation))
+    return input.new_empty((input.shape[0], weight_codes.shape[0], ho, wo))
+
+
+_lib.impl("conv2d_q", _conv2d_q, "CompositeExplicitAutograd")
+_lib.impl("conv2d_q", _conv2d_q_meta, "Meta")
+
+
 def _is(node, target):
     return node is not None and getattr(node, "op", None) == "call_function" and node.target == target
 
@@ -175,10 +338,10 @@ def _per_tensor_quantize(node):
 
 
 def _sole_dequantize(model, node, dtype):
-    """The `dequantize(gemm, scale, None, None, None, input_qmap)` node behind a GEMM (quantize_pt2e.py:409-413: the GEMM
+    """The `dequantize(gemm, scale, None, None, None, input_qmap)` node behind a GEMM or convolution (quantize_pt2e.py:409-413: the GEMM
     output is first rounded to the accelerator's output format through `input_qmap`, then multiplied by s_x * s_w).  Fusable
     when that map is the identity for the model dtype (output_dtype None, or bfloat16 in a bf16 model).
-    Returns (dequantize node, scale node) or None."""
+    Returns (dequantize node, scale node, input map node or None) or None."""
     DQ = torch.ops.quantized_ops.dequantize.default
     users = list(node.users.keys())
     if len(users) != 1 or not _is(users[0], DQ):
@@ -199,7 +362,8 @@ def _sole_dequantize(model, node, dtype):
 
 def fuse_native_gemms(model: GraphModule) -> int:
     """Rewrites quantize -> aten.linear / aten.matmul -> dequantize triples whose operands are int8 (or FP8) codes into
-    linear_q / matmul_q nodes.  Returns the number of fused GEMMs; leaves everything else as it is."""
+    linear_q / matmul_q nodes, and quantize -> aten.conv2d -> dequantize triples on int8 codes (static geometry, Cin a multiple
+    of 32) into conv2d_q nodes.  Returns the number of fused GEMMs and convolutions; leaves everything else as it is."""
     graph = model.graph
     fused = 0
     for node in list(graph.nodes):
@@ -262,11 +426,73 @@ def fuse_native_gemms(model: GraphModule) -> int:
             graph.erase_node(dq)
             graph.erase_node(node)
             fused += 1
+        elif _is(node, torch.ops.aten.conv2d.default):
+            a = _conv_args(node)
+            if a is None:
+                continue
+            x_q, w, bias, stride, padding, dilation, groups = a
+            q = _per_tensor_quantize(x_q)
+            if q is None or getattr(w, "op", None) != "get_attr":
+                continue
+            if q[3].split(",")[0] != "int8" or str(w.meta.get("dtype", "")).split(",")[0] != "int8":
+                continue
+            param = model.get_parameter(w.target) if w.target in dict(model.named_parameters()) else model.get_buffer(w.target)
+            if param.dim() != 4 or param.shape[1] < 32 or param.shape[1] % 32:
+                continue                                     # Cin the kernel never takes (a stem): the node stays as it is
+            tail = _sole_dequantize(model, node, param.dtype)
+            if tail is None:
+                continue
+            dq, s_out, m_out = tail
+            codes = param.detach().to(torch.int8)
+            if not torch.equal(codes.to(param.dtype), param.detach()):
+                continue                                     # not exactly representable: keep the value-tensor convolution
+            name = str(w.target).replace(".", "_") + "_codes"
+            i = 0
+            while hasattr(model, name):
+                i += 1
+                name = f"{str(w.target).replace('.', '_')}_codes_{i}"
+            model.register_buffer(name, codes.permute(0, 2, 3, 1).contiguous(), persistent=False)       # [Cout, kh, kw, Cin]
+            if param.is_contiguous():
+                # a call the kernels decline convolves the values the graph stored: the parameter itself, not a third copy
+                getattr(model, name)._qt_conv_values = param.detach()
+            with graph.inserting_before(dq):
+                c_node = graph.create_node("get_attr", name)
+                new = graph.call_function(torch.ops.quantized_ops.conv2d_q.default,
+                                          (q[0], q[1], q[2], c_node, bias, stride, padding, dilation, groups, s_out, m_out, "int8"))
+            c_node.meta["dtype"] = w.meta.get("dtype")
+            new.meta = dict(dq.meta)
+            dq.replace_all_uses_with(new)
+            graph.erase_node(dq)
+            graph.erase_node(node)
+            fused += 1
     if fused:
         graph.eliminate_dead_code(is_impure_node=lambda n: n.op in {"placeholder", "output"})
         graph.lint()
         model.recompile()
     return fused
+
+
+def _conv_args(node):
+    """(input, weight, bias, stride, padding, dilation, groups) of an aten.conv2d node with the defaults filled in and the geometry as
+    two-element int lists; None when an argument is not static (a graph node, a string padding, a symbolic size)."""
+    names = ("input", "weight", "bias", "stride", "padding", "dilation", "groups")
+    vals = dict(zip(names, (None, None, None, 1, 0, 1, 1)))
+    if len(node.args) > len(names) or any(k not in names for k in node.kwargs):
+        return None
+    vals.update(zip(names, node.args))
+    vals.update(node.kwargs)
+    out = [vals["input"], vals["weight"], vals["bias"]]
+    for k in ("stride", "padding", "dilation"):
+        v = vals[k]
+        v = [v, v] if isinstance(v, int) and not isinstance(v, bool) else v
+        if not isinstance(v, (list, tuple)) or len(v) not in (1, 2) or any(not isinstance(e, int) or isinstance(e, bool) for e in v):
+            return None
+        out.append([int(e) for e in v] * (2 if len(v) == 1 else 1))
+    if not isinstance(vals["groups"], int) or isinstance(vals["groups"], bool):
+        return None
+    if vals["bias"] is not None and not isinstance(vals["bias"], torch.fx.Node):
+        return None
+    return (*out, vals["groups"])
 
 
 def _is_mx_consumer(node):
