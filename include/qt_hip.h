@@ -906,6 +906,23 @@ int qt_q8_conv2d(const int8_t *x_codes, const int8_t *w_codes, void *y, int y_is
                  int out_scale_per_col, int fold_f32, int N, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw, int ph, int pw,
                  int dh, int dw, void *stream);
 
+/* The depthwise convolution of such a graph (groups = Cin = Cout = C) with the same epilogue; no matrix work:
+ *     y[n, ho, wo, c] = round_y( round_y( float(sum_{r, s} x[n, hi, wi, c] w[c, r, s]) + bias[c] ) * out_scale )
+ * x_codes int8 NHWC [N][H][W][C]; w_codes int8 [C][kh][kw], the weight as stored (the kernel transposes a slab of it through LDS
+ * once per workgroup: no second copy in memory); y NHWC [N][Ho][Wo][C] bf16 or fp32; bias [C] (nullable) and out_scale (nullable;
+ * one element, or C with out_scale_per_col) in y's dtype; fold_f32 as in qt_q8_gemm.  Zero padding: a tap outside the plane adds
+ * nothing and loads nothing (no tap reads the next row's pixel or the next image's).  kh kw <= 1023 keeps every partial sum below
+ * 2^24 in magnitude: the int32 accumulator is exact and float() rounds nothing.
+ * QT_ERR_BAD_ARG: a NULL operand or output; C < 16 or C % 16 != 0 (a thread's unit is one 16-byte run of channels, the rule of
+ * qt_quantize_codes_nhwc_*); kh kw > 1023; a non-positive extent, stride or dilation, a negative padding; N Ho Wo or the byte size
+ * of either code array >= 2^31, kh dh, kw dw, strides or paddings >= 2^20.  QT_ERR_UNALIGNED: any pointer off a 16-byte boundary.
+ * All answered before the first HIP call; an empty output (N == 0, no output pixel) is QT_OK without a launch.  Every element of y
+ * is written and nothing else; no atomics, no allocation, no synchronisation: the same bits on every launch, safe under stream
+ * capture. */
+int qt_q8_dwconv2d(const int8_t *x_codes, const int8_t *w_codes, void *y, int y_is_f32, const void *bias, const void *out_scale,
+                   int out_scale_per_col, int fold_f32, int N, int H, int W, int C, int kh, int kw, int sh, int sw, int ph, int pw,
+                   int dh, int dw, void *stream);
+
 /* The activation operand of qt_q8_conv2d in one pass: codes[n][p][c] = narrow(map[index(x[n, c, p] / scale)]), the arithmetic of
  * qt_quantize_* (the same device function) with a per-tensor scale in the tensor's dtype and no zero point, narrowed to int8.
  * x is the [N][HW][C] view of a 4-D tensor given by element strides (batch, row, channel): NCHW-contiguous (C HW, 1, HW) -- a

@@ -71,17 +71,22 @@ struct Mma {
 
 // (acc + bias) rounded to the output dtype, then -- converted per-tensor graphs, quantize_pt2e.py:323-446: the
 // dequantize(s_x * s_w) node behind the GEMM -- multiplied by the dequantize factor and rounded again.
-__device__ __forceinline__ void emit_out(const MxGemmArgs &a, float accv, float bv, float sv, long idx) {
+// out_bits is the one definition of that chain: the fp32 image (out_f32) or the bf16 bits of the element; emit_out stores it.
+__device__ __forceinline__ uint32_t out_bits(const MxGemmArgs &a, float accv, float bv, float sv) {
     float v = accv + bv;
     if (a.out_f32) {
         if (a.out_fold_f32) v = qt_u2f(qt_fold_img(qt_f2u(v)));
         if (a.out_scale) v = v * sv;
-        ((float *)a.C)[idx] = v;
-    } else {
-        uint16_t b = qt_f2bf(v);
-        if (a.out_scale) b = qt_f2bf(qt_bf2f(b) * sv);
-        ((uint16_t *)a.C)[idx] = b;
+        return qt_f2u(v);
     }
+    uint16_t b = qt_f2bf(v);
+    if (a.out_scale) b = qt_f2bf(qt_bf2f(b) * sv);
+    return b;
+}
+__device__ __forceinline__ void emit_out(const MxGemmArgs &a, float accv, float bv, float sv, long idx) {
+    const uint32_t b = out_bits(a, accv, bv, sv);
+    if (a.out_f32) ((uint32_t *)a.C)[idx] = b;
+    else ((uint16_t *)a.C)[idx] = (uint16_t)b;
 }
 __device__ __forceinline__ float out_scale_of(const MxGemmArgs &a, int col) {
     if (!a.out_scale) return 1.0f;
@@ -1366,6 +1371,160 @@ int launch_conv(const MxGemmArgs &g, const MxConvGeom &c, unsigned grid, hipStre
     return qt_launch_status();
 }
 
+// ---- depthwise conv2d on int8 codes (qt_q8_dwconv2d) ---------------------------------------------------------
+// No matrix work: y[n, ho, wo, c] sums kh kw products of channel c alone.  A thread's unit is one 16-byte run of channels
+// (one global_load_dwordx4 of NHWC codes per tap) of P consecutive output pixels; its 16 P sums stay in int32 registers
+// (kh kw <= 1023: |sum| < 2^24, exact).  A workgroup owns a slab of up to 256 channels (a.N = C, c.cpb = C / 16 runs) and
+// 256 / runs strips of pixels.  The weight arrives as stored, [C][kh kw] bytes: the slab's bytes of 16 taps at a time are
+// sign-extended and transposed through LDS into [tap][quad of the run][run][4] int32 -- the 16 runs of a tap's quad fill one
+// 256-byte bank row, so the ds_read_b128 of a wave (lanes of one run read one address) is conflict-free -- and every tap
+// costs a thread four LDS reads for all its P pixels, one v_bfe_i32 and one v_mad_i32_i24 per product.
+// A tap outside the plane loads nothing and adds nothing (the row and column tests are per pixel and per tap: no tap
+// wraps into the next row or image); threads past the slab or past M run the loops (barriers) with no load and no store.
+// The kernel is paced by its chain of dependent memory round trips (weight staging, the groups of taps, bias and factors,
+// the stores: about 9 us for any workgroup, times the generations of workgroups), not by bytes or instructions: the codes of
+// four taps are requested together and the next group before the current group's products are formed (against one tap in
+// flight, MobileNetV2's layers at batch 32: 6 - 14 % less time where the kernel takes 14 us or more, 5 - 13 % more below).
+constexpr int kDwSlab = 256, kDwRuns = kDwSlab / 16, kDwTaps = 16;
+
+template <int P>
+__global__ __launch_bounds__(256) void q8_dwconv_kernel(MxGemmArgs a, MxConvGeom c) {
+    __shared__ __attribute__((aligned(16))) int wl[kDwTaps * kDwSlab];
+    const int C = a.N, taps = c.kh * c.kw;
+    const int nslab = (C + kDwSlab - 1) / kDwSlab;
+    const int slab = blockIdx.x % nslab, pb = blockIdx.x / nslab;
+    const int c0 = slab * kDwSlab, cs = min(kDwSlab, C - c0);
+    const int runs = min(c.cpb, kDwRuns);                  // of a full slab: the thread map is the same in the ragged last slab
+    const int spb = 256 / runs;
+    const int t = threadIdx.x, cg = t % runs, st = t / runs;
+    const bool mine = cg * 16 < cs && st < spb;
+    const long m0 = ((long)pb * spb + st) * P;
+    const int8_t *x = (const int8_t *)a.A + c0 + cg * 16;
+
+    int hi0[P], wi0[P];
+    uint32_t img[P];                                       // pixel index of the image's first pixel
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+        const bool live = mine && m0 + p < a.M;
+        const int mm = live ? (int)(m0 + p) : 0;
+        const int n = mm / (c.Ho * c.Wo), rem = mm - n * (c.Ho * c.Wo), ho = rem / c.Wo, wo = rem - ho * c.Wo;
+        hi0[p] = live ? ho * c.sh - c.ph : -(1 << 28);     // no tap (r dh < 2^20) brings a dead pixel back into the plane
+        wi0[p] = wo * c.sw - c.pw;
+        img[p] = (uint32_t)n * (uint32_t)(c.H * c.W);
+    }
+    // the codes of D consecutive taps from `first` on, for the P pixels: 4 P loads of 16 bytes requested together; (r, s) is the
+    // tap `first` on entry and the tap behind the group on exit
+    constexpr int D = 4;
+    static_assert(kDwTaps % D == 0, "a group of taps never straddles two staging rounds");
+    auto load_group = [&](int first, int &r, int &s, v4i (&v)[D][P]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+#pragma unroll
+            for (int p = 0; p < P; ++p) {
+                const int hi = hi0[p] + r * c.dh, wi = wi0[p] + s * c.dw;
+                v[d][p] = v4i{0, 0, 0, 0};
+                if (first + d < taps && (unsigned)hi < (unsigned)c.H && (unsigned)wi < (unsigned)c.W)
+                    v[d][p] = *(const v4i *)(x + (size_t)(img[p] + (uint32_t)hi * (uint32_t)c.W + (uint32_t)wi) * (size_t)C);
+            }
+            if (++s == c.kw) { s = 0; ++r; }
+        }
+    };
+
+    int acc[P][16];
+#pragma unroll
+    for (int p = 0; p < P; ++p)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[p][i] = 0;
+    int r = 0, s = 0;                                      // the tap whose codes are requested next
+    v4i xn[D][P], xc[D][P];
+    load_group(0, r, s, xn);
+    for (int t0 = 0; t0 < taps; t0 += kDwTaps) {
+        const int nt = min(kDwTaps, taps - t0);
+        if (t0) __syncthreads();
+        for (int e = t; e < cs * nt; e += 256) {           // consecutive threads: consecutive bytes of a channel's taps
+            const int ch = e / nt, j = e - ch * nt;
+            wl[((j * 4 + ((ch >> 2) & 3)) * kDwRuns + (ch >> 4)) * 4 + (ch & 3)] = ((const int8_t *)a.B)[(long)(c0 + ch) * taps + t0 + j];
+        }
+        __syncthreads();
+        for (int j0 = 0; j0 < nt; j0 += D) {               // j0 + D <= kDwTaps
+#pragma unroll
+            for (int d = 0; d < D; ++d)
+#pragma unroll
+                for (int p = 0; p < P; ++p) xc[d][p] = xn[d][p];
+            if (t0 + j0 + D < taps) load_group(t0 + j0 + D, r, s, xn);
+#pragma unroll
+            for (int d = 0; d < D; ++d) {
+                if (j0 + d >= nt) break;                   // wave-uniform: the tail of the last group
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const v4i wq = *(const v4i *)&wl[(((j0 + d) * 4 + q) * kDwRuns + cg) * 4];
+#pragma unroll
+                    for (int p = 0; p < P; ++p) {
+                        const uint32_t v = (uint32_t)xc[d][p][q];
+                        acc[p][4 * q + 0] += __mul24((int)(v << 24) >> 24, wq[0]);
+                        acc[p][4 * q + 1] += __mul24((int)(v << 16) >> 24, wq[1]);
+                        acc[p][4 * q + 2] += __mul24((int)(v << 8) >> 24, wq[2]);
+                        acc[p][4 * q + 3] += __mul24((int)v >> 24, wq[3]);
+                    }
+                }
+            }
+        }
+    }
+    if (!mine) return;
+
+    // epilogue: bias and factors of the run in 16-byte loads, the rounding chain of out_bits, the run's 32 or 64 bytes in 16-byte stores
+    const int col = c0 + cg * 16;
+    auto run16 = [&](const void *src, float (&out)[16]) __attribute__((always_inline)) {
+        if (a.out_f32) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const v4f v = ((const v4f *)((const float *)src + col))[q];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) out[4 * q + k] = v[k];
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const v4i v = ((const v4i *)((const uint16_t *)src + col))[q];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    out[8 * q + 2 * k] = bf_lo((uint32_t)v[k]);
+                    out[8 * q + 2 * k + 1] = bf_hi((uint32_t)v[k]);
+                }
+            }
+        }
+    };
+    float bv[16], sv[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) bv[i] = 0.f;
+    if (a.bias) run16(a.bias, bv);
+    if (a.out_scale && a.out_scale_per_col) run16(a.out_scale, sv);
+    else {
+        const float one = out_scale_of(a, 0);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) sv[i] = one;
+    }
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+        if (m0 + p >= a.M) continue;
+        uint32_t o[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) o[i] = out_bits(a, (float)acc[p][i], bv[i], sv[i]);
+        const long idx = (m0 + p) * (long)C + col;
+        if (a.out_f32) {
+            u32x4 *dst = (u32x4 *)((float *)a.C + idx);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) dst[q] = u32x4{o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]};
+        } else {
+            u32x4 *dst = (u32x4 *)((uint16_t *)a.C + idx);
+#pragma unroll
+            for (int q = 0; q < 2; ++q)
+                dst[q] = u32x4{o[8 * q] | (o[8 * q + 1] << 16), o[8 * q + 2] | (o[8 * q + 3] << 16), o[8 * q + 4] | (o[8 * q + 5] << 16),
+                               o[8 * q + 6] | (o[8 * q + 7] << 16)};
+        }
+    }
+}
+
 // ---- packing: (values, block scales) -> element codes + E8M0 ------------------------------------------------
 // A value that the format holds exactly converts exactly; anything else (and a scale that is not a power of
 // two) raises the `bad` flag so the caller can fall back to the dequantize + GEMM path.
@@ -1838,6 +1997,38 @@ int qt_q8_conv2d(const int8_t *x_codes, const int8_t *w_codes, void *y, int y_is
     const long tiles = ((m + kBM - 1) / kBM) * ((Cout + kBN - 1) / kBN);
     if (tiles >= kLim) return QT_ERR_BAD_ARG;
     return launch_conv<0, 0, true>(g, c, (unsigned)tiles, (hipStream_t)stream);
+}
+
+int qt_q8_dwconv2d(const int8_t *x_codes, const int8_t *w_codes, void *y, int y_is_f32, const void *bias, const void *out_scale,
+                   int out_scale_per_col, int fold_f32, int N, int H, int W, int C, int kh, int kw, int sh, int sw, int ph, int pw,
+                   int dh, int dw, void *stream) {
+    if (!x_codes || !w_codes || !y) return QT_ERR_BAD_ARG;
+    // a thread's unit is one 16-byte run of channels (the rule of qt_quantize_codes_nhwc_*)
+    if (N < 0 || H < 1 || W < 1 || C < 16 || C % 16 != 0 || C > (1 << 24)) return QT_ERR_BAD_ARG;
+    if (kh < 1 || kw < 1 || sh < 1 || sw < 1 || dh < 1 || dw < 1 || ph < 0 || pw < 0) return QT_ERR_BAD_ARG;
+    constexpr long kLim = 1L << 31;
+    auto mul = [](long a, long b) { return a >= kLim || b >= kLim ? kLim : (a * b >= kLim ? kLim : a * b); };
+    const long taps = mul(kh, kw);
+    // kh kw <= 1023: every partial sum has magnitude <= 1023 * 128 * 128 < 2^24, exact in int32 and in its conversion to fp32
+    if (taps > 1023) return QT_ERR_BAD_ARG;
+    const long eh = (long)H + 2L * ph - (long)dh * (kh - 1) - 1, ew = (long)W + 2L * pw - (long)dw * (kw - 1) - 1;
+    if (N == 0 || eh < 0 || ew < 0) return QT_OK;                                               // empty output: nothing to launch
+    if ((((uintptr_t)x_codes | (uintptr_t)w_codes | (uintptr_t)y | (uintptr_t)bias | (uintptr_t)out_scale) & 15u)) return QT_ERR_UNALIGNED;
+    // the index limits of qt_q8_conv2d: 32-bit pixel indices, 32-bit byte offsets into the code arrays
+    const long ho = eh / sh + 1, wo = ew / sw + 1, m = mul(N, mul(ho, wo));
+    if (m >= kLim || mul(N, mul(mul(H, W), C)) >= kLim || mul(C, taps) >= kLim || (long)kh * dh >= (1 << 20) || (long)kw * dw >= (1 << 20) ||
+        ph >= (1 << 20) || pw >= (1 << 20) || sh >= (1 << 20) || sw >= (1 << 20))
+        return QT_ERR_BAD_ARG;
+    const uint8_t *A = (const uint8_t *)x_codes, *B = (const uint8_t *)w_codes;
+    MxGemmArgs g{A, B, nullptr, nullptr, y, bias, (int)m, C, (int)taps, 0, 0, 0, 0, 0, y_is_f32, out_scale, out_scale_per_col, fold_f32};
+    const MxConvGeom c{H, W, kh, kw, sh, sw, ph, pw, dh, dw, (int)ho, (int)wo, C / 16};
+    // two pixels per thread (half the LDS weight reads per product) once that still leaves two waves per SIMD of the chip
+    const long runs = C / 16, spb = 256 / (runs < kDwRuns ? runs : kDwRuns), nslab = (C + kDwSlab - 1) / kDwSlab;
+    const int P = m * runs >= 2L * 64 * 2048 ? 2 : 1;
+    const long blocks = mul(((m + P - 1) / P + spb - 1) / spb, nslab);
+    if (blocks >= kLim) return QT_ERR_BAD_ARG;
+    qt_pick<1, 2>(P, [&](auto PP) { q8_dwconv_kernel<decltype(PP)::value><<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(g, c); });
+    return qt_launch_status();
 }
 
 int qt_mxi_pack(const void *x_dev, const void *scale_dev, int is_f32, const void *code_dev, int n_code, int8_t *codes_dev, float *scales_dev,

@@ -239,6 +239,7 @@ SIGNATURES = {
     "qt_spmm_csr_f32": (c_int, [_P, _P, _P, c_long, c_long, _P, c_long, c_long, c_int, _P, c_long, c_long, c_int, c_int, _P, c_int, _P, _P]),
     "qt_q8_gemm": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, c_int, c_long, c_int, c_int, c_int, c_long, c_long, _P]),
     "qt_q8_conv2d": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, c_int] + [c_int] * 13 + [_P]),
+    "qt_q8_dwconv2d": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, c_int] + [c_int] * 12 + [_P]),
     "qt_quantize_codes_nhwc_bf16": (c_int, [_P, _P] + [c_long] * 6 + [_FMT, _P, _P, _P]),
     "qt_quantize_codes_nhwc_f32": (c_int, [_P, _P] + [c_long] * 6 + [_FMT, _P, _P, _P]),
     "qt_bench_fake_quant_bf16": (c_int, [_P, _P, c_size_t, _FMT, _P, _P, _P, c_int, c_size_t, c_int, _P,

@@ -17,7 +17,8 @@ cores:
     scales (`qt_mx_gemm`; the library GEMM `qt_fp8_gemm` only where that kernel does not take the shape), then the dequantize kernel;
   * int8 convolutions (`quantize -> aten.conv2d -> dequantize`, the ImageNet recipe): one `conv2d_q` node -- the activation to int8
     NHWC codes in one pass (`qt_quantize_codes_nhwc_*`), then `qt_q8_conv2d`, an implicit GEMM on the same instruction with the same
-    epilogue, into a channels_last result.
+    epilogue, into a channels_last result.  Depthwise layers (groups = Cin = Cout, a multiple of 16) run `qt_q8_dwconv2d` on the same
+    codes; 1 x 1, stride 1, unpadded layers over Cin = 16 mod 32 (which the gather kernel declines) run `qt_q8_gemm` on them.
 
 The graph `convert_pt2e` returns is untouched on the CPU (it is pinned node for node to upstream's); fusion is a separate,
 idempotent pass that convert_pt2e applies to device models (`native=None` -> automatic, `QT_PT2E_NATIVE=0` turns it off).
@@ -37,7 +38,7 @@ from .fake_quantize import _stream_ptr
 
 __all__ = ["fuse_native_gemms", "fuse_mx_pairs", "fuse_gwa_linears", "STATS", "GWA_STATS"]
 
-STATS = {"linear_int8": 0, "matmul_int8": 0, "linear_fp8": 0, "matmul_fp8": 0, "conv2d_int8": 0}
+STATS = {"linear_int8": 0, "matmul_int8": 0, "linear_fp8": 0, "matmul_fp8": 0, "conv2d_int8": 0, "conv2d_dw_int8": 0}
 _IDENTITY_DTYPES = (None, "None", "bfloat16", "float32", "float16")
 _FP8 = {"fp8_e4m3": torch.float8_e4m3fn, "fp8_e5m2": torch.float8_e5m2}
 
@@ -192,6 +193,47 @@ def _conv_q_route_takes(m, cout, cin, kh, kw):
     return cout >= cin and tiles >= 208
 
 
+_DW_PROFILE = "profiles/conv2d_q_depthwise.txt"
+_CONV_Q_DW_MAX_TAPS = 1023
+
+
+def _conv_q_dw_route_takes(m, c, kh, kw, sh, sw):
+    """The committed rule for depthwise calls (groups = Cin = Cout = c), a fixed function of the shape (never a timing): m = N Ho Wo
+    output pixels, the filter, the strides.  From profiles/conv2d_q_depthwise.txt (MobileNetV2's ten depthwise shapes at batch 32, a
+    5 x 5 layer over 240 channels, two batch-4 problems; bf16; the method and the bar of profiles/conv2d_q.txt): all thirteen rows
+    clear the bar -- replayed 1.5 - 3.8 x from NCHW input and 2.7 - 5.2 x from channels_last at batch 32, 1.10 x / 1.85 x on the
+    smallest problem (4 x 576 x 14 x 14: 20.6 -> 18.7 us against a spread of 0.1).  The class is what was measured: filters of at most
+    25 taps, strides of at most 2, at least as many output elements as that smallest problem.  Anything else (a 7 x 7 filter, stride
+    3, a smaller problem) was not measured and stays with the graph."""
+    return kh * kw <= 25 and max(sh, sw) <= 2 and m * c >= _DW_MIN_OUTPUTS
+
+
+_DW_MIN_OUTPUTS = 4 * 14 * 14 * 576
+_PW16_MIN_PIXELS, _PW16_MAX_CIN = 32 * 28 * 28, 144
+
+
+def _conv_q_pw16_route_takes(m, cout, cin):
+    """The committed rule for 1 x 1, stride 1, unpadded calls over Cin = 16 mod 32 channels (codes pass + qt_q8_gemm), a fixed function
+    of the shape.  From the three pointwise rows of profiles/conv2d_q_depthwise.txt (16 -> 96 at 112 x 112, 144 -> 24 at 56 x 56,
+    144 -> 32 at 28 x 28, batch 32): all clear the bar, replayed 1.14 - 1.45 x from NCHW input and 1.50 - 3.2 x from channels_last.  The
+    class is what was measured: at least 32 x 28 x 28 output pixels and Cin of at most 144; a longer contraction over fewer pixels
+    is the shape on which the gather kernel's reducing 1 x 1 layers lose, and stays with the graph."""
+    return m >= _PW16_MIN_PIXELS and cin <= _PW16_MAX_CIN
+
+
+def _conv_q_route(input, weight_codes, stride, padding, groups):
+    """Which kernel a 4-D call would run on: "depthwise" (qt_q8_dwconv2d: groups = Cin = Cout, one filter per channel), "pointwise"
+    (qt_q8_gemm: a 1 x 1, stride 1, unpadded convolution over NHWC codes is the GEMM [N H W][Cin] x [Cout][Cin]^T, taken there for the
+    Cin = 16 mod 32 that the gather kernel declines), "gather" (qt_q8_conv2d), or None for any other grouped call."""
+    cin = input.shape[1]
+    cout, kh, kw, wcin = weight_codes.shape
+    if groups != 1:
+        return "depthwise" if groups == cin == cout and wcin == 1 else None
+    if kh == kw == 1 and list(stride) == [1, 1] and list(padding) == [0, 0] and wcin == cin and cin >= 16 and cin % 32 == 16:
+        return "pointwise"
+    return "gather"
+
+
 def _conv_out_hw(h, w, kh, kw, stride, padding, dilation):
     ho = (h + 2 * padding[0] - dilation[0] * (kh - 1) - 1) // stride[0] + 1 if stride[0] > 0 else 0
     wo = (w + 2 * padding[1] - dilation[1] * (kw - 1) - 1) // stride[1] + 1 if stride[1] > 0 else 0
@@ -209,14 +251,21 @@ def _conv_q_decline(input, scale, qmap, weight_codes, bias, stride, padding, dil
         return f"model dtype {input.dtype}"
     if input.dim() != 4 or weight_codes.dim() != 4 or input.numel() == 0 or weight_codes.numel() == 0:
         return f"input {tuple(input.shape)}, weight codes {tuple(weight_codes.shape)}"
-    if groups != 1:
+    route = _conv_q_route(input, weight_codes, stride, padding, groups)
+    if route is None:
         return f"groups {groups}"
     n, cin, h, w = input.shape
     cout, kh, kw, wcin = weight_codes.shape
-    if wcin != cin or cin < 32 or cin % 32:
-        return f"Cin = {cin} / {wcin}: not a multiple of 32"
-    if kh * kw * cin >= _CONV_Q_MAX_K:
-        return f"kh kw Cin = {kh * kw * cin} >= 2^17: the int32 sum could wrap"
+    if route == "depthwise":
+        if cin < 16 or cin % 16:
+            return f"depthwise C = {cin}: not a multiple of 16"
+        if kh * kw > _CONV_Q_DW_MAX_TAPS:
+            return f"depthwise kh kw = {kh * kw} > 1023"
+    else:
+        if route == "gather" and (wcin != cin or cin < 32 or cin % 32):
+            return f"Cin = {cin} / {wcin}: not a multiple of 32"
+        if kh * kw * cin >= _CONV_Q_MAX_K:
+            return f"kh kw Cin = {kh * kw * cin} >= 2^17: the int32 sum could wrap"
     if qmap.dtype != torch.bfloat16 or qmap.numel() != 65536:
         return f"value map of {qmap.numel()} {qmap.dtype} entries"
     if scale.numel() != 1 or scale.dtype != input.dtype:
@@ -231,8 +280,13 @@ def _conv_q_decline(input, scale, qmap, weight_codes, bias, stride, padding, dil
     if input.data_ptr() % 16 or weight_codes.data_ptr() % 16 or not weight_codes.is_contiguous() or qmap.data_ptr() % 2 \
             or not qmap.is_contiguous():
         return "misaligned operand"
-    if _APPLY_CONV_Q_RULE and not _conv_q_route_takes(n * ho * wo, cout, cin, kh, kw):
-        return "route rule: profiles/conv2d_q.txt"
+    if _APPLY_CONV_Q_RULE:
+        if route == "depthwise" and not _conv_q_dw_route_takes(n * ho * wo, cin, kh, kw, stride[0], stride[1]):
+            return f"depthwise route rule: {_DW_PROFILE}"
+        if route == "pointwise" and not _conv_q_pw16_route_takes(n * ho * wo, cout, cin):
+            return f"pointwise route rule: {_DW_PROFILE}"
+        if route == "gather" and not _conv_q_route_takes(n * ho * wo, cout, cin, kh, kw):
+            return "route rule: profiles/conv2d_q.txt"
     return None
 
 
@@ -298,15 +352,22 @@ def _conv2d_q(input, scale, qmap, weight_codes, bias, stride, padding, dilation,
             s = _aligned16(s)
             b = _aligned16(bias.to(dtype).contiguous()) if bias is not None else None
             fold = int(out_map is not None and dtype == torch.float32)
-            rc = _native.lib().qt_q8_conv2d(codes.data_ptr(), weight_codes.data_ptr(), out.data_ptr(), int(dtype == torch.float32),
-                                            b.data_ptr() if b is not None else None, s.data_ptr(), per_col, fold, n, h, w, cin, cout,
-                                            kh, kw, stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1],
-                                            _stream_ptr(input))
+            route = _conv_q_route(input, weight_codes, stride, padding, groups)
+            L = _native.lib()
+            head = (codes.data_ptr(), weight_codes.data_ptr(), out.data_ptr(), int(dtype == torch.float32),
+                    b.data_ptr() if b is not None else None, s.data_ptr(), per_col, fold)
+            geometry = (kh, kw, stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1], _stream_ptr(input))
+            if route == "depthwise":                     # weight_codes [C, kh, kw, 1] is the kernel's [C][kh][kw] as stored
+                entry, key, rc = "qt_q8_dwconv2d", "conv2d_dw_int8", L.qt_q8_dwconv2d(*head, n, h, w, cin, *geometry)
+            elif route == "pointwise":                   # the channels_last result is the row-major [N Ho Wo][Cout] of the GEMM
+                entry, key, rc = "qt_q8_gemm", "conv2d_int8", L.qt_q8_gemm(*head, 1, n * h * w, cout, cin, 0, 0, _stream_ptr(input))
+            else:
+                entry, key, rc = "qt_q8_conv2d", "conv2d_int8", L.qt_q8_conv2d(*head, n, h, w, cin, cout, *geometry)
             if not _native.declined(rc):
-                _native.check(rc, "qt_q8_conv2d")
-                STATS["conv2d_int8"] += 1
+                _native.check(rc, entry)
+                STATS[key] += 1
                 return out
-            why = f"qt_q8_conv2d declined the shape (code {rc})"
+            why = f"{entry} declined the shape (code {rc})"
     if input.device.type == "cuda":
         CONV_Q_REASONS[why] = CONV_Q_REASONS.get(why, 0) + 1
     return _conv2d_q_unfused(input, scale, qmap, weight_codes, bias, stride, padding, dilation, groups, out_scale, out_map)
@@ -362,8 +423,8 @@ def _sole_dequantize(model, node, dtype):
 
 def fuse_native_gemms(model: GraphModule) -> int:
     """Rewrites quantize -> aten.linear / aten.matmul -> dequantize triples whose operands are int8 (or FP8) codes into
-    linear_q / matmul_q nodes, and quantize -> aten.conv2d -> dequantize triples on int8 codes (static geometry, Cin a multiple
-    of 32) into conv2d_q nodes.  Returns the number of fused GEMMs and convolutions; leaves everything else as it is."""
+    linear_q / matmul_q nodes, and quantize -> aten.conv2d -> dequantize triples on int8 codes (static geometry; Cin a multiple
+    of 32, or depthwise over a multiple of 16 channels, or 1 x 1 / stride 1 / unpadded over Cin = 16 mod 32) into conv2d_q nodes.  Returns the number of fused GEMMs and convolutions; leaves everything else as it is."""
     graph = model.graph
     fused = 0
     for node in list(graph.nodes):
@@ -437,8 +498,15 @@ def fuse_native_gemms(model: GraphModule) -> int:
             if q[3].split(",")[0] != "int8" or str(w.meta.get("dtype", "")).split(",")[0] != "int8":
                 continue
             param = model.get_parameter(w.target) if w.target in dict(model.named_parameters()) else model.get_buffer(w.target)
-            if param.dim() != 4 or param.shape[1] < 32 or param.shape[1] % 32:
-                continue                                     # Cin the kernel never takes (a stem): the node stays as it is
+            if param.dim() != 4:
+                continue
+            cout_w, cin_w, kh_w, kw_w = param.shape
+            gather = cin_w >= 32 and cin_w % 32 == 0
+            depthwise = groups > 1 and groups == cout_w and cin_w == 1 and groups % 16 == 0
+            pointwise = (groups == 1 and kh_w == kw_w == 1 and stride == [1, 1] and padding == [0, 0] and cin_w >= 16
+                         and cin_w % 32 == 16)
+            if not (gather or depthwise or pointwise):
+                continue                                     # channels no kernel ever takes (a stem, Cin = 24, any other grouping): the node stays
             tail = _sole_dequantize(model, node, param.dtype)
             if tail is None:
                 continue
