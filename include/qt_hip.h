@@ -923,6 +923,29 @@ int qt_q8_dwconv2d(const int8_t *x_codes, const int8_t *w_codes, void *y, int y_
                    int out_scale_per_col, int fold_f32, int N, int H, int W, int C, int kh, int kw, int sh, int sw, int ph, int pw,
                    int dh, int dw, void *stream);
 
+/* Codes out: qt_q8_conv2d, qt_q8_dwconv2d and qt_q8_gemm whose epilogue writes the NEXT convolution's activation operand -- the int8
+ * NHWC codes qt_quantize_codes_nhwc_* would make of the result -- instead of the value tensor.  Per element, with b the bits the
+ * sibling would store (the same rounding chain, fold_f32 included) and v their value in the model dtype (y_is_f32 names it):
+ *     act == 1:  v = v is NaN ? v : min(max(v, act_lo), act_hi), rounded to the model dtype  (relu: act_lo = 0, act_hi = +inf)
+ *     y[row][col] = narrow(next_qmap[index(v / next_scale)])      the arithmetic of qt_quantize_codes_nhwc_* (the same device function)
+ * y int8 [N Ho Wo][Cout] (qt_q8_gemm_codes: [batch][M][N]); next_scale one element in the model dtype; next_qmap 65 536 bf16 entries.
+ * The leading arguments and their checks are the sibling's.  On top of them QT_ERR_BAD_ARG: Cout (C, N) % 16 != 0 (codes leave the
+ * chip in whole 16-byte runs of a code row, staged through LDS in the two matrix kernels), a NULL map or scale, act outside {0, 1},
+ * act == 1 with act_lo > act_hi or a NaN bound; QT_ERR_UNALIGNED: y off a 16-byte boundary, the map off a 2-byte one, the scale off
+ * its element size.  An empty problem is QT_OK without a launch.  Every code of y is written and nothing else; no atomics, no
+ * allocation, no synchronisation: the same bytes on every launch, safe under stream capture.  qt_q8_gemm_codes runs the
+ * register-staged kernel for every K (the variant a Cin = 16 mod 32 pointwise layer reaches). */
+int qt_q8_conv2d_codes(const int8_t *x_codes, const int8_t *w_codes, int8_t *y, int y_is_f32, const void *bias, const void *out_scale,
+                       int out_scale_per_col, int fold_f32, int N, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw, int ph,
+                       int pw, int dh, int dw, int act, float act_lo, float act_hi, const void *next_scale, const uint16_t *next_qmap,
+                       void *stream);
+int qt_q8_dwconv2d_codes(const int8_t *x_codes, const int8_t *w_codes, int8_t *y, int y_is_f32, const void *bias, const void *out_scale,
+                         int out_scale_per_col, int fold_f32, int N, int H, int W, int C, int kh, int kw, int sh, int sw, int ph, int pw,
+                         int dh, int dw, int act, float act_lo, float act_hi, const void *next_scale, const uint16_t *next_qmap, void *stream);
+int qt_q8_gemm_codes(const int8_t *a_codes, const int8_t *b_codes, int8_t *y, int y_is_f32, const void *bias_dev, const void *out_scale_dev,
+                     int out_scale_per_col, int fold_f32, long batch, int M, int N, int K, long a_batch_stride_rows, long b_batch_stride_rows,
+                     int act, float act_lo, float act_hi, const void *next_scale, const uint16_t *next_qmap, void *stream);
+
 /* The activation operand of qt_q8_conv2d in one pass: codes[n][p][c] = narrow(map[index(x[n, c, p] / scale)]), the arithmetic of
  * qt_quantize_* (the same device function) with a per-tensor scale in the tensor's dtype and no zero point, narrowed to int8.
  * x is the [N][HW][C] view of a 4-D tensor given by element strides (batch, row, channel): NCHW-contiguous (C HW, 1, HW) -- a

@@ -19,6 +19,7 @@
 #include "qt_device.h"
 #include "qt_chain.h"
 #include "qt_dispatch.h"
+#include "qt_qdq.h"
 
 extern "C" float qt_internal_posit_threshold(int nbits, int es);
 extern "C" int qt_internal_fp8_emin(float fp8_min);
@@ -1246,43 +1247,7 @@ __global__ void scale_update_multi_kernel(float *const *__restrict__ hist, const
 }
 
 // ---- generic quantize / dequantize (decomposed.py:166-262); tables read from global memory ------
-struct QdqArgs {
-    const uint16_t *in_lut;    // applied first (dequantize's input_qmap) or NULL
-    const uint16_t *out_lut;   // applied last (quantize's qmap / dequantize's output_qmap) or NULL
-    qt_format out_fmt;         // closed form for out_lut when kind != LUT and out_lut == NULL
-    int use_out;               // 1 = apply out rounding
-    int mode;                  // 0 = x / s [+ zp], 1 = (x [- zp]) * s
-};
-
-// one element of quantize / dequantize: value `v` is kept in the tensor dtype after every op (bf16 ops round to bf16)
-template <int IO>
-__device__ __forceinline__ float qdq_value(float v, const QdqArgs &a, float s, float z, bool has_zp) {
-    auto round_io = [](float f) -> float {
-        if constexpr (IO == kIoBf16) return qt_u2f(pack_bf16x2(f, 0.0f) << 16);
-        else return f;
-    };
-    auto lookup = [&](const uint16_t *t, float f) -> float {
-        uint32_t img = (IO == kIoBf16) ? qt_f2u(f) : qt_fold_img(qt_f2u(f));
-        return qt_bf2f(t[img >> 16]);
-    };
-    if (a.in_lut) v = lookup(a.in_lut, v);
-    if (a.mode == 0) {
-        v = round_io(v / s);
-        if (has_zp) v = round_io(v + z);
-    } else {
-        if (has_zp) v = round_io(v - z);
-        v = round_io(v * s);
-    }
-    if (a.use_out) {
-        if (a.out_lut) v = lookup(a.out_lut, v);
-        else {
-            uint32_t img = (IO == kIoBf16) ? qt_f2u(v) : qt_fold_img(qt_f2u(v));
-            v = qt_u2f(qt_apply_format_img(a.out_fmt, img));
-        }
-    }
-    return v;
-}
-
+// QdqArgs and qdq_value, one element of quantize / dequantize: qt_qdq.h
 template <int IO>
 __global__ __launch_bounds__(256) void qdq_kernel(const void *__restrict__ xv, void *__restrict__ yv, size_t n, QdqArgs a,
                                                  const void *__restrict__ scale, const void *__restrict__ zp) {
@@ -1305,14 +1270,7 @@ __global__ __launch_bounds__(256) void qdq_kernel(const void *__restrict__ xv, v
 }
 
 // ---- quantize -> int8 NHWC codes (qt_quantize_codes_nhwc_*): the activation operand of qt_q8_conv2d in one pass ----------------
-// code = narrow(qdq_value(x)) with the quantize arguments (mode 0, no zero point, the map from global memory): the value the
-// quantize kernel above would store, narrowed as torch's .to(int8) narrows an integer in [-128, 127].  Anything else a map could
-// hold: truncated toward zero, saturated to [-128, 127], NaN -> 0.
-__device__ __forceinline__ uint32_t code_of(float v) {
-    if (v != v) return 0u;
-    v = fminf(fmaxf(v, -128.0f), 127.0f);
-    return (uint32_t)(int)v & 0xFFu;
-}
+// code = code_of(qdq_value(x)) with the quantize arguments (mode 0, no zero point, the map from global memory): qt_qdq.h
 
 constexpr int kCodeTP = 64, kCodeTC = 64;            // pixels x channels of one transposition tile
 constexpr int kCodeRow = kCodeTC + 4;                // LDS bytes per pixel row: 17 words, odd, so 64 pixels of one channel hit 64 words mod 32 evenly

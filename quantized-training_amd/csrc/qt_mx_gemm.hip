@@ -22,6 +22,7 @@
 #include "qt_dispatch.h"
 #include "qt_formats.h"
 #include "qt_mx.h"
+#include "qt_qdq.h"
 
 namespace {
 
@@ -94,6 +95,77 @@ __device__ __forceinline__ float out_scale_of(const MxGemmArgs &a, int col) {
     return a.out_f32 ? ((const float *)a.out_scale)[i] : qt_bf2f(((const uint16_t *)a.out_scale)[i]);
 }
 
+// ---- codes out (qt_q8_*_codes): the epilogue writes the NEXT convolution's int8 NHWC codes instead of the value tensor -------------
+// Replaces, between two conv2d_q nodes of a converted per-tensor int8 graph (quantize_pt2e.py:323-446),
+//     y = dequantize(conv)  ->  aten.relu / aten.hardtanh / aten.clamp(y)  ->  quantize(., s_next, qmap_next) narrowed to int8
+// i.e. the value tensor written, read and written by the activation, and read again by qt_quantize_codes_nhwc_*.  An element's
+// tail: b = out_bits(...) as the value kernels compute it; v = its value in the model dtype; the clamp (NaN stays NaN, as torch's
+// clamp leaves it; the result is a value of the model dtype, or a bound rounded to it); code_of(qdq_value(v)) with exactly the
+// arguments qt_quantize_codes_nhwc_* builds (mode 0, no zero point, the 65 536-entry map read from global memory): qt_qdq.h.
+// The tail is a kernel parameter of the CODES instantiations only: the other instantiations take NoTail, which has no field.
+struct CodesTail {
+    const uint16_t *qmap;        // the consumer's value map
+    const void *scale;           // the consumer's activation scale, one element in the model dtype
+    int act;                     // 1: clamp to [lo, hi] in front of the quantize (relu: lo = 0, hi = +inf)
+    float lo, hi;
+};
+struct NoTail {};
+template <bool CODES>
+using tail_t = std::conditional_t<CODES, CodesTail, NoTail>;
+
+__device__ __forceinline__ float next_scale_of(const MxGemmArgs &a, const CodesTail &ct) {
+    return a.out_f32 ? *(const float *)ct.scale : qt_bf2f(*(const uint16_t *)ct.scale);
+}
+__device__ __forceinline__ uint32_t out_code(const MxGemmArgs &a, const CodesTail &ct, float ns, float accv, float bv, float sv) {
+    const uint32_t b = out_bits(a, accv, bv, sv);
+    float v = a.out_f32 ? qt_u2f(b) : qt_u2f(b << 16);
+    if (ct.act) v = (v != v) ? v : fminf(fmaxf(v, ct.lo), ct.hi);
+    const QdqArgs q{nullptr, ct.qmap, {QT_FMT_LUT, 0, 0, 0.f, 0.f}, 1, 0};
+    if (a.out_f32) return code_of(qdq_value<kIoF32>(v, q, ns, 0.0f, false));
+    return code_of(qdq_value<kIoBf16>(bf16_round(v), q, ns, 0.0f, false));
+}
+
+// The CODES epilogue of the two MFMA kernels.  A lane holds column l & 15 of rows 4 g + e of each 16 x 16 block: its bytes go into
+// the workgroup's 128 x 128 byte tile in LDS -- the operand tiles' space, free behind the barrier that follows the last compute --
+// and every thread then writes four whole 16-byte runs of a code row; rows >= M and runs >= N (N % 16 == 0) are skipped, so no
+// byte outside y is written and no 1-byte store reaches memory.  The row pitch of 144 bytes (36 words) puts the two rows that a
+// 32-lane half of ds_write_b8 touches (4 g + e for two g: 144 words apart) on banks 0-3 and 16-19.
+constexpr int kCodePitch = kBN + 16;
+template <typename ACC>
+__device__ __forceinline__ void emit_codes_tile(const MxGemmArgs &a, const CodesTail &ct, uint8_t *lds, const ACC (&acc)[4][4], int m0,
+                                                int n0, long cbase) {
+    const int t = threadIdx.x, l = t & 63, w = t >> 6;
+    const int r = l & 15, g = l >> 4;
+    const int wm = w >> 1, wn = w & 1;
+    const float ns = next_scale_of(a, ct);
+    __syncthreads();                                      // every wave has read its last fragments
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int lc = wn * 64 + j * 16 + r, col = n0 + lc;
+        if (col >= a.N) continue;
+        float bv = 0.f;
+        if (a.bias) bv = a.out_f32 ? ((const float *)a.bias)[col] : qt_bf2f(((const uint16_t *)a.bias)[col]);
+        const float sv = out_scale_of(a, col);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int lr = wm * 64 + i * 16 + 4 * g + e;
+                if (m0 + lr >= a.M) continue;
+                lds[lr * kCodePitch + lc] = (uint8_t)out_code(a, ct, ns, (float)acc[i][j][e], bv, sv);
+            }
+        }
+    }
+    __syncthreads();
+    int8_t *y = (int8_t *)a.C + cbase;
+#pragma unroll
+    for (int k = 0; k < kBM * (kBN / 16) / 256; ++k) {
+        const int q = t + 256 * k, lr = q / (kBN / 16), run = q % (kBN / 16);
+        if (m0 + lr >= a.M || n0 + run * 16 >= a.N) continue;
+        *(uint4 *)(y + (long)(m0 + lr) * a.N + n0 + run * 16) = *(const uint4 *)(lds + lr * kCodePitch + run * 16);
+    }
+}
+
 // LDS image of a 128-row operand tile.  8- and 4-bit tiles are unpadded with the 16-byte chunk index XOR-swizzled by
 // the row so that the four 16-lane groups of ds_read_b128 ({0-3,12-15,20-27}, ... : sixteen different rows, half of
 // them one chunk further along k) each touch sixteen different 16-byte slots of the 256-byte bank row; 6-bit tiles
@@ -140,8 +212,8 @@ __device__ __forceinline__ v8i read_frag(const uint8_t *tile, int row, int g) {
     return f;
 }
 
-template <int FA, int FB, bool I8 = false>
-__global__ __launch_bounds__(256) void mx_gemm_kernel(MxGemmArgs a) {
+template <int FA, int FB, bool I8 = false, bool CODES = false>
+__global__ __launch_bounds__(256) void mx_gemm_kernel(MxGemmArgs a, tail_t<CODES> ct = {}) {
     using M_ = Mma<FA, FB, I8>;
     using TA = Tile<FA>;
     using TB = Tile<FB>;
@@ -277,6 +349,10 @@ __global__ __launch_bounds__(256) void mx_gemm_kernel(MxGemmArgs a) {
 
     // epilogue: D col = l & 15, row = 4 g + e
     const long cbase = bz * a.bC;
+    if constexpr (CODES) {
+        emit_codes_tile(a, ct, lds, acc, m0, n0, cbase);
+        return;
+    }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int col = n0 + wn * 64 + j * 16 + r;
@@ -1174,8 +1250,8 @@ __device__ __forceinline__ void conv_tap_of(int v, int per, int ts0, int tr0, in
 
 // I8 (qt_q8_conv2d): int8 codes on both sides, int32 accumulators, no scale bytes -- every scale load below is compiled out --
 // and the dequantize factor of emit_out in the epilogue.
-template <int FA, int FB, bool I8 = false>
-__global__ __launch_bounds__(256) void mx_conv_kernel(MxGemmArgs a, MxConvGeom c) {
+template <int FA, int FB, bool I8 = false, bool CODES = false>
+__global__ __launch_bounds__(256) void mx_conv_kernel(MxGemmArgs a, MxConvGeom c, tail_t<CODES> ct = {}) {
     using M_ = Mma<FA, FB, I8>;
     using TA = Tile<FA>;
     using TB = Tile<FB>;
@@ -1343,6 +1419,10 @@ __global__ __launch_bounds__(256) void mx_conv_kernel(MxGemmArgs a, MxConvGeom c
     compute((nk - 1) & 1);
 
     // epilogue: D col = l & 15, row = 4 g + e; y is [M][Cout] = NHWC
+    if constexpr (CODES) {
+        emit_codes_tile(a, ct, lds, acc, m0, n0, 0L);
+        return;
+    }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int col = n0 + wn * 64 + j * 16 + r;
@@ -1363,11 +1443,12 @@ __global__ __launch_bounds__(256) void mx_conv_kernel(MxGemmArgs a, MxConvGeom c
     }
 }
 
-template <int FA, int FB, bool I8 = false>
-int launch_conv(const MxGemmArgs &g, const MxConvGeom &c, unsigned grid, hipStream_t st) {
+template <int FA, int FB, bool I8 = false, bool CODES = false>
+int launch_conv(const MxGemmArgs &g, const MxConvGeom &c, unsigned grid, hipStream_t st, const tail_t<CODES> &ct = {}) {
     constexpr int kLds = 2 * Tile<FA>::kBytes + 2 * Tile<FB>::kBytes;
-    if (const int rc = qt_allow_lds<mx_conv_kernel<FA, FB, I8>>(kLds)) return rc;
-    mx_conv_kernel<FA, FB, I8><<<grid, 256, kLds, st>>>(g, c);
+    static_assert(!CODES || kBM * kCodePitch <= kLds, "the code tile is staged in the operand tiles' space");
+    if (const int rc = qt_allow_lds<mx_conv_kernel<FA, FB, I8, CODES>>(kLds)) return rc;
+    mx_conv_kernel<FA, FB, I8, CODES><<<grid, 256, kLds, st>>>(g, c, ct);
     return qt_launch_status();
 }
 
@@ -1387,8 +1468,8 @@ int launch_conv(const MxGemmArgs &g, const MxConvGeom &c, unsigned grid, hipStre
 // flight, MobileNetV2's layers at batch 32: 6 - 14 % less time where the kernel takes 14 us or more, 5 - 13 % more below).
 constexpr int kDwSlab = 256, kDwRuns = kDwSlab / 16, kDwTaps = 16;
 
-template <int P>
-__global__ __launch_bounds__(256) void q8_dwconv_kernel(MxGemmArgs a, MxConvGeom c) {
+template <int P, bool CODES = false>
+__global__ __launch_bounds__(256) void q8_dwconv_kernel(MxGemmArgs a, MxConvGeom c, tail_t<CODES> ct = {}) {
     __shared__ __attribute__((aligned(16))) int wl[kDwTaps * kDwSlab];
     const int C = a.N, taps = c.kh * c.kw;
     const int nslab = (C + kDwSlab - 1) / kDwSlab;
@@ -1507,6 +1588,14 @@ __global__ __launch_bounds__(256) void q8_dwconv_kernel(MxGemmArgs a, MxConvGeom
 #pragma unroll
     for (int p = 0; p < P; ++p) {
         if (m0 + p >= a.M) continue;
+        if constexpr (CODES) {                             // the run's 16 codes of this pixel: one 16-byte store
+            const float ns = next_scale_of(a, ct);
+            uint32_t k[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int i = 0; i < 16; ++i) k[i >> 2] |= out_code(a, ct, ns, (float)acc[p][i], bv[i], sv[i]) << (8 * (i & 3));
+            *(u32x4 *)((int8_t *)a.C + (m0 + p) * (long)C + col) = u32x4{k[0], k[1], k[2], k[3]};
+            continue;
+        }
         uint32_t o[16];
 #pragma unroll
         for (int i = 0; i < 16; ++i) o[i] = out_bits(a, (float)acc[p][i], bv[i], sv[i]);
@@ -1936,10 +2025,23 @@ int qt_conv2d_mx(const uint8_t *x_codes, const uint8_t *x_e8m0, int x_format, co
     return rc;
 }
 
-int qt_q8_gemm(const int8_t *a_codes, const int8_t *b_codes, void *c_dev, int c_is_f32, const void *bias_dev, const void *out_scale_dev,
-               int out_scale_per_col, int fold_f32, long batch, int M, int N, int K, long a_batch_stride_rows, long b_batch_stride_rows, void *stream) {
+// What a *_codes entry point checks on top of its sibling: whole 16-byte runs of codes, the consumer's map and scale, the clamp.
+static int codes_tail_check(const CodesTail &ct, int cout, const void *y, int y_is_f32) {
+    if (cout % 16 != 0 || !ct.qmap || !ct.scale || (ct.act != 0 && ct.act != 1)) return QT_ERR_BAD_ARG;
+    if (ct.act == 1 && !(ct.lo <= ct.hi)) return QT_ERR_BAD_ARG;                               // false for a NaN bound too
+    if (((uintptr_t)ct.qmap & 1u) || ((uintptr_t)ct.scale & (y_is_f32 ? 3u : 1u)) || ((uintptr_t)y & 15u)) return QT_ERR_UNALIGNED;
+    return QT_OK;
+}
+
+// ct == NULL: the value tensor (qt_q8_gemm); otherwise the consumer's codes (qt_q8_gemm_codes), on the register-staged kernel for any K
+static int q8_gemm_launch(const int8_t *a_codes, const int8_t *b_codes, void *c_dev, int c_is_f32, const void *bias_dev, const void *out_scale_dev,
+                          int out_scale_per_col, int fold_f32, long batch, int M, int N, int K, long a_batch_stride_rows, long b_batch_stride_rows,
+                          void *stream, const CodesTail *ct) {
     if (batch * M * N == 0) return QT_OK;
     if (!a_codes || !b_codes || !c_dev || batch < 0 || batch > 65535 || M < 0 || N < 0 || K < 16 || K % 16) return QT_ERR_BAD_ARG;
+    if (ct) {
+        if (const int rc = codes_tail_check(*ct, N, c_dev, c_is_f32)) return rc;
+    }
     if (((uintptr_t)a_codes | (uintptr_t)b_codes) & 15u) return QT_ERR_UNALIGNED;
     const uint8_t *A = (const uint8_t *)a_codes, *B = (const uint8_t *)b_codes;
     // the scale-byte pointers of the block-scaled kernels are never used by the int8 instruction; the code buffers stand in
@@ -1949,6 +2051,13 @@ int qt_q8_gemm(const int8_t *a_codes, const int8_t *b_codes, void *c_dev, int c_
                  out_scale_per_col, fold_f32};
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(((N + kBN - 1) / kBN) * ((M + kBM - 1) / kBM), (unsigned)batch);
+    if (ct) {
+        constexpr int kLds = 4 * Tile<0>::kBytes;
+        static_assert(kBM * kCodePitch <= kLds, "the code tile is staged in the operand tiles' space");
+        if (const int rc = qt_allow_lds<mx_gemm_kernel<0, 0, true, true>>(kLds)) return rc;
+        mx_gemm_kernel<0, 0, true, true><<<grid, 256, kLds, st>>>(g, *ct);
+        return qt_launch_status();
+    }
     const bool dma_ok = K % kBK == 0;
     const long big_tiles = (long)((M + 255) / 256) * ((N + 255) / 256);
     if (dma_ok && M >= 512 && N >= 512 && big_tiles >= 192) {
@@ -1970,10 +2079,27 @@ int qt_q8_gemm(const int8_t *a_codes, const int8_t *b_codes, void *c_dev, int c_
     return qt_launch_status();
 }
 
-int qt_q8_conv2d(const int8_t *x_codes, const int8_t *w_codes, void *y, int y_is_f32, const void *bias, const void *out_scale,
-                 int out_scale_per_col, int fold_f32, int N, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw, int ph, int pw,
-                 int dh, int dw, void *stream) {
+int qt_q8_gemm(const int8_t *a_codes, const int8_t *b_codes, void *c_dev, int c_is_f32, const void *bias_dev, const void *out_scale_dev,
+               int out_scale_per_col, int fold_f32, long batch, int M, int N, int K, long a_batch_stride_rows, long b_batch_stride_rows, void *stream) {
+    return q8_gemm_launch(a_codes, b_codes, c_dev, c_is_f32, bias_dev, out_scale_dev, out_scale_per_col, fold_f32, batch, M, N, K,
+                          a_batch_stride_rows, b_batch_stride_rows, stream, nullptr);
+}
+
+int qt_q8_gemm_codes(const int8_t *a_codes, const int8_t *b_codes, int8_t *y, int y_is_f32, const void *bias_dev, const void *out_scale_dev,
+                     int out_scale_per_col, int fold_f32, long batch, int M, int N, int K, long a_batch_stride_rows, long b_batch_stride_rows,
+                     int act, float act_lo, float act_hi, const void *next_scale, const uint16_t *next_qmap, void *stream) {
+    const CodesTail ct{next_qmap, next_scale, act, act_lo, act_hi};
+    return q8_gemm_launch(a_codes, b_codes, y, y_is_f32, bias_dev, out_scale_dev, out_scale_per_col, fold_f32, batch, M, N, K,
+                          a_batch_stride_rows, b_batch_stride_rows, stream, &ct);
+}
+
+static int q8_conv2d_launch(const int8_t *x_codes, const int8_t *w_codes, void *y, int y_is_f32, const void *bias, const void *out_scale,
+                            int out_scale_per_col, int fold_f32, int N, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw, int ph,
+                            int pw, int dh, int dw, void *stream, const CodesTail *ct) {
     if (!x_codes || !w_codes || !y) return QT_ERR_BAD_ARG;
+    if (ct) {
+        if (const int rc = codes_tail_check(*ct, Cout < 0 ? 0 : Cout, y, y_is_f32)) return rc;
+    }
     // Cin % 32: a 16-byte chunk never straddles a tap and a 128-byte k tile spans at most four taps beyond its first (conv_tap_of)
     if (N < 0 || H < 1 || W < 1 || Cout < 0 || Cin < 32 || Cin % 32 != 0 || Cin > (1 << 24)) return QT_ERR_BAD_ARG;
     if (kh < 1 || kw < 1 || sh < 1 || sw < 1 || dh < 1 || dw < 1 || ph < 0 || pw < 0) return QT_ERR_BAD_ARG;
@@ -1996,13 +2122,33 @@ int qt_q8_conv2d(const int8_t *x_codes, const int8_t *w_codes, void *y, int y_is
     const MxConvGeom c{H, W, kh, kw, sh, sw, ph, pw, dh, dw, (int)ho, (int)wo, Cin / 32};
     const long tiles = ((m + kBM - 1) / kBM) * ((Cout + kBN - 1) / kBN);
     if (tiles >= kLim) return QT_ERR_BAD_ARG;
+    if (ct) return launch_conv<0, 0, true, true>(g, c, (unsigned)tiles, (hipStream_t)stream, *ct);
     return launch_conv<0, 0, true>(g, c, (unsigned)tiles, (hipStream_t)stream);
 }
 
-int qt_q8_dwconv2d(const int8_t *x_codes, const int8_t *w_codes, void *y, int y_is_f32, const void *bias, const void *out_scale,
-                   int out_scale_per_col, int fold_f32, int N, int H, int W, int C, int kh, int kw, int sh, int sw, int ph, int pw,
-                   int dh, int dw, void *stream) {
+int qt_q8_conv2d(const int8_t *x_codes, const int8_t *w_codes, void *y, int y_is_f32, const void *bias, const void *out_scale,
+                 int out_scale_per_col, int fold_f32, int N, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw, int ph, int pw,
+                 int dh, int dw, void *stream) {
+    return q8_conv2d_launch(x_codes, w_codes, y, y_is_f32, bias, out_scale, out_scale_per_col, fold_f32, N, H, W, Cin, Cout, kh, kw, sh, sw,
+                            ph, pw, dh, dw, stream, nullptr);
+}
+
+int qt_q8_conv2d_codes(const int8_t *x_codes, const int8_t *w_codes, int8_t *y, int y_is_f32, const void *bias, const void *out_scale,
+                       int out_scale_per_col, int fold_f32, int N, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw, int ph,
+                       int pw, int dh, int dw, int act, float act_lo, float act_hi, const void *next_scale, const uint16_t *next_qmap,
+                       void *stream) {
+    const CodesTail ct{next_qmap, next_scale, act, act_lo, act_hi};
+    return q8_conv2d_launch(x_codes, w_codes, y, y_is_f32, bias, out_scale, out_scale_per_col, fold_f32, N, H, W, Cin, Cout, kh, kw, sh, sw,
+                            ph, pw, dh, dw, stream, &ct);
+}
+
+static int q8_dwconv2d_launch(const int8_t *x_codes, const int8_t *w_codes, void *y, int y_is_f32, const void *bias, const void *out_scale,
+                              int out_scale_per_col, int fold_f32, int N, int H, int W, int C, int kh, int kw, int sh, int sw, int ph, int pw,
+                              int dh, int dw, void *stream, const CodesTail *ct) {
     if (!x_codes || !w_codes || !y) return QT_ERR_BAD_ARG;
+    if (ct) {
+        if (const int rc = codes_tail_check(*ct, C < 0 ? 0 : C, y, y_is_f32)) return rc;
+    }
     // a thread's unit is one 16-byte run of channels (the rule of qt_quantize_codes_nhwc_*)
     if (N < 0 || H < 1 || W < 1 || C < 16 || C % 16 != 0 || C > (1 << 24)) return QT_ERR_BAD_ARG;
     if (kh < 1 || kw < 1 || sh < 1 || sw < 1 || dh < 1 || dw < 1 || ph < 0 || pw < 0) return QT_ERR_BAD_ARG;
@@ -2027,8 +2173,24 @@ int qt_q8_dwconv2d(const int8_t *x_codes, const int8_t *w_codes, void *y, int y_
     const int P = m * runs >= 2L * 64 * 2048 ? 2 : 1;
     const long blocks = mul(((m + P - 1) / P + spb - 1) / spb, nslab);
     if (blocks >= kLim) return QT_ERR_BAD_ARG;
-    qt_pick<1, 2>(P, [&](auto PP) { q8_dwconv_kernel<decltype(PP)::value><<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(g, c); });
+    if (ct) qt_pick<1, 2>(P, [&](auto PP) { q8_dwconv_kernel<decltype(PP)::value, true><<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(g, c, *ct); });
+    else qt_pick<1, 2>(P, [&](auto PP) { q8_dwconv_kernel<decltype(PP)::value><<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(g, c); });
     return qt_launch_status();
+}
+
+int qt_q8_dwconv2d(const int8_t *x_codes, const int8_t *w_codes, void *y, int y_is_f32, const void *bias, const void *out_scale,
+                   int out_scale_per_col, int fold_f32, int N, int H, int W, int C, int kh, int kw, int sh, int sw, int ph, int pw,
+                   int dh, int dw, void *stream) {
+    return q8_dwconv2d_launch(x_codes, w_codes, y, y_is_f32, bias, out_scale, out_scale_per_col, fold_f32, N, H, W, C, kh, kw, sh, sw, ph, pw,
+                              dh, dw, stream, nullptr);
+}
+
+int qt_q8_dwconv2d_codes(const int8_t *x_codes, const int8_t *w_codes, int8_t *y, int y_is_f32, const void *bias, const void *out_scale,
+                         int out_scale_per_col, int fold_f32, int N, int H, int W, int C, int kh, int kw, int sh, int sw, int ph, int pw,
+                         int dh, int dw, int act, float act_lo, float act_hi, const void *next_scale, const uint16_t *next_qmap, void *stream) {
+    const CodesTail ct{next_qmap, next_scale, act, act_lo, act_hi};
+    return q8_dwconv2d_launch(x_codes, w_codes, y, y_is_f32, bias, out_scale, out_scale_per_col, fold_f32, N, H, W, C, kh, kw, sh, sw, ph, pw,
+                              dh, dw, stream, &ct);
 }
 
 int qt_mxi_pack(const void *x_dev, const void *scale_dev, int is_f32, const void *code_dev, int n_code, int8_t *codes_dev, float *scales_dev,

@@ -240,6 +240,10 @@ SIGNATURES = {
     "qt_q8_gemm": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, c_int, c_long, c_int, c_int, c_int, c_long, c_long, _P]),
     "qt_q8_conv2d": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, c_int] + [c_int] * 13 + [_P]),
     "qt_q8_dwconv2d": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, c_int] + [c_int] * 12 + [_P]),
+    "qt_q8_gemm_codes": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, c_int, c_long, c_int, c_int, c_int, c_long, c_long,
+                                 c_int, c_float, c_float, _P, _P, _P]),
+    "qt_q8_conv2d_codes": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, c_int] + [c_int] * 13 + [c_int, c_float, c_float, _P, _P, _P]),
+    "qt_q8_dwconv2d_codes": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, c_int] + [c_int] * 12 + [c_int, c_float, c_float, _P, _P, _P]),
     "qt_quantize_codes_nhwc_bf16": (c_int, [_P, _P] + [c_long] * 6 + [_FMT, _P, _P, _P]),
     "qt_quantize_codes_nhwc_f32": (c_int, [_P, _P] + [c_long] * 6 + [_FMT, _P, _P, _P]),
     "qt_bench_fake_quant_bf16": (c_int, [_P, _P, c_size_t, _FMT, _P, _P, _P, c_int, c_size_t, c_int, _P,

@@ -20,6 +20,10 @@ cores:
     epilogue, into a channels_last result.  Depthwise layers (groups = Cin = Cout, a multiple of 16) run `qt_q8_dwconv2d` on the same
     codes; 1 x 1, stride 1, unpadded layers over Cin = 16 mod 32 (which the gather kernel declines) run `qt_q8_gemm` on them.
 
+`fuse_conv_q_chains` (opt-in: `convert_pt2e(chain_convs=True)`) then hands int8 codes from one such convolution to the next:
+`conv2d_q -> aten.relu / hardtanh / clamp -> conv2d_q` becomes two `conv2d_qc` nodes, the first writing the second's codes from its
+epilogue (`qt_q8_*_codes`), the activation node gone, the second running no codes pass; bit-identical to the nodes it replaces.
+
 The graph `convert_pt2e` returns is untouched on the CPU (it is pinned node for node to upstream's); fusion is a separate,
 idempotent pass that convert_pt2e applies to device models (`native=None` -> automatic, `QT_PT2E_NATIVE=0` turns it off).
 Accumulation is exact (int32) where upstream's fp32 / bf16 `aten.linear` rounds, so results agree within the accumulation
@@ -36,9 +40,11 @@ from torch.fx import GraphModule
 from . import _native, mx_operand, switches
 from .fake_quantize import _stream_ptr
 
-__all__ = ["fuse_native_gemms", "fuse_mx_pairs", "fuse_gwa_linears", "STATS", "GWA_STATS"]
+__all__ = ["fuse_native_gemms", "fuse_conv_q_chains", "fuse_mx_pairs", "fuse_gwa_linears", "STATS", "GWA_STATS"]
 
-STATS = {"linear_int8": 0, "matmul_int8": 0, "linear_fp8": 0, "matmul_fp8": 0, "conv2d_int8": 0, "conv2d_dw_int8": 0}
+# conv2d_codes_in / conv2d_codes_out: native conv2d_qc launches that took / wrote a code array (counted in their kernel's key as well)
+STATS = {"linear_int8": 0, "matmul_int8": 0, "linear_fp8": 0, "matmul_fp8": 0, "conv2d_int8": 0, "conv2d_dw_int8": 0,
+         "conv2d_codes_in": 0, "conv2d_codes_out": 0}
 _IDENTITY_DTYPES = (None, "None", "bfloat16", "float32", "float16")
 _FP8 = {"fp8_e4m3": torch.float8_e4m3fn, "fp8_e5m2": torch.float8_e5m2}
 
@@ -335,39 +341,74 @@ def conv_codes_nhwc(input, scale, qmap):
     return codes
 
 
+class _Operand:
+    """What _conv_q_route and _conv_q_decline read of an operand, for one that is not there as a value tensor: the activation of a
+    call that receives codes (their geometry under the model dtype), the scale and map such a call no longer has, a graph node known
+    by its shape alone.  Dense and aligned unless `ptr` says otherwise."""
+
+    def __init__(self, shape, dtype, device, ptr=0):
+        self.shape, self.dtype, self.device, self._ptr = torch.Size(shape), dtype, torch.device(device), ptr
+
+    def dim(self):
+        return len(self.shape)
+
+    def numel(self):
+        return self.shape.numel()
+
+    def data_ptr(self):
+        return self._ptr
+
+    def is_contiguous(self):
+        return True
+
+
+def _conv_q_launch(codes, shape, dtype, weight_codes, bias, stride, padding, dilation, groups, out_scale, out_map, tail=None):
+    """One native launch on the NHWC codes [N H W, Cin] of an activation of logical `shape`, on the kernel _conv_q_route names.
+    tail None: the value tensor [N, Cout, Ho, Wo] in `dtype`, channels_last (qt_q8_dwconv2d / qt_q8_gemm / qt_q8_conv2d).
+    tail (act, lo, hi, next_scale, next_qmap): the consumer's int8 codes in the same layout (the *_codes siblings).
+    -> (result, None), or (None, why) when the entry point declines the shape."""
+    n, cin, h, w = shape
+    cout, kh, kw, _ = weight_codes.shape
+    ho, wo = _conv_out_hw(h, w, kh, kw, stride, padding, dilation)
+    out = torch.empty((n, cout, ho, wo), dtype=dtype if tail is None else torch.int8, device=codes.device, memory_format=torch.channels_last)
+    s, per_col = _scale_arg(out_scale, cout, dtype)
+    s = _aligned16(s)
+    b = _aligned16(bias.to(dtype).contiguous()) if bias is not None else None
+    fold = int(out_map is not None and dtype == torch.float32)
+    route = _conv_q_route(_Operand(shape, dtype, codes.device), weight_codes, stride, padding, groups)
+    L = _native.lib()
+    stream = _stream_ptr(codes)
+    head = (codes.data_ptr(), weight_codes.data_ptr(), out.data_ptr(), int(dtype == torch.float32),
+            b.data_ptr() if b is not None else None, s.data_ptr(), per_col, fold)
+    geometry = (kh, kw, stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1])
+    last, sfx = (stream,), ""
+    if tail is not None:
+        act, lo, hi, next_scale, next_qmap = tail
+        last, sfx = (int(act), float(lo), float(hi), next_scale.data_ptr(), next_qmap.data_ptr(), stream), "_codes"
+    if route == "depthwise":                     # weight_codes [C, kh, kw, 1] is the kernel's [C][kh][kw] as stored
+        entry, key, rc = "qt_q8_dwconv2d" + sfx, "conv2d_dw_int8", getattr(L, "qt_q8_dwconv2d" + sfx)(*head, n, h, w, cin, *geometry, *last)
+    elif route == "pointwise":                   # the channels_last result is the row-major [N Ho Wo][Cout] of the GEMM
+        entry, key, rc = "qt_q8_gemm" + sfx, "conv2d_int8", getattr(L, "qt_q8_gemm" + sfx)(*head, 1, n * h * w, cout, cin, 0, 0, *last)
+    else:
+        entry, key, rc = "qt_q8_conv2d" + sfx, "conv2d_int8", getattr(L, "qt_q8_conv2d" + sfx)(*head, n, h, w, cin, cout, *geometry, *last)
+    if _native.declined(rc):
+        return None, f"{entry} declined the shape (code {rc})"
+    _native.check(rc, entry)
+    STATS[key] += 1
+    return out, None
+
+
 def _conv2d_q(input, scale, qmap, weight_codes, bias, stride, padding, dilation, groups, out_scale, out_map, kind):
     stride, padding, dilation = [int(v) for v in stride], [int(v) for v in padding], [int(v) for v in dilation]
     why = _conv_q_decline(input, scale, qmap, weight_codes, bias, stride, padding, dilation, groups, out_scale, kind)
     if why is None:
-        n, cin, h, w = input.shape
-        cout, kh, kw, _ = weight_codes.shape
-        ho, wo = _conv_out_hw(h, w, kh, kw, stride, padding, dilation)
-        dtype = input.dtype
         codes = conv_codes_nhwc(input, scale, qmap)
         if codes is None:
             why = "qt_quantize_codes_nhwc declined"
         else:
-            out = torch.empty((n, cout, ho, wo), dtype=dtype, device=input.device, memory_format=torch.channels_last)
-            s, per_col = _scale_arg(out_scale, cout, dtype)
-            s = _aligned16(s)
-            b = _aligned16(bias.to(dtype).contiguous()) if bias is not None else None
-            fold = int(out_map is not None and dtype == torch.float32)
-            route = _conv_q_route(input, weight_codes, stride, padding, groups)
-            L = _native.lib()
-            head = (codes.data_ptr(), weight_codes.data_ptr(), out.data_ptr(), int(dtype == torch.float32),
-                    b.data_ptr() if b is not None else None, s.data_ptr(), per_col, fold)
-            geometry = (kh, kw, stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1], _stream_ptr(input))
-            if route == "depthwise":                     # weight_codes [C, kh, kw, 1] is the kernel's [C][kh][kw] as stored
-                entry, key, rc = "qt_q8_dwconv2d", "conv2d_dw_int8", L.qt_q8_dwconv2d(*head, n, h, w, cin, *geometry)
-            elif route == "pointwise":                   # the channels_last result is the row-major [N Ho Wo][Cout] of the GEMM
-                entry, key, rc = "qt_q8_gemm", "conv2d_int8", L.qt_q8_gemm(*head, 1, n * h * w, cout, cin, 0, 0, _stream_ptr(input))
-            else:
-                entry, key, rc = "qt_q8_conv2d", "conv2d_int8", L.qt_q8_conv2d(*head, n, h, w, cin, cout, *geometry)
-            if not _native.declined(rc):
-                _native.check(rc, entry)
-                STATS[key] += 1
+            out, why = _conv_q_launch(codes, input.shape, input.dtype, weight_codes, bias, stride, padding, dilation, groups, out_scale, out_map)
+            if why is None:
                 return out
-            why = f"{entry} declined the shape (code {rc})"
     if input.device.type == "cuda":
         CONV_Q_REASONS[why] = CONV_Q_REASONS.get(why, 0) + 1
     return _conv2d_q_unfused(input, scale, qmap, weight_codes, bias, stride, padding, dilation, groups, out_scale, out_map)
@@ -381,6 +422,134 @@ def _conv2d_q_meta(input, scale, qmap, weight_codes, bias, stride, padding, dila
 
 _lib.impl("conv2d_q", _conv2d_q, "CompositeExplicitAutograd")
 _lib.impl("conv2d_q", _conv2d_q_meta, "Meta")
+
+
+# ---- chained converted convolutions: codes in, codes out ------------------------------------------------------------------------
+# Between two conv2d_q nodes the converted graph runs
+#     y = conv2d_q(...)                       the kernel rounds its int32 sum to the model dtype and writes it
+#     a = aten.relu / hardtanh / clamp(y)     read and written again
+#     conv2d_q(a, s_next, qmap_next, ...)     whose codes pass reads it a third time to write 1 B per element
+# fuse_conv_q_chains makes the producer a conv2d_qc that writes s_next / qmap_next codes from its epilogue (qt_q8_*_codes: the
+# activation and the consumer's quantize applied to the element in its register), erases the activation node, and makes each
+# consumer a conv2d_qc that takes the code array as its input (scale = qmap = None: no codes pass).  conv2d_qc is conv2d_q plus
+#     scale, qmap None      `input` is int8 [N, C, H, W] codes, channels_last; the model dtype is out_scale's
+#     next_scale, next_qmap the result is the int8 [N, Cout, Ho, Wo] codes quantize(act(y), next_scale, next_qmap), channels_last
+#     act_min, act_max      the clamp in front of that quantize (relu: 0, None); only with codes out
+# Eligibility is conv2d_q's (_conv_q_decline and the committed route rules, measured with the codes pass inside the call: a call
+# that receives codes is only cheaper); every decline runs the value-tensor nodes and gives the same bits.
+_lib.define("conv2d_qc(Tensor input, Tensor? scale, Tensor? qmap, Tensor weight_codes, Tensor? bias, int[2] stride, int[2] padding, "
+            "int[2] dilation, int groups, Tensor out_scale, Tensor? out_map, str kind, float? act_min, float? act_max, "
+            "Tensor? next_scale, Tensor? next_qmap) -> Tensor")
+
+
+def _narrow_codes(v):
+    """Values of a quantize node -> int8 by the rule of the device's code_of: NaN -> 0, saturate to [-128, 127], truncate."""
+    return torch.nan_to_num(v.float(), nan=0.0, posinf=127.0, neginf=-128.0).clamp(-128.0, 127.0).to(torch.int8)
+
+
+def _codes_of_values(y, act_min, act_max, next_scale, next_qmap):
+    """The graph's own tail on a value tensor: the activation, then the consumer's quantize as int8 [N, C, H, W], channels_last."""
+    if act_min is not None or act_max is not None:
+        y = torch.clamp(y, min=act_min, max=act_max)
+    n, c, h, w = y.shape
+    codes = None
+    if y.device.type == "cuda" and y.dtype in (torch.bfloat16, torch.float32) and c % 16 == 0 and y.numel() and next_scale.numel() == 1 \
+            and next_scale.dtype == y.dtype and next_qmap.dtype == torch.bfloat16 and next_qmap.numel() == 65536:
+        codes = conv_codes_nhwc(y, next_scale, next_qmap)
+    if codes is not None:
+        return codes.view(n, h, w, c).permute(0, 3, 1, 2)
+    return _narrow_codes(torch.ops.quantized_ops.quantize(y, next_scale, None, None, None, next_qmap)).contiguous(memory_format=torch.channels_last)
+
+
+def _conv2d_qc(input, scale, qmap, weight_codes, bias, stride, padding, dilation, groups, out_scale, out_map, kind, act_min, act_max,
+               next_scale, next_qmap):
+    codes_in, codes_out = scale is None, next_scale is not None
+    if codes_in and (qmap is not None or input.dtype != torch.int8 or input.dim() != 4):
+        raise ValueError("conv2d_qc without a scale takes int8 [N, C, H, W] codes and no map")
+    if not codes_in and qmap is None:
+        raise ValueError("conv2d_qc with a scale needs the value map")
+    if codes_out and next_qmap is None:
+        raise ValueError("conv2d_qc with next_scale needs next_qmap")
+    if not codes_out and (act_min is not None or act_max is not None or next_qmap is not None):
+        raise ValueError("conv2d_qc: the activation bounds and next_qmap go with next_scale (codes out)")
+    if act_min is not None and act_max is not None and not act_min <= act_max:
+        raise ValueError(f"conv2d_qc: clamp bounds {act_min} > {act_max}")
+    args = (weight_codes, bias, stride, padding, dilation, groups, out_scale)
+    if not codes_in and not codes_out:
+        return torch.ops.quantized_ops.conv2d_q(input, scale, qmap, *args, out_map, kind)
+    stride, padding, dilation = [int(v) for v in stride], [int(v) for v in padding], [int(v) for v in dilation]
+    args = (weight_codes, bias, stride, padding, dilation, groups, out_scale)
+    dtype = out_scale.dtype if codes_in else input.dtype
+    device = input.device.type == "cuda"
+
+    def note(why):
+        if device:
+            CONV_Q_REASONS[why] = CONV_Q_REASONS.get(why, 0) + 1
+
+    if codes_in:
+        if not input.permute(0, 2, 3, 1).is_contiguous():
+            input = input.contiguous(memory_format=torch.channels_last)
+        why = _conv_q_decline(_Operand(input.shape, dtype, input.device, input.data_ptr()), _Operand((1,), dtype, input.device),
+                              _Operand((65536,), torch.bfloat16, input.device), *args, kind)
+    else:
+        why = _conv_q_decline(input, scale, qmap, *args, kind)
+    tail = None
+    if codes_out:
+        tail = (int(act_min is not None or act_max is not None), float("-inf") if act_min is None else act_min,
+                float("inf") if act_max is None else act_max, next_scale, next_qmap)
+    why_out = None
+    if why is None and codes_out:
+        cout = weight_codes.shape[0]
+        if cout % 16:
+            why_out = f"codes out: Cout = {cout} is not a multiple of 16"
+        elif next_scale.numel() != 1 or next_scale.dtype != dtype or next_qmap.dtype != torch.bfloat16 or next_qmap.numel() != 65536 \
+                or not next_qmap.is_contiguous():
+            why_out = f"codes out: scale of {next_scale.numel()} {next_scale.dtype}, map of {next_qmap.numel()} {next_qmap.dtype} entries"
+    y = None
+    if why is None:
+        n, c, h, w = input.shape
+        codes = input.permute(0, 2, 3, 1).reshape(n * h * w, c) if codes_in else None
+        if codes_out and why_out is None:
+            if not codes_in:
+                codes = conv_codes_nhwc(input, scale, qmap)
+            if codes is None:
+                why_out = "qt_quantize_codes_nhwc declined"
+            else:
+                out, why_out = _conv_q_launch(codes, input.shape, dtype, *args, out_map, tail)
+                if why_out is None:
+                    STATS["conv2d_codes_out"] += 1
+                    STATS["conv2d_codes_in"] += int(codes_in)
+                    return out
+        if codes_in:                                    # values out, or the value tensor the graph's own tail turns into codes
+            y, why = _conv_q_launch(codes, input.shape, dtype, *args, out_map)
+            if why is None:
+                STATS["conv2d_codes_in"] += 1
+        if why is None and why_out is not None:
+            note(why_out)
+    if y is None and codes_in:
+        # the values quantize would have produced, dense in NCHW order as quantize returns them (a library convolution need not sum
+        # in the same order for two layouts of one tensor), through the graph's own nodes
+        note(why)
+        w_values = _conv_weight_values(weight_codes, dtype)
+        y = torch.nn.functional.conv2d(input.to(dtype).contiguous(), w_values, bias, tuple(stride), tuple(padding), tuple(dilation), groups)
+        y = torch.ops.quantized_ops.dequantize(y, out_scale, None, None, None, out_map)
+    elif y is None:                                     # conv2d_q on whichever route it takes; it records its own decline
+        y = torch.ops.quantized_ops.conv2d_q(input, scale, qmap, *args, out_map, kind)
+    if not codes_out:
+        return y
+    return _codes_of_values(y, act_min, act_max, next_scale, next_qmap)
+
+
+def _conv2d_qc_meta(input, scale, qmap, weight_codes, bias, stride, padding, dilation, groups, out_scale, out_map, kind, act_min, act_max,
+                    next_scale, next_qmap):
+    ho, wo = _conv_out_hw(input.shape[2], input.shape[3], weight_codes.shape[1], weight_codes.shape[2], list(stride), list(padding),
+                          list(dilation))
+    dtype = torch.int8 if next_scale is not None else (out_scale.dtype if scale is None else input.dtype)
+    return input.new_empty((input.shape[0], weight_codes.shape[0], ho, wo), dtype=dtype)
+
+
+_lib.impl("conv2d_qc", _conv2d_qc, "CompositeExplicitAutograd")
+_lib.impl("conv2d_qc", _conv2d_qc_meta, "Meta")
 
 
 def _is(node, target):
@@ -561,6 +730,157 @@ def _conv_args(node):
     if vals["bias"] is not None and not isinstance(vals["bias"], torch.fx.Node):
         return None
     return (*out, vals["groups"])
+
+
+def _static_number(v):
+    return isinstance(v, (int, float)) and not isinstance(v, bool)
+
+
+def _chain_activation(node):
+    """(lo, hi) of an activation the *_codes epilogues apply -- aten.relu(_), hardtanh(_), clamp with two static bounds, lo <= hi --
+    as conv2d_qc's act_min / act_max (None: no bound on that side); None for any other node."""
+    a = torch.ops.aten
+    if getattr(node, "op", None) != "call_function":
+        return None
+    if node.target in (a.relu.default, a.relu_.default):
+        return (0.0, None) if len(node.args) == 1 and not node.kwargs else None
+    if node.target in (a.hardtanh.default, a.hardtanh_.default):
+        names, vals = ("min_val", "max_val"), [-1.0, 1.0]
+    elif node.target == a.clamp.default:
+        names, vals = ("min", "max"), [None, None]
+    else:
+        return None
+    if not 1 <= len(node.args) <= 3 or any(k not in names for k in node.kwargs):
+        return None
+    vals[:len(node.args) - 1] = node.args[1:]
+    for i, k in enumerate(names):
+        vals[i] = node.kwargs.get(k, vals[i])
+    if not all(_static_number(v) for v in vals) or any(v != v for v in vals) or not vals[0] <= vals[1]:
+        return None
+    return float(vals[0]), float(vals[1])
+
+
+def _attr_of(model, node):
+    """The tensor behind a get_attr node, else None."""
+    if getattr(node, "op", None) != "get_attr":
+        return None
+    obj = model
+    for part in str(node.target).split("."):
+        obj = getattr(obj, part, None)
+    return obj if isinstance(obj, torch.Tensor) else None
+
+
+def _conv_q_node(node):
+    """"q" for a conv2d_q node, "qc" for a conv2d_qc node, else None."""
+    ops = torch.ops.quantized_ops
+    if _is(node, ops.conv2d_q.default) and len(node.args) == 12 and not node.kwargs:
+        return "q"
+    if _is(node, ops.conv2d_qc.default) and len(node.args) == 16 and not node.kwargs:
+        return "qc"
+    return None
+
+
+def _node_shape(model, node, seen):
+    """(shape, dtype) of a graph node's value tensor: meta["val"] where the node has one; a conv2d_q / conv2d_qc node (fusion leaves
+    them without one) from its input's shape, its weight codes and _conv_out_hw, in out_scale's dtype; an activation from its input.
+    None when nothing static says."""
+    if not isinstance(node, torch.fx.Node) or node in seen:
+        return None
+    val = node.meta.get("val")
+    if isinstance(val, torch.Tensor) and all(isinstance(d, int) for d in val.shape):
+        return tuple(val.shape), val.dtype
+    seen = seen | {node}
+    if _conv_q_node(node):
+        src, w, s = _node_shape(model, node.args[0], seen), _attr_of(model, node.args[3]), _attr_of(model, node.args[9])
+        if src is None or w is None or s is None or len(src[0]) != 4 or w.dim() != 4:
+            return None
+        ho, wo = _conv_out_hw(src[0][2], src[0][3], w.shape[1], w.shape[2], *node.args[5:8])
+        return (src[0][0], w.shape[0], ho, wo), s.dtype
+    if _chain_activation(node) is not None:
+        return _node_shape(model, node.args[0], seen)
+    return None
+
+
+def _chain_declines(model, node, in_shape):
+    """_conv_q_decline for a conv2d_q / conv2d_qc node whose input has the static shape `in_shape`, as for a device call (the rule part
+    under _APPLY_CONV_Q_RULE, as everywhere).  An operand that is not a buffer of the model declines: nothing static says what it is."""
+    w, s_out = _attr_of(model, node.args[3]), _attr_of(model, node.args[9])
+    bias = _attr_of(model, node.args[4]) if node.args[4] is not None else None
+    if w is None or s_out is None or (node.args[4] is not None and bias is None):
+        return "an operand that is not a buffer"
+    dtype = s_out.dtype
+    if node.args[1] is None:                             # already takes codes
+        scale, qmap = _Operand((1,), dtype, w.device), _Operand((65536,), torch.bfloat16, w.device)
+    else:
+        scale, qmap = _attr_of(model, node.args[1]), _attr_of(model, node.args[2])
+        if scale is None or qmap is None:
+            return "an operand that is not a buffer"
+    return _conv_q_decline(_Operand(in_shape, dtype, w.device), scale, qmap, w, bias, *node.args[5:9], s_out, node.args[11], on_device=True)
+
+
+def fuse_conv_q_chains(model: GraphModule) -> int:
+    """Hands int8 codes from one converted convolution to the next.  For a producer P (a conv2d_q node, or a conv2d_qc node that still
+    writes values) whose sole user is an activation T of _chain_activation -- or T = P -- and whose T feeds nothing but conv2d_q nodes,
+    each as its `input` alone, all quantizing with the same scale node and the same map node:
+        P            -> conv2d_qc(..., act_min, act_max, that scale, that map)      codes out (qt_q8_*_codes)
+        T            erased
+        each user    -> conv2d_qc(P, None, None, ...)                                codes in: no codes pass
+    A consumer that is a producer in turn becomes one node that does both.  An edge is rewritten only where the kernels take both
+    ends as a device call would (P's Cout a multiple of 16, _conv_q_decline None for P and every consumer on the static shapes of
+    the graph): anywhere else it would only add fallback passes.  A tail with any other user (a residual add, the graph output, a
+    pooling), any other activation, a bound that is a tensor, unknown shapes: left exactly as they are.  Idempotent; run after
+    fuse_native_gemms.  Returns the number of producer -> consumer edges rewritten."""
+    ops = torch.ops.quantized_ops
+    graph = model.graph
+    edges = 0
+    for p in list(graph.nodes):
+        kind = _conv_q_node(p)
+        if kind is None or (kind == "qc" and p.args[14] is not None):
+            continue
+        tail, bounds = p, (None, None)
+        users = list(p.users)
+        if len(users) == 1 and _conv_q_node(users[0]) is None:
+            bounds = _chain_activation(users[0])
+            if bounds is None or users[0].args[0] is not p:
+                continue
+            tail = users[0]
+        consumers = list(tail.users)
+        if not consumers or any(_conv_q_node(c) is None or c.args[0] is not tail or c.args[1] is None
+                                or any(a is tail for a in c.args[1:]) for c in consumers):
+            continue
+        s_node, m_node = consumers[0].args[1], consumers[0].args[2]
+        if any(c.args[1] is not s_node or c.args[2] is not m_node for c in consumers) or s_node.op != "get_attr" or m_node.op != "get_attr":
+            continue
+        w = _attr_of(model, p.args[3])
+        src, mid = _node_shape(model, p.args[0], frozenset()), _node_shape(model, p, frozenset())
+        if w is None or w.shape[0] % 16 or src is None or mid is None or len(src[0]) != 4:
+            continue
+        if _chain_declines(model, p, src[0]) is not None or any(_chain_declines(model, c, mid[0]) is not None for c in consumers):
+            continue
+        for n in (s_node, m_node):                       # the consumer's scale and map now feed the producer
+            if n in p.all_input_nodes:
+                continue
+            for earlier in graph.nodes:
+                if earlier is p:
+                    p.prepend(n)
+                    break
+                if earlier is n:
+                    break
+        p.target = ops.conv2d_qc.default
+        p.args = (*p.args[:12], bounds[0], bounds[1], s_node, m_node)
+        p.meta.pop("val", None)
+        if tail is not p:
+            tail.replace_all_uses_with(p)
+            graph.erase_node(tail)
+        for c in consumers:
+            c.target = ops.conv2d_qc.default
+            c.args = (p, None, None, *c.args[3:12], *(c.args[12:] if len(c.args) == 16 else (None, None, None, None)))
+            edges += 1
+    if edges:
+        graph.eliminate_dead_code(is_impure_node=lambda n: n.op in {"placeholder", "output"})
+        graph.lint()
+        model.recompile()
+    return edges
 
 
 def _is_mx_consumer(node):

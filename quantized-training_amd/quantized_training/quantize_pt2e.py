@@ -462,10 +462,11 @@ def _eliminate_dequantize_with_no_effect(model: GraphModule):
     return model
 
 
-def convert_pt2e(model: GraphModule, output_dtype: str = None, eliminate_no_effect: bool = True, native=None):
+def convert_pt2e(model: GraphModule, output_dtype: str = None, eliminate_no_effect: bool = True, native=None, chain_convs=False):
     """Lower every FusedAmaxObsFakeQuantize `call_module` of a prepared (and calibrated) graph to
     quantized_ops nodes (upstream :975-1002): quantize / dequantize for per-tensor and per-channel specs,
-    quantize_mx + *_mx GEMMs for microscaling, stored codes + dequantize for group-wise affine weights."""
+    quantize_mx + *_mx GEMMs for microscaling, stored codes + dequantize for group-wise affine weights.
+    chain_convs=True (with native fusion): consecutive int8 convolutions hand over int8 codes (pt2e_native.fuse_conv_q_chains)."""
     from . import pt2e_fusion
     pt2e_fusion.unfuse_prepared_graph(model)                  # the lowering below works on the plain prepared graph
     modules = dict(model.named_modules(remove_duplicate=False))
@@ -494,4 +495,6 @@ def convert_pt2e(model: GraphModule, output_dtype: str = None, eliminate_no_effe
         pt2e_native.fuse_native_gemms(model)
         pt2e_native.fuse_mx_pairs(model)                         # calculate_mx_qparam + quantize of an activation -> one quantize_mx
         pt2e_native.fuse_gwa_linears(model)                      # group-wise affine weight: dequantize + linear -> linear_gwa on packed codes
+        if chain_convs:
+            pt2e_native.fuse_conv_q_chains(model)                # conv2d_q -> relu / hardtanh -> conv2d_q: the producer writes the consumer's codes
     return model
