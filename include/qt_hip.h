@@ -946,6 +946,31 @@ int qt_q8_gemm_codes(const int8_t *a_codes, const int8_t *b_codes, int8_t *y, in
                      int out_scale_per_col, int fold_f32, long batch, int M, int N, int K, long a_batch_stride_rows, long b_batch_stride_rows,
                      int act, float act_lo, float act_hi, const void *next_scale, const uint16_t *next_qmap, void *stream);
 
+/* A split of K for qt_q8_conv2d / qt_q8_conv2d_codes: a long contraction over few 128 x 128 output tiles (a reducing 1 x 1 layer, a
+ * small batch) otherwise runs on a fraction of the chip.  ksplit workgroups share a tile; split s multiplies the k tiles
+ * [s nk / ksplit, (s + 1) nk / ksplit), nk = ceil(kh kw Cin / 128), and leaves its int32 partial sums in the caller's workspace;
+ * the workgroup that draws the tile's last ticket adds the others' to its own AS INTEGERS and runs the sibling's epilogue, so the
+ * output is bit for bit the sibling's whatever ksplit is and whoever arrives last.  No workgroup waits for another.
+ * qt_q8_conv2d_plan (host only, no HIP call besides the cached CU count): for M = N Ho Wo output pixels, Cout and K = kh kw Cin,
+ * the split the entries choose for ksplit = 0 -- a fixed function of the shape and the device's CU count, 1 whenever the tiles
+ * already give every CU a workgroup -- and what it needs: ws_bytes = tiles * ksplit * 64 KiB, n_tickets = tiles (both 0 when
+ * ksplit == 1).  QT_ERR_BAD_ARG: negative M or Cout, M >= 2^31, K < 32, K % 32 != 0 or K >= 2^17.
+ * qt_q8_conv2d_ws / qt_q8_conv2d_codes_ws: the sibling's arguments and checks, plus ksplit (0: the plan's; an explicit value is
+ * honoured; 1 launches the sibling's kernel and touches neither ws nor tickets), the workspace `ws` (16-byte aligned, ws_bytes >=
+ * tiles * ksplit * 65536) and `tickets` (uint32, n_tickets >= tiles, ZERO before the first launch; every launch leaves them zero).
+ * On top of the sibling's refusals, before any launch: QT_ERR_BAD_ARG for ksplit < 0, ksplit > nk, and -- when the split in use is
+ * > 1 -- a NULL or short workspace or ticket array; QT_ERR_UNALIGNED for ws off a 16-byte or tickets off a 4-byte boundary.
+ * Launches on one stream may share a workspace; concurrent launches (two streams) must not.  No allocation, no host
+ * synchronisation, safe under stream capture. */
+int qt_q8_conv2d_plan(long M, int Cout, int K, int *ksplit, size_t *ws_bytes, size_t *n_tickets);
+int qt_q8_conv2d_ws(const int8_t *x_codes, const int8_t *w_codes, void *y, int y_is_f32, const void *bias, const void *out_scale,
+                    int out_scale_per_col, int fold_f32, int N, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw, int ph, int pw,
+                    int dh, int dw, int ksplit, void *ws, size_t ws_bytes, uint32_t *tickets, size_t n_tickets, void *stream);
+int qt_q8_conv2d_codes_ws(const int8_t *x_codes, const int8_t *w_codes, int8_t *y, int y_is_f32, const void *bias, const void *out_scale,
+                          int out_scale_per_col, int fold_f32, int N, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw, int ph,
+                          int pw, int dh, int dw, int act, float act_lo, float act_hi, const void *next_scale, const uint16_t *next_qmap,
+                          int ksplit, void *ws, size_t ws_bytes, uint32_t *tickets, size_t n_tickets, void *stream);
+
 /* The activation operand of qt_q8_conv2d in one pass: codes[n][p][c] = narrow(map[index(x[n, c, p] / scale)]), the arithmetic of
  * qt_quantize_* (the same device function) with a per-tensor scale in the tensor's dtype and no zero point, narrowed to int8.
  * x is the [N][HW][C] view of a 4-D tensor given by element strides (batch, row, channel): NCHW-contiguous (C HW, 1, HW) -- a

@@ -1248,10 +1248,45 @@ __device__ __forceinline__ void conv_tap_of(int v, int per, int ts0, int tr0, in
     tr = tr0 + wrap;
 }
 
+// ---- split of K (qt_q8_conv2d_ws, I8 only) -----------------------------------------------------------------------------------------
+// A long contraction over few output tiles (a reducing 1 x 1 layer, a small batch) leaves most of the chip idle.  S workgroups
+// then share a tile: split s walks the k tiles [s nk / S, (s + 1) nk / S) (S <= nk: none is empty) and leaves its 64 int32 sums per
+// thread in the caller's workspace, [tile][split][fragment 4 i + j][thread] of int4: a wave's store is one contiguous KiB.  The
+// hand-over is the one of qt_conv_backward.hip / qt_linear_fqt.hip: write-through stores, drained by every wave in front of the
+// workgroup barrier; one lane then draws the tile's ticket (relaxed, agent scope).  Whoever draws the last ticket owns the tile:
+// it reads the other S - 1 partial sums past its L1, adds them AS INTEGERS to the sums it holds in registers (exact in any order:
+// kh kw Cin < 2^17 bounds every partial and the total below 2^31, so the result is bit for bit the unsplit kernel's, whoever
+// arrives last), resets the ticket and runs the unchanged epilogue with its single float(acc).  Nobody waits for anybody; tickets
+// are zero between launches.  The owner is not known before the ticket is drawn, so every split stores (the owner's own 64 KiB
+// are never read).  Like the tail of the CODES instantiations the split state is a kernel parameter of the SPLIT instantiations only.
+struct SplitK {
+    v4i *ws;                     // [tile][split][16 fragments][256 threads]
+    unsigned int *tickets;       // [tile], zero between launches
+    int S;
+};
+struct NoSplit {};
+template <bool SPLIT>
+using split_t = std::conditional_t<SPLIT, SplitK, NoSplit>;
+constexpr long kSplitSlab = 16L * 256;        // int4 per tile and split: 64 KiB
+
+// The compiler pads nothing inside an asm string and knows no hazard of the instruction in it.  Two are live here: the base is
+// computed by scalar adds right in front (an SGPR written by the SALU needs wait states before a vector memory instruction reads it:
+// s_nop 4 opens the string), and the sums are copied out of the accumulation registers into the same four VGPRs for every fragment
+// (a 16-byte store reads its data over several cycles: s_nop 1 ends the string, so that the next copy cannot overwrite them).
+__device__ __forceinline__ void store16_sc1(const v4i *sbase, uint32_t voff, v4i v) {
+    asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 sc1\n\ts_nop 1" ::"v"(voff), "v"(v), "s"(sbase) : "memory");
+}
+__device__ __forceinline__ v4i load16_sc1(const v4i *sbase, uint32_t voff) {
+    v4i v;
+    asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2 sc1" : "=v"(v) : "v"(voff), "s"(sbase) : "memory");
+    return v;
+}
+
 // I8 (qt_q8_conv2d): int8 codes on both sides, int32 accumulators, no scale bytes -- every scale load below is compiled out --
 // and the dequantize factor of emit_out in the epilogue.
-template <int FA, int FB, bool I8 = false, bool CODES = false>
-__global__ __launch_bounds__(256) void mx_conv_kernel(MxGemmArgs a, MxConvGeom c, tail_t<CODES> ct = {}) {
+template <int FA, int FB, bool I8 = false, bool CODES = false, bool SPLIT = false>
+__global__ __launch_bounds__(256) void mx_conv_kernel(MxGemmArgs a, MxConvGeom c, tail_t<CODES> ct = {}, split_t<SPLIT> sp = {}) {
+    static_assert(!SPLIT || I8, "only integer partial sums add exactly in any order");
     using M_ = Mma<FA, FB, I8>;
     using TA = Tile<FA>;
     using TB = Tile<FB>;
@@ -1268,7 +1303,14 @@ __global__ __launch_bounds__(256) void mx_conv_kernel(MxGemmArgs a, MxConvGeom c
     const int tiles_m = (a.M + kBM - 1) / kBM, tiles_n = (a.N + kBN - 1) / kBN;
     const int ntiles = tiles_m * tiles_n;
     int id = blockIdx.x;
-    {
+    int split = 0;
+    if constexpr (SPLIT) {
+        // work item tile S + s through the same remap: the splits of a tile land on one XCD, next to each other
+        const int nitems = ntiles * sp.S, per = nitems / 8, rem = nitems % 8, x = id % 8, q = id / 8;
+        id = x * per + (x < rem ? x : rem) + q;
+        split = id % sp.S;
+        id = id / sp.S;
+    } else {
         const int per = ntiles / 8, rem = ntiles % 8, x = id % 8, q = id / 8;
         id = x * per + (x < rem ? x : rem) + q;                  // XCD x owns a contiguous run of tiles, as in mx_gemm_kernel
     }
@@ -1280,6 +1322,11 @@ __global__ __launch_bounds__(256) void mx_conv_kernel(MxGemmArgs a, MxConvGeom c
     const int nblk = a.K / 32;
     const int nk = (a.K + kBK - 1) / kBK;
     const int pbytes = c.cpb * (RA / 4);                             // P: code bytes of one input pixel
+    int kt0 = 0, kt1 = nk;                                          // this workgroup's k tiles
+    if constexpr (SPLIT) {
+        kt0 = (int)((long)split * nk / sp.S);
+        kt1 = (int)((long)(split + 1) * nk / sp.S);
+    }
 
     // an output pixel's input corner: the pixel index it would have (modulo 2^32: only taps inside the plane are fetched) and its
     // row / column; rows past M get a corner that no tap brings back into the plane
@@ -1331,6 +1378,12 @@ __global__ __launch_bounds__(256) void mx_conv_kernel(MxGemmArgs a, MxConvGeom c
         for (int i = 0; i < 4; ++i) sca[i] = scb[i] = 0;
     }
     int u_blk = 0, u_ts = 0, u_tr = 0;                               // where the next k tile to load starts
+    if constexpr (SPLIT) {                                           // ... which is k tile kt0: once per workgroup
+        const int b0 = 4 * kt0, tap = b0 / c.cpb;
+        u_blk = b0 % c.cpb;
+        u_tr = tap / c.kw;
+        u_ts = tap % c.kw;
+    }
     auto load_tile = [&](int kt) __attribute__((always_inline)) {
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
@@ -1387,8 +1440,8 @@ __global__ __launch_bounds__(256) void mx_conv_kernel(MxGemmArgs a, MxConvGeom c
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = M_::zero();
 
-    load_tile(0);
-    store_tile(0, 0);
+    load_tile(kt0);
+    store_tile(0, kt0);
     int cs_a[4], cs_b[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) { cs_a[i] = sca[i]; cs_b[i] = scb[i]; }
@@ -1405,8 +1458,8 @@ __global__ __launch_bounds__(256) void mx_conv_kernel(MxGemmArgs a, MxConvGeom c
             for (int j = 0; j < 4; ++j)
                 acc[i][j] = M_::run(fa[i], fb[j], acc[i][j], cs_a[i], cs_b[j]);
     };
-    for (int kt = 0; kt + 1 < nk; ++kt) {
-        const int cur = kt & 1;
+    for (int kt = kt0; kt + 1 < kt1; ++kt) {
+        const int cur = (kt - kt0) & 1;
         load_tile(kt + 1);                                // in flight during this tile's MFMAs
         __builtin_amdgcn_sched_barrier(0);
         compute(cur);
@@ -1416,7 +1469,41 @@ __global__ __launch_bounds__(256) void mx_conv_kernel(MxGemmArgs a, MxConvGeom c
         for (int i = 0; i < 4; ++i) { cs_a[i] = sca[i]; cs_b[i] = scb[i]; }
         __syncthreads();
     }
-    compute((nk - 1) & 1);
+    compute((kt1 - 1 - kt0) & 1);
+
+    if constexpr (SPLIT) {
+        const v4i *const tile_ws = sp.ws + (long)id * sp.S * kSplitSlab;
+        const v4i *const mine = tile_ws + (long)split * kSplitSlab;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) store16_sc1(mine + (i * 4 + j) * 256, (uint32_t)t * 16u, acc[i][j]);
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        __syncthreads();                                        // (also: every wave has read its last fragments, the flag reuses the tiles)
+        volatile unsigned int *flag = (volatile unsigned int *)lds;
+        if (t == 0) *flag = __hip_atomic_fetch_add(sp.tickets + id, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __syncthreads();
+        if ((int)*flag != sp.S - 1) return;                     // not the last one: done
+        if (t == 0) __hip_atomic_store(sp.tickets + id, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");      // drop what this XCD's L2 holds of the workspace from earlier launches
+#pragma unroll 1
+        for (int q = 0; q < sp.S; ++q) {
+            if (q == split) continue;
+            v4i part[4][4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) part[i][j] = load16_sc1(tile_ws + (long)q * kSplitSlab + (i * 4 + j) * 256, (uint32_t)t * 16u);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    asm volatile("" : "+v"(part[i][j]));
+                    acc[i][j] += part[i][j];
+                }
+        }
+    }
 
     // epilogue: D col = l & 15, row = 4 g + e; y is [M][Cout] = NHWC
     if constexpr (CODES) {
@@ -1450,6 +1537,51 @@ int launch_conv(const MxGemmArgs &g, const MxConvGeom &c, unsigned grid, hipStre
     if (const int rc = qt_allow_lds<mx_conv_kernel<FA, FB, I8, CODES>>(kLds)) return rc;
     mx_conv_kernel<FA, FB, I8, CODES><<<grid, 256, kLds, st>>>(g, c, ct);
     return qt_launch_status();
+}
+
+// The split-K instantiations of the int8 kernel: grid = tiles * S work items.
+template <bool CODES>
+int launch_conv_split(const MxGemmArgs &g, const MxConvGeom &c, unsigned grid, hipStream_t st, const tail_t<CODES> &ct, const SplitK &sp) {
+    constexpr int kLds = 4 * Tile<0>::kBytes;
+    static_assert(!CODES || kBM * kCodePitch <= kLds, "the code tile is staged in the operand tiles' space");
+    if (const int rc = qt_allow_lds<mx_conv_kernel<0, 0, true, CODES, true>>(kLds)) return rc;
+    mx_conv_kernel<0, 0, true, CODES, true><<<grid, 256, kLds, st>>>(g, c, ct, sp);
+    return qt_launch_status();
+}
+
+// ---- the plan of the split (qt_q8_conv2d_plan) ---------------------------------------------------------------------------------
+// A fixed function of the shape and the CU count.  S = 1 once the 128 x 128 tiles give every CU a workgroup; else the largest
+// S of kConvSplitSet with tiles * S <= CUs that leaves every split at least kConvSplitMinKTiles k tiles.  Both constants are read off
+// profiles/conv2d_q_splitk.txt (MI355X, 256 CUs; the launch alone, replayed, us for S = 1 / 2 / 4 / 8 / 16):
+//   * the set stops at 8: S = 16 is the slowest split wherever it was forced (2048 -> 512 at 7 x 7, 52 tiles, nk = 16:
+//     37.6 / 31.9 / 30.4 / 35.6 / 50.0; 4 x 512 -> 512 3 x 3, 8 tiles, nk = 36: 61.3 / 42.5 / 33.6 / 32.7 / 38.9);
+//   * at least two k tiles per split: one k tile each loses to the unsplit launch on every row (nk = 2, S = 2: 256 -> 64 at 56 x 56
+//     39.6 -> 83.8, 192 -> 64 at 14 x 14 19.1 -> 21.5; nk = 8, S = 8: 960 -> 160 at 7 x 7 28.2 -> 30.3), two each is where the split
+//     starts to pay (nk = 8, S = 4: 960 -> 160 28.2 -> 26.4, 960 -> 320 28.3 -> 27.4; nk = 5, S = 2: ties within about 1 us);
+//   * tiles * S <= CUs: a second round of workgroups costs more than it hides (512 -> 128 at 28 x 28, 196 tiles: 24.1 / 31.7 / 52.5).
+// On all seventeen rows the S this gives is the fastest measured one or within about 1 us of it.
+constexpr int kConvSplitSet[] = {8, 4, 2};
+constexpr int kConvSplitMinKTiles = 2;
+struct ConvSplitPlan {
+    long tiles;
+    int nk, ksplit;
+    size_t ws_bytes() const { return ksplit > 1 ? (size_t)tiles * ksplit * kSplitSlab * sizeof(v4i) : 0; }
+    size_t tickets() const { return ksplit > 1 ? (size_t)tiles : 0; }
+};
+struct ConvSplitWs {             // what the *_ws entry points add to their siblings' arguments
+    int ksplit;
+    void *ws;
+    size_t ws_bytes;
+    uint32_t *tickets;
+    size_t n_tickets;
+};
+ConvSplitPlan conv_split_plan(long m, long cout, long K) {
+    ConvSplitPlan p{((m + kBM - 1) / kBM) * ((cout + kBN - 1) / kBN), (int)((K + kBK - 1) / kBK), 1};
+    const long cus = qt_cu_count();
+    if (p.tiles < 1 || p.tiles >= cus) return p;
+    for (const int s : kConvSplitSet)
+        if (p.tiles * s <= cus && p.nk / s >= kConvSplitMinKTiles) { p.ksplit = s; break; }
+    return p;
 }
 
 // ---- depthwise conv2d on int8 codes (qt_q8_dwconv2d) ---------------------------------------------------------
@@ -2095,8 +2227,9 @@ int qt_q8_gemm_codes(const int8_t *a_codes, const int8_t *b_codes, int8_t *y, in
 
 static int q8_conv2d_launch(const int8_t *x_codes, const int8_t *w_codes, void *y, int y_is_f32, const void *bias, const void *out_scale,
                             int out_scale_per_col, int fold_f32, int N, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw, int ph,
-                            int pw, int dh, int dw, void *stream, const CodesTail *ct) {
+                            int pw, int dh, int dw, void *stream, const CodesTail *ct, const ConvSplitWs *wsp = nullptr) {
     if (!x_codes || !w_codes || !y) return QT_ERR_BAD_ARG;
+    if (wsp && wsp->ksplit < 0) return QT_ERR_BAD_ARG;
     if (ct) {
         if (const int rc = codes_tail_check(*ct, Cout < 0 ? 0 : Cout, y, y_is_f32)) return rc;
     }
@@ -2122,8 +2255,51 @@ static int q8_conv2d_launch(const int8_t *x_codes, const int8_t *w_codes, void *
     const MxConvGeom c{H, W, kh, kw, sh, sw, ph, pw, dh, dw, (int)ho, (int)wo, Cin / 32};
     const long tiles = ((m + kBM - 1) / kBM) * ((Cout + kBN - 1) / kBN);
     if (tiles >= kLim) return QT_ERR_BAD_ARG;
+    if (wsp) {
+        // ksplit 0: the plan's; an explicit value is honoured up to the k tiles there are; 1 is the unsplit launch below
+        ConvSplitPlan p = conv_split_plan(m, Cout, K);
+        if (wsp->ksplit > 0) p.ksplit = wsp->ksplit;
+        if (p.ksplit > p.nk) return QT_ERR_BAD_ARG;
+        if (p.ksplit > 1) {
+            if (tiles * p.ksplit >= kLim) return QT_ERR_BAD_ARG;
+            if (!wsp->ws || !wsp->tickets || wsp->ws_bytes < p.ws_bytes() || wsp->n_tickets < p.tickets()) return QT_ERR_BAD_ARG;
+            if (((uintptr_t)wsp->ws & 15u) || ((uintptr_t)wsp->tickets & 3u)) return QT_ERR_UNALIGNED;
+            const SplitK sp{(v4i *)wsp->ws, wsp->tickets, p.ksplit};
+            const unsigned grid = (unsigned)(tiles * p.ksplit);
+            if (ct) return launch_conv_split<true>(g, c, grid, (hipStream_t)stream, *ct, sp);
+            return launch_conv_split<false>(g, c, grid, (hipStream_t)stream, NoTail{}, sp);
+        }
+    }
     if (ct) return launch_conv<0, 0, true, true>(g, c, (unsigned)tiles, (hipStream_t)stream, *ct);
     return launch_conv<0, 0, true>(g, c, (unsigned)tiles, (hipStream_t)stream);
+}
+
+int qt_q8_conv2d_plan(long M, int Cout, int K, int *ksplit, size_t *ws_bytes, size_t *n_tickets) {
+    if (M < 0 || Cout < 0 || K < 32 || K % 32 != 0 || K >= (1 << 17) || M >= (1L << 31)) return QT_ERR_BAD_ARG;
+    ConvSplitPlan p{0, 0, 1};
+    if (M * Cout != 0) p = conv_split_plan(M, Cout, K);
+    if (ksplit) *ksplit = p.ksplit;
+    if (ws_bytes) *ws_bytes = p.ws_bytes();
+    if (n_tickets) *n_tickets = p.tickets();
+    return QT_OK;
+}
+
+int qt_q8_conv2d_ws(const int8_t *x_codes, const int8_t *w_codes, void *y, int y_is_f32, const void *bias, const void *out_scale,
+                    int out_scale_per_col, int fold_f32, int N, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw, int ph, int pw,
+                    int dh, int dw, int ksplit, void *ws, size_t ws_bytes, uint32_t *tickets, size_t n_tickets, void *stream) {
+    const ConvSplitWs wsp{ksplit, ws, ws_bytes, tickets, n_tickets};
+    return q8_conv2d_launch(x_codes, w_codes, y, y_is_f32, bias, out_scale, out_scale_per_col, fold_f32, N, H, W, Cin, Cout, kh, kw, sh, sw,
+                            ph, pw, dh, dw, stream, nullptr, &wsp);
+}
+
+int qt_q8_conv2d_codes_ws(const int8_t *x_codes, const int8_t *w_codes, int8_t *y, int y_is_f32, const void *bias, const void *out_scale,
+                          int out_scale_per_col, int fold_f32, int N, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw, int ph,
+                          int pw, int dh, int dw, int act, float act_lo, float act_hi, const void *next_scale, const uint16_t *next_qmap,
+                          int ksplit, void *ws, size_t ws_bytes, uint32_t *tickets, size_t n_tickets, void *stream) {
+    const CodesTail ct{next_qmap, next_scale, act, act_lo, act_hi};
+    const ConvSplitWs wsp{ksplit, ws, ws_bytes, tickets, n_tickets};
+    return q8_conv2d_launch(x_codes, w_codes, y, y_is_f32, bias, out_scale, out_scale_per_col, fold_f32, N, H, W, Cin, Cout, kh, kw, sh, sw,
+                            ph, pw, dh, dw, stream, &ct, &wsp);
 }
 
 int qt_q8_conv2d(const int8_t *x_codes, const int8_t *w_codes, void *y, int y_is_f32, const void *bias, const void *out_scale,

@@ -243,6 +243,10 @@ SIGNATURES = {
     "qt_q8_gemm_codes": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, c_int, c_long, c_int, c_int, c_int, c_long, c_long,
                                  c_int, c_float, c_float, _P, _P, _P]),
     "qt_q8_conv2d_codes": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, c_int] + [c_int] * 13 + [c_int, c_float, c_float, _P, _P, _P]),
+    "qt_q8_conv2d_plan": (c_int, [c_long, c_int, c_int, POINTER(c_int), POINTER(c_size_t), POINTER(c_size_t)]),
+    "qt_q8_conv2d_ws": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, c_int] + [c_int] * 13 + [c_int, _P, c_size_t, _P, c_size_t, _P]),
+    "qt_q8_conv2d_codes_ws": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, c_int] + [c_int] * 13 + [c_int, c_float, c_float, _P, _P] +
+                              [c_int, _P, c_size_t, _P, c_size_t, _P]),
     "qt_q8_dwconv2d_codes": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, c_int] + [c_int] * 12 + [c_int, c_float, c_float, _P, _P, _P]),
     "qt_quantize_codes_nhwc_bf16": (c_int, [_P, _P] + [c_long] * 6 + [_FMT, _P, _P, _P]),
     "qt_quantize_codes_nhwc_f32": (c_int, [_P, _P] + [c_long] * 6 + [_FMT, _P, _P, _P]),
@@ -316,6 +320,13 @@ def check(code, what=""):
         if code == QT_ERR_BAD_DTYPE:
             raise ValueError(f"Unsupported dtype: {what}")
         raise QtError(f"libqt_hip {what}: {msg} (code {code})")
+
+
+def q8_conv_plan(m, cout, k):
+    """(ksplit, workspace bytes, tickets) of qt_q8_conv2d_ws for m output pixels, cout channels and k = kh kw Cin (host only)."""
+    ks, wb, nt = c_int(0), c_size_t(0), c_size_t(0)
+    check(lib().qt_q8_conv2d_plan(m, cout, k, ctypes.byref(ks), ctypes.byref(wb), ctypes.byref(nt)), "qt_q8_conv2d_plan")
+    return ks.value, wb.value, nt.value
 
 
 def declined(code, dtype=False):

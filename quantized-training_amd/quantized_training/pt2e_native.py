@@ -19,6 +19,8 @@ cores:
     NHWC codes in one pass (`qt_quantize_codes_nhwc_*`), then `qt_q8_conv2d`, an implicit GEMM on the same instruction with the same
     epilogue, into a channels_last result.  Depthwise layers (groups = Cin = Cout, a multiple of 16) run `qt_q8_dwconv2d` on the same
     codes; 1 x 1, stride 1, unpadded layers over Cin = 16 mod 32 (which the gather kernel declines) run `qt_q8_gemm` on them.
+    `fuse_native_gemms(model, split_k=True)` (opt-in: `convert_pt2e(split_k=True)`) marks the gather layers' codes buffers: a marked
+    layer launches `qt_q8_conv2d_ws` with the plan's split of K (the same bits) and has a route rule of its own.
 
 `fuse_conv_q_chains` (opt-in: `convert_pt2e(chain_convs=True)`) then hands int8 codes from one such convolution to the next:
 `conv2d_q -> aten.relu / hardtanh / clamp -> conv2d_q` becomes two `conv2d_qc` nodes, the first writing the second's codes from its
@@ -43,8 +45,9 @@ from .fake_quantize import _stream_ptr
 __all__ = ["fuse_native_gemms", "fuse_conv_q_chains", "fuse_mx_pairs", "fuse_gwa_linears", "STATS", "GWA_STATS"]
 
 # conv2d_codes_in / conv2d_codes_out: native conv2d_qc launches that took / wrote a code array (counted in their kernel's key as well)
+# conv2d_split_k: gather-kernel launches that split K over more than one workgroup per tile (counted in conv2d_int8 as well)
 STATS = {"linear_int8": 0, "matmul_int8": 0, "linear_fp8": 0, "matmul_fp8": 0, "conv2d_int8": 0, "conv2d_dw_int8": 0,
-         "conv2d_codes_in": 0, "conv2d_codes_out": 0}
+         "conv2d_codes_in": 0, "conv2d_codes_out": 0, "conv2d_split_k": 0}
 _IDENTITY_DTYPES = (None, "None", "bfloat16", "float32", "float16")
 _FP8 = {"fp8_e4m3": torch.float8_e4m3fn, "fp8_e5m2": torch.float8_e5m2}
 
@@ -199,6 +202,39 @@ def _conv_q_route_takes(m, cout, cin, kh, kw):
     return cout >= cin and tiles >= 208
 
 
+_SPLIT_PROFILE = "profiles/conv2d_q_splitk.txt"
+
+
+def mark_split_k(weight_codes):
+    """Opts a gather layer's int8 codes buffer into the split of K (fuse_native_gemms(split_k=True) does this for every gather
+    layer).  The mark is an attribute of the tensor object, like _qt_conv_values: a copy or a move of the buffer loses it, and the
+    layer then routes exactly as an unmarked one."""
+    weight_codes._qt_split_k = True
+    return weight_codes
+
+
+def _split_k_marked(weight_codes):
+    return getattr(weight_codes, "_qt_split_k", False) is True
+
+
+def _conv_q_split_route_takes(m, cout, cin, kh, kw):
+    """The committed rule for gather layers whose codes buffer carries the split-K mark, consulted where _conv_q_route_takes says
+    no; a fixed function of the shape (never a timing).  From profiles/conv2d_q_splitk.txt (seventeen rows, bf16: ResNet-50's four
+    reducing 1 x 1 layers and 512 -> 512 3 x 3 at 7 x 7, batch 32; the four batch-4 problems of profiles/conv2d_q.txt; MobileNetV2's
+    eight projecting layers over Cin % 32 == 0, batch 32; the method and the bar of profiles/conv2d_q.txt, judged at the split
+    qt_q8_conv2d_plan chooses; t = 128 x 128 output tiles, nk = k tiles of 128).  One class is listed:
+      * filters larger than 1 x 1 with nk >= 36 and t >= 8: both measured rows clear -- 4 x 512 -> 512 3 x 3 at 7 x 7 (t = 8, S = 8:
+        replayed 45.4 -> 42.5 us from NCHW input, 49.9 -> 38.3 from channels_last, where the unsplit kernel takes 71.3 / 66.7) and
+        the same layer at batch 32 (t = 52, S = 4: 93.6 -> 46.9 / 99.2 -> 42.6 against 72.5 / 67.4 unsplit; _conv_q_route_takes
+        lists it already).
+    Not listed, because a row of the class loses: reducing 1 x 1 layers -- the split shortens the launch (2048 -> 512: 37.6 -> 30.4 us
+    alone) but the call with its codes pass still loses from NCHW input (36.4 -> 45.3 us; 1024 -> 256: 40.0 -> 46.3); MobileNetV2's
+    projecting layers (960 -> 160 clears at S = 4 by 0.8 us; 960 -> 320, 576 -> 96, 576 -> 160 and 384 -> 96 lose replayed from NCHW input:
+    no class separates them but the rows themselves); the three small batch-4 problems (nk <= 5: 0.79 - 0.95 x)."""
+    tiles, nk = -(-m // 128) * -(-cout // 128), -(-kh * kw * cin // 128)
+    return kh * kw > 1 and nk >= 36 and tiles >= 8
+
+
 _DW_PROFILE = "profiles/conv2d_q_depthwise.txt"
 _CONV_Q_DW_MAX_TAPS = 1023
 
@@ -292,7 +328,10 @@ def _conv_q_decline(input, scale, qmap, weight_codes, bias, stride, padding, dil
         if route == "pointwise" and not _conv_q_pw16_route_takes(n * ho * wo, cout, cin):
             return f"pointwise route rule: {_DW_PROFILE}"
         if route == "gather" and not _conv_q_route_takes(n * ho * wo, cout, cin, kh, kw):
-            return "route rule: profiles/conv2d_q.txt"
+            if not _split_k_marked(weight_codes):
+                return "route rule: profiles/conv2d_q.txt"
+            if not _conv_q_split_route_takes(n * ho * wo, cout, cin, kh, kw):
+                return f"split-K route rule: {_SPLIT_PROFILE}"
     return None
 
 
@@ -381,7 +420,7 @@ def _conv_q_launch(codes, shape, dtype, weight_codes, bias, stride, padding, dil
     head = (codes.data_ptr(), weight_codes.data_ptr(), out.data_ptr(), int(dtype == torch.float32),
             b.data_ptr() if b is not None else None, s.data_ptr(), per_col, fold)
     geometry = (kh, kw, stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1])
-    last, sfx = (stream,), ""
+    last, sfx, split = (stream,), "", 1
     if tail is not None:
         act, lo, hi, next_scale, next_qmap = tail
         last, sfx = (int(act), float(lo), float(hi), next_scale.data_ptr(), next_qmap.data_ptr(), stream), "_codes"
@@ -389,12 +428,21 @@ def _conv_q_launch(codes, shape, dtype, weight_codes, bias, stride, padding, dil
         entry, key, rc = "qt_q8_dwconv2d" + sfx, "conv2d_dw_int8", getattr(L, "qt_q8_dwconv2d" + sfx)(*head, n, h, w, cin, *geometry, *last)
     elif route == "pointwise":                   # the channels_last result is the row-major [N Ho Wo][Cout] of the GEMM
         entry, key, rc = "qt_q8_gemm" + sfx, "conv2d_int8", getattr(L, "qt_q8_gemm" + sfx)(*head, 1, n * h * w, cout, cin, 0, 0, *last)
+    elif _split_k_marked(weight_codes):          # the plan's split (1: the unsplit kernel, no workspace) through the *_ws sibling
+        from .fused import splitk_scratch
+        split, wbytes, ntick = _native.q8_conv_plan(n * ho * wo, cout, kh * kw * cin)
+        ws, tickets = splitk_scratch("conv_q", wbytes, ntick, codes.device) if split > 1 else (None, None)
+        scratch = (split, ws.data_ptr() if split > 1 else None, ws.numel() * 4 if split > 1 else 0,
+                   tickets.data_ptr() if split > 1 else None, tickets.numel() if split > 1 else 0)
+        entry, key = "qt_q8_conv2d" + sfx + "_ws", "conv2d_int8"
+        rc = getattr(L, entry)(*head, n, h, w, cin, cout, *geometry, *last[:-1], *scratch, stream)
     else:
         entry, key, rc = "qt_q8_conv2d" + sfx, "conv2d_int8", getattr(L, "qt_q8_conv2d" + sfx)(*head, n, h, w, cin, cout, *geometry, *last)
     if _native.declined(rc):
         return None, f"{entry} declined the shape (code {rc})"
     _native.check(rc, entry)
     STATS[key] += 1
+    STATS["conv2d_split_k"] += int(split > 1)
     return out, None
 
 
@@ -590,10 +638,13 @@ def _sole_dequantize(model, node, dtype):
     return dq, a[1], a[5]
 
 
-def fuse_native_gemms(model: GraphModule) -> int:
+def fuse_native_gemms(model: GraphModule, split_k: bool = False) -> int:
     """Rewrites quantize -> aten.linear / aten.matmul -> dequantize triples whose operands are int8 (or FP8) codes into
     linear_q / matmul_q nodes, and quantize -> aten.conv2d -> dequantize triples on int8 codes (static geometry; Cin a multiple
-    of 32, or depthwise over a multiple of 16 channels, or 1 x 1 / stride 1 / unpadded over Cin = 16 mod 32) into conv2d_q nodes.  Returns the number of fused GEMMs and convolutions; leaves everything else as it is."""
+    of 32, or depthwise over a multiple of 16 channels, or 1 x 1 / stride 1 / unpadded over Cin = 16 mod 32) into conv2d_q nodes.  Returns the number of fused GEMMs and convolutions; leaves everything else as it is.
+    split_k=True marks the int8 codes buffer of every gather layer (groups = 1, Cin a multiple of 32) with mark_split_k: such a layer
+    launches qt_q8_conv2d_ws / qt_q8_conv2d_codes_ws with the plan's split and is routed by _conv_q_split_route_takes where
+    _conv_q_route_takes declines it.  The graph itself is the same either way."""
     graph = model.graph
     fused = 0
     for node in list(graph.nodes):
@@ -692,6 +743,8 @@ def fuse_native_gemms(model: GraphModule) -> int:
             if param.is_contiguous():
                 # a call the kernels decline convolves the values the graph stored: the parameter itself, not a third copy
                 getattr(model, name)._qt_conv_values = param.detach()
+            if split_k and gather and groups == 1:
+                mark_split_k(getattr(model, name))
             with graph.inserting_before(dq):
                 c_node = graph.create_node("get_attr", name)
                 new = graph.call_function(torch.ops.quantized_ops.conv2d_q.default,

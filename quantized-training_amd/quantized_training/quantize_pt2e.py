@@ -462,11 +462,13 @@ def _eliminate_dequantize_with_no_effect(model: GraphModule):
     return model
 
 
-def convert_pt2e(model: GraphModule, output_dtype: str = None, eliminate_no_effect: bool = True, native=None, chain_convs=False):
+def convert_pt2e(model: GraphModule, output_dtype: str = None, eliminate_no_effect: bool = True, native=None, chain_convs=False, split_k=False):
     """Lower every FusedAmaxObsFakeQuantize `call_module` of a prepared (and calibrated) graph to
     quantized_ops nodes (upstream :975-1002): quantize / dequantize for per-tensor and per-channel specs,
     quantize_mx + *_mx GEMMs for microscaling, stored codes + dequantize for group-wise affine weights.
-    chain_convs=True (with native fusion): consecutive int8 convolutions hand over int8 codes (pt2e_native.fuse_conv_q_chains)."""
+    chain_convs=True (with native fusion): consecutive int8 convolutions hand over int8 codes (pt2e_native.fuse_conv_q_chains).
+    split_k=True (with native fusion): the int8 gather convolutions may split K over idle CUs (pt2e_native.fuse_native_gemms(split_k=True):
+    the same graph, a mark on the layers' codes buffers)."""
     from . import pt2e_fusion
     pt2e_fusion.unfuse_prepared_graph(model)                  # the lowering below works on the plain prepared graph
     modules = dict(model.named_modules(remove_duplicate=False))
@@ -492,7 +494,7 @@ def convert_pt2e(model: GraphModule, output_dtype: str = None, eliminate_no_effe
     # cores (pt2e_native.py).  The graph above is upstream's node for node; this pass only runs where it can execute natively.
     from . import pt2e_native
     if native or (native is None and pt2e_native.enabled_for(model)):
-        pt2e_native.fuse_native_gemms(model)
+        pt2e_native.fuse_native_gemms(model, split_k=split_k)
         pt2e_native.fuse_mx_pairs(model)                         # calculate_mx_qparam + quantize of an activation -> one quantize_mx
         pt2e_native.fuse_gwa_linears(model)                      # group-wise affine weight: dequantize + linear -> linear_gwa on packed codes
         if chain_convs:
