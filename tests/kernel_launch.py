@@ -1,4 +1,4 @@
-"""What the kernel tests that launch through the C ABI share (tests/test_gpu_row_kernels.py, tests/test_gpu_elementwise_ops.py): guarded
+"""What the kernel tests that launch through the C ABI share (tests/test_gpu_row_kernels.py, tests/test_gpu_elementwise_ops.py, tests/test_gpu_gemm_fq.py): guarded
 output buffers, the two-launch and refused-call checks, the interval check with its per-family statistics, and the single fake-quant
 passes the fused variants are compared with.  A plain module, imported by name; it holds no tests."""
 import ctypes
