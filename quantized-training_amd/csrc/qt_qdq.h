@@ -1,6 +1,6 @@
 // qt_qdq.h -- one element of quantized_ops::quantize / dequantize (decomposed.py:166-262) and its narrowing to an int8 code, shared by
 // the elementwise kernels (qt_elementwise.hip: qt_quantize_*, qt_dequantize_*, qt_quantize_codes_nhwc_*) and by the convolution
-// epilogues that write the next layer's codes (qt_mx_gemm.hip: qt_q8_*_codes): one definition, so the two cannot drift apart.
+// epilogues that write the next layer's codes (qt_mx_tile.h: emit_codes_tile behind qt_q8_*_codes): one definition, so the two cannot drift apart.
 #pragma once
 #include "qt_device.h"
 

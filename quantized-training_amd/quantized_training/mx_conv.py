@@ -2,7 +2,7 @@
 
 The reference states the op as "multiply each operand by its block scales expanded along the channel axis, then F.conv2d".  For the
 operands mx_gemm takes (element values in one of the five formats of v_mfma_scale_f32_16x16x128_f8f6f4, power-of-two scales over
-blocks of a multiple of 32 channels) the same sum is computed by qt_conv2d_mx (csrc/qt_mx_gemm.hip), an implicit GEMM that gathers
+blocks of a multiple of 32 channels) the same sum is computed by qt_conv2d_mx (csrc/qt_mx_conv.hip), an implicit GEMM that gathers
 the element codes and E8M0 bytes of each filter tap from NHWC operands: no dequantized copy of either operand is ever written.
 
 Weight [Cout, Cin, kh, kw]: packed once as [Cout][kh kw Cin] with the packer's check on, cached on the tensor object.

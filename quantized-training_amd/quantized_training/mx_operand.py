@@ -25,7 +25,7 @@ operand: a consumer that still believed the format would pack the modified value
 write in place CANNOT be seen there.  It imports torch and, to compare a map by content, fake_quantize's tables; no routing."""
 import torch
 
-# ---- what the kernels take (csrc/qt_mx_gemm.hip) -----------------------------------------------------------------------------------
+# ---- what the kernels take (csrc/qt_mx_tile.h) -----------------------------------------------------------------------------------
 FMT_ID = {"fp8_e4m3": 0, "fp8_e5m2": 1, "fp6_e2m3": 2, "fp6_e3m2": 3, "fp4_e2m1": 4}
 BITS = {0: 8, 1: 8, 2: 6, 3: 6, 4: 4}
 PAIRS = {(0, 0), (0, 1), (1, 0), (1, 1), (2, 2), (3, 3), (4, 4), (0, 4), (2, 4), (3, 4)}      # (first, second) operand format ids

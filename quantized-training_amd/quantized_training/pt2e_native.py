@@ -172,7 +172,7 @@ _lib.impl("linear_q", _linear_q, "CompositeExplicitAutograd")
 _lib.impl("matmul_q", _matmul_q, "CompositeExplicitAutograd")
 
 
-# ---- quantize -> aten.conv2d -> dequantize: conv2d_q (csrc/qt_mx_gemm.hip qt_q8_conv2d, csrc/qt_elementwise.hip qt_quantize_codes_nhwc_*) ----
+# ---- quantize -> aten.conv2d -> dequantize: conv2d_q (csrc/qt_mx_conv.hip qt_q8_conv2d, csrc/qt_elementwise.hip qt_quantize_codes_nhwc_*) ----
 # weight_codes is int8 [Cout, kh, kw, Cin]: its shape carries the filter geometry and, flattened, it is the kernel's [Cout][kh kw Cin]
 # operand.  The activation becomes int8 NHWC codes in one pass (no value tensor), the implicit GEMM accumulates in int32 and its
 # epilogue keeps the rounding points of the three nodes.  Everything the kernels do not take runs those three nodes verbatim.

@@ -1,5 +1,5 @@
 """Shared by tests/test_conv_q_splitk_cpu.py and tests/test_gpu_conv_q_splitk.py: the problems of the split-K int8 convolution
-(qt_q8_conv2d_ws / qt_q8_conv2d_codes_ws, csrc/qt_mx_gemm.hip), their exact sums and the epilogue's rounding chain on the host
+(qt_q8_conv2d_ws / qt_q8_conv2d_codes_ws, csrc/qt_mx_conv.hip), their exact sums and the epilogue's rounding chain on the host
 (restated from tests/test_gpu_conv_q.py), and the small converted CNN with a projecting 1 x 1 layer.  A plain module, imported by
 name; it holds no tests."""
 import functools

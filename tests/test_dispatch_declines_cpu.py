@@ -90,7 +90,7 @@ def test_unsupported_format_declines_with_the_family_s_code(name, fmt, lut, code
     assert CALLS[name][0](_native.lib(), ctypes.byref(fmt), lut) == code
 
 
-# the ten element-format pairs of csrc/qt_mx_gemm.hip (QT_MX_E4M3 0, E5M2 1, E2M3 2, E3M2 3, E2M1 4)
+# the ten element-format pairs of csrc/qt_mx_tile.h (QT_MX_E4M3 0, E5M2 1, E2M3 2, E3M2 3, E2M1 4)
 MX_PAIRS = {(0, 0), (0, 1), (1, 0), (1, 1), (2, 2), (3, 3), (4, 4), (0, 4), (2, 4), (3, 4)}
 
 

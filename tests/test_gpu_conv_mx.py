@@ -1,4 +1,4 @@
-"""conv2d_mx on the device: qt_conv2d_mx (csrc/qt_mx_gemm.hip) through the C ABI, the three sources of its activation operand, the
+"""conv2d_mx on the device: qt_conv2d_mx (csrc/qt_mx_conv.hip) through the C ABI, the three sources of its activation operand, the
 operator, its fallbacks and a converted CNN.
 
 Exact tier: element values out of {0, +-0.5, +-1, +-2} (in all five formats) and block scales out of {0.5, 1, 2}: every product is a

@@ -1,4 +1,4 @@
-"""Converted per-tensor int8 convolutions on the device: qt_q8_conv2d (csrc/qt_mx_gemm.hip) and qt_quantize_codes_nhwc_*
+"""Converted per-tensor int8 convolutions on the device: qt_q8_conv2d (csrc/qt_mx_conv.hip) and qt_quantize_codes_nhwc_*
 (csrc/qt_elementwise.hip) through the C ABI, the operator quantized_ops.conv2d_q, its fallbacks, a converted CNN and its graph capture.
 
 Exact tier: random int8 codes.  The reference is the fp64 unfold + matmul on the host (every sum is an integer below 2^53: exact)

@@ -1,5 +1,5 @@
 """Chained converted int8 convolutions on the device: the codes-out entry points qt_q8_conv2d_codes, qt_q8_dwconv2d_codes and
-qt_q8_gemm_codes (csrc/qt_mx_gemm.hip) through the C ABI, the operator quantized_ops.conv2d_qc with its fallbacks, the graph pass
+qt_q8_gemm_codes (csrc/qt_mx_conv.hip, csrc/qt_mx_gemm.hip) through the C ABI, the operator quantized_ops.conv2d_qc with its fallbacks, the graph pass
 fuse_conv_q_chains on converted blocks and their graph capture.
 
 Every comparison is bit for bit: the new path adds no arithmetic whose order is free.  Exact tier: random int8 codes; the reference

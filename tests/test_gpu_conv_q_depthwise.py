@@ -1,4 +1,4 @@
-"""Converted per-tensor int8 depthwise and narrow pointwise convolutions on the device: qt_q8_dwconv2d (csrc/qt_mx_gemm.hip) through the C ABI,
+"""Converted per-tensor int8 depthwise and narrow pointwise convolutions on the device: qt_q8_dwconv2d (csrc/qt_mx_conv.hip) through the C ABI,
 the operator quantized_ops.conv2d_q on its depthwise and pointwise routes, its fallbacks, a converted inverted-residual block and its
 graph capture.  The method is that of tests/test_gpu_conv_q.py.
 

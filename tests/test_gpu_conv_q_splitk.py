@@ -1,4 +1,4 @@
-"""The split of K of the native int8 convolution on the device: qt_q8_conv2d_ws / qt_q8_conv2d_codes_ws (csrc/qt_mx_gemm.hip) through
+"""The split of K of the native int8 convolution on the device: qt_q8_conv2d_ws / qt_q8_conv2d_codes_ws (csrc/qt_mx_conv.hip) through
 the C ABI, the operator conv2d_q on a layer the pass marked (convert_pt2e(split_k=True)), a converted CNN with a projecting 1 x 1
 layer, its graph capture and its chained form.
 

@@ -1,4 +1,4 @@
-"""The block-scaled GEMM for integer and codebook operands (qt_mxi_pack / qt_mxi_gemm, csrc/qt_mx_gemm.hip) and its route through
+"""The block-scaled GEMM for integer and codebook operands (qt_mxi_pack / qt_mxi_gemm, csrc/qt_mxi_gemm.hip) and its route through
 linear_mx / matmul_mx (quantized_training/mx_gemm.py).
 
     C[b][m][n] = rd( bias[n] + sum_kb (sA[b][m][kb] sB[b][n][kb]) * p_kb ),     p_kb = sum over block kb of a[b][m][k] b[b][n][k]

@@ -1,4 +1,4 @@
-"""conv2d_mx, both routes in one process on one box: the operator on the block-scaled matrix instruction (qt_conv2d_mx, csrc/qt_mx_gemm.hip,
+"""conv2d_mx, both routes in one process on one box: the operator on the block-scaled matrix instruction (qt_conv2d_mx, csrc/qt_mx_conv.hip,
 through quantized_training/mx_conv.py) against the composite it replaces (QT_MX_GEMM=0: both operands times their expanded block scales,
 then the library's convolution), on ResNet-50's body layers at batch 32 -- the shapes of profiles/conv2d_routes.txt.
 

@@ -1,4 +1,4 @@
-"""The split of K of the native int8 convolution (qt_q8_conv2d_ws, csrc/qt_mx_gemm.hip), all routes in one process on one box:
+"""The split of K of the native int8 convolution (qt_q8_conv2d_ws, csrc/qt_mx_conv.hip), all routes in one process on one box:
 reducing 1 x 1 and few-tile layers, the shapes on which profiles/conv2d_q.txt shows the unsplit kernel losing to the graph.
 
 Per row, in bf16: the three nodes of the converted graph (quantize + aten.conv2d + dequantize) on an NCHW-contiguous and on a
@@ -12,7 +12,7 @@ calls of each route between two events; median [min, max] per route, for eager c
 The bar is the one of profiles/conv2d_q.txt: the native median must beat the three nodes' median by more than the three nodes' own
 min - max spread, in both layouts and both modes.  It is evaluated for the plan's S (the route a marked layer takes) and printed for
 the unsplit kernel and every forced S as well.  The table this prints is committed as profiles/conv2d_q_splitk.txt; it decides
-pt2e_native._conv_q_split_route_takes and the plan's constants (kConvSplitSet, kConvSplitMinKTiles in csrc/qt_mx_gemm.hip).
+pt2e_native._conv_q_split_route_takes and the plan's constants (kConvSplitSet, kConvSplitMinKTiles in csrc/qt_mx_conv.hip).
 
     timeout -k 10 900 python tools/exp_conv_q_splitk.py [--iters 50] [--repeats 7] [--rows resnet,batch4,mobilenet]
 """

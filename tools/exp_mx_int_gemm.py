@@ -1,5 +1,5 @@
 """linear_mx / matmul_mx on integer operands, both routes in one process on one box: the integer block-scaled GEMM (qt_mxi_pack +
-qt_mxi_gemm, csrc/qt_mx_gemm.hip, through quantized_training/mx_gemm.py) against the composite it replaces (QT_MX_GEMM=0: both operands
+qt_mxi_gemm, csrc/qt_mxi_gemm.hip, through quantized_training/mx_gemm.py) against the composite it replaces (QT_MX_GEMM=0: both operands
 times their expanded block scales, then the library's GEMM).
 
 Rows: LLaMA-2-7B's projections at 1024 tokens in bf16 and fp32 with `int6,bs=64,scale=fp8_e5m3` and `int8,bs=32`; Q . K^T and P . V of
