@@ -235,7 +235,11 @@ int qt_fake_quant_pc_f32(const float *x_dev, float *y_dev, size_t outer, size_t 
  *   s = amax(block) / quant_max; s = scale_lut ? vmap(s, scale_lut) : s; s = s > 0 ? s : 1;
  *   y = vmap(x / s, lut) * s          (all in the tensor's dtype)
  * sf_dev receives the rows * cols / block_size block scales in the tensor's dtype.
- * block_size: power of two, 8..512 (bf16) / 4..256 (fp32); cols % block_size == 0. */
+ * block_size: power of two, 8..512 (bf16) / 4..256 (fp32); cols % block_size == 0.
+ * Declines, all answered before the launch: QT_ERR_BAD_ARG for NULL x / y / sf / fmt, a block_size that is below one 16-byte
+ * vector (8 bf16 / 4 fp32 elements), not a power of two or above 64 vectors (512 / 256), a table format without its table, a
+ * fmt->kind that is none of QT_FMT_*; QT_ERR_UNALIGNED for cols % block_size != 0, x or y off a 16-byte boundary.  quant_max is
+ * not checked (the scale of a block is amax / quant_max whatever it is).  QT_OK without a launch for an empty tensor. */
 int qt_fake_quant_mx_bf16(const uint16_t *x_dev, uint16_t *y_dev, uint16_t *sf_dev, size_t rows, size_t cols,
                           int block_size, const qt_format *fmt, const uint16_t *lut_dev, float quant_max,
                           const uint16_t *scale_lut_dev, void *stream);
@@ -990,7 +994,12 @@ int qt_quantize_codes_nhwc_f32(const float *x_dev, int8_t *codes_dev, long N, lo
  * codes / e8m0 are given (requires force_pow2, block_size % 32 == 0, pack_format = the QT_MX_* format the map rounds
  * to), the packed operand for qt_mx_gemm.  force_pow2: scale = 2^(floor(log2 amax) - floor(log2 quant_max)) with the
  * reference's in-dtype logarithm; otherwise scale = amax / quant_max [-> scale_lut].  block_size: power of two,
- * 8..512 (bf16) / 4..256 (fp32), dividing cols. */
+ * 8..512 (bf16) / 4..256 (fp32), dividing cols.
+ * Declines, all answered before the launch: QT_ERR_BAD_ARG for NULL x / scales / fmt, a block_size that is below one 16-byte
+ * vector (8 bf16 / 4 fp32 elements), not a power of two or above 64 vectors (512 / 256), quant_max <= 0 or NaN, a table format
+ * without its table, only one of codes / e8m0, a pack without force_pow2, with block_size % 32 != 0 or with a pack_format
+ * outside 0..4; QT_ERR_UNALIGNED for cols % block_size != 0, x or q off a 16-byte boundary.  scales and e8m0 are written
+ * element by element; codes in one lane's piece (at most 8 bytes).  QT_OK without a launch for an empty tensor. */
 int qt_quantize_mx_bf16(const uint16_t *x_dev, uint16_t *q_dev, uint16_t *scales_dev, uint8_t *codes_dev, uint8_t *e8m0_dev,
                         size_t rows, size_t cols, int block_size, const qt_format *fmt, const uint16_t *lut_dev,
                         float quant_max, int force_pow2, const uint16_t *scale_lut_dev, int pack_format, void *stream);

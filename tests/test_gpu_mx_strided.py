@@ -17,13 +17,11 @@ import pytest
 import torch
 
 from kernel_launch import Guarded, launch, nv, refused, stream  # noqa: F401
+from mx_cases import (BF16, BITS, F32, IO_IDS, assert_same, bits_of, canon, cpu_pair, expected_pack, maps_for, oracle_fake_quant, qmax_of,
+                      unpack_codes)
 from oracle import qt_oracle as o
 
 pytestmark = pytest.mark.gpu
-
-BF16, F32 = torch.bfloat16, torch.float32
-IO_IDS = {BF16: "bf16", F32: "f32"}
-BITS = {"fp8_e4m3": 8, "fp8_e5m2": 8, "fp6_e2m3": 6, "fp6_e3m2": 6, "fp4_e2m1": 4}
 
 
 def view_of(shape, ax):
@@ -50,46 +48,6 @@ def recipe(shape, ax, bs, dtype, seed, extra=()):
             if not np.isfinite(v):
                 nonfinite.add((oo, c))
     return x.reshape(shape).to(dtype), nonfinite
-
-
-def bits_of(t):
-    """tensor (any device) -> canonical bit patterns on the host"""
-    t = t.detach().cpu().contiguous()
-    if t.dtype == BF16:
-        return o.canon_nan16(t.view(torch.int16).numpy().view(np.uint16))
-    return o.canon_nan32(t.view(torch.int32).numpy().view(np.uint32))
-
-
-def canon(a):
-    return o.canon_nan16(a) if a.dtype == np.uint16 else o.canon_nan32(a)
-
-
-def assert_same(got, want, what):
-    got, want = got.reshape(-1), want.reshape(-1)
-    bad = np.flatnonzero(got != want)
-    assert bad.size == 0, f"{what}: {bad.size} of {want.size} differ, first at {bad[:4]}: got {got[bad[:4]]} expected {want[bad[:4]]}"
-
-
-def maps_for(nv, name, row_form):
-    """(host map, device map, the qt_format of the launch).  row_form: the row words behind the device map (qt_format.p1 bit 0)."""
-    from quantized_training.fake_quantize import _launch_format, get_quantization_map
-    host, devm = get_quantization_map(name, "cpu"), get_quantization_map(name, "cuda")
-    fmt = nv.QtFormat(nv.QT_FMT_LUT, 0, 0, 0.0, 0.0)
-    if row_form:
-        fmt = _launch_format(fmt, devm)
-        assert fmt.p1 & 1, f"{name}: the device map carries no row form"
-    return host, devm, fmt
-
-
-def qmax_of(name):
-    from quantized_training.quantizer.quantizer import get_quant_min_max
-    return float(get_quant_min_max(name)[1])
-
-
-def cpu_pair(x, ax, bs, host_map, qmax, pow2, smap=None):
-    s = torch.ops.quantized_ops.calculate_mx_qparam(x, [ax], bs, qmax, pow2, smap)
-    q = torch.ops.quantized_ops.quantize(x, s, None, [ax], bs, host_map)
-    return s, q
 
 
 def c_quantize(nv, x, ax, bs, fmt, lut, qmax, pow2, smap=None, pack=None, want_q=True, what=""):
@@ -124,15 +82,6 @@ def c_fake_quant(nv, x, ax, bs, fmt, lut, qmax, pow2, smap=None, what=""):
                   smap.data_ptr() if smap is not None else None, stream())
     out = launch(call, {"y": ((outer, n, inner), npdt), "s": ((outer, n // bs, inner), npdt)}, what)
     return {k: canon(v) for k, v in out.items()}
-
-
-def oracle_fake_quant(x, ax, bs, name, qmax, pow2, smap_name=None):
-    xf = x.float().numpy()
-    y, s = o.mx_fake_quant(xf, x.dtype == BF16, o.get_quantization_map(name), ax, bs, qmax, pow2,
-                           o.get_quantization_map(smap_name) if smap_name else None)
-    if x.dtype == BF16:
-        return o.canon_nan16(o.f32_to_bf16(y).reshape(y.shape)), o.canon_nan16(o.f32_to_bf16(s).reshape(s.shape))
-    return o.canon_nan32(np.ascontiguousarray(y, np.float32).view(np.uint32)), o.canon_nan32(np.ascontiguousarray(s, np.float32).view(np.uint32))
 
 
 # ---- 1. layout sweep through the C ABI ----------------------------------------------------------------------------------------------
@@ -229,21 +178,6 @@ def test_scale_map(nv, dtype):
 PACK_SHAPES = [(3, 64, 80), (1, 32, 24), (2, 160, 16), (2, 192, 16)]     # [B, K, N]; K = 160, 192: a multi-block tile ends ragged
 
 
-def expected_pack(s_ref, q_ref, name, bs):
-    """-> (codes, e8m0, rows compared).  Columns whose values and scales are finite; a block whose scale is below 2^-127 is flushed:
-    codes 0 and byte 0, which is what mx_pack makes of zeros at scale 2^-127."""
-    B, K, N = q_ref.shape
-    qt = q_ref.float().transpose(1, 2).reshape(B * N, K).numpy().astype(np.float64)
-    st = s_ref.float().transpose(1, 2).reshape(B * N, K // bs).numpy().astype(np.float64)
-    rows = np.flatnonzero(np.isfinite(qt).all(axis=1) & np.isfinite(st).all(axis=1))
-    qt, st = qt[rows].copy(), st[rows].copy()
-    flushed = st < 2.0 ** -127
-    qt[np.repeat(flushed, bs, axis=1)] = 0.0
-    st[flushed] = 2.0 ** -127
-    codes, e8 = o.mx_pack(qt, st, name, bs)
-    return codes, e8, rows, int(flushed.sum())
-
-
 @pytest.mark.parametrize("dtype", [BF16, F32], ids=IO_IDS.get)
 @pytest.mark.parametrize("name", sorted(BITS))
 def test_pack_equals_the_host_packer(nv, name, dtype):
@@ -294,13 +228,6 @@ def test_pack_with_blocks_of_64_and_96(nv):
         assert_same(got["q"], bits_of(q_ref), f"q bs={bs}")
         assert_same(got["codes"][rows], want_codes, f"codes bs={bs}")
         assert_same(got["e8"][rows], want_e8, f"e8m0 bs={bs}")
-
-
-def unpack_codes(codes, bits):
-    """[rows, K bits / 8] bytes -> [rows, K] element codes (element i in bits [i bits, (i + 1) bits) of the row, little-endian)"""
-    b = np.unpackbits(np.ascontiguousarray(codes), axis=1, bitorder="little")
-    b = b.reshape(codes.shape[0], -1, bits).astype(np.uint32)
-    return (b << np.arange(bits, dtype=np.uint32)).sum(axis=-1)
 
 
 @pytest.mark.parametrize("dtype", [BF16, F32], ids=IO_IDS.get)
