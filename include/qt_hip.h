@@ -180,6 +180,30 @@ int qt_fake_quant_bf16_fp8(const uint16_t *x_dev, uint16_t *y_dev, uint8_t *y8_d
 int qt_fake_quant_bf16_fp8_multi(const uint16_t *const *xs_dev, const size_t *ns, int count, uint8_t *y8_dev,
                                  const qt_format *fmt, void *stream);
 
+/* ---- FusedAmaxObsFakeQuantize's record_histogram option          fake_quantize.py:348-350
+ *     exp = floor(log2(|float(x)|));  histogram += histc(exp, 254, min=-126, max=127)
+ * as ONE launch that reads x once.  For a bf16 / fp16 element the bin is the exponent field E of its exact fp32 image: 1 <= E <= 254
+ * counts into bin E - 1; zeros, fp32-subnormal magnitudes (E = 0), inf and NaN (E = 255) count nowhere, as histc leaves them out.
+ * (There is no fp32 entry: floor(log2f(x)) rounds up just below a power of two, which the closed form does not reproduce.)
+ * Per call and per bin:  hist[b] = fl32(hist[b] + fl32(c_b)),  c_b the EXACT count of the call -- the composite's result whenever its
+ * own count is exact (no bin takes more than 2^24 elements in one call; beyond that histc saturates or depends on the order of its
+ * atomics on the device, and the exact count is the definition).  Integer counting only, no float atomics: run-to-run bit-identical.
+ * hist_f32_dev [254] fp32; counts_u32_dev [256] and ticket_dev [1]: scratch, ZERO before the first launch, left zero by every
+ * launch, used by one ordered sequence of launches only.  Any 2-byte aligned x, any n < 2^32 (QT_ERR_BAD_ARG above: counts are u32);
+ * n == 0 launches nothing.  qt_exp_histogram_plan: the elements one workgroup takes per round and the largest grid (host only). */
+int qt_exp_histogram_bf16(const uint16_t *x_dev, size_t n, float *hist_f32_dev, uint32_t *counts_u32_dev, uint32_t *ticket_dev,
+                          void *stream);
+int qt_exp_histogram_f16(const uint16_t *x_dev, size_t n, float *hist_f32_dev, uint32_t *counts_u32_dev, uint32_t *ticket_dev,
+                         void *stream);
+int qt_exp_histogram_plan(size_t *tile_elems, size_t *max_workgroups);
+/* qt_fake_quant_bf16 that takes the histogram of its INPUT (each element as it is read, before the division by the scale) on the way:
+ * y and the amax slot are qt_fake_quant_bf16's bit for bit, hist is qt_exp_histogram_bf16's.  One launch for 16-byte aligned x / y of
+ * n >= 4096 in a closed-form format (intN, FP8-like) or a table format in its row form short enough to read the rows from global
+ * memory; anything else runs qt_exp_histogram_bf16 followed by the unchanged qt_fake_quant_bf16 -- two launches, the same results. */
+int qt_fake_quant_hist_bf16(const uint16_t *x_dev, uint16_t *y_dev, size_t n, const qt_format *fmt, const uint16_t *lut_dev,
+                            const float *scale_f32_dev, uint32_t *amax_bits_dev, float *hist_f32_dev, uint32_t *counts_u32_dev,
+                            uint32_t *ticket_dev, void *stream);
+
 /* Many per-tensor fake-quant calls of ONE format as one launch: item i is `qt_fake_quant_bf16(x, y, 8 * nvec, fmt, lut, scale, amax)`
  * with its own scale and amax slot (fake_quantize.py:230-246 per tensor, unchanged).  For the weight fake-quantizers of a training
  * step (modules/qat/linear.py:40-41 issues one per Linear and forward; run_glue_no_trainer.py:647-667): the weights do not change

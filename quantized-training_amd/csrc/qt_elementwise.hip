@@ -19,6 +19,7 @@
 #include "qt_device.h"
 #include "qt_chain.h"
 #include "qt_dispatch.h"
+#include "qt_histogram.h"
 #include "qt_qdq.h"
 
 extern "C" float qt_internal_posit_threshold(int nbits, int es);
@@ -97,9 +98,10 @@ __device__ __forceinline__ void st_vec(uint4 *p, uint4 v, bool nt) {
     }
 }
 
-template <int IO, int KIND, int DIV, bool OBS, int BLOCK, int kUnroll, int NT>
+// HIST (bf16 only): every input vector is also counted into the workgroup's exponent-histogram rows `hs` (qt_histogram.h), as it was read.
+template <int IO, int KIND, int DIV, bool OBS, int BLOCK, int kUnroll, int NT, bool HIST = false>
 __device__ __forceinline__ void fq_stream(const uint4 *__restrict__ x, uint4 *__restrict__ y, size_t nvec, const UniformDiv &dv,
-                                          const Rounder<KIND> &rnd, uint32_t &amax) {
+                                          const Rounder<KIND> &rnd, uint32_t &amax, uint32_t *hs = nullptr) {
     constexpr size_t kTile = (size_t)BLOCK * kUnroll;
     const size_t nfull = nvec / kTile;
     for (size_t t = blockIdx.x; t < nfull; t += gridDim.x) {
@@ -109,6 +111,7 @@ __device__ __forceinline__ void fq_stream(const uint4 *__restrict__ x, uint4 *__
         for (int u = 0; u < kUnroll; ++u) v[u] = ld_vec(x + base + (size_t)u * BLOCK, NT & 1);
 #pragma unroll
         for (int u = 0; u < kUnroll; ++u) {
+            if constexpr (HIST) hist_add_vec<false>(hs, v[u]);
             uint4 r = fq_vec<IO, KIND, DIV, OBS>(v[u], dv, rnd, amax);
             if (y) st_vec(y + base + (size_t)u * BLOCK, r, NT & 2);
         }
@@ -116,7 +119,9 @@ __device__ __forceinline__ void fq_stream(const uint4 *__restrict__ x, uint4 *__
     // ragged last tile: the block that would own it in the grid-stride order
     if (nfull % gridDim.x == blockIdx.x) {
         for (size_t i = nfull * kTile + threadIdx.x; i < nvec; i += BLOCK) {
-            uint4 r = fq_vec<IO, KIND, DIV, OBS>(x[i], dv, rnd, amax);
+            const uint4 v = x[i];
+            if constexpr (HIST) hist_add_vec<false>(hs, v);
+            uint4 r = fq_vec<IO, KIND, DIV, OBS>(v, dv, rnd, amax);
             if (y) y[i] = r;
         }
     }
@@ -139,10 +144,14 @@ __device__ __forceinline__ void fq_stream(const uint4 *__restrict__ x, uint4 *__
 // most of a [2048, 768] launch's 10.9 us queueing there.
 constexpr int kTableLds = 0, kTableGlobal = 1;
 
-template <int IO, int KIND, bool OBS, int BLOCK, int kUnroll = 1, int NT = 0, int TABLE = kTableLds>
+// HIST: the pass also takes the exponent histogram of its input (qt_fake_quant_hist_bf16): `hist` is that state, a parameter the other
+// instantiations do not have (the pack is empty there: even an empty struct would move the hidden kernel arguments behind it), and the
+// 32 KiB of replica rows exist in these instantiations only.
+template <int IO, int KIND, bool OBS, int BLOCK, int kUnroll = 1, int NT = 0, int TABLE = kTableLds, bool HIST = false, typename... H>
 __global__ __launch_bounds__(BLOCK) void fq_kernel(const void *__restrict__ xv, void *__restrict__ yv, size_t nvec,
                                                   size_t n, qt_format fmt, const uint16_t *__restrict__ lut,
-                                                  const float *__restrict__ scale, uint32_t *amax_out) {
+                                                  const float *__restrict__ scale, uint32_t *amax_out, H... hist) {
+    static_assert(sizeof...(H) == (HIST ? 1 : 0), "HIST instantiations take one HistArgs, the others nothing");
     constexpr bool kMapInLds = KIND == QT_FMT_LUT && TABLE == kTableLds, kRowsInLds = KIND == kFmtRows && TABLE == kTableLds;
     __shared__ uint4 s_table[kMapInLds ? kMapVecs : (kRowsInLds ? 512 : 1)];
     Rounder<KIND> rnd{fmt, lut, lut};
@@ -157,14 +166,26 @@ __global__ __launch_bounds__(BLOCK) void fq_kernel(const void *__restrict__ xv, 
     }
     const PassScale ps = pass_scale<IO>(scale);
     uint32_t amax = 0;
+    uint32_t *hs = nullptr;
+    if constexpr (HIST) {
+        static_assert(IO == kIoBf16, "the exponent field is read from bf16 words");
+        __shared__ uint32_t s_hist[kHistWords];
+        hs = s_hist;
+        hist_lds_zero<BLOCK>(s_hist);
+        __syncthreads();
+    }
     with_div(ps, [&](auto div) __attribute__((always_inline)) {
-        fq_stream<IO, KIND, decltype(div)::value, OBS, BLOCK, kUnroll, NT>((const uint4 *)xv, (uint4 *)yv, nvec, ps.dv, rnd, amax);
+        fq_stream<IO, KIND, decltype(div)::value, OBS, BLOCK, kUnroll, NT, HIST>((const uint4 *)xv, (uint4 *)yv, nvec, ps.dv, rnd, amax, hs);
     });
     constexpr int kPer = IO == kIoBf16 ? 8 : 4;
     if (blockIdx.x == gridDim.x - 1) {
-        for (size_t i = nvec * kPer + threadIdx.x; i < n; i += BLOCK) fq_one<IO, KIND, OBS>(xv, yv, i, ps.s, ps.unit, rnd, amax);
+        for (size_t i = nvec * kPer + threadIdx.x; i < n; i += BLOCK) {
+            if constexpr (HIST) hist_add_elem<false>(hs, ((const uint16_t *)xv)[i]);
+            fq_one<IO, KIND, OBS>(xv, yv, i, ps.s, ps.unit, rnd, amax);
+        }
     }
     if constexpr (OBS) block_amax_commit<BLOCK>(amax, amax_out);
+    if constexpr (HIST) hist_commit<BLOCK>(hs, hist...);
 }
 
 // Element-granular variant with the table read from global memory (L1/L2-resident, 128 KiB):
@@ -1483,6 +1504,31 @@ int launch_fq_kind(const void *x, void *y, size_t n, const qt_format &fmt, const
     return qt_launch_status();
 }
 
+// qt_fake_quant_hist_bf16's one-launch form: 1024-thread workgroups, at most two per compute unit (each carries 32 KiB of histogram
+// rows and ends in the histogram's agent-scope adds, so there are few), for the closed forms and the row form read where it lies.
+// False: not taken (the caller runs the histogram's own launch and the unchanged pass).
+template <int KIND>
+bool launch_fq_hist_kind(const void *x, void *y, size_t n, const qt_format &fmt, const uint16_t *lut, const float *scale, uint32_t *amax,
+                         const HistArgs &h, hipStream_t st) {
+    const size_t nv = n / 8;
+    const unsigned grid = grid_for(nv, 1024 * 2, 2);
+    constexpr int kTable = KIND == kFmtRows ? kTableGlobal : kTableLds;
+    qt_pick_bool(amax != nullptr, [&](auto OBS) {
+        fq_kernel<kIoBf16, KIND, decltype(OBS)::value, 1024, 1, 0, kTable, true><<<grid, 1024, 0, st>>>(x, y, nv, n, fmt, lut, scale, amax, h);
+    });
+    return true;
+}
+
+bool launch_fq_hist(const void *x, void *y, size_t n, const qt_format &fmt, const uint16_t *lut, const float *scale, uint32_t *amax,
+                    const HistArgs &h, hipStream_t st) {
+    if (!y || n < 4096 || ((((uintptr_t)x | (uintptr_t)y) & 15u) != 0)) return false;          // launch_fq_kind's gather cases
+    if (fmt.kind == QT_FMT_FP_SAT) return launch_fq_hist_kind<QT_FMT_FP_SAT>(x, y, n, fmt, lut, scale, amax, h, st);
+    if (fmt.kind == QT_FMT_INT) return launch_fq_hist_kind<QT_FMT_INT>(x, y, n, fmt, lut, scale, amax, h, st);
+    if (fmt.kind == QT_FMT_LUT && lut && (fmt.p1 & 1) && n / 8 <= kRowsDirectMaxVecs)
+        return launch_fq_hist_kind<kFmtRows>(x, y, n, fmt, lut, scale, amax, h, st);
+    return false;
+}
+
 template <int IO>
 int launch_fq(const void *x, void *y, size_t n, const qt_format *fmt, const uint16_t *lut, const float *scale,
               uint32_t *amax, void *stream) {
@@ -1663,6 +1709,16 @@ int qt_fake_quant_bf16(const uint16_t *x, uint16_t *y, size_t n, const qt_format
 int qt_fake_quant_f32(const float *x, float *y, size_t n, const qt_format *fmt, const uint16_t *lut, const float *scale,
                       uint32_t *amax, void *stream) {
     return launch_fq<kIoF32>(x, y, n, fmt, lut, scale, amax, stream);
+}
+int qt_fake_quant_hist_bf16(const uint16_t *x, uint16_t *y, size_t n, const qt_format *fmt, const uint16_t *lut, const float *scale,
+                            uint32_t *amax, float *hist, uint32_t *counts, uint32_t *ticket, void *stream) {
+    if (n == 0) return QT_OK;
+    if (!x || !fmt || (!y && !amax) || !hist || !counts || !ticket || n > 0xFFFFFFFFull) return QT_ERR_BAD_ARG;
+    if (((uintptr_t)x | (uintptr_t)y) % 2 || (((uintptr_t)hist | (uintptr_t)counts | (uintptr_t)ticket) & 3u)) return QT_ERR_UNALIGNED;
+    if (fmt->kind == QT_FMT_LUT && y && !lut) return QT_ERR_BAD_ARG;
+    if (launch_fq_hist(x, y, n, *fmt, lut, scale, amax, HistArgs{hist, counts, ticket}, (hipStream_t)stream)) return qt_launch_status();
+    if (const int rc = qt_exp_histogram_bf16(x, n, hist, counts, ticket, stream)) return rc;
+    return launch_fq<kIoBf16>(x, y, n, fmt, lut, scale, amax, stream);
 }
 int qt_fake_quant_pc_bf16(const uint16_t *x, uint16_t *y, size_t outer, size_t C, size_t inner, const qt_format *fmt,
                           const uint16_t *lut, const float *scale, uint32_t *amax, void *stream) {

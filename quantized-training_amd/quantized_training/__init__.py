@@ -29,6 +29,7 @@ from .quantize_pt2e import (  # noqa: F401
 from .quantizer import XNNPACKQuantizer, QuantizationConfig, get_node_name_to_scope  # noqa: F401
 from .training_args import add_qspec_args  # noqa: F401
 from .utils import setup_logging  # noqa: F401
+from .histogram import get_grouped_histogram, plot_histogram, plot_layer_range  # noqa: F401
 from . import modules  # noqa: F401
 
 __all__ = [
@@ -37,7 +38,7 @@ __all__ = [
     "quantize_to_fp8_e4m3", "quantize_to_fp8_e5m2", "quantize_to_posit", "quantize_to_nf", "replace_softmax",
     "setup_logging", "get_quantization_map", "vmap", "dequantize",
     "get_default_quantizer", "prepare_pt2e", "convert_pt2e", "export_model", "derive_bias_qparams_fn",
-    "get_node_name_to_scope",
+    "get_node_name_to_scope", "get_grouped_histogram", "plot_histogram", "plot_layer_range",
 ]
 
 

@@ -112,6 +112,10 @@ SIGNATURES = {
     "qt_fake_quant_bf16": (c_int, [_P, _P, c_size_t, _FMT, _P, _P, _P, _P]),
     "qt_fake_quant_f32": (c_int, [_P, _P, c_size_t, _FMT, _P, _P, _P, _P]),
     "qt_fake_quant_bf16_fp8": (c_int, [_P, _P, _P, c_size_t, _FMT, _P, _P, _P]),
+    "qt_exp_histogram_bf16": (c_int, [_P, c_size_t, _P, _P, _P, _P]),
+    "qt_exp_histogram_f16": (c_int, [_P, c_size_t, _P, _P, _P, _P]),
+    "qt_exp_histogram_plan": (c_int, [POINTER(c_size_t), POINTER(c_size_t)]),
+    "qt_fake_quant_hist_bf16": (c_int, [_P, _P, c_size_t, _FMT, _P, _P, _P, _P, _P, _P, _P]),
     "qt_fake_quant_rows_bf16": (c_int, [_P, _P, c_long, c_long, c_long, c_long, c_long, c_long, c_long, _FMT, _P, _P, _P, _P]),
     "qt_fake_quant_mx_bf16": (c_int, [_P, _P, _P, c_size_t, c_size_t, c_int, _FMT, _P, c_float, _P, _P]),
     "qt_fake_quant_mx_f32": (c_int, [_P, _P, _P, c_size_t, c_size_t, c_int, _FMT, _P, c_float, _P, _P]),

@@ -24,7 +24,7 @@ from typing import Optional
 import torch
 from torch.ao.quantization import FakeQuantizeBase
 
-from . import _native, handover, mx_operand, precomputed
+from . import _native, handover, histogram, mx_operand, precomputed
 from .quantizer.quantizer import QScheme
 
 # (forward() tests its own __dict__ for these before it calls into precomputed: a call nothing was left for pays one lookup per slot)
@@ -352,8 +352,9 @@ def _channel_view(shape, ch_axis):
     return outer, shape[ax], inner
 
 
-def _hip_fake_quant(x, y, fmt, lut, scale, amax_hist, per_channel, ch_axis):
-    """One fused HIP pass.  y may be None (observe only); amax_hist may be None (observer off)."""
+def _hip_fake_quant(x, y, fmt, lut, scale, amax_hist, per_channel, ch_axis, hist_state=None):
+    """One fused HIP pass.  y may be None (observe only); amax_hist may be None (observer off).  hist_state (histogram.fused_state):
+    the per-tensor bf16 pass also adds the exponent histogram of x to its buffer (qt_fake_quant_hist_bf16)."""
     L = _native.lib()
     n = x.numel()
     if n == 0:
@@ -364,10 +365,18 @@ def _hip_fake_quant(x, y, fmt, lut, scale, amax_hist, per_channel, ch_axis):
     sp = scale.data_ptr() if scale is not None else None
     ap = amax_hist.data_ptr() if amax_hist is not None else None     # slot 0 of the history
     st = _stream_ptr(x)
+    if hist_state is not None and (per_channel or not bf16):
+        raise _native.QtError("record_histogram: the fused pass is the per-tensor bf16 launch only")      # (never a silent drop)
     if per_channel:
         outer, C, inner = _channel_view(tuple(x.shape), ch_axis)
         fn = L.qt_fake_quant_pc_bf16 if bf16 else L.qt_fake_quant_pc_f32
         _native.check(fn(xp, yp, outer, C, inner, ctypes.byref(_launch_format(fmt, lut)), lp, sp, ap, st), "qt_fake_quant_pc")
+    elif hist_state is not None:
+        hist, counts, ticket = hist_state
+        _native.check(L.qt_fake_quant_hist_bf16(xp, yp, n, ctypes.byref(_launch_format(fmt, lut)), lp, sp, ap, hist.data_ptr(), counts, ticket,
+                                                st), "qt_fake_quant_hist")
+        histogram.STATS["histogram_fused"] += 1
+        return
     else:
         fn = L.qt_fake_quant_bf16 if bf16 else L.qt_fake_quant_f32
         _native.check(fn(xp, yp, n, ctypes.byref(_launch_format(fmt, lut)), lp, sp, ap, st), "qt_fake_quant")
@@ -430,7 +439,9 @@ class FusedAmaxObsFakeQuantFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, input, observer_enabled, fake_quant_enabled, qmap, amax_history, scale,
                 amax_history_len, quant_max, ch_axis=None, per_row_fake_quant=False,
-                force_scale_power_of_two=False, qt_format=None, emit_fp8=None):
+                force_scale_power_of_two=False, qt_format=None, emit_fp8=None, hist_state=None):
+        # hist_state (histogram.fused_state, the module's record_histogram option): the plain per-tensor bf16 launch at the end also
+        # takes the exponent histogram of `input`; the module passes it only where the call ends in that launch
         observe = _as_flag(observer_enabled)
         quantize = _as_flag(fake_quant_enabled)
         if not observe and not quantize:
@@ -484,12 +495,12 @@ class FusedAmaxObsFakeQuantFunction(torch.autograd.Function):
                 raise ValueError(f"per-channel scale has {scale.numel()} entries, tensor has "
                                  f"{_channel_view(tuple(x.shape), ch_axis)[1]} channels on axis {ch_axis}")
             per_channel = False                                         # single broadcast scale
-        _hip_fake_quant(x, y, fmt, qmap, scale, amax_history if observe else None, per_channel, ch_axis)
+        _hip_fake_quant(x, y, fmt, qmap, scale, amax_history if observe else None, per_channel, ch_axis, hist_state)
         return y if quantize else input
 
     @staticmethod
     def backward(ctx, grad_output, *unused):
-        return (grad_output,) + (None,) * 12
+        return (grad_output,) + (None,) * 13
 
 
 class MXFakeQuantFunction(torch.autograd.Function):
@@ -974,9 +985,15 @@ class FusedAmaxObsFakeQuantize(FakeQuantizeBase):
                 return _PrecomputedFakeQuant.apply(X, out)
         self._move_to(X.device)
 
-        if self.record_histogram:                                            # upstream :348-350
-            exp = torch.floor(torch.log2(torch.abs(X.detach().float())))
-            self.histogram += torch.histc(exp, 254, min=-126, max=127)
+        hist_state = None
+        if self.record_histogram:                                            # upstream :348-350 (histogram.py: kernel or composite)
+            # the plain per-tensor launch of qt_fake_quant_bf16 below takes the histogram on the way; every other path gets it in front
+            if (self._quantize and self.outlier_threshold is None and not self.is_per_channel
+                    and self.qscheme not in (QScheme.MICROSCALING, QScheme.GROUP_WISE_AFFINE)
+                    and not (self._emit_fp8 and self.fp8_exact())):
+                hist_state = histogram.fused_state(X, self.histogram)
+            if hist_state is None:
+                histogram.record(X, self.histogram)
 
         if self.outlier_threshold is not None:                              # upstream :353-359
             orig_X = X.clone()
@@ -1009,7 +1026,7 @@ class FusedAmaxObsFakeQuantize(FakeQuantizeBase):
             X, self._observe, self._quantize, self.qmap, self.amax_history, self.scale,
             self.amax_history_len, self.quant_max, self.ch_axis, self.is_per_channel,
             self.force_scale_power_of_two, self._qt_format,
-            self._emit_fp8 if (self._emit_fp8 and self.fp8_exact()) else None,
+            self._emit_fp8 if (self._emit_fp8 and self.fp8_exact()) else None, hist_state,
         )
         if isinstance(X, tuple):
             X, x8 = X

@@ -3,7 +3,9 @@ when it is called (nothing is cached: a switch may be flipped in mid-process); a
 checked against this one (tests/test_switches_cpu.py).
 kinds       ON: on unless "0" | OFF: off unless "1" | TRI: "auto" / "0" / "1", anything else counts as "auto" |
             LEVEL: "0" / "1" / "2", anything else counts as "1" | MASK: an integer in any base Python reads | RAW: the string itself
-categories  product: read by the package | native: read by libqt_hip.so | bench: read by bench.py   (the last two: listed only)"""
+categories  product: read by the package | native: read by libqt_hip.so | bench: read by bench.py   (the last two: listed only) |
+            option: read by the package too -- the route of a per-call quantizer option, added after the 27 `product` switches whose
+            names tests/test_switches_cpu.py pins"""
 import os
 
 ON, OFF, TRI, LEVEL, MASK, RAW = "on", "off", "tri", "level", "mask", "raw"
@@ -36,6 +38,7 @@ SWITCHES = {
     "QT_CONV_GEMM": ("auto", TRI, "product", "in-tree implicit-GEMM Conv2d: by the committed rule / never / wherever it applies"),
     "QT_TRAIN_GEMM": ("1", ON, "product", "training step: a QAT Linear's three products on qt_train_gemm_bf16 (else torch's GEMMs)"),
     "QT_HIP_LIB": (None, RAW, "product", "tools only: load another build of the library"),
+    "QT_HISTOGRAM": ("1", ON, "option", "record_histogram on bf16 / fp16 device tensors as one HIP launch (else the torch composite)"),
     "QT_MX_WIDE": (None, RAW, "native", "test hook: force the 128 x 128 / the wide block-scaled kernel"),
     "QT_MX_WIDE_TM": (None, RAW, "native", "test hook: the wide block-scaled kernel's tile height"),
     "QT_BENCH_DROPOUT": (None, RAW, "bench", "bench.py, training workload: another dropout probability"),
