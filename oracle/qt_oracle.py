@@ -616,16 +616,21 @@ def softmax_fq_f32(scores, mask, scaling, qmap):
     return p, (vmap_f32(p, qmap) if qmap is not None else p)
 
 
-def attention_fq(q_bits, k_bits, v_bits, mask_bits, scaling, qmap):
+def attention_fq(q_bits, k_bits, v_bits, mask_bits, scaling, qmap, scale_bits=None):
     """q [B,H,Sq,D], k / v [B,H,Sk,D] as uint16 bf16 patterns (already fake-quantized); returns the attention output
-    [B,H,Sq,D] as bf16 patterns plus the quantized probabilities' patterns."""
+    [B,H,Sq,D] as bf16 patterns plus the quantized probabilities' patterns.  scale_bits: the bf16 pattern of the probabilities'
+    fake-quantizer's scale (fq_bf16), None for unit scale."""
     q = bf16_to_f32(q_bits).astype(np.float64)
     k = bf16_to_f32(k_bits).astype(np.float64)
     v = bf16_to_f32(v_bits).astype(np.float64)
-    scores = f32_to_bf16(np.einsum("bhqd,bhkd->bhqk", q, k).astype(np.float32))
-    _, pq_bits = softmax_fq(scores, mask_bits, scaling, qmap)
-    pq = bf16_to_f32(pq_bits).astype(np.float64)
-    out = np.einsum("bhqk,bhkd->bhqd", pq, v)
+    with np.errstate(invalid="ignore"):
+        scores = f32_to_bf16(np.einsum("bhqd,bhkd->bhqk", q, k).astype(np.float32))
+    with np.errstate(invalid="ignore", over="ignore"):
+        p_bits, pq_bits = softmax_fq(scores, mask_bits, scaling, qmap)
+        if scale_bits is not None and qmap is not None:
+            pq_bits = fq_bf16(p_bits, qmap, np.asarray(scale_bits, U16))
+        pq = bf16_to_f32(pq_bits).astype(np.float64)
+        out = np.einsum("bhqk,bhkd->bhqd", pq, v)
     return f32_to_bf16(out.astype(np.float32)), pq_bits
 
 
@@ -1083,3 +1088,212 @@ def gelu(x_bits):
     x_bits = np.asarray(x_bits, U16)
     v, rho, lo, hi = _gelu_table()
     return RowInterval(v[x_bits], rho[x_bits], lo[x_bits], hi[x_bits])
+
+
+# ---- the attention cores: fused QK^T, scaling, mask, softmax, fq_P, P.V (csrc/qt_attention.hip, qt_attention_rows.hip, qt_attention_fp8.hip)
+class AttentionIntervals(NamedTuple):
+    """What attention_interval() returns."""
+    out: RowInterval            # O, [B, H, Sq, D]
+    probs: RowInterval          # P' = fq_P(P), [B, H, Sq, Sk]
+    amax: RowInterval           # the observer's amax: the largest P in front of fq_P, shape (1,)
+    pv_exact: np.ndarray        # bool [B, H, Sq]: the P'.V sums of the row carry no radius (exact in fp32 in any order)
+
+
+ATTENTION_KERNELS = ("online", "strip", "strip_fp8")
+
+
+def _lowbit(x):
+    """The weight of the lowest set bit of |x| (float64); inf for 0 and for non-finite x.  Every x is an integer multiple of it."""
+    x = np.asarray(x, np.float64)
+    ok = np.isfinite(x) & (x != 0)
+    m, e = np.frexp(np.where(ok, np.abs(x), 1.0))
+    M = (m * 2.0 ** 53).astype(np.int64)
+    return np.where(ok, np.ldexp((M & -M).astype(np.float64), e - 53), np.inf)
+
+
+def _sums_exact_in_f32(abs_sum, granule):
+    """A sum whose terms are integer multiples of `granule` and whose absolute values add up to abs_sum: every partial sum, in any order,
+    is a multiple of the granule of magnitude <= abs_sum, so it has at most 24 significant bits -- exact in fp32 -- when
+    abs_sum <= 2^24 granule."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        return np.where(np.isfinite(granule), abs_sum <= 2.0 ** 24 * granule, True)
+
+
+def attention_probs_interval(t, kernel):
+    """The probabilities of one attention core from its bit-defined logits t = bf16(bf16(S x scaling) + mask) (float64, [..., Sk]), with
+    the admissible interval of p = bf16(exp(t - max) / sum): v = exp(a) / sum exp(a), a = t - max, exp and the sum in float64.  The error
+    model is softmax_interval's (U_F32, SUM_DEPTH, the __expf term, the 2^-126 allowance); the radius follows how the kernel forms the sum.
+
+    kernel = "strip" (and "strip_fp8", the same softmax) -- qt_attention_rows.hip:249-277, qt_attention_fp8.hip:263-291 and the
+      probability at rows:306 / fp8:318.  The whole
+      strip is in registers, the maximum is final before any exponential: e_i = exp2((t_i - max) * log2e) once per logit (the subtraction
+      of two bf16 values rounds: u |a|; the product with log2e and v_exp_f32: the __expf term), so rel_i = (2 + 1.4427 |a_i|) 2^-23 + u |a_i|.
+      The sum: at most 64 serial additions per lane and accumulator (two accumulators, 8 blocks x 4 tiles x 2), their sum, two shuffles
+      and the other key group's half: 68 <= d = SUM_DEPTH.  1 / sum: 4 u; e * inv: u.
+          rho = v (rel_i + sum_j v_j rel_j + (d + 5) u) + 2^-126                          (softmax_interval's radius, unchanged)
+    kernel = "online" -- qt_attention.hip:302-338 (pass 1) and :361 (pass 2).  Pass 1 walks 64-key tiles with a running maximum:
+      l = l * __expf(m - ref) + part, part = sum over the tile of __expf(t - ref), ref = the maximum so far.  A term's exponential
+      therefore is a PRODUCT of up to K exponentials whose non-positive arguments telescope: |t - ref| + sum |m_i - m_i+1| = |t - max|.
+      Only their count grows: K = 1 + the number of tiles at which the row's running maximum rises (__expf(0) = 1 and l * 1 are
+      exact), so rel'_j = (2 K + 1.4427 |a_j|) 2^-23 + u |a_j| for the SUM's terms.  The sum's depth: 16 additions per lane and tile, two
+      shuffles, and one product and one addition per tile: d' = SUM_DEPTH + 2 ntiles.  Pass 2 evaluates __expf(t - max) * (1 / l) with
+      the final maximum: the element's own factor is rel_i with ONE exponential, 1 / l: 4 u, the product u.
+          rho = v (rel_i + sum_j v_j rel'_j + (d' + 5) u) + 2^-126
+      Skipped key tiles (qt_attention.hip:240-299) hold logits <= -1e30 for every row of the workgroup: their exponentials are exactly 0
+      counted or not, unless the row has no other key -- and then the kernel counts every tile again (:335-336).
+    Where a < -104.5 every fp32 evaluation gives exactly 0 (softmax_interval); a row holding a NaN or a +inf logit, and a row of -inf
+    logits only (inf - inf), is NaN in every element, as torch's softmax gives.  A row of equal finite logits (all keys at the bf16
+    minimum: fully masked) is the uniform row over all Sk keys.  Returns the RowInterval of p (lo >= 0)."""
+    if kernel not in ATTENTION_KERNELS:
+        raise ValueError(f"kernel must be one of {ATTENTION_KERNELS}")
+    t = np.asarray(t, np.float64)
+    Sk = t.shape[-1]
+    with np.errstate(all="ignore"):
+        a = t - t.max(axis=-1, keepdims=True)
+        e = np.exp(a)
+        s = e.sum(axis=-1, keepdims=True)
+        v = e / s
+        fin = np.isfinite(a)
+        absa = np.where(fin, np.abs(a), 0.0)
+        rel = np.where(fin, (2 + 1.4427 * absa) * 2.0 ** -23 + U_F32 * absa, 0.0)
+        if kernel == "online":
+            ntiles = -(-Sk // 64)
+            pad = np.full(t.shape[:-1] + (ntiles * 64 - Sk,), -np.inf)
+            tm = np.concatenate([t, pad], axis=-1).reshape(t.shape[:-1] + (ntiles, 64)).max(axis=-1)
+            run = np.maximum.accumulate(tm, axis=-1)
+            K = 1 + (run[..., 1:] > run[..., :-1]).sum(axis=-1, keepdims=True)
+            rel_sum = np.where(fin, (2 * K + 1.4427 * absa) * 2.0 ** -23 + U_F32 * absa, 0.0)
+            depth = SUM_DEPTH + 2 * ntiles
+        else:
+            rel_sum, depth = rel, SUM_DEPTH
+        rho = v * (rel + (v * rel_sum).sum(axis=-1, keepdims=True) + (depth + 5) * U_F32) + 2.0 ** -126
+        gone = a < -104.5
+        v, rho = np.where(gone, 0.0, v), np.where(gone, 0.0, rho)
+        nanrow = np.broadcast_to(np.isnan(s), v.shape)
+        v, rho = np.where(nanrow, np.nan, v), np.where(nanrow | np.isnan(v), np.nan, rho)
+        iv = _interval(v, rho)
+        neg = bf16_order(iv.lo) < 0
+    return RowInterval(iv.v, iv.rho, np.where(neg & ~iv.nan, U16(0), iv.lo), iv.hi)
+
+
+def _prob_fq(qmap, scale_bits):
+    """fq_P on bf16 patterns: identity, the value map, or the map between bf16(p / s) and bf16(. * s)."""
+    if qmap is None:
+        return lambda bits: canon_nan16(bits)
+    if scale_bits is None:
+        return lambda bits: canon_nan16(vmap_bf16(bits, qmap))
+    return lambda bits: canon_nan16(fq_bf16(bits, qmap, np.asarray(scale_bits, U16)))
+
+
+def _image_of_interval(table, lo, hi):
+    """The image of the pattern interval [lo, hi] (non-negative bf16 patterns, or NaN in both) under a map given as a table over the
+    patterns 0 .. 0x7F80: (smallest, largest) mapped pattern in value order over EVERY pattern in between.  For a monotone map that is
+    (table[lo], table[hi]); the reference's maps are monotone up to artefacts of their bf16 arithmetic (fp4_e2m1 sends 0x3E7F, just
+    below 0.25, to 0.5 and 0.25 to 0), and this is the exact image whatever the map."""
+    lo, hi = np.asarray(lo, U16), np.asarray(hi, U16)
+    nan = (lo == 0x7FC0) | (hi == 0x7FC0)
+    l, h = np.where(nan, 0, lo).astype(np.int64), np.where(nan, 0, hi).astype(np.int64)
+    assert l.max(initial=0) <= 0x7F80 and h.max(initial=0) <= 0x7F80 and np.all(l <= h), "a probability's interval left [0, +inf]"
+    key = bf16_order(table).astype(np.int64)
+    out_lo, out_hi = table[l], table[h]
+    und = np.nonzero((l != h).reshape(-1))[0]
+    if und.size:
+        lu, hu = l.reshape(-1)[und], h.reshape(-1)[und]
+        imin, imax = lu.copy(), lu.copy()
+        for step in range(1, int((hu - lu).max()) + 1):
+            i = np.minimum(lu + step, hu)
+            imin = np.where(key[i] < key[imin], i, imin)
+            imax = np.where(key[i] > key[imax], i, imax)
+        out_lo.reshape(-1)[und], out_hi.reshape(-1)[und] = table[imin], table[imax]
+    return np.where(nan, U16(0x7FC0), out_lo).astype(U16), np.where(nan, U16(0x7FC0), out_hi).astype(U16)
+
+
+def _row_granules(grid_bits, plo, phi):
+    """Per row of admissible probabilities [plo, phi] (float64 values on the grid `grid_bits` of fq_P): a weight that every non-zero
+    admissible P' of the row is an integer multiple of.  Grids are finer near zero, so it is the smallest lowest-bit weight (_lowbit)
+    among the grid's values FROM the row's smallest non-zero admissible value UP; an element that may be zero or not (plo = 0 < phi)
+    admits every grid value below phi, so it counts with the grid's smallest non-zero value.  A row without a non-zero value: inf."""
+    grid = np.unique(_b64(grid_bits))
+    grid = grid[np.isfinite(grid) & (grid > 0)]
+    from_here_up = np.minimum.accumulate(_lowbit(grid)[::-1])[::-1]
+    smallest = np.where(plo > 0, plo, np.where(phi > 0, grid[0], np.inf)).min(axis=-1)
+    idx = np.minimum(np.searchsorted(grid, smallest), len(grid) - 1)
+    return np.where(np.isfinite(smallest), from_here_up[idx], np.inf)
+
+
+def attention_interval(q_bits, k_bits, v_bits, mask_bits, scaling, qmap, scale_bits=None, out_qmap=None, kernel="online"):
+    """A whole attention core on bf16 patterns with the admissible interval of every output: q [B,H,Sq,D], k / v [B,H,Sk,D] (already
+    fake-quantized), mask additive bf16 broadcastable to [B,H,Sq,Sk] or None, scaling a python float (multiplied as fp32), qmap / scale_bits
+    the probabilities' fake-quantizer (None: none / unit scale; scale_bits: ONE bf16 pattern, what the kernels round *scale to),
+    out_qmap the consumer's value map applied to the result (out_fq), kernel one of ATTENTION_KERNELS (attention_probs_interval).
+    The chain, with its rounding points (modules/quantizable/modeling_bert.py:118-158):
+
+        S = bf16(q k^T)            REQUIRED EXACT: q and k are small integers times a power of two, so every partial sum of the products,
+                                   in any order, fits 24 bits (_sums_exact_in_f32); ValueError otherwise -- a case that breaks the premise
+                                   fails here and does not loosen a check.  S is then bit-defined (one rounding of the exact sum),
+        t = bf16(bf16(S x scaling) + mask)       bit-defined (scale_and_mask),
+        p = bf16(softmax(t))       FIRST INEXACT ROUNDING: attention_probs_interval(t, kernel) -> [p_lo, p_hi],
+        P' = fq_P(p)               a map of the pattern: the image of [p_lo, p_hi] (_image_of_interval; [fq(p_lo), fq(p_hi)] where monotone),
+        O = bf16(sum_k P'_k v_k)   bounds: O_lo = sum_k (v_k >= 0 ? P'_lo : P'_hi) v_k, O_hi likewise with the ends swapped.
+
+    The P'.V sum: P' lies on the grid of fq_P's values, v is a multiple of its own lowest bit; where the products' granule keeps the
+    row's sum of absolute values within 24 bits the fp32 sum is exact in any order and the bounds above are final (asserted by the tests
+    for e4m3, e5m2, posit8_1, fp4_e2m1 and int8 at a power-of-two scale); so are they where a sum has at most one non-zero term.
+    Otherwise (no fq_P, posit8_2, other scales) the sum carries d_pv u sum |P'_hi v|, d_pv = max(SUM_DEPTH, ceil(Sk / 32) + 16): one
+    accumulator rounding per 32-key matrix instruction (qt_attention.hip:400, qt_attention_rows.hip:322) and 16 for the additions inside
+    one, the other key group's half included (qt_attention_rows.hip:337).  The granule of a row is _row_granules' (the grid's finest step from
+    the row's smallest admissible P' up) times the lowest-bit weight of v.
+    kernel = "strip_fp8" (qt_attention_fp8.hip) does NOT add in fp32: both products run on v_mfma_scale_f32_16x16x128_f8f6f4, which adds
+    its 128 products in a tree of its own.  What that tree keeps when the products of one instruction span many binades -- the
+    probabilities' do: 2^-18 .. 2 on the e5m2 grid -- is not documented, so no radius can be DERIVED for a P'.V sum of several terms
+    (:335) and this kernel is pinned only where a sum has at most ONE non-zero term (v holds one key per column: exact whatever the
+    tree does); ValueError otherwise.  For the scores (:114) the premise is exactness as above: their products are multiples of 2^-4
+    spanning at most 2^6, the sum at most 2^12 granules; the GPU test's P' comparison then holds the tree to that, to the bit.
+    Then ONE rounding to bf16 (_bf16_of) and, with out_qmap, the consumer's map (monotone).
+    Rows: a NaN row of P stays NaN in every output element (NaN x 0 = NaN); fully masked rows as in attention_probs_interval.
+    The observer's amax is max P in front of fq_P: [max p_lo, max p_hi], NaN if any row is.
+    Returns AttentionIntervals."""
+    q, k, v = _b64(q_bits), _b64(k_bits), _b64(v_bits)
+    with np.errstate(all="ignore"):
+        qf, kf = np.where(np.isfinite(q), q, 0.0), np.where(np.isfinite(k), k, 0.0)
+        granule = _lowbit(qf).min() * _lowbit(kf).min()
+        abs_s = np.einsum("bhqd,bhkd->bhqk", np.abs(qf), np.abs(kf))
+        if not bool(np.all(_sums_exact_in_f32(abs_s, granule))):
+            raise ValueError("attention_interval: the score sums are not exact in fp32 (q, k must be small integers times a power of two)")
+        S = np.einsum("bhqd,bhkd->bhqk", q, k)
+        # (np.einsum adds 0 x inf = NaN terms like the hardware; an fp64 sum of exactly representable partial sums is exact)
+        s_bits = f32_to_bf16(S.astype(F32))
+    t = scale_and_mask(s_bits, mask_bits, scaling)
+    p = attention_probs_interval(t, kernel)
+    table = _prob_fq(qmap, scale_bits)(np.arange(0x7F81, dtype=U32).astype(U16))      # fq_P of every non-negative bf16 pattern, +inf included
+    grid_bits = table[:0x3F81]                                                        # ... of [0, 1]
+    plo_bits, phi_bits = _image_of_interval(table, p.lo, p.hi)
+    probs = RowInterval(p.v, p.rho, plo_bits, phi_bits)
+    # amax
+    nan_any = bool(p.nan.any())
+    klo, khi = bf16_order(p.lo), bf16_order(p.hi)
+    i_lo, i_hi = np.unravel_index(np.argmax(klo), klo.shape), np.unravel_index(np.argmax(khi), khi.shape)
+    amax = RowInterval(np.array([np.nan if nan_any else np.nanmax(p.v)]), np.array([np.nan if nan_any else np.nanmax(p.rho)]),
+                       np.array([0x7FC0 if nan_any else p.lo[i_lo]], U16), np.array([0x7FC0 if nan_any else p.hi[i_hi]], U16))
+    # P'.V
+    with np.errstate(all="ignore"):
+        plo, phi = _b64(probs.lo), _b64(probs.hi)
+        vp, vn = np.maximum(v, 0.0), np.minimum(v, 0.0)
+        o_lo = plo @ vp + phi @ vn
+        o_hi = phi @ vp + plo @ vn
+        abs_o = phi @ np.abs(v)
+        nnz = (phi > 0).astype(np.float64) @ (v != 0).astype(np.float64)
+        granule_pv = (np.zeros(plo.shape[:-1]) if qmap is None else _row_granules(grid_bits, plo, phi)) * _lowbit(v).min()
+        row_abs = np.where(np.isnan(abs_o), 0.0, abs_o).max(axis=-1)
+        pv_exact = np.asarray(_sums_exact_in_f32(row_abs, granule_pv), bool) & (granule_pv > 0)
+        d_pv = max(SUM_DEPTH, -(-k.shape[-2] // 32) + 16)
+        if kernel == "strip_fp8":
+            if np.any(nnz > 1):
+                raise ValueError("attention_interval: kernel 'strip_fp8' takes a v with at most one non-zero key per column")
+            pv_exact = np.ones_like(pv_exact)
+        rho_o = np.where(pv_exact[..., None] | (nnz <= 1), 0.0, d_pv * U_F32 * abs_o)
+        lo, hi = _bf16_of(o_lo - rho_o), _bf16_of(o_hi + rho_o)
+    if out_qmap is not None:
+        lo, hi = vmap_bf16(lo, out_qmap), vmap_bf16(hi, out_qmap)
+    out = RowInterval((o_lo + o_hi) / 2, (o_hi - o_lo) / 2 + rho_o, lo, hi)
+    return AttentionIntervals(out, probs, amax, pv_exact)
