@@ -860,6 +860,23 @@ int qt_conv2d_mx(const uint8_t *x_codes, const uint8_t *x_e8m0, int x_format, co
                  void *y, int y_is_f32, const void *bias, int N, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw, int ph,
                  int pw, int dh, int dw, void *stream);
 
+/* The same operator for the operands of qt_mxi_pack (integer elements, integer codebooks, block scales of any finite positive value
+ * over blocks of 32, 64 or 128 channels), an implicit GEMM on the integer matrix cores:
+ *     y[n, ho, wo, co] = rd( bias[co] + sum_{(r, s, kb)} (sx[n, hi, wi, kb] * sw[co, r, s, kb]) * p ),
+ *     p = sum over the channels c of block kb of x[n, hi, wi, c] * w[co, r, s, c],      hi = ho sh - ph + r dh, wi = wo sw - pw + s dw
+ * x_codes NHWC [N][H][W][Cin] int8 with x_scales [N][H][W][Cin / block_size] fp32; w_codes [Cout][kh][kw][Cin] with w_scales
+ * [Cout][kh][kw][Cin / block_size]; y NHWC [N][Ho][Wo][Cout], bf16 or fp32; bias [Cout] in y's dtype, nullable.  p is exact in int32,
+ * multiplied by the fp32 product of its two scales and added by one fma into an fp32 accumulator, terms in (r, s, kb) order; bias added
+ * in fp32; one rounding.  Zero padding, groups = 1, any Cout, filter, stride, padding and dilation.  Declines before its first HIP call:
+ * QT_ERR_BAD_ARG for a NULL operand or output, a non-positive extent, a block size other than 32 / 64 / 128, Cin % block_size != 0,
+ * N Ho Wo, kh kw Cin or either code array at 2^31 or more, kh dh, kw dw, a stride or a padding at 2^20 or more; QT_ERR_UNALIGNED for
+ * codes off a 16-byte boundary, scales off 4 bytes, y or bias off their element size.  An empty output is QT_OK without a launch.  No
+ * address outside the operands is read (a tap in the padding is zero codes under the scale 0).  No atomics, no allocation, no
+ * synchronisation: safe under stream capture, the same bits on every launch. */
+int qt_conv2d_mxi(const int8_t *x_codes, const float *x_scales, const int8_t *w_codes, const float *w_scales, int block_size, void *y,
+                  int y_is_f32, const void *bias, int N, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw, int ph, int pw,
+                  int dh, int dw, void *stream);
+
 /* ---- the outlier side path of a block-scaled linear layer: filter_outlier / spmm_csr            decomposed.py:450-566
  * qt_filter_outlier_*: replaces filter_outlier (decomposed.py:450-507, the nested Python loops over .item()).  x is the [rows][cols]
  * view of a contiguous tensor (cols = its last axis).  threshold is the operator's threshold ALREADY ROUNDED to the tensor's dtype,

@@ -16,20 +16,7 @@ namespace {
 // operand, so no address outside x_codes / x_e8m0 is ever formed into a load.
 // A k tile starts at 32-block u_blk of tap (u_tr, u_ts): wave-uniform, moved on by additions.  A lane's chunk or scale byte
 // lies at most four taps further (128 k over Cin >= 32), found by comparisons; a lane's pixel never changes over the k loop.
-struct MxConvGeom {
-    int H, W, kh, kw, sh, sw, ph, pw, dh, dw, Ho, Wo;
-    int cpb;                      // 32-blocks per input pixel, Cin / 32
-};
-
-// position v (< 5 per) counted from the start of tap (tr0, ts0 < kw) -> offset inside its tap, and that tap
-__device__ __forceinline__ void conv_tap_of(int v, int per, int ts0, int tr0, int kw, int &off, int &ts, int &tr) {
-    const int q = (v >= per) + (v >= 2 * per) + (v >= 3 * per) + (v >= 4 * per);
-    const int s = ts0 + q;                                            // < kw + 4 <= 5 kw
-    const int wrap = (s >= kw) + (s >= 2 * kw) + (s >= 3 * kw) + (s >= 4 * kw);
-    off = v - q * per;
-    ts = s - wrap * kw;
-    tr = tr0 + wrap;
-}
+// (MxConvGeom, conv_tap_of and the checked shape of a launch, conv_shape: qt_mx_tile.h, shared with qt_mxi_conv.hip)
 
 // ---- split of K (qt_q8_conv2d_ws, I8 only) -----------------------------------------------------------------------------------------
 // A long contraction over few output tiles (a reducing 1 x 1 layer, a small batch) leaves most of the chip idle.  S workgroups
@@ -460,42 +447,6 @@ __global__ __launch_bounds__(256) void q8_dwconv_kernel(MxGemmArgs a, MxConvGeom
                                o[8 * q + 6] | (o[8 * q + 7] << 16)};
         }
     }
-}
-
-// ---- the checked shape of a convolution launch ---------------------------------------------------------------------------------
-// What qt_conv2d_mx, qt_q8_conv2d* and qt_q8_dwconv2d* check alike, in the order their callers see: the common argument errors; the
-// caller's own verdict `rule_rc` (its channel rule and whatever else it reports for an empty output too); an empty output, which is
-// QT_OK with nothing to launch; the alignment of the pointers or-ed into `ptrs`; the index limits -- 32-bit row and pixel indices,
-// 32-bit byte offsets into the code arrays (x_pixel_bytes per input pixel, w_tap_bytes per output channel and tap), a contraction
-// taps * kchan below 2^31; the output is indexed in 64 bits.
-// (a product that reaches 2^31 saturates there, so that no argument can overflow the 64-bit arithmetic of the checks)
-constexpr long kLim = 1L << 31;
-long mul_sat(long a, long b) { return a >= kLim || b >= kLim ? kLim : (a * b >= kLim ? kLim : a * b); }
-
-struct ConvShape {
-    MxConvGeom c;                // cpb is the caller's
-    long m, taps;                // output pixels N Ho Wo, filter taps kh kw
-    bool empty;
-};
-int conv_shape(int N, int H, int W, int cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int rule_rc, uintptr_t ptrs,
-               long kchan, long x_pixel_bytes, long w_tap_bytes, ConvShape &s) {
-    s.empty = true;
-    if (N < 0 || H < 1 || W < 1 || cout < 0) return QT_ERR_BAD_ARG;
-    if (kh < 1 || kw < 1 || sh < 1 || sw < 1 || dh < 1 || dw < 1 || ph < 0 || pw < 0) return QT_ERR_BAD_ARG;
-    if (rule_rc) return rule_rc;
-    const long eh = (long)H + 2L * ph - (long)dh * (kh - 1) - 1, ew = (long)W + 2L * pw - (long)dw * (kw - 1) - 1;
-    if (N == 0 || cout == 0 || eh < 0 || ew < 0) return QT_OK;                                  // empty output: nothing to launch
-    if (ptrs & 15u) return QT_ERR_UNALIGNED;
-    const long ho = eh / sh + 1, wo = ew / sw + 1;
-    s.m = mul_sat(N, mul_sat(ho, wo));
-    s.taps = mul_sat(kh, kw);
-    if (s.m >= kLim || mul_sat(s.taps, kchan) >= kLim || mul_sat(N, mul_sat(mul_sat(H, W), x_pixel_bytes)) >= kLim ||
-        mul_sat(cout, mul_sat(s.taps, w_tap_bytes)) >= kLim || (long)kh * dh >= (1 << 20) || (long)kw * dw >= (1 << 20) ||
-        ph >= (1 << 20) || pw >= (1 << 20) || sh >= (1 << 20) || sw >= (1 << 20))
-        return QT_ERR_BAD_ARG;
-    s.c = MxConvGeom{H, W, kh, kw, sh, sw, ph, pw, dh, dw, (int)ho, (int)wo, 0};
-    s.empty = false;
-    return QT_OK;
 }
 
 }  // namespace

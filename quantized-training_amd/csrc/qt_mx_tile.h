@@ -1,9 +1,10 @@
 // qt_mx_tile.h -- what the kernels on 128-deep k tiles of packed codes share: the launch arguments, the matrix step (Mma), the LDS
 // image of an operand tile and its fragment read (Tile, read_frag), the workgroup-id -> tile map, the dense register-staged operand
 // side (DenseSide), the multiplication of one staged k tile (mma_tile), and the epilogues: values (emit_tile) or the next
-// convolution's codes (emit_codes_tile).
+// convolution's codes (emit_codes_tile); the integer family's scale image and block product (Mxi, read_frag32, mxi_block); the
+// convolutions' geometry, tap walk and checked launch shape (MxConvGeom, conv_tap_of, conv_shape).
 // Used by qt_mx_gemm.hip (block-scaled float GEMM and the int8 GEMM on its kernels), qt_mx_conv.hip (conv2d_mx / conv2d_q as implicit
-// GEMMs, depthwise conv2d_q) and qt_mxi_gemm.hip (integer / codebook operands under any block scale).
+// GEMMs, depthwise conv2d_q), qt_mxi_gemm.hip (integer / codebook operands under any block scale) and qt_mxi_conv.hip (their conv2d_mx).
 //
 // Operand memory layout ("packed MX operand"): codes[rows][K * bits / 8] row-major, K contiguous, element i of a row
 // in bits [i*bits, (i+1)*bits) little-endian; scales[rows][K / 32] E8M0 bytes (2^(byte - 127)).
@@ -331,6 +332,94 @@ inline int codes_tail_check(const CodesTail &ct, int cout, const void *y, int y_
     if (cout % 16 != 0 || !ct.qmap || !ct.scale || (ct.act != 0 && ct.act != 1)) return QT_ERR_BAD_ARG;
     if (ct.act == 1 && !(ct.lo <= ct.hi)) return QT_ERR_BAD_ARG;                               // false for a NaN bound too
     if (((uintptr_t)ct.qmap & 1u) || ((uintptr_t)ct.scale & (y_is_f32 ? 3u : 1u)) || ((uintptr_t)y & 15u)) return QT_ERR_UNALIGNED;
+    return QT_OK;
+}
+
+// ---- the integer family (qt_mxi_gemm.hip, qt_mxi_conv.hip): int8 codes in Tile<0>, the fp32 block scales of a k tile next to them ----
+template <int BS>
+struct Mxi {
+    static constexpr int kScales = kBK / BS;                              // block scales per row and k tile
+    static constexpr int kScaleFloats = 2 * kScales * 128;                // one stage: both operands
+    static constexpr int kLds = 4 * Tile<0>::kBytes + 2 * kScaleFloats * 4;
+};
+
+// the four 32-blocks of a 128-deep tile row, eight bytes each: f[2 blk], f[2 blk + 1]
+__device__ __forceinline__ v8i read_frag32(const uint8_t *tile, int row, int g) {
+    v8i f;
+#pragma unroll
+    for (int blk = 0; blk < 4; ++blk) {
+        const uint2 v = *(const uint2 *)(tile + Tile<0>::chunk_off(row, 2 * blk + (g >> 1)) + 8 * (g & 1));
+        f[2 * blk] = v.x;
+        f[2 * blk + 1] = v.y;
+    }
+    return f;
+}
+
+// the exact int32 sum of block `blk` of the k tile for one 16 x 16 output tile
+template <int BS>
+__device__ __forceinline__ v4i mxi_block(const v8i &a, const v8i &b, int blk) {
+    const v4i z = {0, 0, 0, 0};
+    if constexpr (BS == 32) {
+        const long la = (long)(((unsigned long)(uint32_t)a[2 * blk + 1] << 32) | (uint32_t)a[2 * blk]);
+        const long lb = (long)(((unsigned long)(uint32_t)b[2 * blk + 1] << 32) | (uint32_t)b[2 * blk]);
+        return __builtin_amdgcn_mfma_i32_16x16x32_i8(la, lb, z, 0, 0, 0);
+    } else if constexpr (BS == 64) {
+        const int o = 4 * blk;
+        return __builtin_amdgcn_mfma_i32_16x16x64_i8(v4i{a[o], a[o + 1], a[o + 2], a[o + 3]}, v4i{b[o], b[o + 1], b[o + 2], b[o + 3]}, z, 0, 0, 0);
+    } else {
+        return Mma<0, 0, true>::run(a, b, z, 0, 0);
+    }
+}
+
+// ---- the implicit-GEMM convolutions (qt_mx_conv.hip, qt_mxi_conv.hip): geometry, the tap walk, the checked shape of a launch ------
+struct MxConvGeom {
+    int H, W, kh, kw, sh, sw, ph, pw, dh, dw, Ho, Wo;
+    int cpb;                      // 32-blocks per input pixel, Cin / 32
+};
+
+// position v (< 5 per) counted from the start of tap (tr0, ts0 < kw) -> offset inside its tap, and that tap
+__device__ __forceinline__ void conv_tap_of(int v, int per, int ts0, int tr0, int kw, int &off, int &ts, int &tr) {
+    const int q = (v >= per) + (v >= 2 * per) + (v >= 3 * per) + (v >= 4 * per);
+    const int s = ts0 + q;                                            // < kw + 4 <= 5 kw
+    const int wrap = (s >= kw) + (s >= 2 * kw) + (s >= 3 * kw) + (s >= 4 * kw);
+    off = v - q * per;
+    ts = s - wrap * kw;
+    tr = tr0 + wrap;
+}
+
+// ---- the checked shape of a convolution launch ---------------------------------------------------------------------------------
+// What qt_conv2d_mx, qt_conv2d_mxi, qt_q8_conv2d* and qt_q8_dwconv2d* check alike, in the order their callers see: the common argument errors; the
+// caller's own verdict `rule_rc` (its channel rule and whatever else it reports for an empty output too); an empty output, which is
+// QT_OK with nothing to launch; the alignment of the pointers or-ed into `ptrs`; the index limits -- 32-bit row and pixel indices,
+// 32-bit byte offsets into the code arrays (x_pixel_bytes per input pixel, w_tap_bytes per output channel and tap), a contraction
+// taps * kchan below 2^31; the output is indexed in 64 bits.
+// (a product that reaches 2^31 saturates there, so that no argument can overflow the 64-bit arithmetic of the checks)
+constexpr long kLim = 1L << 31;
+long mul_sat(long a, long b) { return a >= kLim || b >= kLim ? kLim : (a * b >= kLim ? kLim : a * b); }
+
+struct ConvShape {
+    MxConvGeom c;                // cpb is the caller's
+    long m, taps;                // output pixels N Ho Wo, filter taps kh kw
+    bool empty;
+};
+int conv_shape(int N, int H, int W, int cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int rule_rc, uintptr_t ptrs,
+               long kchan, long x_pixel_bytes, long w_tap_bytes, ConvShape &s) {
+    s.empty = true;
+    if (N < 0 || H < 1 || W < 1 || cout < 0) return QT_ERR_BAD_ARG;
+    if (kh < 1 || kw < 1 || sh < 1 || sw < 1 || dh < 1 || dw < 1 || ph < 0 || pw < 0) return QT_ERR_BAD_ARG;
+    if (rule_rc) return rule_rc;
+    const long eh = (long)H + 2L * ph - (long)dh * (kh - 1) - 1, ew = (long)W + 2L * pw - (long)dw * (kw - 1) - 1;
+    if (N == 0 || cout == 0 || eh < 0 || ew < 0) return QT_OK;                                  // empty output: nothing to launch
+    if (ptrs & 15u) return QT_ERR_UNALIGNED;
+    const long ho = eh / sh + 1, wo = ew / sw + 1;
+    s.m = mul_sat(N, mul_sat(ho, wo));
+    s.taps = mul_sat(kh, kw);
+    if (s.m >= kLim || mul_sat(s.taps, kchan) >= kLim || mul_sat(N, mul_sat(mul_sat(H, W), x_pixel_bytes)) >= kLim ||
+        mul_sat(cout, mul_sat(s.taps, w_tap_bytes)) >= kLim || (long)kh * dh >= (1 << 20) || (long)kw * dw >= (1 << 20) ||
+        ph >= (1 << 20) || pw >= (1 << 20) || sh >= (1 << 20) || sw >= (1 << 20))
+        return QT_ERR_BAD_ARG;
+    s.c = MxConvGeom{H, W, kh, kw, sh, sw, ph, pw, dh, dw, (int)ho, (int)wo, 0};
+    s.empty = false;
     return QT_OK;
 }
 

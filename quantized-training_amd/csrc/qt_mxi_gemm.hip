@@ -18,41 +18,6 @@
 namespace {
 
 template <int BS>
-struct Mxi {
-    static constexpr int kScales = kBK / BS;                              // block scales per row and k tile
-    static constexpr int kScaleFloats = 2 * kScales * 128;                // one stage: both operands
-    static constexpr int kLds = 4 * Tile<0>::kBytes + 2 * kScaleFloats * 4;
-};
-
-// the four 32-blocks of a 128-deep tile row, eight bytes each: f[2 blk], f[2 blk + 1]
-__device__ __forceinline__ v8i read_frag32(const uint8_t *tile, int row, int g) {
-    v8i f;
-#pragma unroll
-    for (int blk = 0; blk < 4; ++blk) {
-        const uint2 v = *(const uint2 *)(tile + Tile<0>::chunk_off(row, 2 * blk + (g >> 1)) + 8 * (g & 1));
-        f[2 * blk] = v.x;
-        f[2 * blk + 1] = v.y;
-    }
-    return f;
-}
-
-// the exact int32 sum of block `blk` of the k tile for one 16 x 16 output tile
-template <int BS>
-__device__ __forceinline__ v4i mxi_block(const v8i &a, const v8i &b, int blk) {
-    const v4i z = {0, 0, 0, 0};
-    if constexpr (BS == 32) {
-        const long la = (long)(((unsigned long)(uint32_t)a[2 * blk + 1] << 32) | (uint32_t)a[2 * blk]);
-        const long lb = (long)(((unsigned long)(uint32_t)b[2 * blk + 1] << 32) | (uint32_t)b[2 * blk]);
-        return __builtin_amdgcn_mfma_i32_16x16x32_i8(la, lb, z, 0, 0, 0);
-    } else if constexpr (BS == 64) {
-        const int o = 4 * blk;
-        return __builtin_amdgcn_mfma_i32_16x16x64_i8(v4i{a[o], a[o + 1], a[o + 2], a[o + 3]}, v4i{b[o], b[o + 1], b[o + 2], b[o + 3]}, z, 0, 0, 0);
-    } else {
-        return Mma<0, 0, true>::run(a, b, z, 0, 0);
-    }
-}
-
-template <int BS>
 __global__ __launch_bounds__(256) void mxi_gemm_kernel(MxGemmArgs a) {
     using T = Tile<0>;
     constexpr int NS = Mxi<BS>::kScales;

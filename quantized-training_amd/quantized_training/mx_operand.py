@@ -12,8 +12,9 @@ the per-tensor FP8 path):
   _qt_mx_packed, _qt_mx_packed_conv
                         on a weight: (key, (format id, codes, e8m0) or None), the packed constant operand of the GEMM / the
                         convolution.  The key carries both version counters, so these two need no stamp.
-  _qt_mxi_packed        on a weight: (key, (codes int8, scales fp32) or None), its operand in the integer family (qt_mxi_gemm); the
-                        key carries the version counters of weight, scale and codebook
+  _qt_mxi_packed, _qt_mxi_packed_conv
+                        on a weight: (key, (codes int8, scales fp32) or None), its operand in the integer family (qt_mxi_gemm / the
+                        [Cout][kh kw Cin] one of qt_conv2d_mxi); the key carries the version counters of weight, scale and codebook
   _qt_mxi_code          on a codebook: (version, whether the integer GEMM takes it): one host read per codebook
 
 `_qt_mx_fmt` also names the integer formats (INT_BITS): `quantize` with a block size and `quantize_mx` write it for an integer map
@@ -261,19 +262,20 @@ def weight_operand(weight, scale, block_size, slot, as_rows, extent, pack):
     return result
 
 
-INT_SLOT = "_qt_mxi_packed"
+INT_SLOT, INT_CONV_SLOT = "_qt_mxi_packed", "_qt_mxi_packed_conv"
 
 
-def int_weight_operand(weight, scale, code, block_size, pack):
+def int_weight_operand(weight, scale, code, block_size, pack, slot=INT_SLOT):
     """A weight's operand in the integer family, (codes int8, scales fp32) or None when the packer's check refuses it: packed once,
-    cached on the tensor object under its own slot (the float family's GEMM_SLOT is another cache).  pack() -> (codes, scales) or
-    None, with the check on.  The key carries the version counters of weight, scale and codebook."""
+    cached on the tensor object under its own slot (the float family's GEMM_SLOT is another cache; the convolution's [Cout][kh kw Cin]
+    layout has INT_CONV_SLOT next to the GEMM's).  pack() -> (codes, scales) or None, with the check on.  The key carries the version
+    counters of weight, scale and codebook."""
     key = (weight._version, scale.data_ptr(), scale._version, block_size,
            None if code is None else (code.data_ptr(), code._version))
-    hit = getattr(weight, INT_SLOT, None)
+    hit = getattr(weight, slot, None)
     if hit is not None and hit[0] == key:
         return hit[1]
     result = pack()
-    setattr(weight, INT_SLOT, (key, result))
+    setattr(weight, slot, (key, result))
     return result
 
