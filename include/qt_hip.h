@@ -341,6 +341,29 @@ int qt_linear_gwa_bf16(const uint16_t *x_dev, const uint8_t *packed_dev, const u
                        const uint16_t *bias_dev, uint16_t *y_dev, int M, int N, int K, int block_size, int bits, float quant_min,
                        int tile_m, void *stream);
 
+/* qt_linear_gwa_tall_bf16 (csrc/qt_gwa_tall.hip): the same product, the same packed operand and the same arithmetic for MANY rows.
+ * A workgroup of 8 waves owns tile_m x 128 outputs (tile_m = 128 or 256), converts each k tile of its 128 columns ONCE into a
+ * swizzled LDS image (gwa_dequant; the dequantized weight never reaches memory) and multiplies it with x tiles that arrive by
+ * LDS-DMA.  `ksplit` workgroups (1, 2, 4 or 8) share a tile over contiguous ranges of super steps; their fp32 partial tiles meet in
+ * ws_dev and the last to arrive adds them in split order: fixed summation order, no float atomics, the same bits on every run,
+ * capturable.  tile_m / ksplit: 0 = by qt_linear_gwa_tall_plan, else forced (tests, tools; a split beyond the super steps is empty).
+ * With ksplit > 1 the caller passes ws_dev (>= ws_bytes of the plan, 16-byte aligned; contents irrelevant) and tickets_dev
+ * (>= n_tickets uint32, ZERO before the first launch; every launch leaves them zero).
+ *
+ * qt_linear_gwa_tall_plan (host only): a fixed function of the shape and the CU count -- 256-row tiles where they alone give every
+ * other CU a workgroup, else 128; the largest split with tiles x ksplit <= CUs and at least two super steps per split;
+ * ws_bytes = tiles x ksplit x tile_m x 128 x 4 and n_tickets = tiles when ksplit > 1, else 0.  tile_m forces the row tile.
+ *
+ * Declined before any device call as qt_linear_gwa_bf16 declines, and: QT_ERR_BAD_ARG for a tile_m outside {0, 128, 256}, a ksplit
+ * outside {0, 1, 2, 4, 8}, with a split a NULL or too small workspace or ticket buffer; QT_ERR_UNALIGNED for a workspace off a
+ * 16-byte boundary or tickets off a 4-byte one.  M == 0 returns QT_OK without a launch. */
+int qt_linear_gwa_tall_plan(int M, int N, int K, int bits, int tile_m, int *tile_m_out, int *ksplit_out, size_t *ws_bytes,
+                            size_t *n_tickets);
+int qt_linear_gwa_tall_bf16(const uint16_t *x_dev, const uint8_t *packed_dev, const uint16_t *scale_dev, const uint16_t *zp_dev,
+                            const uint16_t *bias_dev, uint16_t *y_dev, int M, int N, int K, int block_size, int bits,
+                            float quant_min, int tile_m, int ksplit, float *ws_dev, size_t ws_bytes, uint32_t *tickets_dev,
+                            size_t n_tickets, void *stream);
+
 /* ---- A9/A10: fake-quant GEMMs (bf16 in, fp32 accumulate on MFMA, bf16 out) ---------------
  * qt_linear_fq_bf16 replaces  F.linear(fq_a(x), weight_fake_quant(W), b)
  *     modules/qat/linear.py:40-41 + the activation pre-hook quantize.py:128-140

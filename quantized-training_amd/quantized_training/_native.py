@@ -130,6 +130,9 @@ SIGNATURES = {
     "qt_gwa_dequantize_bf16": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P]),
     "qt_linear_gwa_tile": (c_int, [c_int]),
     "qt_linear_gwa_bf16": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, c_int, _P]),
+    "qt_linear_gwa_tall_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_size_t), POINTER(c_size_t)]),
+    "qt_linear_gwa_tall_bf16": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_int, _P, c_size_t, _P, c_size_t,
+                                        _P]),
     "qt_fake_quant_pc_bf16": (c_int, [_P, _P, c_size_t, c_size_t, c_size_t, _FMT, _P, _P, _P, _P]),
     "qt_fake_quant_pc_f32": (c_int, [_P, _P, c_size_t, c_size_t, c_size_t, _FMT, _P, _P, _P, _P]),
     "qt_linear_fq_bf16": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _OPQ, _OPQ, _P]),
@@ -325,6 +328,17 @@ def check(code, what=""):
         if code == QT_ERR_BAD_DTYPE:
             raise ValueError(f"Unsupported dtype: {what}")
         raise QtError(f"libqt_hip {what}: {msg} (code {code})")
+
+
+def gwa_tall_plan(m, n, k, bits, tile_m=0):
+    """(tile_m, ksplit, workspace bytes, tickets) of qt_linear_gwa_tall_bf16 for an [m, k] x [n, k] product (host only), or None
+    for a shape the kernel declines."""
+    bm, ks, wb, nt = c_int(0), c_int(0), c_size_t(0), c_size_t(0)
+    rc = lib().qt_linear_gwa_tall_plan(m, n, k, bits, tile_m, ctypes.byref(bm), ctypes.byref(ks), ctypes.byref(wb), ctypes.byref(nt))
+    if declined(rc):
+        return None
+    check(rc, "qt_linear_gwa_tall_plan")
+    return bm.value, ks.value, wb.value, nt.value
 
 
 def q8_conv_plan(m, cout, k):

@@ -1016,6 +1016,7 @@ def enabled_for(model) -> bool:
 # dequantize-GEMM where the committed rule takes the shape and the one-pass dequantize kernel + the library GEMM elsewhere.
 GWA_BLOCKS = (32, 64, 128, 256, 512)
 GWA_TILES = (16, 32, 64)                  # row-tile heights of qt_linear_gwa_bf16 (tile_m; 0 = by M)
+GWA_TALL_TILES = (128, 256)               # row-tile heights of qt_linear_gwa_tall_bf16 (tile_m; 0 = by the plan)
 GWA_ROUTES = {}                           # "gwa:MxNxK" -> route of the first call with that shape (fused.routes_report)
 
 
@@ -1025,7 +1026,7 @@ class _GwaStats:
         self.reset()
 
     def reset(self):
-        self.fused = self.dequant = self.reference = 0
+        self.fused = self.tall = self.dequant = self.reference = 0
         self.reasons = {}
 
     def note(self, why):
@@ -1134,9 +1135,44 @@ def gwa_dequantize(packed, scale, zero_point, block_size, quant_min, bits, K):
     return w
 
 
-def linear_gwa_route(input, packed, scale, zero_point, bias, block_size, quant_min, bits, K, route=None, tile_m=0):
-    """linear_gwa with the route in the caller's hands: None = the committed rule, "fused" / "dequant" / "reference" = that route
-    (a forced route the kernels decline falls through to the next one, as the rule's does), tile_m = the fused kernel's variant."""
+def _gwa_tall_route_takes(M, N, K, bits):
+    """The committed rule of the tall kernel (qt_linear_gwa_tall_bf16), consulted only where _gwa_route_takes declines; a fixed function
+    of the problem.  A class -- one M and one code width -- enters it only where, in profiles/gwa_tall.txt, the tall kernel's slowest
+    round beat the fastest round of qt_gwa_dequantize_bf16 + the library GEMM on every weight of the class.  None does (the file's
+    "# class" lines): at M = 96 .. 192 the kernel wins on 4096 x 4096 and 4096 x 11008 (1.07 - 1.47 x at the medians) and loses on
+    11008 x 4096 (0.62 - 0.86 x: 86 tiles, split 2, 172 of 256 CUs); from M = 256 on it runs at 0.53 - 0.93 x on every weight.  So the
+    rule is empty: everything -- small N K and M just above 32 included -- stays with the dequantize kernel + the library GEMM, and the
+    tall kernel is reached with route="tall" (the one route for M > 32 that allocates no copy of the weight)."""
+    return False
+
+
+def _gwa_tall_launch(x, packed, s, z, b, M, N, K, block_size, quant_min, bits, tile_m, split):
+    """One qt_linear_gwa_tall_bf16 launch -> y [M, N], or None when the kernel declines.  The workspace and the tickets of a split
+    come from fused.splitk_scratch, per stream and capture, as _conv_q_launch's do."""
+    plan = _native.gwa_tall_plan(M, N, K, bits, tile_m) if tile_m in (0,) + GWA_TALL_TILES else None
+    if plan is None or split not in (0, 1, 2, 4, 8):
+        return None
+    bm, ks = plan[0], split or plan[1]
+    tiles = -(-M // bm) * -(-N // 128)
+    ws = tickets = None
+    if ks > 1:
+        from .fused import splitk_scratch
+        ws, tickets = splitk_scratch("gwa_tall", tiles * ks * bm * 128 * 4, tiles, x.device)
+    y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    rc = _native.lib().qt_linear_gwa_tall_bf16(
+        x.data_ptr(), packed.data_ptr(), s.data_ptr(), z.data_ptr(), b.data_ptr() if b is not None else None, y.data_ptr(), M, N, K,
+        block_size, bits, float(quant_min), bm, ks, ws.data_ptr() if ws is not None else None, ws.numel() * 4 if ws is not None else 0,
+        tickets.data_ptr() if tickets is not None else None, tickets.numel() if tickets is not None else 0, _stream_ptr(x))
+    if _native.declined(rc):
+        return None
+    _native.check(rc, "qt_linear_gwa_tall_bf16")
+    return y
+
+
+def linear_gwa_route(input, packed, scale, zero_point, bias, block_size, quant_min, bits, K, route=None, tile_m=0, split=0):
+    """linear_gwa with the route in the caller's hands: None = the committed rules, "fused" / "tall" / "dequant" / "reference" = that
+    route (a forced route the kernels decline falls through to the next one, as the rules' does), tile_m = the kernel's variant,
+    split = the tall kernel's split of K (0 = by its plan)."""
     N = scale.shape[0]
     device_ok = (input.device.type == "cuda" and input.dtype == torch.bfloat16 and scale.dtype == torch.bfloat16
                  and zero_point.dtype == torch.bfloat16 and packed.dtype == torch.uint8 and input.shape[-1] == K
@@ -1164,6 +1200,14 @@ def linear_gwa_route(input, packed, scale, zero_point, bias, block_size, quant_m
             GWA_ROUTES.setdefault(key, "fused_gwa_gemm")
             return y.view(*input.shape[:-1], N)
         GWA_STATS.note("qt_linear_gwa_bf16 declined")
+    elif route == "tall" or (route is None and _gwa_tall_route_takes(M, N, K, bits)):
+        y = _gwa_tall_launch(input.reshape(M, K).contiguous(), packed, s, z, bias.contiguous() if bias is not None else None, M, N, K,
+                             block_size, quant_min, bits, tile_m, split)
+        if y is not None:
+            GWA_STATS.tall += 1
+            GWA_ROUTES.setdefault(key, "fused_gwa_tall_gemm")
+            return y.view(*input.shape[:-1], N)
+        GWA_STATS.note("qt_linear_gwa_tall_bf16 declined")
     elif route is None:
         GWA_STATS.note("route rule")
     w = gwa_dequantize(packed, s, z, block_size, quant_min, bits, K)
