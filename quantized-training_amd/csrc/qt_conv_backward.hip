@@ -25,9 +25,8 @@
 // k loop) of the input pixel its k row's output pixel reads, or zeros in the padding and past M.  A lane's (n, ho, wo) moves on by 64
 // pixels per k tile with two carries.  The output is small and K is huge, so the contraction is split: `ksplit` workgroups share an
 // output tile, each multiplies a contiguous range of k tiles and leaves its fp32 partial sums in the caller's workspace; the workgroup
-// that draws the tile's last ticket adds them IN SPLIT ORDER, rounds once, and resets the ticket (the hand-off of qt_linear_fqt.hip:
-// write-through stores, drained in front of the barrier that precedes the relaxed ticket; the owner reads past its L1).  The split
-// factor is a fixed function of the shape and the CU count.
+// that draws the tile's last ticket adds them IN SPLIT ORDER, rounds once, and resets the ticket (the hand-over of qt_splitk.h).  The
+// split factor is a fixed function of the shape and the CU count.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -36,6 +35,7 @@
 #include "../../include/qt_hip.h"
 #include "qt_device.h"
 #include "qt_gemm_ring.h"
+#include "qt_splitk.h"
 
 namespace {
 
@@ -44,22 +44,13 @@ __device__ __attribute__((aligned(128))) const uint32_t kZeroRow[32] = {0};     
 struct BwdArgs {
     const uint16_t *gy, *w, *x;
     uint16_t *out;                    // gx (dgrad) or gw (wgrad)
-    float *ws;                        // wgrad, ksplit > 1: [tile][split][wave][fragment][64 lanes][4] fp32
+    f32x4 *ws;                        // wgrad, ksplit > 1: the partial sums (splitk_slab)
     unsigned int *tickets;            // wgrad, ksplit > 1: [tile] arrival counters, zero between launches
     int N, H, W, Cin, Cout, kh, kw, sh, sw, ph, pw, dh, dw;
     int Ho, Wo, M, Min;               // M = N Ho Wo output pixels, Min = N H W input pixels
     int tiles_m, tiles_n;
     int ksplit, kper, nkt;            // wgrad: splits, k tiles per split, k tiles in all
 };
-
-__device__ __forceinline__ void store16_sc1(const float *sbase, uint32_t voff, f32x4 v) {
-    asm volatile("global_store_dwordx4 %0, %1, %2 sc1" ::"v"(voff), "v"(v), "s"(sbase) : "memory");
-}
-__device__ __forceinline__ f32x4 load16_sc1(const float *sbase, uint32_t voff) {
-    f32x4 v;
-    asm volatile("global_load_dwordx4 %0, %1, %2 sc1" : "=v"(v) : "v"(voff), "s"(sbase) : "memory");
-    return v;
-}
 
 // ---- dgrad ------------------------------------------------------------------------------------------------------------------------------
 template <int BM, int BN>
@@ -310,45 +301,16 @@ __global__ __launch_bounds__(kThreads) void conv2d_wgrad_kernel(const BwdArgs a)
     }
     drain<S - 2, kPieces>(kt, compute);
 
-    if (a.ksplit > 1) {
-        // ---- split-K hand-off (qt_linear_fqt.hip).  Partial sums leave in fragment order, write-through; every wave drains its stores;
-        // behind the workgroup barrier ONE lane takes the tile's ticket.  Whoever draws the last ticket owns the tile: it adds ALL the
-        // partial sums, its own included, in split order -- the result does not depend on who arrived last.  Nobody waits for anybody.
-        constexpr long kSlab = (long)WM * WN * 256;                      // floats per wave
-        float *const mine = a.ws + (((long)tile * a.ksplit + split) * 8 + wave) * kSlab;
+    if (a.ksplit > 1) {                                                 // the hand-over of qt_splitk.h
+        f32x4 *const mine = splitk_slab<8, WM * WN>(a.ws, tile, a.ksplit, split);
 #pragma unroll
         for (int i = 0; i < WM; ++i)
 #pragma unroll
-            for (int j = 0; j < WN; ++j) store16_sc1(mine + (i * WN + j) * 256, (uint32_t)lane * 16u, acc[i][j]);
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __syncthreads();                                                // (also: every wave is done with the ring, the flag below reuses it)
-        volatile unsigned int *flag = (volatile unsigned int *)lds;
-        if (t == 0) *flag = __hip_atomic_fetch_add(a.tickets + tile, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        if ((int)*flag != a.ksplit - 1) return;                         // not the last one: done
-        if (t == 0) __hip_atomic_store(a.tickets + tile, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");              // drop what this XCD's L2 holds of the workspace from earlier launches
-        const float *const base = a.ws + ((long)tile * a.ksplit * 8 + wave) * kSlab;
-#pragma unroll
-        for (int i = 0; i < WM; ++i)
-#pragma unroll
-            for (int j = 0; j < WN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 1
-        for (int q = 0; q < a.ksplit; ++q) {
-            f32x4 part[WM][WN];
-#pragma unroll
-            for (int i = 0; i < WM; ++i)
-#pragma unroll
-                for (int j = 0; j < WN; ++j) part[i][j] = load16_sc1(base + (long)q * 8 * kSlab + (i * WN + j) * 256, (uint32_t)lane * 16u);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-            for (int i = 0; i < WM; ++i)
-#pragma unroll
-                for (int j = 0; j < WN; ++j) {
-                    asm volatile("" : "+v"(part[i][j]));
-                    acc[i][j] += part[i][j];
-                }
-        }
+            for (int j = 0; j < WN; ++j) store16_sc1(mine + (i * WN + j) * 64, splitk_lane_off(), acc[i][j]);
+        // (the ring is dead behind the draw's first barrier: the ticket travels through its first word)
+        if ((int)splitk_draw(a.tickets + tile, 1u, (volatile unsigned int *)lds) != a.ksplit - 1) return;      // not the last one: done
+        splitk_own(a.tickets + tile);
+        splitk_sum<8>(acc, a.ws, tile, a.ksplit);                       // ALL the partial sums, its own included
     }
     store_tile<BM, BN>(acc, a.out, (long)NC, nullptr, m0, n0, a.Cout, NC, wr, wc, r, g);
 }
@@ -485,13 +447,12 @@ int qt_conv2d_wgrad_bf16(const uint16_t *gy, const uint16_t *x, uint16_t *gw, in
     if (!gy || !x || !gw || !bwd_geometry(a)) return QT_ERR_BAD_ARG;
     const WgradPlan p = wgrad_plan(a);
     if (p.ksplit > 1) {
-        if (!ws || !tickets || ws_bytes < p.ws_bytes() || n_tickets < p.tickets()) return QT_ERR_BAD_ARG;
-        if (((uintptr_t)ws & 15u) || ((uintptr_t)tickets & 3u)) return QT_ERR_UNALIGNED;
+        if (const int rc = qt_splitk_scratch_status(ws, ws_bytes, p.ws_bytes(), tickets, n_tickets, p.tickets())) return rc;
     }
     if (((uintptr_t)gy | (uintptr_t)x) & 15u) return QT_ERR_UNALIGNED;
     if ((uintptr_t)gw & 7u) return QT_ERR_UNALIGNED;
     a.tiles_m = p.tiles_m; a.tiles_n = p.tiles_n; a.ksplit = p.ksplit; a.kper = p.kper; a.nkt = p.nkt;
-    a.ws = ws; a.tickets = tickets;
+    a.ws = (f32x4 *)ws; a.tickets = tickets;
     hipStream_t st = (hipStream_t)stream;
     if (p.bm == 128) return wgrad_launch<128, 128>(a, st);
     return wgrad_launch<64, 64>(a, st);

@@ -44,29 +44,7 @@ namespace {
 typedef short v8s __attribute__((ext_vector_type(8)));
 typedef float v4f __attribute__((ext_vector_type(4)));
 
-template <int BITS>
-struct Geo {
-    static constexpr int kJ = BITS == 4 ? 4 : 2;      // k steps (of 32) per super step
-    static constexpr int kSK = 32 * kJ;               // k per super step
-};
 constexpr int kDepth = 4;                             // super steps a wave requests ahead
-
-inline long gwa_nss(int K, int bits) { return bits == 4 ? (K + 127) / 128 : (K + 63) / 64; }
-inline long gwa_pieces(int N, int K, int bits) { return (long)((N + 15) / 16) * gwa_nss(K, bits) * 64; }
-
-// the eight codes of k step j of a lane's 16 bytes, as floats q = code + quant_min (exact)
-template <int BITS>
-__device__ __forceinline__ void piece_codes(const u32x4 &p, int j, float qmin, float (&q)[8]) {
-    const uint32_t w[4] = {p.x, p.y, p.z, p.w};
-    if constexpr (BITS == 4) {
-        const uint32_t v = w[j];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) q[e] = (float)((v >> (4 * e)) & 15u) + qmin;
-    } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) q[e] = (float)((w[2 * j + (e >> 2)] >> (8 * (e & 3))) & 255u) + qmin;
-    }
-}
 
 // ---- pack ------------------------------------------------------------------------------------------------------------------------
 template <int BITS>
@@ -283,45 +261,23 @@ int launch_tile(Args &a, int tile_m, hipStream_t st) {
     }
 }
 
-inline bool aligned(const void *p, uintptr_t n) { return (((uintptr_t)p) & (n - 1)) == 0; }
-
-// log2 of a supported block size, or -1
-inline int bs_shift_of(int bs) {
-    switch (bs) {
-        case 32: return 5;
-        case 64: return 6;
-        case 128: return 7;
-        case 256: return 8;
-        case 512: return 9;
-        default: return -1;
-    }
-}
-
-// what every entry point asks of the weight's shape
-int shape_status(int N, int K, int bits) {
-    if ((bits != 4 && bits != 8) || N < 1 || K < 1) return QT_ERR_BAD_ARG;
-    if (K % 32 != 0 || N % 8 != 0) return QT_ERR_UNALIGNED;
-    if ((long)N * K > (1L << 40)) return QT_ERR_BAD_ARG;
-    return QT_OK;
-}
-
 }  // namespace
 
 extern "C" {
 
 size_t qt_gwa_packed_bytes(int N, int K, int bits) {
-    if (shape_status(N, K, bits) != QT_OK) return 0;
+    if (gwa_shape_status(N, K, bits) != QT_OK) return 0;
     return (size_t)gwa_pieces(N, K, bits) * 16;
 }
 
 int qt_gwa_pack(const uint16_t *codes_dev, uint8_t *packed_dev, int N, int K, int bits, float quant_min, float quant_max, int *bad_dev,
                 void *stream) {
     if (!codes_dev || !packed_dev) return QT_ERR_BAD_ARG;
-    if (const int rc = shape_status(N, K, bits)) return rc;
+    if (const int rc = gwa_shape_status(N, K, bits)) return rc;
     if (!(quant_max >= quant_min) || quant_max - quant_min > (bits == 4 ? 15.0f : 255.0f) || quant_min != rintf(quant_min) ||
         quant_max != rintf(quant_max))
         return QT_ERR_BAD_ARG;
-    if (!aligned(codes_dev, 16) || !aligned(packed_dev, 16) || !aligned(bad_dev, 4)) return QT_ERR_UNALIGNED;
+    if (!gwa_aligned(codes_dev, 16) || !gwa_aligned(packed_dev, 16) || !gwa_aligned(bad_dev, 4)) return QT_ERR_UNALIGNED;
     const long pieces = gwa_pieces(N, K, bits);
     const int nss = (int)gwa_nss(K, bits);
     const unsigned grid = grid_for((size_t)pieces, 256, 16);
@@ -334,11 +290,11 @@ int qt_gwa_pack(const uint16_t *codes_dev, uint8_t *packed_dev, int N, int K, in
 int qt_gwa_dequantize_bf16(const uint8_t *packed_dev, const uint16_t *scale_dev, const uint16_t *zp_dev, uint16_t *y_dev, int N, int K,
                            int block_size, int bits, float quant_min, void *stream) {
     if (!packed_dev || !scale_dev || !zp_dev || !y_dev) return QT_ERR_BAD_ARG;
-    if (const int rc = shape_status(N, K, bits)) return rc;
+    if (const int rc = gwa_shape_status(N, K, bits)) return rc;
     const int shift = bs_shift_of(block_size);
     if (shift < 0) return QT_ERR_BAD_ARG;
     if (K % block_size != 0) return QT_ERR_UNALIGNED;
-    if (!aligned(packed_dev, 16) || !aligned(y_dev, 16) || !aligned(scale_dev, 2) || !aligned(zp_dev, 2)) return QT_ERR_UNALIGNED;
+    if (!gwa_aligned(packed_dev, 16) || !gwa_aligned(y_dev, 16) || !gwa_aligned(scale_dev, 2) || !gwa_aligned(zp_dev, 2)) return QT_ERR_UNALIGNED;
     const long pieces = gwa_pieces(N, K, bits);
     const int nss = (int)gwa_nss(K, bits);
     const unsigned grid = grid_for((size_t)pieces, 256, 16);
@@ -353,15 +309,9 @@ int qt_linear_gwa_tile(int M) { return M <= 16 ? 16 : M <= 32 ? 32 : 64; }
 int qt_linear_gwa_bf16(const uint16_t *x_dev, const uint8_t *packed_dev, const uint16_t *scale_dev, const uint16_t *zp_dev,
                        const uint16_t *bias_dev, uint16_t *y_dev, int M, int N, int K, int block_size, int bits, float quant_min, int tile_m,
                        void *stream) {
-    if (!x_dev || !packed_dev || !scale_dev || !zp_dev || !y_dev || M < 0) return QT_ERR_BAD_ARG;
-    if (const int rc = shape_status(N, K, bits)) return rc;
-    const int shift = bs_shift_of(block_size);
-    if (shift < 0 || !(tile_m == 0 || tile_m == 16 || tile_m == 32 || tile_m == 64)) return QT_ERR_BAD_ARG;
-    if (K % block_size != 0) return QT_ERR_UNALIGNED;
-    if ((long)M * K > (1L << 40) || (long)M * N > (1L << 40)) return QT_ERR_BAD_ARG;
-    if (!aligned(x_dev, 16) || !aligned(packed_dev, 16) || !aligned(y_dev, 16) || !aligned(scale_dev, 2) || !aligned(zp_dev, 2) ||
-        !aligned(bias_dev, 8))
-        return QT_ERR_UNALIGNED;
+    int shift;
+    const bool knobs_ok = tile_m == 0 || tile_m == 16 || tile_m == 32 || tile_m == 64;
+    if (const int rc = linear_gwa_status(x_dev, packed_dev, scale_dev, zp_dev, bias_dev, y_dev, M, N, K, block_size, bits, knobs_ok, shift)) return rc;
     if (M == 0) return QT_OK;
     Args a{};
     a.x = x_dev; a.packed = (const u32x4 *)packed_dev; a.scale = scale_dev; a.zp = zp_dev; a.bias = bias_dev; a.y = y_dev;

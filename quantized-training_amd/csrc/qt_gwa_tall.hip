@@ -29,7 +29,7 @@
 // clamped for reading; rows >= M and columns >= N are never stored.
 // Split of K.  `ksplit` workgroups share a tile over contiguous ranges of super steps; each leaves its fp32 partial tile in the
 // caller's workspace (write-through), and the one that draws the tile's last ticket adds the partial sums IN SPLIT ORDER, its own
-// included, resets the ticket and runs the epilogue (the hand-over of qt_conv_backward.hip).  Nobody waits; the bits do not depend
+// included, resets the ticket and runs the epilogue (the hand-over of qt_splitk.h).  Nobody waits; the bits do not depend
 // on who arrived last.  fp32 accumulation in k order, bias added in fp32, one rounding to bf16; no atomics on floats, no scratch.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -39,6 +39,7 @@
 #include "qt_dispatch.h"
 #include "qt_gemm_ring.h"
 #include "qt_gwa.h"
+#include "qt_splitk.h"
 
 namespace {
 
@@ -49,12 +50,6 @@ __device__ __attribute__((aligned(128))) const uint32_t kZeroRow[32] = {0};     
 constexpr int kBN = 128;                                  // columns of a tile: 8 groups of 16, one per wave
 constexpr int kMaxSplit = 8;
 
-template <int BITS>
-struct Geo {
-    static constexpr int kJ = BITS == 4 ? 4 : 2;          // k steps (of 32) per super step
-    static constexpr int kSK = 32 * kJ;                   // k per super step
-    static constexpr int kKT = kSK / kBK;                 // k tiles per super step
-};
 template <int BM>
 struct TallRing {
     static constexpr int kStages = BM == 128 ? 4 : 3;
@@ -63,8 +58,6 @@ struct TallRing {
     static constexpr int kBytes = kStage * kStages;
 };
 
-inline int tall_nss(int K, int bits) { return bits == 4 ? (K + 127) / 128 : (K + 63) / 64; }
-
 struct Args {
     const uint16_t *x;        // [M][K] bf16
     const u32x4 *packed;      // [n16][nss][64] pieces
@@ -72,7 +65,7 @@ struct Args {
     const uint16_t *zp;       // [N][K / bs] bf16
     const uint16_t *bias;     // [N] bf16 or NULL
     uint16_t *y;              // [M][N] bf16
-    float *ws;                // ksplit > 1: [tile][split][wave][fragment][64 lanes][4] fp32
+    f32x4 *ws;                // ksplit > 1: the partial sums (splitk_slab)
     unsigned int *tickets;    // ksplit > 1: [tile] arrival counters, zero between launches
     int M, N, K;
     int nkb, bs_shift;        // K / bs, log2 bs
@@ -99,32 +92,20 @@ __device__ __forceinline__ void wait_loads(u32x4 &pc, uint32_t (&sr)[NB], uint32
     for (int b = 0; b < NB; ++b) asm volatile("" : "+v"(sr[b]), "+v"(zr[b]));
 }
 
-__device__ __forceinline__ void store16_sc1(const float *sbase, uint32_t voff, f32x4 v) {
-    asm volatile("global_store_dwordx4 %0, %1, %2 sc1" ::"v"(voff), "v"(v), "s"(sbase) : "memory");
-}
-__device__ __forceinline__ f32x4 load16_sc1(const float *sbase, uint32_t voff) {
-    f32x4 v;
-    asm volatile("global_load_dwordx4 %0, %1, %2 sc1" : "=v"(v) : "v"(voff), "s"(sbase) : "memory");
-    return v;
-}
-
 // the eight bf16 values of k step j of a lane's piece, as one 16-byte chunk
 template <int BITS>
 __device__ __forceinline__ u32x4 chunk_of(const u32x4 &p, int j, float qmin, float z, float s) {
-    const uint32_t w[4] = {p.x, p.y, p.z, p.w};
     float q[8];
+    piece_codes<BITS>(p, j, qmin, q);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const uint32_t c = BITS == 4 ? (w[j] >> (4 * e)) & 15u : (w[2 * j + (e >> 2)] >> (8 * (e & 3))) & 255u;
-        q[e] = gwa_dequant<kIoBf16>((float)c + qmin, z, s);
-    }
+    for (int e = 0; e < 8; ++e) q[e] = gwa_dequant<kIoBf16>(q[e], z, s);
     return u32x4{pack_bf16x2(q[0], q[1]), pack_bf16x2(q[2], q[3]), pack_bf16x2(q[4], q[5]), pack_bf16x2(q[6], q[7])};
 }
 
 template <int BITS, int BM, int NB>
 __global__ __launch_bounds__(kThreads) void linear_gwa_tall_kernel(const Args a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    constexpr int J = Geo<BITS>::kJ, SK = Geo<BITS>::kSK, KT = Geo<BITS>::kKT;
+    constexpr int J = Geo<BITS>::kJ, SK = Geo<BITS>::kSK, KT = SK / kBK;     // KT: k tiles per super step
     constexpr int S = TallRing<BM>::kStages, kXImg = TallRing<BM>::kXImg, kStage = TallRing<BM>::kStage;
     constexpr int kAV = BM / 64;                                          // DMA pieces (1 KiB) per wave and k tile
     constexpr int WM = BM / 64, WN = kBN / 32;
@@ -241,45 +222,16 @@ __global__ __launch_bounds__(kThreads) void linear_gwa_tall_kernel(const Args a)
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");         // the zero tiles requested past the range
     }
 
-    if (a.ksplit > 1) {
-        // ---- the hand-over (qt_conv_backward.hip).  Partial sums leave in fragment order, write-through; every wave drains its stores;
-        // behind the workgroup barrier ONE lane takes the tile's ticket.  Whoever draws the last ticket owns the tile: it adds ALL the
-        // partial sums, its own included, in split order.
-        constexpr long kSlab = (long)WM * WN * 256;                       // floats per wave
-        float *const mine = a.ws + (((long)tile * a.ksplit + split) * 8 + wave) * kSlab;
+    if (a.ksplit > 1) {                                                   // the hand-over of qt_splitk.h
+        f32x4 *const mine = splitk_slab<8, WM * WN>(a.ws, tile, a.ksplit, split);
 #pragma unroll
         for (int i = 0; i < WM; ++i)
 #pragma unroll
-            for (int j = 0; j < WN; ++j) store16_sc1(mine + (i * WN + j) * 256, (uint32_t)lane * 16u, acc[i][j]);
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __syncthreads();                                                  // (also: every wave is done with the ring, the flag below reuses it)
-        volatile unsigned int *flag = (volatile unsigned int *)lds;
-        if (t == 0) *flag = __hip_atomic_fetch_add(a.tickets + tile, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        if ((int)*flag != a.ksplit - 1) return;                           // not the last one: done
-        if (t == 0) __hip_atomic_store(a.tickets + tile, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");                // drop what this XCD's L2 holds of the workspace from earlier launches
-        const float *const base = a.ws + ((long)tile * a.ksplit * 8 + wave) * kSlab;
-#pragma unroll
-        for (int i = 0; i < WM; ++i)
-#pragma unroll
-            for (int j = 0; j < WN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 1
-        for (int q = 0; q < a.ksplit; ++q) {
-            f32x4 part[WM][WN];
-#pragma unroll
-            for (int i = 0; i < WM; ++i)
-#pragma unroll
-                for (int j = 0; j < WN; ++j) part[i][j] = load16_sc1(base + (long)q * 8 * kSlab + (i * WN + j) * 256, (uint32_t)lane * 16u);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-            for (int i = 0; i < WM; ++i)
-#pragma unroll
-                for (int j = 0; j < WN; ++j) {
-                    asm volatile("" : "+v"(part[i][j]));
-                    acc[i][j] += part[i][j];
-                }
-        }
+            for (int j = 0; j < WN; ++j) store16_sc1(mine + (i * WN + j) * 64, splitk_lane_off(), acc[i][j]);
+        // (the ring is dead behind the draw's first barrier: the ticket travels through its first word)
+        if ((int)splitk_draw(a.tickets + tile, 1u, (volatile unsigned int *)lds) != a.ksplit - 1) return;      // not the last one: done
+        splitk_own(a.tickets + tile);
+        splitk_sum<8>(acc, a.ws, tile, a.ksplit);                         // ALL the partial sums, its own included
     }
     store_tile<BM, kBN>(acc, a.y, (long)a.N, a.bias, m0, n0, a.M, a.N, wr, wc, r, g);
 }
@@ -304,32 +256,11 @@ TallPlan tall_plan(int M, int N, int K, int bits, int tile_m, int ksplit) {
     p.tiles_n = (int)tn;
     p.ksplit = ksplit;
     if (!ksplit) {
-        const int nss = tall_nss(K, bits);
+        const long nss = gwa_nss(K, bits);
         p.ksplit = 1;
         for (int s = 2; s <= kMaxSplit && p.tiles() * s <= cus && nss / s >= 2; s *= 2) p.ksplit = s;
     }
     return p;
-}
-
-inline bool aligned(const void *p, uintptr_t n) { return (((uintptr_t)p) & (n - 1)) == 0; }
-
-inline int bs_shift_of(int bs) {
-    switch (bs) {
-        case 32: return 5;
-        case 64: return 6;
-        case 128: return 7;
-        case 256: return 8;
-        case 512: return 9;
-        default: return -1;
-    }
-}
-
-// what the family asks of the weight's shape (qt_gwa_gemm.hip)
-int shape_status(int N, int K, int bits) {
-    if ((bits != 4 && bits != 8) || N < 1 || K < 1) return QT_ERR_BAD_ARG;
-    if (K % 32 != 0 || N % 8 != 0) return QT_ERR_UNALIGNED;
-    if ((long)N * K > (1L << 40)) return QT_ERR_BAD_ARG;
-    return QT_OK;
 }
 
 template <int BITS, int BM, int NB>
@@ -347,7 +278,7 @@ extern "C" {
 
 int qt_linear_gwa_tall_plan(int M, int N, int K, int bits, int tile_m, int *tile_m_out, int *ksplit_out, size_t *ws_bytes, size_t *n_tickets) {
     if (M < 0 || !(tile_m == 0 || tile_m == 128 || tile_m == 256)) return QT_ERR_BAD_ARG;
-    if (const int rc = shape_status(N, K, bits)) return rc;
+    if (const int rc = gwa_shape_status(N, K, bits)) return rc;
     const TallPlan p = tall_plan(M, N, K, bits, tile_m, 0);
     if (tile_m_out) *tile_m_out = p.bm;
     if (ksplit_out) *ksplit_out = p.ksplit;
@@ -359,30 +290,22 @@ int qt_linear_gwa_tall_plan(int M, int N, int K, int bits, int tile_m, int *tile
 int qt_linear_gwa_tall_bf16(const uint16_t *x_dev, const uint8_t *packed_dev, const uint16_t *scale_dev, const uint16_t *zp_dev,
                             const uint16_t *bias_dev, uint16_t *y_dev, int M, int N, int K, int block_size, int bits, float quant_min, int tile_m,
                             int ksplit, float *ws_dev, size_t ws_bytes, uint32_t *tickets_dev, size_t n_tickets, void *stream) {
-    if (!x_dev || !packed_dev || !scale_dev || !zp_dev || !y_dev || M < 0) return QT_ERR_BAD_ARG;
-    if (const int rc = shape_status(N, K, bits)) return rc;
-    const int shift = bs_shift_of(block_size);
-    if (shift < 0 || !(tile_m == 0 || tile_m == 128 || tile_m == 256)) return QT_ERR_BAD_ARG;
-    if (!(ksplit == 0 || ksplit == 1 || ksplit == 2 || ksplit == 4 || ksplit == 8)) return QT_ERR_BAD_ARG;
-    if (K % block_size != 0) return QT_ERR_UNALIGNED;
-    if ((long)M * K > (1L << 40) || (long)M * N > (1L << 40)) return QT_ERR_BAD_ARG;
-    if (!aligned(x_dev, 16) || !aligned(packed_dev, 16) || !aligned(y_dev, 16) || !aligned(scale_dev, 2) || !aligned(zp_dev, 2) ||
-        !aligned(bias_dev, 8))
-        return QT_ERR_UNALIGNED;
+    int shift;
+    const bool knobs_ok = (tile_m == 0 || tile_m == 128 || tile_m == 256) && (ksplit == 0 || ksplit == 1 || ksplit == 2 || ksplit == 4 || ksplit == 8);
+    if (const int rc = linear_gwa_status(x_dev, packed_dev, scale_dev, zp_dev, bias_dev, y_dev, M, N, K, block_size, bits, knobs_ok, shift)) return rc;
     if (M == 0) return QT_OK;
     const TallPlan p = tall_plan(M, N, K, bits, tile_m, ksplit);
     if (p.ksplit > 1) {
-        if (!ws_dev || !tickets_dev || ws_bytes < p.ws_bytes() || n_tickets < p.tickets()) return QT_ERR_BAD_ARG;
-        if (!aligned(ws_dev, 16) || !aligned(tickets_dev, 4)) return QT_ERR_UNALIGNED;
+        if (const int rc = qt_splitk_scratch_status(ws_dev, ws_bytes, p.ws_bytes(), tickets_dev, n_tickets, p.tickets())) return rc;
     }
     const long grid = p.tiles() * p.ksplit;
     if (grid > 0x7FFFFFFFL) return QT_ERR_BAD_ARG;
     Args a{};
     a.x = x_dev; a.packed = (const u32x4 *)packed_dev; a.scale = scale_dev; a.zp = zp_dev; a.bias = bias_dev; a.y = y_dev;
-    a.ws = ws_dev; a.tickets = tickets_dev;
+    a.ws = (f32x4 *)ws_dev; a.tickets = tickets_dev;
     a.M = M; a.N = N; a.K = K;
     a.nkb = K / block_size; a.bs_shift = shift;
-    a.nss = tall_nss(K, bits); a.n16 = (N + 15) / 16; a.tiles_m = p.tiles_m; a.ksplit = p.ksplit;
+    a.nss = (int)gwa_nss(K, bits); a.n16 = (N + 15) / 16; a.tiles_m = p.tiles_m; a.ksplit = p.ksplit;
     a.qmin = quant_min;
     hipStream_t st = (hipStream_t)stream;
     // blocks per super step: the scale and zero-point loads of a conversion (1 where a block spans the super step)

@@ -36,6 +36,7 @@
 #include "../../include/qt_hip.h"
 #include "qt_device.h"
 #include "qt_formats.h"
+#include "qt_splitk.h"
 
 namespace {
 
@@ -58,25 +59,13 @@ struct Args {
     // split-K (narrow outputs: too few tiles to fill the chip): `ksplit` workgroups share a tile, each multiplies a contiguous range of
     // k steps and writes its fp32 partial sums to `ws`; the LAST one to arrive at the tile's ticket adds them in split order and writes y
     int ksplit;
-    float *ws;                // [tile][split][wave][kRT x kMaxNTW fragments][64 lanes][4] fp32
+    v4f *ws;                  // the partial sums (splitk_slab: 8 waves x kRT x kMaxNTW fragments)
     unsigned int *tickets;    // [tile] arrival counters, zero between launches (the last arriver resets its tile's)
     Segment seg[kMaxSeg];
 #ifdef QT_TUNING_BUILD
     unsigned long long *stamps;   // tools/ only (QT_FQT_STAMPS = device address): see LinearFqt's STAMPS
 #endif
 };
-
-// Split-K hand-off between workgroups: every byte is stored write-through (sc1) and loaded past the L1 (sc1); the stores are drained
-// (s_waitcnt vmcnt(0)) in front of the workgroup barrier that precedes the ticket's atomic add.
-// Addresses are a wave-uniform base (SGPR pair) + a 32-bit lane offset: no address registers per access.
-__device__ __forceinline__ void store16_sc1(const float *sbase, uint32_t voff, v4f v) {
-    asm volatile("global_store_dwordx4 %0, %1, %2 sc1" ::"v"(voff), "v"(v), "s"(sbase) : "memory");
-}
-__device__ __forceinline__ v4f load16_sc1(const float *sbase, uint32_t voff) {
-    v4f v;
-    asm volatile("global_load_dwordx4 %0, %1, %2 sc1" : "=v"(v) : "v"(voff), "s"(sbase) : "memory");
-    return v;
-}
 
 // Both operand tiles: row-major 64-byte rows (32 bf16 = four 16-byte k chunks).  A fragment read is sixteen rows x one chunk per
 // 16-lane group of ds_read_b128; rows four apart share a bank row, so chunk c of row R sits at position c ^ pi((R >> 2) & 3),
@@ -501,46 +490,30 @@ struct LinearFqt {
         if (a.ksplit <= 1) {
             if (flagged) return true;
         } else {
-            // ---- split-K hand-off.  Partial sums leave in fragment order (a wave's store instruction writes one contiguous KiB),
-            // write-through; every wave drains its stores; behind the workgroup barrier ONE lane takes the tile's ticket.  Whoever
-            // draws the last ticket owns the tile: it adds the partial sums IN SPLIT ORDER (so the result does not depend on who
-            // arrived last) and runs the ordinary epilogue.  Nobody ever waits for another workgroup.  A
-            // flagged split says so in the ticket's upper half and the owner redoes the whole tile through the map.
-            constexpr long kSlab = (long)kRT * kMaxNTW * 256;                    // floats per wave
-            float *const mine = a.ws + (((long)tile_lin * a.ksplit + split) * 8 + w) * kSlab;
+            // ---- the hand-over of qt_splitk.h, the fragment of (i, j) at index i kMaxNTW + j of the wave's slab.  A flagged split stores
+            // nothing and says so in the ticket's upper half; the owner then redoes the whole tile through the map.
+            constexpr int kFrags = kRT * kMaxNTW;
             if constexpr (NTW > 0) {
                 if (!flagged) {
+                    v4f *const mine = splitk_slab<8, kFrags>(a.ws, tile_lin, a.ksplit, split);
 #pragma unroll
                     for (int i = 0; i < kRT; ++i)
 #pragma unroll
-                        for (int j = 0; j < NTW; ++j) store16_sc1(mine + (i * kMaxNTW + j) * 256, (uint32_t)l * 16u, acc[i][j]);
+                        for (int j = 0; j < NTW; ++j) store16_sc1(mine + (i * kMaxNTW + j) * 64, splitk_lane_off(), acc[i][j]);
                 }
             }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            // (RELAXED on purpose: the ordering is the sc1 stores + s_waitcnt + barrier in front and the sc1 loads behind -- valid on gfx942 /
-            // gfx950, which qt_device.h asserts at compile time; an agent-scope acquire / release here writes back and invalidates the
-            // whole L2, behind 20 MB of partial sums)
-            if (w == 0 && l == 0) {
-                const unsigned int old = __hip_atomic_fetch_add(a.tickets + tile_lin, 1u + (flagged ? 0x10000u : 0u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                *flag = (int)old;
-            }
-            __syncthreads();
-            const unsigned int old = (unsigned int)*flag;
+            const unsigned int old = splitk_draw(a.tickets + tile_lin, 1u + (flagged ? 0x10000u : 0u), (volatile unsigned int *)lds);
             if ((int)(old & 0xFFFFu) != a.ksplit - 1) return false;               // not the last one: done
-            if (w == 0 && l == 0) __hip_atomic_store(a.tickets + tile_lin, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            splitk_own(a.tickets + tile_lin);                                     // (its acquire fence also runs in front of a redo, which reads no workspace: harmless, and rare)
             if ((old >> 16) != 0u || flagged) return true;                        // some split met a flagged row: redo the tile
-            // reader's side: whatever this XCD's L2 still holds of the workspace from an earlier launch is dropped (acquire = invalidate,
-            // nothing is written back; only the owner of a tile pays it)
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
             if constexpr (NTW > 0) {
                 // Every split's partial sums come back from the workspace, this workgroup's own included (no instruction depends
                 // on which split arrived last): t = p_0 + p_1 + ... in split order, + bias, rounded to bf16, stored straight from
                 // the fragment layout (8 bytes per lane: the owner's stores are a small part of the launch).  A rolled loop over
                 // batches of four fragments with nothing but the batch live: the unrolled form over the whole accumulator array made
                 // hipcc keep two copies of it and spill; S x 8 (S = 4: x 4) loads of 16 bytes in flight per lane.
-                const float *const base = a.ws + ((long)tile_lin * a.ksplit * 8 + w) * kSlab;
-                const uint32_t voff = (uint32_t)l * 16u;
+                const v4f *const base = splitk_slab<8, kFrags>(a.ws, tile_lin, a.ksplit, 0);
+                const uint32_t voff = splitk_lane_off();
                 const int row0 = m0 + wm * (TM / 4) + r;
                 auto reduce = [&](auto sc) __attribute__((always_inline)) {
                     constexpr int S = decltype(sc)::value, kB = 4, kFrag = kRT * NTW;
@@ -552,7 +525,7 @@ struct LinearFqt {
 #pragma unroll
                             for (int b = 0; b < kB; ++b) {
                                 const int f = f0 + b < kFrag ? f0 + b : kFrag - 1;      // (a ragged last batch re-reads the last fragment)
-                                part[q][b] = load16_sc1(base + (long)q * 8 * kSlab + ((f / NTW) * kMaxNTW + f % NTW) * 256, voff);
+                                part[q][b] = load16_sc1(base + (long)q * 8 * kFrags * 64 + ((f / NTW) * kMaxNTW + f % NTW) * 64, voff);
                             }
                         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
@@ -846,8 +819,7 @@ int linear_fqt(const uint16_t *x_dev, const uint16_t *const *w_devs, const uint1
     const long groups = ntot / 16;
     const Tiling t = make_tiling(M, groups, K, may_split);
     if (t.ksplit > 1) {
-        if (!ws_dev || !tickets_dev || ws_bytes < t.ws_bytes() || n_tickets < t.tickets()) return QT_ERR_BAD_ARG;
-        if (((uintptr_t)ws_dev & 15u) || ((uintptr_t)tickets_dev & 3u)) return QT_ERR_UNALIGNED;
+        if (const int rc = qt_splitk_scratch_status(ws_dev, ws_bytes, t.ws_bytes(), tickets_dev, n_tickets, t.tickets())) return rc;
     }
     Args a{};
     a.x = x_dev; a.y = y_dev; a.rows = rows_dev; a.map = map_dev; a.sign_mask = sign_mask;
@@ -856,7 +828,7 @@ int linear_fqt(const uint16_t *x_dev, const uint16_t *const *w_devs, const uint1
     if (const char *e_st = getenv("QT_FQT_STAMPS")) a.stamps = (unsigned long long *)strtoull(e_st, nullptr, 0);
 #endif
     a.tiles_m = t.tiles_m; a.tiles_n = t.tiles_n; a.gbase = t.gbase; a.gextra = t.gextra;
-    a.ksplit = t.ksplit; a.ws = ws_dev; a.tickets = tickets_dev;
+    a.ksplit = t.ksplit; a.ws = (v4f *)ws_dev; a.tickets = tickets_dev;
     int nseg = 0, g0 = 0;
     for (int i = 0; i < count; ++i) {
         if (ns[i] == 0) continue;

@@ -2,6 +2,7 @@
 // per-tensor graphs on the integer one (qt_q8_conv2d* with the split of K and the codes-out chain) and their depthwise kernel
 // (qt_q8_dwconv2d*).  Tile image, matrix step, dense B side, tile map and epilogues: qt_mx_tile.h.
 #include "qt_mx_tile.h"
+#include "qt_splitk.h"
 
 namespace {
 
@@ -21,36 +22,19 @@ namespace {
 // ---- split of K (qt_q8_conv2d_ws, I8 only) -----------------------------------------------------------------------------------------
 // A long contraction over few output tiles (a reducing 1 x 1 layer, a small batch) leaves most of the chip idle.  S workgroups
 // then share a tile: split s walks the k tiles [s nk / S, (s + 1) nk / S) (S <= nk: none is empty) and leaves its 64 int32 sums per
-// thread in the caller's workspace, [tile][split][fragment 4 i + j][thread] of int4: a wave's store is one contiguous KiB.  The
-// hand-over is the one of qt_conv_backward.hip / qt_linear_fqt.hip: write-through stores, drained by every wave in front of the
-// workgroup barrier; one lane then draws the tile's ticket (relaxed, agent scope).  Whoever draws the last ticket owns the tile:
-// it reads the other S - 1 partial sums past its L1, adds them AS INTEGERS to the sums it holds in registers (exact in any order:
-// kh kw Cin < 2^17 bounds every partial and the total below 2^31, so the result is bit for bit the unsplit kernel's, whoever
-// arrives last), resets the ticket and runs the unchanged epilogue with its single float(acc).  Nobody waits for anybody; tickets
-// are zero between launches.  The owner is not known before the ticket is drawn, so every split stores (the owner's own 64 KiB
-// are never read).  Like the tail of the CODES instantiations the split state is a kernel parameter of the SPLIT instantiations only.
+// thread in the caller's workspace; the hand-over is the one of qt_splitk.h.  Whoever draws the last ticket adds the other S - 1
+// partial sums AS INTEGERS to the sums it holds in registers (exact in any order: kh kw Cin < 2^17 bounds every partial and the total
+// below 2^31, so the result is bit for bit the unsplit kernel's, whoever arrives last) and runs the unchanged epilogue with its single
+// float(acc).  Like the tail of the CODES instantiations the split state is a kernel parameter of the SPLIT instantiations only.
 struct SplitK {
-    v4i *ws;                     // [tile][split][16 fragments][256 threads]
+    v4i *ws;                     // the partial sums (splitk_slab: 4 waves x 16 fragments)
     unsigned int *tickets;       // [tile], zero between launches
     int S;
 };
 struct NoSplit {};
 template <bool SPLIT>
 using split_t = std::conditional_t<SPLIT, SplitK, NoSplit>;
-constexpr long kSplitSlab = 16L * 256;        // int4 per tile and split: 64 KiB
-
-// The compiler pads nothing inside an asm string and knows no hazard of the instruction in it.  Two are live here: the base is
-// computed by scalar adds right in front (an SGPR written by the SALU needs wait states before a vector memory instruction reads it:
-// s_nop 4 opens the string), and the sums are copied out of the accumulation registers into the same four VGPRs for every fragment
-// (a 16-byte store reads its data over several cycles: s_nop 1 ends the string, so that the next copy cannot overwrite them).
-__device__ __forceinline__ void store16_sc1(const v4i *sbase, uint32_t voff, v4i v) {
-    asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 sc1\n\ts_nop 1" ::"v"(voff), "v"(v), "s"(sbase) : "memory");
-}
-__device__ __forceinline__ v4i load16_sc1(const v4i *sbase, uint32_t voff) {
-    v4i v;
-    asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2 sc1" : "=v"(v) : "v"(voff), "s"(sbase) : "memory");
-    return v;
-}
+constexpr long kSplitSlab = 4L * 16 * 64;     // int4 per tile and split: 64 KiB
 
 // I8 (qt_q8_conv2d): int8 codes on both sides, int32 accumulators, no scale bytes -- every scale load below is compiled out --
 // and the dequantize factor of emit_out in the epilogue.
@@ -193,21 +177,17 @@ __global__ __launch_bounds__(256) void mx_conv_kernel(MxGemmArgs a, MxConvGeom c
     }
     mma_tile<FA, FB, I8>(s_a((kt1 - 1 - kt0) & 1), s_b((kt1 - 1 - kt0) & 1), cs_a, cs_b, acc);
 
-    if constexpr (SPLIT) {
-        const v4i *const tile_ws = sp.ws + (long)id * sp.S * kSplitSlab;
-        const v4i *const mine = tile_ws + (long)split * kSplitSlab;
+    if constexpr (SPLIT) {                                      // the hand-over of qt_splitk.h
+        v4i *const mine = splitk_slab<4, 16>(sp.ws, id, sp.S, split);
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) store16_sc1(mine + (i * 4 + j) * 256, (uint32_t)t * 16u, acc[i][j]);
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __syncthreads();                                        // (also: every wave has read its last fragments, the flag reuses the tiles)
-        volatile unsigned int *flag = (volatile unsigned int *)lds;
-        if (t == 0) *flag = __hip_atomic_fetch_add(sp.tickets + id, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        if ((int)*flag != sp.S - 1) return;                     // not the last one: done
-        if (t == 0) __hip_atomic_store(sp.tickets + id, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");      // drop what this XCD's L2 holds of the workspace from earlier launches
+            for (int j = 0; j < 4; ++j) store16_sc1(mine + (i * 4 + j) * 64, splitk_lane_off(), acc[i][j]);
+        // (every wave has read its last fragments behind the draw's first barrier: the ticket travels through the tiles' first word)
+        if ((int)splitk_draw(sp.tickets + id, 1u, (volatile unsigned int *)lds) != sp.S - 1) return;      // not the last one: done
+        splitk_own(sp.tickets + id);
+        // the other splits' sums onto the ones in registers, in split order; the loop of splitk_sum written here (see there)
+        const v4i *const base = splitk_slab<4, 16>((const v4i *)sp.ws, id, sp.S, 0);
 #pragma unroll 1
         for (int q = 0; q < sp.S; ++q) {
             if (q == split) continue;
@@ -215,7 +195,7 @@ __global__ __launch_bounds__(256) void mx_conv_kernel(MxGemmArgs a, MxConvGeom c
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) part[i][j] = load16_sc1(tile_ws + (long)q * kSplitSlab + (i * 4 + j) * 256, (uint32_t)t * 16u);
+                for (int j = 0; j < 4; ++j) part[i][j] = load16_sc1(base + (long)q * kSplitSlab + (i * 4 + j) * 64, splitk_lane_off());
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
             for (int i = 0; i < 4; ++i)
@@ -509,8 +489,7 @@ static int q8_conv2d_launch(const int8_t *x_codes, const int8_t *w_codes, void *
         if (p.ksplit > p.nk) return QT_ERR_BAD_ARG;
         if (p.ksplit > 1) {
             if (tiles * p.ksplit >= kLim) return QT_ERR_BAD_ARG;
-            if (!wsp->ws || !wsp->tickets || wsp->ws_bytes < p.ws_bytes() || wsp->n_tickets < p.tickets()) return QT_ERR_BAD_ARG;
-            if (((uintptr_t)wsp->ws & 15u) || ((uintptr_t)wsp->tickets & 3u)) return QT_ERR_UNALIGNED;
+            if (const int rc = qt_splitk_scratch_status(wsp->ws, wsp->ws_bytes, p.ws_bytes(), wsp->tickets, wsp->n_tickets, p.tickets())) return rc;
             const SplitK sp{(v4i *)wsp->ws, wsp->tickets, p.ksplit};
             const unsigned grid = (unsigned)(tiles * p.ksplit);
             if (ct) return launch_conv_split<true>(g, c, grid, (hipStream_t)stream, *ct, sp);
