@@ -1053,6 +1053,43 @@ int qt_quantize_codes_nhwc_bf16(const uint16_t *x_dev, int8_t *codes_dev, long N
 int qt_quantize_codes_nhwc_f32(const float *x_dev, int8_t *codes_dev, long N, long HW, long C, long batch_stride, long row_stride,
                                long channel_stride, const qt_format *fmt, const uint16_t *lut_dev, const float *scale_dev, void *stream);
 
+/* The same pass for 1 <= C <= 4 channels, the activation operand of qt_q8_stem_conv2d: ONE uint32 per pixel, codes4[n][p] byte c =
+ * narrow(map[index(x[n, c, p] / scale)]) for c < C (the same device function, the same narrowing rule), bytes c >= C zero.  x by the
+ * same element strides, NCHW-contiguous (reads run along HW) or channels_last-dense; a single channel has no stride of its own, so
+ * for C == 1 channel_stride is not looked at.  One read of x, one dword written per pixel.
+ * QT_ERR_BAD_ARG: NULL x / codes / scale / fmt, a table format without its table, C > 4, N HW >= 2^31, any other stride triple;
+ * QT_ERR_UNALIGNED: x or codes off a 16-byte boundary.  All answered before the first HIP call; QT_OK without a launch for an
+ * empty tensor. */
+int qt_quantize_codes_nhwc4_bf16(const uint16_t *x_dev, uint32_t *codes4_dev, long N, long HW, long C, long batch_stride, long row_stride,
+                                 long channel_stride, const qt_format *fmt, const uint16_t *lut_dev, const uint16_t *scale_dev, void *stream);
+int qt_quantize_codes_nhwc4_f32(const float *x_dev, uint32_t *codes4_dev, long N, long HW, long C, long batch_stride, long row_stride,
+                                long channel_stride, const qt_format *fmt, const uint16_t *lut_dev, const float *scale_dev, void *stream);
+
+/* The FIRST convolution of such a graph (1 <= Cin <= 4: the stem qt_q8_conv2d's gather cannot take) on v_mfma_i32_16x16x64_i8, with
+ * qt_q8_conv2d's epilogue and result:
+ *     y[n, ho, wo, co] = round_y( round_y( float(sum_{r, s, c} x[n, hi, wi, c] w[co, r, s, c]) + bias[co] ) * out_scale )
+ * x_codes4: the dwords of qt_quantize_codes_nhwc4_* , [N][H][W] x 4 bytes (a byte >= Cin is multiplied by a zero weight: its content
+ * never reaches a sum); w_codes int8 [Cout][kh][kw][Cin], the weight as stored for conv2d_q (a workgroup pads it into its LDS image:
+ * no second copy in memory); y NHWC [N][Ho][Wo][Cout] bf16 or fp32; bias, out_scale, out_scale_per_col, fold_f32 as in qt_q8_conv2d.
+ * A workgroup stages the input halo of an 8 x 16 patch of output pixels into LDS once (zero dwords outside the plane; no address
+ * outside x is read) and contracts in (r, s, c4) order with kw rounded up to a multiple of 4, so a lane's 16-byte A fragment is four
+ * neighbouring pixel dwords of one halo row.  kh kw 4 <= 1024 keeps |sum| <= 2^24: int32 is exact and float() rounds nothing.
+ * QT_ERR_BAD_ARG: a NULL operand or output; Cin < 1 or Cin > 4; kh or kw > 16; a dilation other than 1; Cout % 16 != 0; strides
+ * whose halo -- (7 sh + kh') x (15 sw + kw') dwords next to the weight image -- exceeds the kernel's 96 KiB of LDS; a non-positive
+ * extent or stride, a negative padding; N Ho Wo or the byte size of either code array >= 2^31, strides or paddings >= 2^20.
+ * QT_ERR_UNALIGNED: any pointer off a 16-byte boundary.  All answered before the first HIP call; an empty output is QT_OK without a
+ * launch.  Every element of y is written and nothing else; no atomics, no allocation, no synchronisation: the same bits on every
+ * launch, safe under stream capture.
+ * qt_q8_stem_conv2d_codes: the codes-out sibling (see qt_q8_conv2d_codes: the same trailing arguments, checks and per-element tail);
+ * y int8 [N Ho Wo][Cout], written in whole 16-byte runs. */
+int qt_q8_stem_conv2d(const int8_t *x_codes4, const int8_t *w_codes, void *y, int y_is_f32, const void *bias, const void *out_scale,
+                      int out_scale_per_col, int fold_f32, int N, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw, int ph,
+                      int pw, int dh, int dw, void *stream);
+int qt_q8_stem_conv2d_codes(const int8_t *x_codes4, const int8_t *w_codes, int8_t *y, int y_is_f32, const void *bias, const void *out_scale,
+                            int out_scale_per_col, int fold_f32, int N, int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw, int ph,
+                            int pw, int dh, int dw, int act, float act_lo, float act_hi, const void *next_scale, const uint16_t *next_qmap,
+                            void *stream);
+
 /* Fused quantize_mx for blocks along the last axis (decomposed.py:365-448 with axes = [-1]): x [rows][cols] in the
  * tensor dtype -> q (element values map[x / scale], nullable), scales [rows][cols / block_size] (same dtype), and, when
  * codes / e8m0 are given (requires force_pow2, block_size % 32 == 0, pack_format = the QT_MX_* format the map rounds

@@ -1364,6 +1364,30 @@ __global__ __launch_bounds__(256) void codes_flat_kernel(const void *__restrict_
     }
 }
 
+// 1 - 4 channels (qt_quantize_codes_nhwc4_*, the operand of qt_q8_stem_conv2d): one pixel per thread and round, its C codes in the
+// low bytes of ONE dword, the bytes >= C zero.  x is the [N][HW][C] view by element strides (bs, rs, cs): from NCHW input the lanes of
+// a wave read 64 consecutive elements of one channel plane per instruction, from channels_last input 64 C consecutive elements.
+template <int IO>
+__global__ __launch_bounds__(256) void codes_nhwc4_kernel(const void *__restrict__ xv, uint32_t *__restrict__ codes, size_t npix, size_t HW, int C,
+                                                         size_t bs, size_t rs, size_t cs, QdqArgs a, const void *__restrict__ scale) {
+    float s;
+    if constexpr (IO == kIoBf16) s = qt_bf2f(*(const uint16_t *)scale);
+    else s = *(const float *)scale;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < npix; i += (size_t)gridDim.x * 256) {
+        const size_t n = i / HW, base = n * bs + (i - n * HW) * rs;
+        uint32_t w = 0u;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            if (c >= C) break;
+            float v;
+            if constexpr (IO == kIoBf16) v = qt_bf2f(((const uint16_t *)xv)[base + c * cs]);
+            else v = ((const float *)xv)[base + c * cs];
+            w |= code_of(qdq_value<IO>(v, a, s, 0.0f, false)) << (8 * c);
+        }
+        codes[i] = w;
+    }
+}
+
 // fp16 vmap: index through the fp32 image, looked-up bf16 value cast to fp16 (decomposed.py:151-161)
 __global__ __launch_bounds__(256) void vmap_f16_kernel(const _Float16 *__restrict__ x, _Float16 *__restrict__ y, size_t n,
                                                       qt_format fmt, const uint16_t *__restrict__ lut) {
@@ -1627,6 +1651,25 @@ int launch_codes_nhwc(const void *x, int8_t *codes, long N, long HW, long C, lon
         return qt_launch_status();
     }
     return QT_ERR_BAD_ARG;                                          // any other layout: the caller makes it one of the two
+}
+
+template <int IO>
+int launch_codes_nhwc4(const void *x, uint32_t *codes, long N, long HW, long C, long bs, long rs, long cs, const qt_format *fmt,
+                       const uint16_t *lut, const void *scale, void *stream) {
+    if (!fmt || (fmt->kind == QT_FMT_LUT && !lut)) return QT_ERR_BAD_ARG;
+    if (N < 0 || HW < 0 || C < 0) return QT_ERR_BAD_ARG;
+    if (N == 0 || HW == 0 || C == 0) return QT_OK;
+    if (!x || !codes || !scale) return QT_ERR_BAD_ARG;
+    if (C > 4 || N >= (1L << 31) || HW >= (1L << 31) || N * HW >= (1L << 31)) return QT_ERR_BAD_ARG;
+    if ((((uintptr_t)x | (uintptr_t)codes) & 15u)) return QT_ERR_UNALIGNED;
+    // the two layouts of the sibling; a single channel has no stride of its own
+    const bool chlast = (cs == 1 || C == 1) && rs == C && bs == HW * C, nchw = rs == 1 && (cs == HW || C == 1) && bs == C * HW;
+    if (!chlast && !nchw) return QT_ERR_BAD_ARG;
+    const QdqArgs a{nullptr, fmt->kind == QT_FMT_LUT ? lut : nullptr, *fmt, 1, 0};
+    const size_t npix = (size_t)(N * HW);
+    codes_nhwc4_kernel<IO><<<grid_for(npix, 256, 8), 256, 0, (hipStream_t)stream>>>(x, codes, npix, (size_t)HW, (int)C, (size_t)bs, (size_t)rs,
+                                                                                    (size_t)(C == 1 ? 0 : cs), a, scale);
+    return qt_launch_status();
 }
 
 
@@ -2044,6 +2087,14 @@ int qt_quantize_codes_nhwc_bf16(const uint16_t *x, int8_t *codes, long N, long H
 int qt_quantize_codes_nhwc_f32(const float *x, int8_t *codes, long N, long HW, long C, long batch_stride, long row_stride,
                                long channel_stride, const qt_format *fmt, const uint16_t *lut, const float *scale, void *stream) {
     return launch_codes_nhwc<kIoF32>(x, codes, N, HW, C, batch_stride, row_stride, channel_stride, fmt, lut, scale, stream);
+}
+int qt_quantize_codes_nhwc4_bf16(const uint16_t *x, uint32_t *codes, long N, long HW, long C, long batch_stride, long row_stride,
+                                 long channel_stride, const qt_format *fmt, const uint16_t *lut, const uint16_t *scale, void *stream) {
+    return launch_codes_nhwc4<kIoBf16>(x, codes, N, HW, C, batch_stride, row_stride, channel_stride, fmt, lut, scale, stream);
+}
+int qt_quantize_codes_nhwc4_f32(const float *x, uint32_t *codes, long N, long HW, long C, long batch_stride, long row_stride,
+                                long channel_stride, const qt_format *fmt, const uint16_t *lut, const float *scale, void *stream) {
+    return launch_codes_nhwc4<kIoF32>(x, codes, N, HW, C, batch_stride, row_stride, channel_stride, fmt, lut, scale, stream);
 }
 int qt_dequantize_bf16(const uint16_t *x, uint16_t *y, size_t n, const uint16_t *scale, const uint16_t *zp,
                        const uint16_t *in_lut, const uint16_t *out_lut, void *stream) {

@@ -21,6 +21,9 @@ cores:
     codes; 1 x 1, stride 1, unpadded layers over Cin = 16 mod 32 (which the gather kernel declines) run `qt_q8_gemm` on them.
     `fuse_native_gemms(model, split_k=True)` (opt-in: `convert_pt2e(split_k=True)`) marks the gather layers' codes buffers: a marked
     layer launches `qt_q8_conv2d_ws` with the plan's split of K (the same bits) and has a route rule of its own.
+    `fuse_native_gemms(model, stem=True)` (opt-in: `convert_pt2e(native_stem=True)`) also rewrites the first convolution (groups = 1,
+    Cin <= 4) and marks its codes buffer: a marked layer packs a pixel's codes into one dword (`qt_quantize_codes_nhwc4_*`) and runs
+    `qt_q8_stem_conv2d`; its route rule is `_conv_q_stem_route_takes`.
 
 `fuse_conv_q_chains` (opt-in: `convert_pt2e(chain_convs=True)`) then hands int8 codes from one such convolution to the next:
 `conv2d_q -> aten.relu / hardtanh / clamp -> conv2d_q` becomes two `conv2d_qc` nodes, the first writing the second's codes from its
@@ -46,8 +49,9 @@ __all__ = ["fuse_native_gemms", "fuse_conv_q_chains", "fuse_mx_pairs", "fuse_gwa
 
 # conv2d_codes_in / conv2d_codes_out: native conv2d_qc launches that took / wrote a code array (counted in their kernel's key as well)
 # conv2d_split_k: gather-kernel launches that split K over more than one workgroup per tile (counted in conv2d_int8 as well)
+# conv2d_stem_int8: launches of the stem kernel (qt_q8_stem_conv2d*: Cin <= 4, a marked codes buffer); counted here alone
 STATS = {"linear_int8": 0, "matmul_int8": 0, "linear_fp8": 0, "matmul_fp8": 0, "conv2d_int8": 0, "conv2d_dw_int8": 0,
-         "conv2d_codes_in": 0, "conv2d_codes_out": 0, "conv2d_split_k": 0}
+         "conv2d_codes_in": 0, "conv2d_codes_out": 0, "conv2d_split_k": 0, "conv2d_stem_int8": 0}
 _IDENTITY_DTYPES = (None, "None", "bfloat16", "float32", "float16")
 _FP8 = {"fp8_e4m3": torch.float8_e4m3fn, "fp8_e5m2": torch.float8_e5m2}
 
@@ -235,6 +239,52 @@ def _conv_q_split_route_takes(m, cout, cin, kh, kw):
     return kh * kw > 1 and nk >= 36 and tiles >= 8
 
 
+_STEM_PROFILE = "profiles/conv2d_q_stem.txt"
+_STEM_MAX_TAPS, _STEM_LDS_BUDGET = 16, 96 * 1024
+_STEM_MAX_COUT, _STEM_MIN_PIXELS, _STEM_MIN_PIXELS_WIDE = 64, 4 * 112 * 112, 32 * 55 * 55
+
+
+def mark_stem(weight_codes):
+    """Opts a Cin <= 4 layer's int8 codes buffer into the stem kernel (fuse_native_gemms(stem=True) does this for every such layer).
+    An attribute of the tensor object, like mark_split_k's: a copy or a move of the buffer loses it, and the call then declines
+    exactly as an unmarked one."""
+    weight_codes._qt_stem = True
+    return weight_codes
+
+
+def _stem_marked(weight_codes):
+    return getattr(weight_codes, "_qt_stem", False) is True
+
+
+def _stem_lds_bytes(cout, kh, kw, sh, sw, codes_out=False):
+    """LDS of one qt_q8_stem_conv2d workgroup (csrc/qt_q8_stem_conv.hip: q8_stem_launch): the halo of an 8 x 16 patch of output pixels
+    (or the code tile of the *_codes sibling, if larger) and the padded weight image of one column tile."""
+    upr = -(-kw // 4)
+    nsteps = -(-kh * upr // 4)
+    r_last = (4 * nsteps - 1) // upr
+    halo = 4 * (15 * sw + 4 * upr) * (7 * sh + r_last + 1)
+    if codes_out:
+        halo = max(halo, 8 * 16 * 80)
+    return -(-halo // 16) * 16 + 16 * (2 if cout <= 32 else 4) * (nsteps * 64 + 16)
+
+
+def _conv_q_stem_route_takes(m, cout, cin, kh, kw, sh, sw):
+    """The committed rule for marked stem calls, a fixed function of the shape (never a timing): m = N Ho Wo output pixels, the
+    channels, the filter, the strides.  From profiles/conv2d_q_stem.txt (five rows over 3 x 224 x 224 input, bf16: ResNet-50's 7 x 7 / 2
+    -> 64 and MobileNetV2's 3 x 3 / 2 -> 32 at batch 32 and batch 4, an 11 x 11 / 4 -> 64 stem at batch 32; the method and the bar of
+    profiles/conv2d_q.txt).  All five rows clear the bar on both layouts in both modes -- replayed from NCHW / channels_last input
+    1.63 / 1.74 x and 1.84 / 2.07 x (7 x 7, batch 32 and 4), 2.17 / 2.44 x and 2.35 / 2.83 x (3 x 3), 1.13 / 1.25 x (11 x 11: 94.6 -> 83.7 us
+    against a spread of 0.5) -- so the classes are what was measured, at most 64 output channels each:
+      * filters of at most 49 taps at strides of at most 2, from 4 x 112 x 112 output pixels on;
+      * filters of at most 121 taps at strides of at most 4, from 32 x 55 x 55 output pixels on.
+    Anything else (a wider layer, a smaller image or batch, a larger stride) was not measured and stays with the graph."""
+    if cout > _STEM_MAX_COUT:
+        return False
+    if kh * kw <= 49 and max(sh, sw) <= 2:
+        return m >= _STEM_MIN_PIXELS
+    return kh * kw <= 121 and max(sh, sw) <= 4 and m >= _STEM_MIN_PIXELS_WIDE
+
+
 _DW_PROFILE = "profiles/conv2d_q_depthwise.txt"
 _CONV_Q_DW_MAX_TAPS = 1023
 
@@ -266,11 +316,14 @@ def _conv_q_pw16_route_takes(m, cout, cin):
 def _conv_q_route(input, weight_codes, stride, padding, groups):
     """Which kernel a 4-D call would run on: "depthwise" (qt_q8_dwconv2d: groups = Cin = Cout, one filter per channel), "pointwise"
     (qt_q8_gemm: a 1 x 1, stride 1, unpadded convolution over NHWC codes is the GEMM [N H W][Cin] x [Cout][Cin]^T, taken there for the
-    Cin = 16 mod 32 that the gather kernel declines), "gather" (qt_q8_conv2d), or None for any other grouped call."""
+    Cin = 16 mod 32 that the gather kernel declines), "stem" (qt_q8_stem_conv2d: Cin <= 4 and a codes buffer that carries mark_stem's
+    mark, nothing else), "gather" (qt_q8_conv2d), or None for any other grouped call."""
     cin = input.shape[1]
     cout, kh, kw, wcin = weight_codes.shape
     if groups != 1:
         return "depthwise" if groups == cin == cout and wcin == 1 else None
+    if 1 <= cin <= 4 and _stem_marked(weight_codes):
+        return "stem"
     if kh == kw == 1 and list(stride) == [1, 1] and list(padding) == [0, 0] and wcin == cin and cin >= 16 and cin % 32 == 16:
         return "pointwise"
     return "gather"
@@ -303,6 +356,17 @@ def _conv_q_decline(input, scale, qmap, weight_codes, bias, stride, padding, dil
             return f"depthwise C = {cin}: not a multiple of 16"
         if kh * kw > _CONV_Q_DW_MAX_TAPS:
             return f"depthwise kh kw = {kh * kw} > 1023"
+    elif route == "stem":
+        if wcin != cin:
+            return f"stem Cin = {cin} / {wcin}"
+        if kh > _STEM_MAX_TAPS or kw > _STEM_MAX_TAPS:
+            return f"stem filter {kh} x {kw}: more than 16 taps on an axis"
+        if list(dilation) != [1, 1]:
+            return f"stem dilation {list(dilation)}"
+        if cout % 16:
+            return f"stem Cout = {cout}: not a multiple of 16"
+        if min(stride) < 1 or _stem_lds_bytes(cout, kh, kw, stride[0], stride[1], True) > _STEM_LDS_BUDGET:
+            return f"stem strides {list(stride)}: the halo does not fit the LDS budget"
     else:
         if route == "gather" and (wcin != cin or cin < 32 or cin % 32):
             return f"Cin = {cin} / {wcin}: not a multiple of 32"
@@ -327,6 +391,8 @@ def _conv_q_decline(input, scale, qmap, weight_codes, bias, stride, padding, dil
             return f"depthwise route rule: {_DW_PROFILE}"
         if route == "pointwise" and not _conv_q_pw16_route_takes(n * ho * wo, cout, cin):
             return f"pointwise route rule: {_DW_PROFILE}"
+        if route == "stem" and not _conv_q_stem_route_takes(n * ho * wo, cout, cin, kh, kw, stride[0], stride[1]):
+            return f"stem route rule: {_STEM_PROFILE}"
         if route == "gather" and not _conv_q_route_takes(n * ho * wo, cout, cin, kh, kw):
             if not _split_k_marked(weight_codes):
                 return "route rule: profiles/conv2d_q.txt"
@@ -360,19 +426,20 @@ def _conv2d_q_unfused(input, scale, qmap, weight_codes, bias, stride, padding, d
     return torch.ops.quantized_ops.dequantize(y, out_scale, None, None, None, out_map)
 
 
-def conv_codes_nhwc(input, scale, qmap):
-    """int8 codes [N H W, C] of quantize(input, scale, qmap) in one pass (qt_quantize_codes_nhwc_*), or None when declined."""
+def conv_codes_nhwc(input, scale, qmap, stem=False):
+    """int8 codes [N H W, C] of quantize(input, scale, qmap) in one pass (qt_quantize_codes_nhwc_*), or None when declined.
+    stem: C <= 4, the codes of a pixel in the low bytes of one dword, [N H W, 4] (qt_quantize_codes_nhwc4_*)."""
     from .decomposed import _lut_format, _scalar_like
     from .mx_conv import _nhwc_strides
     n, c, h, w = input.shape
     xs = _nhwc_strides(input)
     if xs is None:
         input, xs = input.contiguous(), (c * h * w, 1, h * w)
-    codes = torch.empty((n * h * w, c), dtype=torch.int8, device=input.device)
+    codes = torch.empty((n * h * w, 4 if stem else c), dtype=torch.int8, device=input.device)
     s = _scalar_like(scale, input)
     fmt = _lut_format()
     L = _native.lib()
-    fn = L.qt_quantize_codes_nhwc_bf16 if input.dtype == torch.bfloat16 else L.qt_quantize_codes_nhwc_f32
+    fn = getattr(L, ("qt_quantize_codes_nhwc4_" if stem else "qt_quantize_codes_nhwc_") + ("bf16" if input.dtype == torch.bfloat16 else "f32"))
     rc = fn(input.data_ptr(), codes.data_ptr(), n, h * w, c, *xs, ctypes.byref(fmt), qmap.data_ptr(), s.data_ptr(), _stream_ptr(input))
     if _native.declined(rc):
         return None
@@ -402,7 +469,8 @@ class _Operand:
 
 
 def _conv_q_launch(codes, shape, dtype, weight_codes, bias, stride, padding, dilation, groups, out_scale, out_map, tail=None):
-    """One native launch on the NHWC codes [N H W, Cin] of an activation of logical `shape`, on the kernel _conv_q_route names.
+    """One native launch on the NHWC codes [N H W, Cin] of an activation of logical `shape` (stem route: its [N H W, 4] pixel dwords),
+    on the kernel _conv_q_route names.
     tail None: the value tensor [N, Cout, Ho, Wo] in `dtype`, channels_last (qt_q8_dwconv2d / qt_q8_gemm / qt_q8_conv2d).
     tail (act, lo, hi, next_scale, next_qmap): the consumer's int8 codes in the same layout (the *_codes siblings).
     -> (result, None), or (None, why) when the entry point declines the shape."""
@@ -428,6 +496,8 @@ def _conv_q_launch(codes, shape, dtype, weight_codes, bias, stride, padding, dil
         entry, key, rc = "qt_q8_dwconv2d" + sfx, "conv2d_dw_int8", getattr(L, "qt_q8_dwconv2d" + sfx)(*head, n, h, w, cin, *geometry, *last)
     elif route == "pointwise":                   # the channels_last result is the row-major [N Ho Wo][Cout] of the GEMM
         entry, key, rc = "qt_q8_gemm" + sfx, "conv2d_int8", getattr(L, "qt_q8_gemm" + sfx)(*head, 1, n * h * w, cout, cin, 0, 0, *last)
+    elif route == "stem":
+        entry, key, rc = "qt_q8_stem_conv2d" + sfx, "conv2d_stem_int8", getattr(L, "qt_q8_stem_conv2d" + sfx)(*head, n, h, w, cin, cout, *geometry, *last)
     elif _split_k_marked(weight_codes):          # the plan's split (1: the unsplit kernel, no workspace) through the *_ws sibling
         from .fused import splitk_scratch
         split, wbytes, ntick = _native.q8_conv_plan(n * ho * wo, cout, kh * kw * cin)
@@ -450,7 +520,7 @@ def _conv2d_q(input, scale, qmap, weight_codes, bias, stride, padding, dilation,
     stride, padding, dilation = [int(v) for v in stride], [int(v) for v in padding], [int(v) for v in dilation]
     why = _conv_q_decline(input, scale, qmap, weight_codes, bias, stride, padding, dilation, groups, out_scale, kind)
     if why is None:
-        codes = conv_codes_nhwc(input, scale, qmap)
+        codes = conv_codes_nhwc(input, scale, qmap, _conv_q_route(input, weight_codes, stride, padding, groups) == "stem")
         if codes is None:
             why = "qt_quantize_codes_nhwc declined"
         else:
@@ -539,6 +609,8 @@ def _conv2d_qc(input, scale, qmap, weight_codes, bias, stride, padding, dilation
             input = input.contiguous(memory_format=torch.channels_last)
         why = _conv_q_decline(_Operand(input.shape, dtype, input.device, input.data_ptr()), _Operand((1,), dtype, input.device),
                               _Operand((65536,), torch.bfloat16, input.device), *args, kind)
+        if why is None and _conv_q_route(input, weight_codes, stride, padding, groups) == "stem":
+            why = "stem route: takes no codes (a stem is a producer only)"
     else:
         why = _conv_q_decline(input, scale, qmap, *args, kind)
     tail = None
@@ -559,7 +631,7 @@ def _conv2d_qc(input, scale, qmap, weight_codes, bias, stride, padding, dilation
         codes = input.permute(0, 2, 3, 1).reshape(n * h * w, c) if codes_in else None
         if codes_out and why_out is None:
             if not codes_in:
-                codes = conv_codes_nhwc(input, scale, qmap)
+                codes = conv_codes_nhwc(input, scale, qmap, _conv_q_route(input, weight_codes, stride, padding, groups) == "stem")
             if codes is None:
                 why_out = "qt_quantize_codes_nhwc declined"
             else:
@@ -638,13 +710,16 @@ def _sole_dequantize(model, node, dtype):
     return dq, a[1], a[5]
 
 
-def fuse_native_gemms(model: GraphModule, split_k: bool = False) -> int:
+def fuse_native_gemms(model: GraphModule, split_k: bool = False, stem: bool = False) -> int:
     """Rewrites quantize -> aten.linear / aten.matmul -> dequantize triples whose operands are int8 (or FP8) codes into
     linear_q / matmul_q nodes, and quantize -> aten.conv2d -> dequantize triples on int8 codes (static geometry; Cin a multiple
     of 32, or depthwise over a multiple of 16 channels, or 1 x 1 / stride 1 / unpadded over Cin = 16 mod 32) into conv2d_q nodes.  Returns the number of fused GEMMs and convolutions; leaves everything else as it is.
     split_k=True marks the int8 codes buffer of every gather layer (groups = 1, Cin a multiple of 32) with mark_split_k: such a layer
     launches qt_q8_conv2d_ws / qt_q8_conv2d_codes_ws with the plan's split and is routed by _conv_q_split_route_takes where
-    _conv_q_route_takes declines it.  The graph itself is the same either way."""
+    _conv_q_route_takes declines it.  The graph itself is the same either way.
+    stem=True also rewrites a groups = 1 convolution over Cin <= 4 channels (the first layer of a CNN, which otherwise stays
+    aten.conv2d) and marks its codes buffer with mark_stem: qt_quantize_codes_nhwc4_* + qt_q8_stem_conv2d, routed by
+    _conv_q_stem_route_takes."""
     graph = model.graph
     fused = 0
     for node in list(graph.nodes):
@@ -725,8 +800,9 @@ def fuse_native_gemms(model: GraphModule, split_k: bool = False) -> int:
             depthwise = groups > 1 and groups == cout_w and cin_w == 1 and groups % 16 == 0
             pointwise = (groups == 1 and kh_w == kw_w == 1 and stride == [1, 1] and padding == [0, 0] and cin_w >= 16
                          and cin_w % 32 == 16)
-            if not (gather or depthwise or pointwise):
-                continue                                     # channels no kernel ever takes (a stem, Cin = 24, any other grouping): the node stays
+            stem_layer = stem and groups == 1 and 1 <= cin_w <= 4
+            if not (gather or depthwise or pointwise or stem_layer):
+                continue                                     # channels no kernel ever takes (a stem without stem=True, Cin = 24, any other grouping): the node stays
             tail = _sole_dequantize(model, node, param.dtype)
             if tail is None:
                 continue
@@ -745,6 +821,8 @@ def fuse_native_gemms(model: GraphModule, split_k: bool = False) -> int:
                 getattr(model, name)._qt_conv_values = param.detach()
             if split_k and gather and groups == 1:
                 mark_split_k(getattr(model, name))
+            if stem_layer:
+                mark_stem(getattr(model, name))
             with graph.inserting_before(dq):
                 c_node = graph.create_node("get_attr", name)
                 new = graph.call_function(torch.ops.quantized_ops.conv2d_q.default,
