@@ -770,6 +770,19 @@ int qt_attention_fp8(const uint8_t *q8_dev, const uint8_t *k8_dev, const uint8_t
                      long mask_sb, long mask_sh, long mask_sq, const int *row_live_dev, long live_sb, long live_sh, long live_sq,
                      int mask_is_simple, const int *mask_irregular_dev, uint16_t *out_dev, uint8_t *out8_dev, const qt_format *out_format, long B,
                      int H, int Sq, int Sk, int head_dim, float scaling, void *stream);
+/* The same core for LONGER key ranges, ONE launch (csrc/qt_attention_fp8_long.hip): Sk % 128 == 0, 128 <= Sk <= 16384.  Replaces the same
+ * lines (modules/quantizable/modeling_llama.py:228-246, modeling_bert.py:118-158), which beyond 1024 keys otherwise run as
+ * library GEMM -> qt_softmax_fq_bf16_fp8 -> library GEMM with the S x S scores and probability codes written and read back.  Same operands
+ * (q8 / k8 codes, vt8 from qt_value_codes_t), mask forms (read / row extents / mask_is_simple / device flag), rounding points and output modes
+ * (out, out + out8, codes only) as qt_attention_fp8, and the same refusals with the new key range.  A strip of 16 x Sk scores does not fit
+ * in registers here, so the keys are streamed twice: sweep 1 forms the row maximum and the sum of exponentials with a running maximum that
+ * advances per 128-key block in key order (a term is rescaled only where the row's maximum rises), sweep 2 recomputes the scores (bit-identical),
+ * evaluates bf16(exp(t - max) / sum) with the final maximum and multiplies by V.  Fully masked rows attend to every key alike; a row with
+ * a NaN or +inf logit, or with -inf logits only, is NaN throughout. */
+int qt_attention_fp8_long(const uint8_t *q8_dev, const uint8_t *k8_dev, const uint8_t *vt8_dev, int operand_format, const uint16_t *mask_dev,
+                          long mask_sb, long mask_sh, long mask_sq, const int *row_live_dev, long live_sb, long live_sh, long live_sq,
+                          int mask_is_simple, const int *mask_irregular_dev, uint16_t *out_dev, uint8_t *out8_dev, const qt_format *out_format,
+                          long B, int H, int Sq, int Sk, int head_dim, float scaling, void *stream);
 int qt_softmax_fq_bf16_fp8_live(const uint16_t *scores_dev, const uint16_t *mask_dev, uint8_t *out8_dev, long batch, int heads, int q_len,
                                 long cols, long mask_sb, long mask_sh, long mask_sq, float scaling, const qt_format *fmt,
                                 const int *row_live_dev, long live_sb, long live_sh, long live_sq, void *stream);

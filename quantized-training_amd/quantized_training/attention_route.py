@@ -217,9 +217,29 @@ def attention_output_plan(attn):
     return fq_o, fq_o is not None and own is not None and pc.no_foreign_hooks(attn) and codes_only_ok([proj])
 
 
+ATTENTION_ROUTES = {}      # "attention:BxHxQxCxD" -> "attention_fp8_long": the long-key problems the streaming core took (fused.routes_report)
+
+# (B, H, Q, C, D) -> does qt_attention_fp8_long beat the library FP8 GEMM -> score pass -> library FP8 GEMM chain?  Measured with
+# tools/exp_attention_fp8_long.py (profiles/attention_fp8_long.txt): a class is listed as taken when the kernel's median beats the
+# chain's by more than the chain's min-max spread, eager AND replayed from a graph.
+_FP8_LONG_TABLE = {                          # chain / kernel, us, eager; replayed
+    (1, 32, 2048, 2048, 128): True,          # 219.5 / 98.4; 221.8 / 104.4   (causal)
+    (1, 32, 4096, 4096, 128): True,          # 839.7 / 284.7; 847.5 / 293.6  (causal)
+    (4, 12, 2048, 2048, 64): True,           # 319.0 / 170.3; 322.7 / 175.0  (no mask)
+}                                            # (B 1, H 32, S 8192: the chain's score pass stops at 4096 columns -- nothing to compare with, not listed)
+
+
+def _fp8_long_route_takes(B, H, Q, C, D):
+    """The default route of a long-key problem (1024 < C <= 16384): the committed table; a shape it does not list stays on the chain.
+    Never a measurement at run time (fused.fq8_route_is_fused says why)."""
+    return _FP8_LONG_TABLE.get((B, H, Q, C, D), False)
+
+
 def _attention_fp8_or_none(attn, query, key, value, attention_mask, scaling, fqs):
     """qt_attention_fp8: the attention core in one launch on FP8 codes (head_dim 128 or 64, keys in blocks of 128 up to 1024) when the
-    four fake-quantizers around the two matmuls are stateless E4M3 / E5M2 ones of one format.  q / k either arrive with their codes (the
+    four fake-quantizers around the two matmuls are stateless E4M3 / E5M2 ones of one format.  Beyond 1024 keys (up to 16384) the same
+    launch is qt_attention_fp8_long, the streaming two-sweep core: where _fp8_long_route_takes lists the shape, and wherever it applies
+    under QT_FUSED_ATTENTION=1.  q / k either arrive with their codes (the
     rotary kernel attaches them) or are [B, H, S, D] views of the projections' outputs (BERT's transpose_for_scores), whose codes a
     codes-only pass over the view writes here -- that pass IS the fq_q / fq_k call.  Counts the four fake-quant calls the reference
     issues: q and k (handed through by their modules, or the passes just named), the value pass (qt_value_codes_t) and the
@@ -227,7 +247,10 @@ def _attention_fp8_or_none(attn, query, key, value, attention_mask, scaling, fqs
     fq_q, fq_k, fq_p, fq_v = fqs
     B, H, Q, D = query.shape
     C = key.shape[2]
-    if D not in (64, 128) or C % 128 != 0 or C > 1024 or B * H > 65535:
+    if D not in (64, 128) or C % 128 != 0 or C > 16384 or B * H > 65535:
+        return None
+    long_keys = C > 1024
+    if long_keys and not (switches.mode("QT_FUSED_ATTENTION") == "1" or _fp8_long_route_takes(B, H, Q, C, D)):
         return None
     if not all(isinstance(f, FusedAmaxObsFakeQuantize) and f.producer_fusable() for f in fqs):
         return None
@@ -299,10 +322,12 @@ def _attention_fp8_or_none(attn, query, key, value, attention_mask, scaling, fqs
     out8 = torch.empty((B, Q, H, D), dtype=torch.uint8, device=query.device) if fq_o is not None else None
     shape = (B, Q, H, D)
     out = handover.unwritten(shape, torch.bfloat16, query.device) if codes_only else torch.empty(shape, dtype=torch.bfloat16, device=query.device)
-    _native.check(L.qt_attention_fp8(q8.data_ptr(), k8.data_ptr(), vt8.data_ptr(), 1 if fmt.p0 == 2 else 0, mk.ptr, *mk.strides, *live[:4], 0, live[4],
-                                     None if codes_only else out.data_ptr(), out8.data_ptr() if out8 is not None else None,
-                                     ctypes.byref(fq_o._qt_format) if fq_o is not None else None, B, H, Q, C, D, float(scaling), st),
-                  "qt_attention_fp8")
+    entry = "qt_attention_fp8_long" if long_keys else "qt_attention_fp8"
+    _native.check(getattr(L, entry)(q8.data_ptr(), k8.data_ptr(), vt8.data_ptr(), 1 if fmt.p0 == 2 else 0, mk.ptr, *mk.strides, *live[:4], 0, live[4],
+                                    None if codes_only else out.data_ptr(), out8.data_ptr() if out8 is not None else None,
+                                    ctypes.byref(fq_o._qt_format) if fq_o is not None else None, B, H, Q, C, D, float(scaling), st), entry)
+    if long_keys:
+        ATTENTION_ROUTES.setdefault(f"attention:{B}x{H}x{Q}x{C}x{D}", "attention_fp8_long")
     if codes_only:
         handover.stamp(out, fq_o, handover.fp8_view(out8, fq_o), lazy=True)
     if fq_o is not None:
