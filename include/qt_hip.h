@@ -783,6 +783,21 @@ int qt_attention_fp8_long(const uint8_t *q8_dev, const uint8_t *k8_dev, const ui
                           long mask_sb, long mask_sh, long mask_sq, const int *row_live_dev, long live_sb, long live_sh, long live_sq,
                           int mask_is_simple, const int *mask_irregular_dev, uint16_t *out_dev, uint8_t *out8_dev, const qt_format *out_format,
                           long B, int H, int Sq, int Sk, int head_dim, float scaling, void *stream);
+/* The same core at head_dim 32, ONE launch (csrc/qt_attention_fp8_d32.hip): MobileBERT's attention, 4 heads of 32 at up to 512 positions
+ * (modules/quantizable/modeling_mobilebert.py:80-93), which otherwise runs as library GEMM -> qt_softmax_fq_bf16_fp8 -> library GEMM.
+ * The argument list, operands (q8 / k8 codes [B][H][S][32]; vt8 [B][H][32][Sk] from qt_value_codes_t_d32, which IS the fq_v call), mask forms
+ * (read / row extents / mask_is_simple / device flag), rounding points (bf16 scores, bf16(score * scaling), bf16(. + mask), fp32 softmax
+ * over the whole row with no running rescale, bf16 probabilities -> FP8 codes, fp32 P.V, bf16 out), output modes (out, out + out8, codes
+ * only), fully masked rows and NaN rows of qt_attention_fp8.  Q.K^T runs on v_mfma_f32_16x16x32_fp8_fp8 / _bf8_bf8, whose depth is the
+ * head_dim; a head's whole K and V^T stay in LDS.  Contract: head_dim == 32, Sk % 128 == 0, 128 <= Sk <= 512, B * H <= 65535,
+ * operand_format 0 (E4M3) or 1 (E5M2), the alignments of qt_attention_fp8; anything else returns an error status with nothing written
+ * (qt_value_codes_t, qt_attention_fp8 and qt_attention_fp8_long keep refusing head_dim 32). */
+int qt_value_codes_t_d32(const uint16_t *v_dev, uint8_t *vt8_dev, long B, long H, long Sk, long stride_b, long stride_h, long stride_k,
+                         const qt_format *fmt, void *stream);
+int qt_attention_fp8_d32(const uint8_t *q8_dev, const uint8_t *k8_dev, const uint8_t *vt8_dev, int operand_format, const uint16_t *mask_dev,
+                         long mask_sb, long mask_sh, long mask_sq, const int *row_live_dev, long live_sb, long live_sh, long live_sq,
+                         int mask_is_simple, const int *mask_irregular_dev, uint16_t *out_dev, uint8_t *out8_dev, const qt_format *out_format,
+                         long B, int H, int Sq, int Sk, int head_dim, float scaling, void *stream);
 int qt_softmax_fq_bf16_fp8_live(const uint16_t *scores_dev, const uint16_t *mask_dev, uint8_t *out8_dev, long batch, int heads, int q_len,
                                 long cols, long mask_sb, long mask_sh, long mask_sq, float scaling, const qt_format *fmt,
                                 const int *row_live_dev, long live_sb, long live_sh, long live_sq, void *stream);

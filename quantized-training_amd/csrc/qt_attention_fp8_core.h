@@ -1,6 +1,6 @@
-// qt_attention_fp8_core.h -- what the two attention kernels on FP8 codes share: attention_fp8_split_kernel (qt_attention_fp8.hip, the
-// score strip in registers, up to 1024 keys) and attention_fp8_long_kernel (qt_attention_fp8_long.hip, the keys streamed, up to 16384).
-// Both hold a wave's 16 query rows against the keys 16 t + 4 g + {0..3} of each 16-key tile t in lane (r, g), read K / V^T blocks that
+// qt_attention_fp8_core.h -- what the attention kernels on FP8 codes share: attention_fp8_split_kernel (qt_attention_fp8.hip, the
+// score strip in registers, up to 1024 keys), attention_fp8_long_kernel (qt_attention_fp8_long.hip, the keys streamed, up to 16384) and
+// attention_fp8_d32_kernel (qt_attention_fp8_d32.hip, head_dim 32, up to 512 keys; its K image in LDS is its own).  All hold a wave's 16 query rows against the keys 16 t + 4 g + {0..3} of each 16-key tile t in lane (r, g), read K / V^T blocks that
 // arrived by LDS-DMA with the same swizzle, and send the scores through the same rounding chain.
 #pragma once
 #include "qt_device.h"
@@ -50,7 +50,8 @@ __device__ __forceinline__ uint32_t prob_codes(uint32_t p0, uint32_t p1) {
 }
 
 // scores of the four tiles t0 .. t0 + 3 of one K block.  MODE 0: no mask arithmetic; 1: row-extent mask applied from my_live
-// (tiles from `tiles` on lie beyond every row of the wave); 2: additive mask read from mrow
+// (tiles from `tiles` on lie beyond every row of the wave); 2: additive mask read from mrow.  head_dim 32: f_lo is the lane's 8 bytes of a
+// tile, f_hi unused
 template <int F, int D, int MODE>
 __device__ __forceinline__ void score_half(const uint8_t *blk, int t0, const v8i &qf, int f_lo, int f_hi, float scaling, float (*ev)[4], float &mx,
                                            const uint16_t *mrow, int key0, int my_live, int tiles) {
@@ -65,16 +66,27 @@ __device__ __forceinline__ void score_half(const uint8_t *blk, int t0, const v8i
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         if (MODE == 1 && j >= tiles) continue;
-        klo[j] = *(const u32x4 *)(blk + (t0 + j) * (16 * D) + f_lo);
-        if (D == 128) khi[j] = *(const u32x4 *)(blk + (t0 + j) * (16 * D) + f_hi);
-        else khi[j] = u32x4{0u, 0u, 0u, 0u};                             // head_dim 64: the upper half of the 128-deep product is 0 x 0
+        if constexpr (D == 32) {                                         // head_dim 32: 8 bytes of a key, the depth of the 32-deep instruction
+            const uint2 k2 = *(const uint2 *)(blk + (t0 + j) * (16 * D) + f_lo);
+            klo[j] = u32x4{k2.x, k2.y, 0u, 0u};
+        } else {
+            klo[j] = *(const u32x4 *)(blk + (t0 + j) * (16 * D) + f_lo);
+            if (D == 128) khi[j] = *(const u32x4 *)(blk + (t0 + j) * (16 * D) + f_hi);
+            else khi[j] = u32x4{0u, 0u, 0u, 0u};                         // head_dim 64: the upper half of the 128-deep product is 0 x 0
+        }
     }
     v4f s[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         if (MODE == 1 && j >= tiles) continue;
-        const v8i kf = {(int)klo[j].x, (int)klo[j].y, (int)klo[j].z, (int)klo[j].w, (int)khi[j].x, (int)khi[j].y, (int)khi[j].z, (int)khi[j].w};
-        s[j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(kf, qf, v4f{0.f, 0.f, 0.f, 0.f}, F, F, 0, kUnit, 0, kUnit);
+        if constexpr (D == 32) {                                         // v_mfma_f32_16x16x32_fp8_fp8 / _bf8_bf8: qf's first two words are the fragment
+            const long kf = (long)(((unsigned long)klo[j].y << 32) | klo[j].x), q2 = (long)(((unsigned long)(uint32_t)qf[1] << 32) | (uint32_t)qf[0]);
+            if constexpr (F == 1) s[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf8_bf8(kf, q2, v4f{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+            else s[j] = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(kf, q2, v4f{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+        } else {
+            const v8i kf = {(int)klo[j].x, (int)klo[j].y, (int)klo[j].z, (int)klo[j].w, (int)khi[j].x, (int)khi[j].y, (int)khi[j].z, (int)khi[j].w};
+            s[j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(kf, qf, v4f{0.f, 0.f, 0.f, 0.f}, F, F, 0, kUnit, 0, kUnit);
+        }
     }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll

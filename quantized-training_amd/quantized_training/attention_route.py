@@ -217,7 +217,8 @@ def attention_output_plan(attn):
     return fq_o, fq_o is not None and own is not None and pc.no_foreign_hooks(attn) and codes_only_ok([proj])
 
 
-ATTENTION_ROUTES = {}      # "attention:BxHxQxCxD" -> "attention_fp8_long": the long-key problems the streaming core took (fused.routes_report)
+ATTENTION_ROUTES = {}      # "attention:BxHxQxCxD" -> "attention_fp8_long" / "attention_fp8_d32": the problems the streaming core and the
+                           # head_dim 32 core took (fused.routes_report)
 
 # (B, H, Q, C, D) -> does qt_attention_fp8_long beat the library FP8 GEMM -> score pass -> library FP8 GEMM chain?  Measured with
 # tools/exp_attention_fp8_long.py (profiles/attention_fp8_long.txt): a class is listed as taken when the kernel's median beats the
@@ -235,11 +236,44 @@ def _fp8_long_route_takes(B, H, Q, C, D):
     return _FP8_LONG_TABLE.get((B, H, Q, C, D), False)
 
 
+# (B, H, Q, C) -> does qt_value_codes_t_d32 + qt_attention_fp8_d32 (head_dim 32, C <= 512) beat the chain that serves MobileBERT's
+# attention otherwise -- library FP8 GEMM -> score pass -> value pass -> library FP8 GEMM?  Measured with tools/exp_attention_fp8_d32.py
+# (profiles/attention_fp8_d32.txt), the bar of _FP8_LONG_TABLE: a class is listed as taken when the kernel's median beats the chain's by
+# more than the chain's min-max spread, eager AND replayed, with the padding mask AND without a mask.
+_FP8_D32_TABLE = {                           # chain / kernel, us, padding mask: eager; replayed   (no mask: within 1 us of these, except as noted)
+    (16, 4, 384, 384): True,                 # 59.5 / 13.3; 62.1 / 17.8      (the SQuAD recipe; no mask, replayed: 59.4 / 18.0)
+    (32, 4, 128, 128): True,                 # 60.2 / 13.6; 31.5 / 18.0
+    (16, 4, 512, 512): True,                 # 59.0 / 13.3; 48.9 / 19.0      (no mask, replayed: 46.2 / 18.6)
+}                                            # (eager, both routes are bound by the host's launches -- four against two -- not by the device)
+
+
+def _fp8_d32_route_takes(B, H, Q, C):
+    """The default route of a head_dim 32 problem (C <= 512): the committed table; a shape it does not list stays on the chain."""
+    return _FP8_D32_TABLE.get((B, H, Q, C), False)
+
+
+def _fp8_core_for(B, H, Q, C, D):
+    """The entry point that takes a problem of this shape -- on the default route, or wherever it applies under QT_FUSED_ATTENTION=1 -- or
+    None: qt_attention_fp8 (head_dim 128 / 64, up to 1024 keys), qt_attention_fp8_long (beyond, up to 16384), qt_attention_fp8_d32
+    (head_dim 32, 128 .. 512 keys)."""
+    forced = switches.mode("QT_FUSED_ATTENTION") == "1"
+    if C % 128 != 0 or B * H > 65535:
+        return None
+    if D == 32:
+        return "qt_attention_fp8_d32" if 128 <= C <= 512 and (forced or _fp8_d32_route_takes(B, H, Q, C)) else None
+    if D not in (64, 128) or C > 16384:
+        return None
+    if C <= 1024:
+        return "qt_attention_fp8"
+    return "qt_attention_fp8_long" if forced or _fp8_long_route_takes(B, H, Q, C, D) else None
+
+
 def _attention_fp8_or_none(attn, query, key, value, attention_mask, scaling, fqs):
     """qt_attention_fp8: the attention core in one launch on FP8 codes (head_dim 128 or 64, keys in blocks of 128 up to 1024) when the
     four fake-quantizers around the two matmuls are stateless E4M3 / E5M2 ones of one format.  Beyond 1024 keys (up to 16384) the same
-    launch is qt_attention_fp8_long, the streaming two-sweep core: where _fp8_long_route_takes lists the shape, and wherever it applies
-    under QT_FUSED_ATTENTION=1.  q / k either arrive with their codes (the
+    launch is qt_attention_fp8_long, the streaming two-sweep core, and at head_dim 32 (128 .. 512 keys, MobileBERT) it is
+    qt_attention_fp8_d32 behind its own value pass qt_value_codes_t_d32: each where its committed rule (_fp8_long_route_takes,
+    _fp8_d32_route_takes) lists the shape, and wherever it applies under QT_FUSED_ATTENTION=1 (_fp8_core_for).  q / k either arrive with their codes (the
     rotary kernel attaches them) or are [B, H, S, D] views of the projections' outputs (BERT's transpose_for_scores), whose codes a
     codes-only pass over the view writes here -- that pass IS the fq_q / fq_k call.  Counts the four fake-quant calls the reference
     issues: q and k (handed through by their modules, or the passes just named), the value pass (qt_value_codes_t) and the
@@ -247,10 +281,8 @@ def _attention_fp8_or_none(attn, query, key, value, attention_mask, scaling, fqs
     fq_q, fq_k, fq_p, fq_v = fqs
     B, H, Q, D = query.shape
     C = key.shape[2]
-    if D not in (64, 128) or C % 128 != 0 or C > 16384 or B * H > 65535:
-        return None
-    long_keys = C > 1024
-    if long_keys and not (switches.mode("QT_FUSED_ATTENTION") == "1" or _fp8_long_route_takes(B, H, Q, C, D)):
+    entry = _fp8_core_for(B, H, Q, C, D)
+    if entry is None:
         return None
     if not all(isinstance(f, FusedAmaxObsFakeQuantize) and f.producer_fusable() for f in fqs):
         return None
@@ -290,7 +322,7 @@ def _attention_fp8_or_none(attn, query, key, value, attention_mask, scaling, fqs
         return rs if (t.stride(3) == 1 and t.stride(1) == d_ and t.stride(0) == s_ * rs and rs % 8 == 0 and rs >= h_ * d_) else None
 
     vt8 = None
-    if (q8 is None and k8 is None and Q == C and key.shape[1] == H and value.shape[1] == H and token_rows(query) is not None
+    if (D != 32 and q8 is None and k8 is None and Q == C and key.shape[1] == H and value.shape[1] == H and token_rows(query) is not None
             and token_rows(key) is not None and switches.on("QT_ROPE_VALUE_LAUNCH")):
         # q and k codes and the value codes in ONE launch (qt_rope_fq_value without a rotation): the three calls fq_q, fq_k, fq_v
         q8 = torch.empty((B, H, Q, D), dtype=torch.uint8, device=query.device)
@@ -312,8 +344,12 @@ def _attention_fp8_or_none(attn, query, key, value, attention_mask, scaling, fqs
         vt8 = early[1]                                       # written by the launch that carried the rotary kernel (model_fusions.rope_fq)
     else:
         vt8 = torch.empty((B, H, D, C), dtype=torch.uint8, device=query.device)
-        _native.check(L.qt_value_codes_t(value.data_ptr(), vt8.data_ptr(), B, H, C, D, value.stride(0), value.stride(1), value.stride(2),
-                                         ctypes.byref(fmt), st), "qt_value_codes_t")
+        if D == 32:
+            _native.check(L.qt_value_codes_t_d32(value.data_ptr(), vt8.data_ptr(), B, H, C, value.stride(0), value.stride(1), value.stride(2),
+                                                 ctypes.byref(fmt), st), "qt_value_codes_t_d32")
+        else:
+            _native.check(L.qt_value_codes_t(value.data_ptr(), vt8.data_ptr(), B, H, C, D, value.stride(0), value.stride(1), value.stride(2),
+                                             ctypes.byref(fmt), st), "qt_value_codes_t")
     STATS.add(value.numel())                                 # fq_v, evaluated by that pass
     STATS.add(B * H * Q * C)                                 # fq_p, evaluated inside the kernel
     # the output projection's stateless FP8 input fake-quantizer rides on the epilogue (as model_fusions.attention_output does for the
@@ -322,12 +358,11 @@ def _attention_fp8_or_none(attn, query, key, value, attention_mask, scaling, fqs
     out8 = torch.empty((B, Q, H, D), dtype=torch.uint8, device=query.device) if fq_o is not None else None
     shape = (B, Q, H, D)
     out = handover.unwritten(shape, torch.bfloat16, query.device) if codes_only else torch.empty(shape, dtype=torch.bfloat16, device=query.device)
-    entry = "qt_attention_fp8_long" if long_keys else "qt_attention_fp8"
     _native.check(getattr(L, entry)(q8.data_ptr(), k8.data_ptr(), vt8.data_ptr(), 1 if fmt.p0 == 2 else 0, mk.ptr, *mk.strides, *live[:4], 0, live[4],
                                     None if codes_only else out.data_ptr(), out8.data_ptr() if out8 is not None else None,
                                     ctypes.byref(fq_o._qt_format) if fq_o is not None else None, B, H, Q, C, D, float(scaling), st), entry)
-    if long_keys:
-        ATTENTION_ROUTES.setdefault(f"attention:{B}x{H}x{Q}x{C}x{D}", "attention_fp8_long")
+    if entry != "qt_attention_fp8":
+        ATTENTION_ROUTES.setdefault(f"attention:{B}x{H}x{Q}x{C}x{D}", entry[3:])
     if codes_only:
         handover.stamp(out, fq_o, handover.fp8_view(out8, fq_o), lazy=True)
     if fq_o is not None:
@@ -337,7 +372,8 @@ def _attention_fp8_or_none(attn, query, key, value, attention_mask, scaling, fqs
 
 def fused_attention_or_none(attn, query, key, value, attention_mask, scaling, dropout):
     """The whole attention core in ONE HIP launch (qt_attention_fq_bf16): QK^T, scaling, mask, softmax,
-    fake-quant of the probabilities and P.V on the matrix cores, the S x S tensor never written.  q, k, v go
+    fake-quant of the probabilities and P.V on the matrix cores, the S x S tensor never written (head_dim 32: the FP8 core
+    qt_attention_fp8_d32 where _fp8_core_for names it, and no other kernel).  q, k, v go
     through their own per-tensor fake-quantizers first (elementwise passes that also write the contiguous
     [B, H, S, D] layout).  Same applicability rules as the fused score path, plus head_dim in {64, 128};
     returns the attention output already in [B, Sq, H, D], or None.
@@ -346,7 +382,7 @@ def fused_attention_or_none(attn, query, key, value, attention_mask, scaling, dr
     faster than the library-GEMM chain (B16 H12 S384: 85 vs 113 us); at head_dim 128 the chain wins (92 vs 122 us at
     B1 H32 S1024), so the chain stays the default there."""
     mode = switches.mode("QT_FUSED_ATTENTION")
-    fp8_kernel = query.dim() == 4 and query.shape[-1] in (64, 128) and switches.on("QT_FP8_ATTENTION_KERNEL")
+    fp8_kernel = query.dim() == 4 and query.shape[-1] in (32, 64, 128) and switches.on("QT_FP8_ATTENTION_KERNEL")
     if mode == "0" or (mode != "1" and query.shape[-1] != 64 and not fp8_kernel):
         return None
     if not (query.device.type == "cuda" and query.dtype == torch.bfloat16 and query.dim() == 4):
@@ -357,7 +393,9 @@ def fused_attention_or_none(attn, query, key, value, attention_mask, scaling, dr
         return None
     B, H, Q, D = query.shape
     C = key.shape[2]
-    if D not in (64, 128) or C % 4 != 0 or key.shape != (B, H, C, D) or value.shape != (B, H, C, D) or B * H > 65535:
+    # head_dim 32: the FP8 kernel (qt_attention_fp8_d32) or nothing -- the two-pass and rows kernels do not take it
+    d32 = D == 32 and fp8_kernel and switches.on("QT_FP8_ATTENTION") and _fp8_core_for(B, H, Q, C, D) is not None
+    if (D not in (64, 128) and not d32) or C % 4 != 0 or key.shape != (B, H, C, D) or value.shape != (B, H, C, D) or B * H > 65535:
         return None
     # (backward hooks are looked at on none of the four modules: this is the no_grad path -- gradients were declined above)
     for mod in (attn.attn_scaling, attn.softmax):
@@ -381,6 +419,8 @@ def fused_attention_or_none(attn, query, key, value, attention_mask, scaling, dr
         out = _attention_fp8_or_none(attn, query, key, value, attention_mask, scaling, (fq_q, fq_k, fq_p, fq_v))
         if out is not None:
             return out
+    if d32:
+        return None
     table_p = (fq_p is not None and fq_p._quantize and fq_p._qt_format.kind == _native.QT_FMT_LUT)
     if mode != "1" and query.shape[-1] != 64 and not table_p:
         # head_dim 128 without the FP8 kernel: the library-GEMM chain (see above) -- except for table formats (posit, fpN, ...),
