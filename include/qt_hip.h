@@ -798,6 +798,22 @@ int qt_attention_fp8_d32(const uint8_t *q8_dev, const uint8_t *k8_dev, const uin
                          long mask_sb, long mask_sh, long mask_sq, const int *row_live_dev, long live_sb, long live_sh, long live_sq,
                          int mask_is_simple, const int *mask_irregular_dev, uint16_t *out_dev, uint8_t *out8_dev, const qt_format *out_format,
                          long B, int H, int Sq, int Sk, int head_dim, float scaling, void *stream);
+/* The same core at ANY key count 1 <= Sk <= 512, head_dim 64 or 128, ONE launch (csrc/qt_attention_fp8_ragged.hip): a batch padded to
+ * its longest sample, a last partial batch, ViT's 197 tokens (modules/quantizable/modeling_bert.py:118-158), which otherwise leave the
+ * FP8 core (the entry points above take multiples of 128 only).  The argument list, q8 / k8 operands, mask forms (read / row extents /
+ * mask_is_simple / device flag), rounding points, output modes (out, out + out8, codes only), fully masked rows (uniform over the Sk
+ * keys) and NaN rows of qt_attention_fp8.  vt8: [B][H][D][Skp], Skp = 128 ceil(Sk / 128), from qt_value_codes_t_ragged (the
+ * argument list of qt_value_codes_t; it IS the fq_v call): the slot <-> key permutation of qt_value_codes_t inside every 128-block,
+ * code 0 in every slot of a key >= Sk.  Keys >= Sk are never read from k8 or from the mask; their logits are -inf whatever the padded
+ * products hold.  The mask may have any element strides and any 2-byte-aligned base (it is read 2 bytes at a time); row_live entries lie
+ * in [0, Sk].  Contract: head_dim 64 or 128, 1 <= Sk <= 512 (multiples of 128 included), Sq >= 1, B * H <= 65535, operand_format 0
+ * (E4M3) or 1 (E5M2), q8 / k8 / vt8 / out / out8 16-byte aligned; anything else returns an error status with nothing written. */
+int qt_value_codes_t_ragged(const uint16_t *v_dev, uint8_t *vt8_dev, long B, long H, long Sk, int head_dim, long stride_b, long stride_h,
+                            long stride_k, const qt_format *fmt, void *stream);
+int qt_attention_fp8_ragged(const uint8_t *q8_dev, const uint8_t *k8_dev, const uint8_t *vt8_dev, int operand_format, const uint16_t *mask_dev,
+                            long mask_sb, long mask_sh, long mask_sq, const int *row_live_dev, long live_sb, long live_sh, long live_sq,
+                            int mask_is_simple, const int *mask_irregular_dev, uint16_t *out_dev, uint8_t *out8_dev, const qt_format *out_format,
+                            long B, int H, int Sq, int Sk, int head_dim, float scaling, void *stream);
 int qt_softmax_fq_bf16_fp8_live(const uint16_t *scores_dev, const uint16_t *mask_dev, uint8_t *out8_dev, long batch, int heads, int q_len,
                                 long cols, long mask_sb, long mask_sh, long mask_sq, float scaling, const qt_format *fmt,
                                 const int *row_live_dev, long live_sb, long live_sh, long live_sq, void *stream);

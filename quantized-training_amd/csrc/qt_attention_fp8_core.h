@@ -1,6 +1,7 @@
 // qt_attention_fp8_core.h -- what the attention kernels on FP8 codes share: attention_fp8_split_kernel (qt_attention_fp8.hip, the
 // score strip in registers, up to 1024 keys), attention_fp8_long_kernel (qt_attention_fp8_long.hip, the keys streamed, up to 16384) and
-// attention_fp8_d32_kernel (qt_attention_fp8_d32.hip, head_dim 32, up to 512 keys; its K image in LDS is its own).  All hold a wave's 16 query rows against the keys 16 t + 4 g + {0..3} of each 16-key tile t in lane (r, g), read K / V^T blocks that
+// attention_fp8_d32_kernel (qt_attention_fp8_d32.hip, head_dim 32, up to 512 keys; its K image in LDS is its own) and
+// attention_fp8_ragged_kernel (qt_attention_fp8_ragged.hip, any key count up to 512).  All hold a wave's 16 query rows against the keys 16 t + 4 g + {0..3} of each 16-key tile t in lane (r, g), read K / V^T blocks that
 // arrived by LDS-DMA with the same swizzle, and send the scores through the same rounding chain.
 #pragma once
 #include "qt_device.h"
@@ -51,21 +52,35 @@ __device__ __forceinline__ uint32_t prob_codes(uint32_t p0, uint32_t p1) {
 
 // scores of the four tiles t0 .. t0 + 3 of one K block.  MODE 0: no mask arithmetic; 1: row-extent mask applied from my_live
 // (tiles from `tiles` on lie beyond every row of the wave); 2: additive mask read from mrow.  head_dim 32: f_lo is the lane's 8 bytes of a
-// tile, f_hi unused
-template <int F, int D, int MODE>
+// tile, f_hi unused.  MODE + 4, the tail forms (qt_attention_fp8_ragged.hip: the key count is no multiple of 16): the lane's columns
+// j * 16 + e >= sk_left do not exist -- their logit is -inf whatever the product and the mask arithmetic gave, a NaN included, and the mask
+// (read 2 bytes at a time: its rows may start at any even address) is not read there; tiles from `tiles` on are skipped in every mode
+template <int F, int D, int MODE_>
 __device__ __forceinline__ void score_half(const uint8_t *blk, int t0, const v8i &qf, int f_lo, int f_hi, float scaling, float (*ev)[4], float &mx,
-                                           const uint16_t *mrow, int key0, int my_live, int tiles) {
+                                           const uint16_t *mrow, int key0, int my_live, int tiles, int sk_left = 0) {
+    constexpr int MODE = MODE_ & 3;
+    constexpr bool TAIL = (MODE_ & 4) != 0;
     // staged by hand -- all fragment reads, then the MFMAs back to back, then the rounding chains -- because the compiler keeps
     // source order and a read -> MFMA -> chain sequence per tile exposes the LDS and MFMA latencies four times over
     uint2 m[4];
     if (MODE == 2) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) m[j] = *(const uint2 *)(mrow + key0 + j * 16);
+        for (int j = 0; j < 4; ++j) {
+            if constexpr (TAIL) {
+                if (j >= tiles) continue;
+                const uint16_t *p = mrow + key0 + j * 16;
+                const int left = sk_left - j * 16;
+                const uint32_t e0 = left > 0 ? p[0] : 0u, e1 = left > 1 ? p[1] : 0u, e2 = left > 2 ? p[2] : 0u, e3 = left > 3 ? p[3] : 0u;
+                m[j] = uint2{e0 | (e1 << 16), e2 | (e3 << 16)};
+            } else {
+                m[j] = *(const uint2 *)(mrow + key0 + j * 16);
+            }
+        }
     }
     u32x4 klo[4], khi[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        if (MODE == 1 && j >= tiles) continue;
+        if ((MODE == 1 || TAIL) && j >= tiles) continue;
         if constexpr (D == 32) {                                         // head_dim 32: 8 bytes of a key, the depth of the 32-deep instruction
             const uint2 k2 = *(const uint2 *)(blk + (t0 + j) * (16 * D) + f_lo);
             klo[j] = u32x4{k2.x, k2.y, 0u, 0u};
@@ -78,7 +93,7 @@ __device__ __forceinline__ void score_half(const uint8_t *blk, int t0, const v8i
     v4f s[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        if (MODE == 1 && j >= tiles) continue;
+        if ((MODE == 1 || TAIL) && j >= tiles) continue;
         if constexpr (D == 32) {                                         // v_mfma_f32_16x16x32_fp8_fp8 / _bf8_bf8: qf's first two words are the fragment
             const long kf = (long)(((unsigned long)klo[j].y << 32) | klo[j].x), q2 = (long)(((unsigned long)(uint32_t)qf[1] << 32) | (uint32_t)qf[0]);
             if constexpr (F == 1) s[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf8_bf8(kf, q2, v4f{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
@@ -91,7 +106,7 @@ __device__ __forceinline__ void score_half(const uint8_t *blk, int t0, const v8i
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        if (MODE == 1 && j >= tiles) {
+        if ((MODE == 1 || TAIL) && j >= tiles) {
             ev[j][0] = ev[j][1] = ev[j][2] = ev[j][3] = -INFINITY;
             continue;
         }
@@ -108,6 +123,10 @@ __device__ __forceinline__ void score_half(const uint8_t *blk, int t0, const v8i
             const int left = my_live - (key0 + j * 16);                    // columns of this lane's four still inside its row's extent
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = (e < left || v[e] != v[e]) ? v[e] : -3.3895313892515355e38f;
+        }
+        if constexpr (TAIL) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = j * 16 + e < sk_left ? v[e] : -INFINITY;
         }
         ev[j][0] = v[0]; ev[j][1] = v[1]; ev[j][2] = v[2]; ev[j][3] = v[3];
         mx = max3(mx, v[0], v[1]);

@@ -217,8 +217,8 @@ def attention_output_plan(attn):
     return fq_o, fq_o is not None and own is not None and pc.no_foreign_hooks(attn) and codes_only_ok([proj])
 
 
-ATTENTION_ROUTES = {}      # "attention:BxHxQxCxD" -> "attention_fp8_long" / "attention_fp8_d32": the problems the streaming core and the
-                           # head_dim 32 core took (fused.routes_report)
+ATTENTION_ROUTES = {}      # "attention:BxHxQxCxD" -> "attention_fp8_long" / "attention_fp8_d32" / "attention_fp8_ragged": the problems the
+                           # streaming core, the head_dim 32 core and the any-key-count core took (fused.routes_report)
 
 # (B, H, Q, C, D) -> does qt_attention_fp8_long beat the library FP8 GEMM -> score pass -> library FP8 GEMM chain?  Measured with
 # tools/exp_attention_fp8_long.py (profiles/attention_fp8_long.txt): a class is listed as taken when the kernel's median beats the
@@ -252,13 +252,37 @@ def _fp8_d32_route_takes(B, H, Q, C):
     return _FP8_D32_TABLE.get((B, H, Q, C), False)
 
 
+# (B, H, Q, C, D) -> does the route through qt_value_codes_t_ragged + qt_attention_fp8_ragged (C % 128 != 0, C <= 512, head_dim 64 / 128) beat
+# the route the call takes otherwise -- the two-pass bf16 core behind three fake-quant passes (head_dim 64, C % 4 == 0), else the library /
+# torch chain?  Measured with tools/exp_attention_fp8_ragged.py (profiles/attention_fp8_ragged.txt), whole routes through the module path's
+# entry, the bar of _FP8_D32_TABLE: a class is listed as taken when the kernel route's median beats the other's by more than that
+# route's min-max spread, eager AND replayed, with the padding mask AND without a mask.
+_FP8_RAGGED_TABLE = {                        # other route / kernel route, us, padding mask: eager; replayed   (no mask: within 15 us of these)
+    (16, 12, 197, 197, 64): True,            # 248.2 / 84.5; 113.9 / 28.0    (ViT-base; the torch chain: 197 % 4 != 0)
+    (32, 12, 77, 77, 64): True,              # 249.3 / 84.4; 78.3 / 24.5     (the torch chain)
+    (32, 12, 136, 136, 64): True,            # 128.2 / 83.2; 55.1 / 34.2     (the two-pass core, here and below)
+    (32, 12, 200, 200, 64): True,            # 128.5 / 83.1; 70.7 / 40.1
+    (16, 12, 300, 300, 64): True,            # 127.7 / 82.7; 64.9 / 39.6
+    (16, 16, 376, 376, 64): True,            # 126.7 / 82.6; 93.4 / 53.6
+    (4, 32, 200, 200, 128): True,            # 229.6 / 83.2; 88.6 / 32.7     (the library chain)
+}                                            # (eager, both routes are bound by the host's launches, not by the device)
+
+
+def _fp8_ragged_route_takes(B, H, Q, C, D):
+    """The default route of a problem whose key count is no multiple of 128 (C <= 512): the committed table; a shape it does not list
+    stays where it was."""
+    return _FP8_RAGGED_TABLE.get((B, H, Q, C, D), False)
+
+
 def _fp8_core_for(B, H, Q, C, D):
     """The entry point that takes a problem of this shape -- on the default route, or wherever it applies under QT_FUSED_ATTENTION=1 -- or
     None: qt_attention_fp8 (head_dim 128 / 64, up to 1024 keys), qt_attention_fp8_long (beyond, up to 16384), qt_attention_fp8_d32
-    (head_dim 32, 128 .. 512 keys)."""
+    (head_dim 32, 128 .. 512 keys), qt_attention_fp8_ragged (head_dim 128 / 64, a key count up to 512 that is no multiple of 128)."""
     forced = switches.mode("QT_FUSED_ATTENTION") == "1"
-    if C % 128 != 0 or B * H > 65535:
+    if B * H > 65535:
         return None
+    if C % 128 != 0:
+        return "qt_attention_fp8_ragged" if 1 <= C <= 512 and D in (64, 128) and (forced or _fp8_ragged_route_takes(B, H, Q, C, D)) else None
     if D == 32:
         return "qt_attention_fp8_d32" if 128 <= C <= 512 and (forced or _fp8_d32_route_takes(B, H, Q, C)) else None
     if D not in (64, 128) or C > 16384:
@@ -273,7 +297,10 @@ def _attention_fp8_or_none(attn, query, key, value, attention_mask, scaling, fqs
     four fake-quantizers around the two matmuls are stateless E4M3 / E5M2 ones of one format.  Beyond 1024 keys (up to 16384) the same
     launch is qt_attention_fp8_long, the streaming two-sweep core, and at head_dim 32 (128 .. 512 keys, MobileBERT) it is
     qt_attention_fp8_d32 behind its own value pass qt_value_codes_t_d32: each where its committed rule (_fp8_long_route_takes,
-    _fp8_d32_route_takes) lists the shape, and wherever it applies under QT_FUSED_ATTENTION=1 (_fp8_core_for).  q / k either arrive with their codes (the
+    _fp8_d32_route_takes) lists the shape, and wherever it applies under QT_FUSED_ATTENTION=1 (_fp8_core_for).  At a key count that is
+    no multiple of 128 (up to 512, head_dim 128 / 64) it is qt_attention_fp8_ragged behind qt_value_codes_t_ragged, whose V^T has rows of
+    128 ceil(C / 128) bytes (so neither the combined qt_rope_fq_value launch nor a value pass written ahead serves it); its mask may lie
+    at any even address with any strides.  q / k either arrive with their codes (the
     rotary kernel attaches them) or are [B, H, S, D] views of the projections' outputs (BERT's transpose_for_scores), whose codes a
     codes-only pass over the view writes here -- that pass IS the fq_q / fq_k call.  Counts the four fake-quant calls the reference
     issues: q and k (handed through by their modules, or the passes just named), the value pass (qt_value_codes_t) and the
@@ -298,7 +325,8 @@ def _attention_fp8_or_none(attn, query, key, value, attention_mask, scaling, fqs
     q8, k8 = handed(query, fq_q, Q), handed(key, fq_k, C)
     if (q8 is None and not readable_in_place(query)) or (k8 is None and not readable_in_place(key)):
         return None
-    mk = AttentionMask.of(attention_mask, B, H, Q, C, query.device, 4)
+    ragged = entry == "qt_attention_fp8_ragged"
+    mk = AttentionMask.of(attention_mask, B, H, Q, C, query.device, 1 if ragged else 4)
     if mk is None:
         return None
     L = _native.lib()
@@ -322,7 +350,7 @@ def _attention_fp8_or_none(attn, query, key, value, attention_mask, scaling, fqs
         return rs if (t.stride(3) == 1 and t.stride(1) == d_ and t.stride(0) == s_ * rs and rs % 8 == 0 and rs >= h_ * d_) else None
 
     vt8 = None
-    if (D != 32 and q8 is None and k8 is None and Q == C and key.shape[1] == H and value.shape[1] == H and token_rows(query) is not None
+    if (D != 32 and not ragged and q8 is None and k8 is None and Q == C and key.shape[1] == H and value.shape[1] == H and token_rows(query) is not None
             and token_rows(key) is not None and switches.on("QT_ROPE_VALUE_LAUNCH")):
         # q and k codes and the value codes in ONE launch (qt_rope_fq_value without a rotation): the three calls fq_q, fq_k, fq_v
         q8 = torch.empty((B, H, Q, D), dtype=torch.uint8, device=query.device)
@@ -337,9 +365,13 @@ def _attention_fp8_or_none(attn, query, key, value, attention_mask, scaling, fqs
     else:
         q8, k8 = codes(query, fq_q, q8), codes(key, fq_k, k8)
     fmt = fq_v._qt_format
-    early = precomputed.VALUE_CODES_T.take(attn, value)
+    early = None if ragged else precomputed.VALUE_CODES_T.take(attn, value)      # (ragged: nobody writes its padded rows ahead)
     if vt8 is not None:
         pass                                                 # written by the launch above
+    elif ragged:
+        vt8 = torch.empty((B, H, D, (C + 127) // 128 * 128), dtype=torch.uint8, device=query.device)
+        _native.check(L.qt_value_codes_t_ragged(value.data_ptr(), vt8.data_ptr(), B, H, C, D, value.stride(0), value.stride(1), value.stride(2),
+                                                ctypes.byref(fmt), st), "qt_value_codes_t_ragged")
     elif isinstance(early, tuple) and early[0] is fq_v:
         vt8 = early[1]                                       # written by the launch that carried the rotary kernel (model_fusions.rope_fq)
     else:
@@ -395,7 +427,10 @@ def fused_attention_or_none(attn, query, key, value, attention_mask, scaling, dr
     C = key.shape[2]
     # head_dim 32: the FP8 kernel (qt_attention_fp8_d32) or nothing -- the two-pass and rows kernels do not take it
     d32 = D == 32 and fp8_kernel and switches.on("QT_FP8_ATTENTION") and _fp8_core_for(B, H, Q, C, D) is not None
-    if (D not in (64, 128) and not d32) or C % 4 != 0 or key.shape != (B, H, C, D) or value.shape != (B, H, C, D) or B * H > 65535:
+    # a key count that is no multiple of 4: the FP8 kernel (qt_attention_fp8_ragged) or nothing, likewise
+    odd = (D in (64, 128) and C % 4 != 0 and fp8_kernel and switches.on("QT_FP8_ATTENTION")
+           and _fp8_core_for(B, H, Q, C, D) == "qt_attention_fp8_ragged")
+    if (D not in (64, 128) and not d32) or (C % 4 != 0 and not odd) or key.shape != (B, H, C, D) or value.shape != (B, H, C, D) or B * H > 65535:
         return None
     # (backward hooks are looked at on none of the four modules: this is the no_grad path -- gradients were declined above)
     for mod in (attn.attn_scaling, attn.softmax):
@@ -419,7 +454,7 @@ def fused_attention_or_none(attn, query, key, value, attention_mask, scaling, dr
         out = _attention_fp8_or_none(attn, query, key, value, attention_mask, scaling, (fq_q, fq_k, fq_p, fq_v))
         if out is not None:
             return out
-    if d32:
+    if d32 or odd:
         return None
     table_p = (fq_p is not None and fq_p._quantize and fq_p._qt_format.kind == _native.QT_FMT_LUT)
     if mode != "1" and query.shape[-1] != 64 and not table_p:

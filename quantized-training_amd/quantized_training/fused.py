@@ -84,7 +84,7 @@ def routes_report():
     out.update(sorted(CONV_ROUTES.items()))
     from .pt2e_native import GWA_ROUTES                        # packed group-wise affine Linears (csrc/qt_gwa_gemm.hip or dequantize + library GEMM)
     out.update(sorted(GWA_ROUTES.items()))
-    from .attention_route import ATTENTION_ROUTES              # long-key and head_dim 32 FP8 attention cores (csrc/qt_attention_fp8_long.hip, _d32.hip)
+    from .attention_route import ATTENTION_ROUTES              # long-key, head_dim 32 and ragged FP8 attention cores (csrc/qt_attention_fp8_long.hip, _d32.hip, _ragged.hip)
     out.update(sorted(ATTENTION_ROUTES.items()))
     return out
 
