@@ -814,6 +814,22 @@ int qt_attention_fp8_ragged(const uint8_t *q8_dev, const uint8_t *k8_dev, const 
                             long mask_sb, long mask_sh, long mask_sq, const int *row_live_dev, long live_sb, long live_sh, long live_sq,
                             int mask_is_simple, const int *mask_irregular_dev, uint16_t *out_dev, uint8_t *out8_dev, const qt_format *out_format,
                             long B, int H, int Sq, int Sk, int head_dim, float scaling, void *stream);
+/* The streaming core for GROUPED-QUERY heads, ONE launch (csrc/qt_attention_fp8_gqa.hip): H query heads over Hkv = H / G key / value
+ * heads, K and V^T taken UNREPEATED where the module chain (modules/quantizable/modeling_llama.py: repeat_kv before qk_matmul) multiplies
+ * G copies of both.  The argument list of qt_attention_fp8_long plus Hkv: q8 [B][H][Sq][D]; k8 [B][Hkv][Sk][D]; vt8 [B][Hkv][D][Sk], exactly
+ * what qt_value_codes_t writes when called with H = Hkv.  Query head h reads kv head h / G (the order of repeat_kv).  The mask, row_live
+ * and mask_irregular_dev are addressed by QUERY head, as everywhere above; out / out8 are [B][Sq][H][D].  Mask forms (read / row extents /
+ * mask_is_simple / device flag), rounding points, output modes (out, out + out8, codes only), fully masked rows and NaN rows of
+ * qt_attention_fp8_long, and per query row its operations in its order: the result is bit for bit what qt_attention_fp8_long returns for
+ * the same q8 with k8 / vt8 repeated G times.  A workgroup of 8 waves owns one (batch, kv head) and 128 / G query rows of each of the
+ * group's G heads; every K / V^T block is brought into LDS once for all of them.  Contract: G = H / Hkv in {2, 4, 8}, H % Hkv == 0,
+ * head_dim 64 or 128, Sk % 128 == 0, 128 <= Sk <= 16384, Sq >= 1 (at most 65535 blocks of 128 / G rows), B * Hkv <= 65535, operand_format
+ * 0 (E4M3) or 1 (E5M2), the alignments of qt_attention_fp8; anything else -- G = 1, for which the entry points above exist, and
+ * G = 3, 5, 6, 7 included -- returns an error status with nothing written. */
+int qt_attention_fp8_gqa(const uint8_t *q8_dev, const uint8_t *k8_dev, const uint8_t *vt8_dev, int operand_format, const uint16_t *mask_dev,
+                         long mask_sb, long mask_sh, long mask_sq, const int *row_live_dev, long live_sb, long live_sh, long live_sq,
+                         int mask_is_simple, const int *mask_irregular_dev, uint16_t *out_dev, uint8_t *out8_dev, const qt_format *out_format,
+                         long B, int H, int Hkv, int Sq, int Sk, int head_dim, float scaling, void *stream);
 int qt_softmax_fq_bf16_fp8_live(const uint16_t *scores_dev, const uint16_t *mask_dev, uint8_t *out8_dev, long batch, int heads, int q_len,
                                 long cols, long mask_sb, long mask_sh, long mask_sq, float scaling, const qt_format *fmt,
                                 const int *row_live_dev, long live_sb, long live_sh, long live_sq, void *stream);

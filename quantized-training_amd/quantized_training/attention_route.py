@@ -218,7 +218,8 @@ def attention_output_plan(attn):
 
 
 ATTENTION_ROUTES = {}      # "attention:BxHxQxCxD" -> "attention_fp8_long" / "attention_fp8_d32" / "attention_fp8_ragged": the problems the
-                           # streaming core, the head_dim 32 core and the any-key-count core took (fused.routes_report)
+                           # streaming core, the head_dim 32 core and the any-key-count core took (fused.routes_report);
+                           # "attention:BxHxHkvxQxCxD" -> "attention_fp8_gqa": those the grouped-query core took
 
 # (B, H, Q, C, D) -> does qt_attention_fp8_long beat the library FP8 GEMM -> score pass -> library FP8 GEMM chain?  Measured with
 # tools/exp_attention_fp8_long.py (profiles/attention_fp8_long.txt): a class is listed as taken when the kernel's median beats the
@@ -274,6 +275,37 @@ def _fp8_ragged_route_takes(B, H, Q, C, D):
     return _FP8_RAGGED_TABLE.get((B, H, Q, C, D), False)
 
 
+# (B, H, Hkv, Q, C, D) -> does the route through qt_attention_fp8_gqa (grouped-query heads, K and V^T unrepeated) beat the route the call
+# takes otherwise -- _repeat_kv's copies of K and V, the code passes over G times the data, then qt_attention_fp8 / _long / the chain?
+# Measured with tools/exp_attention_fp8_gqa.py (profiles/attention_fp8_gqa.txt), whole routes through the module path's entry, the bar of
+# _FP8_RAGGED_TABLE: a class is listed as taken when the kernel route's median beats the other's by more than that route's min-max
+# spread, eager AND replayed, with the causal mask AND without a mask.
+_FP8_GQA_TABLE = {                           # other route / kernel route, us, causal mask: eager; replayed   (no mask: see the profile)
+    (1, 32, 8, 1024, 1024, 128): True,       # 129.6 / 103.3; 62.4 / 57.4    (Llama-3-8B, Mistral-7B; the other route: repeat + qt_attention_fp8)
+    (1, 32, 8, 2048, 2048, 128): True,       # 134.5 / 102.3; 135.6 / 102.8  (repeat + qt_attention_fp8_long, here and below)
+    (1, 32, 8, 4096, 4096, 128): True,       # 344.2 / 314.5; 346.7 / 315.5
+    (1, 32, 8, 2048, 2048, 64): True,        # 175.9 / 112.2; 173.1 / 90.4   (Llama-3.2-1B; repeat + the library chain, here and below)
+    (1, 32, 4, 2048, 2048, 64): True,        # 176.6 / 112.8; 173.9 / 90.0   (TinyLlama)
+    (1, 64, 8, 4096, 4096, 128): True,       # 1954.4 / 606.8; 1951.7 / 602.8  (Llama-2-70B)
+}
+
+
+def _fp8_gqa_route_takes(B, H, Hkv, Q, C, D):
+    """The default route of a grouped-query problem: the committed table; a shape it does not list keeps the repeat and what follows it."""
+    return _FP8_GQA_TABLE.get((B, H, Hkv, Q, C, D), False)
+
+
+def _fp8_gqa_core_for(B, H, Hkv, Q, C, D):
+    """"qt_attention_fp8_gqa" when the entry point's contract holds for H query heads over Hkv key / value heads -- G = H / Hkv in
+    {2, 4, 8}, head_dim 64 / 128, 128 .. 16384 keys in blocks of 128 -- and the route is the default (_fp8_gqa_route_takes) or forced
+    (QT_FUSED_ATTENTION=1); else None: the caller repeats K and V and goes on as without this route."""
+    if Hkv < 1 or H % Hkv or H // Hkv not in (2, 4, 8) or D not in (64, 128) or C % 128 or not 128 <= C <= 16384 or Q < 1:
+        return None
+    if B * Hkv > 65535 or (Q + 128 // (H // Hkv) - 1) // (128 // (H // Hkv)) > 65535:
+        return None
+    return "qt_attention_fp8_gqa" if switches.mode("QT_FUSED_ATTENTION") == "1" or _fp8_gqa_route_takes(B, H, Hkv, Q, C, D) else None
+
+
 def _fp8_core_for(B, H, Q, C, D):
     """The entry point that takes a problem of this shape -- on the default route, or wherever it applies under QT_FUSED_ATTENTION=1 -- or
     None: qt_attention_fp8 (head_dim 128 / 64, up to 1024 keys), qt_attention_fp8_long (beyond, up to 16384), qt_attention_fp8_d32
@@ -304,11 +336,15 @@ def _attention_fp8_or_none(attn, query, key, value, attention_mask, scaling, fqs
     rotary kernel attaches them) or are [B, H, S, D] views of the projections' outputs (BERT's transpose_for_scores), whose codes a
     codes-only pass over the view writes here -- that pass IS the fq_q / fq_k call.  Counts the four fake-quant calls the reference
     issues: q and k (handed through by their modules, or the passes just named), the value pass (qt_value_codes_t) and the
-    probabilities inside the kernel.  Returns [B, Sq, H, D] or None."""
+    probabilities inside the kernel.  Grouped-query heads (key / value with Hk = H / G heads, offered UNREPEATED by grouped_attention_or_none):
+    qt_attention_fp8_gqa where _fp8_gqa_core_for names it -- the key codes are the rotary launch's [B][Hk][C][D] ones or a pass over the
+    unrepeated key, qt_value_codes_t runs with H = Hk, the mask and its extents stay per query head, and the counts are those of the
+    repeated tensors the reference quantizes.  Returns [B, Sq, H, D] or None."""
     fq_q, fq_k, fq_p, fq_v = fqs
     B, H, Q, D = query.shape
-    C = key.shape[2]
-    entry = _fp8_core_for(B, H, Q, C, D)
+    Hk, C = key.shape[1], key.shape[2]
+    G = H // Hk if Hk and H % Hk == 0 else 0
+    entry = _fp8_core_for(B, H, Q, C, D) if G == 1 else _fp8_gqa_core_for(B, H, Hk, Q, C, D)
     if entry is None:
         return None
     if not all(isinstance(f, FusedAmaxObsFakeQuantize) and f.producer_fusable() for f in fqs):
@@ -316,13 +352,13 @@ def _attention_fp8_or_none(attn, query, key, value, attention_mask, scaling, fqs
     if len({f._qt_format.key() for f in fqs}) != 1 or not readable_in_place(value):
         return None
 
-    def handed(t, fq, rows):
+    def handed(t, fq, heads, rows):
         t8 = handover.codes(t)
-        if t8 is None or handover.done_by(t) is not fq or not t8.is_contiguous() or tuple(t8.shape) != (B, H, rows, D):
+        if t8 is None or handover.done_by(t) is not fq or not t8.is_contiguous() or tuple(t8.shape) != (B, heads, rows, D):
             return None
         return t8
 
-    q8, k8 = handed(query, fq_q, Q), handed(key, fq_k, C)
+    q8, k8 = handed(query, fq_q, H, Q), handed(key, fq_k, Hk, C)
     if (q8 is None and not readable_in_place(query)) or (k8 is None and not readable_in_place(key)):
         return None
     ragged = entry == "qt_attention_fp8_ragged"
@@ -333,14 +369,14 @@ def _attention_fp8_or_none(attn, query, key, value, attention_mask, scaling, fqs
     st = _stream_ptr(query)
     live = mk.row_live(B, H, Q, C, st)
 
-    def codes(t, fq, t8):
+    def codes(t, fq, t8, copies=1):
         if t8 is not None:
             # hand-over, counted as the fake-quantizer's own forward would (calling it would also decode codes-only tensors, see
             # model_fusions.rope_fq: nothing here reads the bf16 values)
-            count_call(fq, t.numel())
+            count_call(fq, copies * t.numel())
             return t8
         t8 = fp8_codes_of_view(t, fq, st)
-        STATS.add(t.numel())
+        STATS.add(copies * t.numel())
         return t8
 
     def token_rows(t):
@@ -363,9 +399,10 @@ def _attention_fp8_or_none(attn, query, key, value, attention_mask, scaling, fqs
         STATS.add(query.numel())
         STATS.add(key.numel())
     else:
-        q8, k8 = codes(query, fq_q, q8), codes(key, fq_k, k8)
+        q8, k8 = codes(query, fq_q, q8), codes(key, fq_k, k8, G)             # (grouped: the reference quantizes the G copies)
     fmt = fq_v._qt_format
-    early = None if ragged else precomputed.VALUE_CODES_T.take(attn, value)      # (ragged: nobody writes its padded rows ahead)
+    # (ragged: nobody writes its padded rows ahead; grouped: _attention_value_plan declines, the value codes are a launch of their own)
+    early = None if ragged or G > 1 else precomputed.VALUE_CODES_T.take(attn, value)
     if vt8 is not None:
         pass                                                 # written by the launch above
     elif ragged:
@@ -375,14 +412,14 @@ def _attention_fp8_or_none(attn, query, key, value, attention_mask, scaling, fqs
     elif isinstance(early, tuple) and early[0] is fq_v:
         vt8 = early[1]                                       # written by the launch that carried the rotary kernel (model_fusions.rope_fq)
     else:
-        vt8 = torch.empty((B, H, D, C), dtype=torch.uint8, device=query.device)
+        vt8 = torch.empty((B, Hk, D, C), dtype=torch.uint8, device=query.device)
         if D == 32:
             _native.check(L.qt_value_codes_t_d32(value.data_ptr(), vt8.data_ptr(), B, H, C, value.stride(0), value.stride(1), value.stride(2),
                                                  ctypes.byref(fmt), st), "qt_value_codes_t_d32")
         else:
-            _native.check(L.qt_value_codes_t(value.data_ptr(), vt8.data_ptr(), B, H, C, D, value.stride(0), value.stride(1), value.stride(2),
+            _native.check(L.qt_value_codes_t(value.data_ptr(), vt8.data_ptr(), B, Hk, C, D, value.stride(0), value.stride(1), value.stride(2),
                                              ctypes.byref(fmt), st), "qt_value_codes_t")
-    STATS.add(value.numel())                                 # fq_v, evaluated by that pass
+    STATS.add(G * value.numel())                             # fq_v, evaluated by that pass
     STATS.add(B * H * Q * C)                                 # fq_p, evaluated inside the kernel
     # the output projection's stateless FP8 input fake-quantizer rides on the epilogue (as model_fusions.attention_output does for the
     # library-GEMM chain): HF reshapes the result before the projection's hook sees it, so the hand-over is an expectation
@@ -392,14 +429,69 @@ def _attention_fp8_or_none(attn, query, key, value, attention_mask, scaling, fqs
     out = handover.unwritten(shape, torch.bfloat16, query.device) if codes_only else torch.empty(shape, dtype=torch.bfloat16, device=query.device)
     _native.check(getattr(L, entry)(q8.data_ptr(), k8.data_ptr(), vt8.data_ptr(), 1 if fmt.p0 == 2 else 0, mk.ptr, *mk.strides, *live[:4], 0, live[4],
                                     None if codes_only else out.data_ptr(), out8.data_ptr() if out8 is not None else None,
-                                    ctypes.byref(fq_o._qt_format) if fq_o is not None else None, B, H, Q, C, D, float(scaling), st), entry)
-    if entry != "qt_attention_fp8":
+                                    ctypes.byref(fq_o._qt_format) if fq_o is not None else None, B, H, *((Hk,) if G > 1 else ()), Q, C, D,
+                                    float(scaling), st), entry)
+    if G > 1:
+        ATTENTION_ROUTES.setdefault(f"attention:{B}x{H}x{Hk}x{Q}x{C}x{D}", entry[3:])
+    elif entry != "qt_attention_fp8":
         ATTENTION_ROUTES.setdefault(f"attention:{B}x{H}x{Q}x{C}x{D}", entry[3:])
     if codes_only:
         handover.stamp(out, fq_o, handover.fp8_view(out8, fq_o), lazy=True)
     if fq_o is not None:
         fq_o.expect_prequantized(out, handover.fp8_view(out8, fq_o))
     return out
+
+
+def _inference_call(attn, query, key, value, dropout):
+    """What every core here asks of a call: bf16 [B, H, S, D] device tensors, no gradient wanted, no active dropout."""
+    if not (query.device.type == "cuda" and query.dtype == torch.bfloat16 and query.dim() == 4):
+        return False
+    if torch.is_grad_enabled() and (query.requires_grad or key.requires_grad or value.requires_grad):
+        return False
+    return not (dropout and attn.training)
+
+
+def _matmul_fake_quantizers(attn):
+    """(fq_q, fq_k, fq_p, fq_v) of the block's two matmuls -- four times None when they carry none -- or None where a core must decline:
+    a hooked scaling / softmax module, a foreign hook on a matmul, fake-quantizers not created yet or not plain per-tensor ones."""
+    # (backward hooks are looked at on none of the four modules: this is the no_grad path -- gradients were declined above)
+    for mod in (attn.attn_scaling, attn.softmax):
+        if getattr(mod, "activation_pre_process", None) is not None or not pc.no_forward_hooks(mod):
+            return None
+    hq, hv = getattr(attn.qk_matmul, "activation_pre_process", None), getattr(attn.av_matmul, "activation_pre_process", None)
+    if (hq is None) != (hv is None):
+        return None
+    # quantize()'s one pre-hook per matmul with its holder, no hook at all without; never a forward hook
+    if not all(pc.quantize_hooks_only(mod, 0 if hq is None else 1) for mod in (attn.qk_matmul, attn.av_matmul)):
+        return None
+    if hq is None:
+        return None, None, None, None
+    fqs_qk, fqs_av = (pc.holder_fqs(mod, "activation_pre_process", "0", "1", exact=False) for mod in (attn.qk_matmul, attn.av_matmul))
+    if fqs_qk is None or fqs_av is None:
+        return None                           # first call: let the hooks create the fake-quantizers
+    fqs = (*fqs_qk, *fqs_av)
+    return fqs if all(pc.plain_per_tensor(f) for f in fqs) else None
+
+
+def grouped_attention_or_none(attn, query, key, value, attention_mask, scaling, dropout):
+    """Grouped-query heads: the whole core in ONE launch on the UNREPEATED key / value [B, Hkv, C, D] (qt_attention_fp8_gqa, through
+    _attention_fp8_or_none) behind the gates of fused_attention_or_none's FP8 branch -- the switches, an inference call, the four stateless
+    FP8 fake-quantizers of one format --, where _fp8_gqa_core_for names it.  Returns [B, Sq, H, D], or None: the caller then repeats K
+    and V and goes on exactly as without this route.  Out of scope: ragged key counts, head_dim 32, G outside {2, 4, 8}, the value
+    codes from the rotary launch (qt_rope_fq_value, _attention_value_plan), the training core."""
+    if switches.mode("QT_FUSED_ATTENTION") == "0" or not (switches.on("QT_FP8_ATTENTION_KERNEL") and switches.on("QT_FP8_ATTENTION")):
+        return None
+    if not _inference_call(attn, query, key, value, dropout):
+        return None
+    B, H, Q, D = query.shape
+    if key.dim() != 4 or key.shape != value.shape or key.shape[0] != B or key.shape[3] != D:
+        return None
+    if _fp8_gqa_core_for(B, H, key.shape[1], Q, key.shape[2], D) is None:
+        return None
+    fqs = _matmul_fake_quantizers(attn)
+    if fqs is None or fqs[0] is None:
+        return None
+    return _attention_fp8_or_none(attn, query, key, value, attention_mask, scaling, fqs)
 
 
 def fused_attention_or_none(attn, query, key, value, attention_mask, scaling, dropout):
@@ -417,11 +509,7 @@ def fused_attention_or_none(attn, query, key, value, attention_mask, scaling, dr
     fp8_kernel = query.dim() == 4 and query.shape[-1] in (32, 64, 128) and switches.on("QT_FP8_ATTENTION_KERNEL")
     if mode == "0" or (mode != "1" and query.shape[-1] != 64 and not fp8_kernel):
         return None
-    if not (query.device.type == "cuda" and query.dtype == torch.bfloat16 and query.dim() == 4):
-        return None
-    if torch.is_grad_enabled() and (query.requires_grad or key.requires_grad or value.requires_grad):
-        return None
-    if dropout and attn.training:
+    if not _inference_call(attn, query, key, value, dropout):
         return None
     B, H, Q, D = query.shape
     C = key.shape[2]
@@ -432,24 +520,10 @@ def fused_attention_or_none(attn, query, key, value, attention_mask, scaling, dr
            and _fp8_core_for(B, H, Q, C, D) == "qt_attention_fp8_ragged")
     if (D not in (64, 128) and not d32) or (C % 4 != 0 and not odd) or key.shape != (B, H, C, D) or value.shape != (B, H, C, D) or B * H > 65535:
         return None
-    # (backward hooks are looked at on none of the four modules: this is the no_grad path -- gradients were declined above)
-    for mod in (attn.attn_scaling, attn.softmax):
-        if getattr(mod, "activation_pre_process", None) is not None or not pc.no_forward_hooks(mod):
-            return None
-    hq, hv = getattr(attn.qk_matmul, "activation_pre_process", None), getattr(attn.av_matmul, "activation_pre_process", None)
-    if (hq is None) != (hv is None):
+    fqs = _matmul_fake_quantizers(attn)
+    if fqs is None:
         return None
-    fq_q = fq_k = fq_p = fq_v = None
-    # quantize()'s one pre-hook per matmul with its holder, no hook at all without; never a forward hook
-    if not all(pc.quantize_hooks_only(mod, 0 if hq is None else 1) for mod in (attn.qk_matmul, attn.av_matmul)):
-        return None
-    if hq is not None:
-        fqs_qk, fqs_av = (pc.holder_fqs(mod, "activation_pre_process", "0", "1", exact=False) for mod in (attn.qk_matmul, attn.av_matmul))
-        if fqs_qk is None or fqs_av is None:
-            return None                       # first call: let the hooks create the fake-quantizers
-        fq_q, fq_k, fq_p, fq_v = *fqs_qk, *fqs_av
-        if not all(pc.plain_per_tensor(f) for f in (fq_q, fq_k, fq_p, fq_v)):
-            return None
+    fq_q, fq_k, fq_p, fq_v = fqs
     if fp8_kernel and fq_q is not None and switches.on("QT_FP8_ATTENTION"):
         out = _attention_fp8_or_none(attn, query, key, value, attention_mask, scaling, (fq_q, fq_k, fq_p, fq_v))
         if out is not None:

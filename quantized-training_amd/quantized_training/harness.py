@@ -220,6 +220,7 @@ LLAMA_SHAPES = {
     "llama-2-13b": (5120, 40, 40, 40, 13824, 32000),
     "llama-tiny": (128, 2, 4, 4, 352, 512),
     "llama-mid": (1024, 8, 8, 8, 2816, 2048),          # head_dim 128 like the 7B / 13B shapes; tests of accumulated drift
+    "llama-gqa-tiny": (256, 2, 4, 2, 704, 512),        # grouped-query heads: 4 query heads of 64 over 2 kv heads (qt_attention_fp8_gqa)
 }
 
 

@@ -80,16 +80,32 @@ def _causal_mask(q_len, k_len, dtype, device):
     return m
 
 
+def _grouped_core_or_none(module, query, key, value, attention_mask, scaling, dropout, causal):
+    """Grouped-query heads: the mask first (it depends on the key COUNT only), then the unrepeated key / value offered to the router
+    (attention_route.grouped_attention_or_none: qt_attention_fp8_gqa).  None: the caller repeats K and V and continues as before."""
+    attention_mask = _additive_mask(attention_mask, query.dtype)
+    if causal is None:
+        causal = getattr(module, "is_causal", False)
+    if attention_mask is None and query.shape[2] > 1 and causal:
+        attention_mask = _causal_mask(query.shape[2], key.shape[2], query.dtype, query.device)
+    from ...attention_route import grouped_attention_or_none
+    return grouped_attention_or_none(module, query, key, value, attention_mask, scaling, dropout)
+
+
 def quantizable_attention_forward(module, query, key, value, attention_mask, scaling=None, dropout=0.0, **kwargs):
     """Drop-in for HF's ``eager_attention_forward`` that goes through the module's hookable ops:
     ``av_matmul(softmax(attn_scaling(qk_matmul(q, k^T), scale) + mask), v)``."""
     from ..qat.linear import flush_forward
     flush_forward()                            # projections whose forward products are still pending (a training step: one launch for q / k / v)
     n_rep = getattr(module, "num_key_value_groups", 1)
-    key = _repeat_kv(key, n_rep)
-    value = _repeat_kv(value, n_rep)
     if scaling is None:
         scaling = query.size(-1) ** -0.5
+    if n_rep > 1:
+        core = _grouped_core_or_none(module, query, key, value, attention_mask, scaling, dropout, kwargs.get("is_causal"))
+        if core is not None:
+            return core, None
+    key = _repeat_kv(key, n_rep)
+    value = _repeat_kv(value, n_rep)
     attention_mask = _additive_mask(attention_mask, query.dtype)
     causal = kwargs.get("is_causal")
     if causal is None:
