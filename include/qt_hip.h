@@ -1328,6 +1328,25 @@ int qt_rope_fq_inner_value(const uint16_t *q_dev, const uint16_t *k_dev, const u
                            const qt_format *inner_k, const uint16_t *v_dev, uint8_t *vt8_dev, long v_stride_b, long v_stride_h,
                            long v_stride_k, const qt_format *fmt_v, void *stream);
 
+/* ---- the attention core of the block-scaled integer recipe (csrc/qt_attention_mxi.hip) --------------------------------------------
+ * Replaces, in a converted bf16 graph whose attention matmuls are `intN,qs=microscaling,bs=64` pairs (examples/language_modeling/
+ * prepare_model.py: matmul6, linear4_matmul6_fp8), the span
+ *     matmul_mx(q, k^T) -> mul / div by a scalar -> + mask -> softmax(-1) -> quantize_mx(p, ax=-1) -> matmul_mx(p', v)
+ *                                                                          (decomposed.py:304-363, 365-448)
+ * with every rounding of those nodes kept (the file header states the chain).  Operands as qt_mxi_pack writes them: q_codes [B][H][Q][D],
+ * k_codes [B][H][C][D] (rows view of K^T), v_codes [B][H][D][C]; fp32 scales [..][D/64], [..][D/64], [..][C/64]; block_size 64 for
+ * all four operands, head_dim 64 or 128, C % 64 == 0, 64 <= C <= 16384, Q >= 0, B H <= 65535.  v_work ([B][H][D][C] bytes) and
+ * v_scales_work ([B][H][C/64][D] floats) are caller-owned scratch that the prepare launch fills.  mask_dev: additive bf16 mask, keys
+ * contiguous, element strides for (b, h, q), 8-byte aligned with strides % 4 == 0, or NULL.  scaling_is_div: 0 = `* scaling`,
+ * 1 = `/ scaling`.  P's quantizer as quantize_mx gets it: p_format an intN element format in closed form (QT_FMT_INT, N <= 8),
+ * quant_max, force_scale_power_of_two, scale_map_dev (the 65 536-entry bf16 map of the scale dtype, or NULL).  out_dev bf16
+ * [B][H][Q][D].  QT_ERR_BAD_ARG / QT_ERR_UNALIGNED for everything else, before any launch. */
+int qt_attention_mxi(const int8_t *q_codes, const float *q_scales, const int8_t *k_codes, const float *k_scales, const int8_t *v_codes,
+                     const float *v_scales, int8_t *v_work, float *v_scales_work, const uint16_t *mask_dev, long mask_sb, long mask_sh,
+                     long mask_sq, float scaling, int scaling_is_div, const qt_format *p_format, float quant_max,
+                     int force_scale_power_of_two, const uint16_t *scale_map_dev, uint16_t *out_dev, long B, int H, int Q, int C,
+                     int head_dim, int block_size, void *stream);
+
 /* ---- plain FP8 GEMM on already fake-quantized operands, through hipBLASLt with the algorithm NAMED by the caller ----------
  * C[b][M][N] (bf16) = A[b][M][K] . op(B) (+ bias[N], bf16); A, B are OCP FP8 bytes (format 0 = E4M3, 1 = E5M2) whose
  * values are exactly the fake-quantized bf16 values (unit scale), so the products are the reference's

@@ -458,6 +458,37 @@ _lib.impl("linear_mx", _linear_mx_impl, "CompositeExplicitAutograd")
 _lib.impl("matmul_mx", _matmul_mx_impl, "CompositeExplicitAutograd")
 
 
+# ---- the attention core between the quantize_mx nodes of q, k^T and v (pt2e_native.fuse_mx_attention) -------------------------------
+# One node for   matmul_mx(q, kT) -> * scaling or / scaling -> + mask -> softmax(-1) [in fp32, cast back] -> quantize_mx(p, [-1]) ->
+# matmul_mx(p', v).   On a device tensor inside the kernel's contract: three qt_mxi_pack launches + qt_attention_mxi
+# (mx_attention.py, csrc/qt_attention_mxi.hip).  Everywhere else the nodes below, literally: the same bits as the unfused graph.
+_lib.define("attention_mx(Tensor q, Tensor q_scale, Tensor kT, Tensor kT_scale, Tensor v, Tensor v_scale, Tensor? mask, float scaling, "
+            "bool scaling_is_div, Tensor p_qmap, float p_quant_max, bool p_force_scale_power_of_two, Tensor? p_scale_qmap, "
+            "bool softmax_in_f32, int block_size, Tensor? q_code=None, Tensor? k_code=None, Tensor? v_code=None) -> Tensor")
+
+
+def _attention_mx_impl(q, q_scale, kT, kT_scale, v, v_scale, mask, scaling, scaling_is_div, p_qmap, p_quant_max,
+                       p_force_scale_power_of_two, p_scale_qmap, softmax_in_f32, block_size, q_code=None, k_code=None, v_code=None):
+    if q.device.type == "cuda":
+        from .mx_attention import attention_mx_or_none
+        out = attention_mx_or_none(q, q_scale, kT, kT_scale, v, v_scale, mask, scaling, scaling_is_div, p_qmap, p_quant_max,
+                                   p_force_scale_power_of_two, p_scale_qmap, block_size, q_code, k_code, v_code)
+        if out is not None:
+            return out
+    ops = torch.ops.quantized_ops
+    s = ops.matmul_mx(q, kT, input_scale=q_scale, weight_scale=kT_scale, block_size=block_size, input_code=q_code, weight_code=k_code)
+    s = torch.ops.aten.div.Tensor(s, scaling) if scaling_is_div else torch.ops.aten.mul.Tensor(s, scaling)     # (no scaling: * 1.0, exact)
+    if mask is not None:
+        s = s + mask
+    p = torch.softmax(s, -1, dtype=torch.float32).to(s.dtype) if softmax_in_f32 else torch.softmax(s, -1)
+    p_scale, p_q = ops.quantize_mx(p, p_qmap, [-1], block_size, p_quant_max, p_force_scale_power_of_two, p_scale_qmap, None)
+    return ops.matmul_mx(p_q, v, input_scale=p_scale, weight_scale=v_scale, block_size=block_size, input_code=None, weight_code=v_code)
+
+
+_lib.impl("attention_mx", _attention_mx_impl, "CompositeExplicitAutograd")
+_lib.impl("attention_mx", lambda q, q_scale, kT, kT_scale, v, *a, **k: q.new_empty(tuple(q.shape[:-1]) + (v.shape[-1],)), "Meta")
+
+
 # ---- outlier side path of a block-scaled linear layer (upstream decomposed.py:450-566) ---------------------------
 # filter_outlier splits an activation into its inliers (|x| <= threshold, outliers zeroed) and the outliers as a CSR
 # matrix of the [rows, C] view, padded to int(numel * max_pct) entries; spmm_csr multiplies that sparse matrix by the

@@ -86,6 +86,8 @@ def routes_report():
     out.update(sorted(GWA_ROUTES.items()))
     from .attention_route import ATTENTION_ROUTES              # long-key, head_dim 32 and ragged FP8 attention cores (csrc/qt_attention_fp8_long.hip, _d32.hip, _ragged.hip)
     out.update(sorted(ATTENTION_ROUTES.items()))
+    from .mx_attention import ATTENTION_MXI_ROUTES             # the block-scaled integer attention core (csrc/qt_attention_mxi.hip or the nodes it replaces)
+    out.update(sorted(ATTENTION_MXI_ROUTES.items()))
     return out
 
 

@@ -35,7 +35,9 @@ Accumulation is exact (int32) where upstream's fp32 / bf16 `aten.linear` rounds,
 bound, not bit for bit.  STATS counts the native launches (tests assert the route was taken).
 
 `fuse_mx_pairs` is the same kind of pass for microscaling graphs: an activation's `calculate_mx_qparam` + `quantize` pair becomes
-one `quantize_mx` node (one device pass, bit-identical results).
+one `quantize_mx` node (one device pass, bit-identical results).  `fuse_mx_attention` (opt-in: `convert_pt2e(fuse_attention=True)`)
+runs behind it and folds the attention core between the quantize_mx nodes of q, k^T and v -- matmul_mx, scaling, mask, softmax,
+quantize_mx, matmul_mx -- into one `attention_mx` node (csrc/qt_attention_mxi.hip where its route takes the call, the same nodes elsewhere).
 """
 import ctypes
 
@@ -45,7 +47,7 @@ from torch.fx import GraphModule
 from . import _native, mx_operand, switches
 from .fake_quantize import _stream_ptr
 
-__all__ = ["fuse_native_gemms", "fuse_conv_q_chains", "fuse_mx_pairs", "fuse_gwa_linears", "STATS", "GWA_STATS"]
+__all__ = ["fuse_native_gemms", "fuse_conv_q_chains", "fuse_mx_pairs", "fuse_mx_attention", "fuse_gwa_linears", "STATS", "GWA_STATS"]
 
 # conv2d_codes_in / conv2d_codes_out: native conv2d_qc launches that took / wrote a code array (counted in their kernel's key as well)
 # conv2d_split_k: gather-kernel launches that split K over more than one workgroup per tile (counted in conv2d_int8 as well)
@@ -1071,6 +1073,151 @@ def fuse_mx_pairs(model: GraphModule) -> int:
         s.replace_all_uses_with(s_new)
         graph.erase_node(q)
         graph.erase_node(s)
+        fused += 1
+    if fused:
+        graph.lint()
+        model.recompile()
+    return fused
+
+
+_DEBUG = False            # set pt2e_native._DEBUG = True to print why fuse_mx_attention left a block-scaled P.V matmul alone
+
+
+def _mx_kwargs(node):
+    """(input_scale, weight_scale, block_size, input_code, weight_code) of a matmul_mx node with two positional operands, or None."""
+    if len(node.args) != 2 or set(node.kwargs) - {"input_scale", "weight_scale", "block_size", "input_code", "weight_code"}:
+        return None
+    return tuple(node.kwargs.get(k) for k in ("input_scale", "weight_scale", "block_size", "input_code", "weight_code"))
+
+
+def _last_dim(d):
+    return d in (-1, 3) and not isinstance(d, bool)
+
+
+def _static_scalar(v):
+    """The float value of a static scalar, or None: a Python number, or the 0-dim constant that export lifts a Python number into
+    (`a * 0.125` on a tensor arrives as get_attr `_tensor_constant<i>` / `lifted_tensor_<i>`, which no node of the graph writes)."""
+    if _static_number(v):
+        return float(v)
+    if getattr(v, "op", None) != "get_attr" or not str(v.target).startswith(("_tensor_constant", "lifted_tensor")):
+        return None
+    t = getattr(v.graph.owning_module, v.target, None)
+    return float(t) if isinstance(t, torch.Tensor) and t.dim() == 0 and t.is_floating_point() else None
+
+
+def _match_mx_attention(mm2):
+    """The arguments of the attention_mx node that replaces the span ending in `mm2`, or a string that says why there is none."""
+    import operator
+    ops, aten = torch.ops.quantized_ops, torch.ops.aten
+    kw2 = _mx_kwargs(mm2)
+    if kw2 is None:
+        return "matmul_mx with other arguments"
+    ps, vs, bs, p_code, v_code = kw2
+    pq, v = mm2.args
+    if not (_is(pq, operator.getitem) and _is(ps, operator.getitem) and pq.args[0] is ps.args[0] and pq.args[1] == 1 and ps.args[1] == 0):
+        return "the first operand and its scale are not the getitems of one quantize_mx"
+    mx = pq.args[0]
+    if not _is(mx, ops.quantize_mx.default) or mx.kwargs or not 5 <= len(mx.args) <= 8:
+        return "the first operand is not a quantize_mx"
+    p, qmap, axes, mx_bs, qmax, pow2, smap, out_code = list(mx.args) + [False, None, None][len(mx.args) - 5:]
+    axes = _axes_list(axes)
+    if axes is None or len(axes) != 1 or not _last_dim(axes[0]) or mx_bs != bs or out_code is not None or p_code is not None \
+            or not isinstance(bs, int) or not _static_number(qmax) or not isinstance(pow2, bool):
+        return "quantize_mx over another axis, block size or with a codebook"
+    if len(mx.users) != 2 or len(pq.users) != 1 or len(ps.users) != 1:
+        return "the quantized probabilities have a second user"
+    span = [pq, ps, mx]
+
+    def sole(node):                                  # a call_function node of the span: one user
+        return getattr(node, "op", None) == "call_function" and len(node.users) == 1
+
+    node, in_f32 = p, False
+    if _is(node, aten.dropout.default):
+        if not sole(node) or not (node.args[1] == 0 or node.args[2] is False):
+            return "dropout with p > 0"
+        span.append(node)
+        node = node.args[0]
+    if _is(node, aten.to.dtype) or _is(node, aten._to_copy.default):
+        dtype = node.args[1] if _is(node, aten.to.dtype) else node.kwargs.get("dtype")
+        if not sole(node) or dtype != torch.bfloat16 or (set(node.kwargs) - {"dtype"}) or len(node.args) > 2:
+            return "a cast that is not a plain cast to bfloat16"
+        span.append(node)
+        node, in_f32 = node.args[0], True
+    if _is(node, aten.softmax.int):
+        dim = node.args[1]
+        dtype = node.args[2] if len(node.args) > 2 else node.kwargs.get("dtype")
+        if (dtype == torch.float32) != in_f32 or dtype not in (None, torch.float32):
+            return "softmax in another dtype"
+    elif _is(node, aten._softmax.default) and not in_f32:
+        dim = node.args[1]
+        if node.args[2] is not False:
+            return "softmax in another dtype"
+    else:
+        return "no softmax in front of the quantize_mx"
+    if not sole(node) or not _last_dim(dim):
+        return "a softmax over another dim, or with a second user"
+    span.append(node)
+    node = node.args[0]
+    mask = None
+    if _is(node, aten.add.Tensor):
+        if not sole(node) or node.kwargs or len(node.args) != 2:
+            return "an add with alpha, or with a second user"
+        x, y = node.args
+        chain = [n for n in (x, y) if any(_is(n, t) for t in (aten.mul.Tensor, aten.div.Tensor, ops.matmul_mx.default))]
+        if len(chain) != 1:
+            return "an add whose operands are not (scores, mask)"
+        mask = y if chain[0] is x else x
+        if not isinstance(mask, torch.fx.Node):
+            return "a mask that is no tensor"
+        span.append(node)
+        node = chain[0]
+    scaling, is_div = 1.0, False
+    if _is(node, aten.mul.Tensor) or _is(node, aten.div.Tensor):
+        if not sole(node) or node.kwargs or len(node.args) != 2 or _static_scalar(node.args[1]) is None:
+            return "a non-static scale"
+        scaling, is_div = _static_scalar(node.args[1]), _is(node, aten.div.Tensor)
+        span.append(node)
+        if isinstance(node.args[1], torch.fx.Node) and len(node.args[1].users) == 1:
+            span.append(node.args[1])                   # the lifted constant's get_attr goes with its only user
+        node = node.args[0]
+    if not _is(node, ops.matmul_mx.default) or not sole(node):
+        return "no matmul_mx in front of the softmax, or its scores have a second user"
+    kw1 = _mx_kwargs(node)
+    if kw1 is None or kw1[2] != bs or kw1[0] is None or kw1[1] is None or vs is None:
+        return "the two matmuls differ in block size, or lack scales"
+    span.append(node)
+    q, kT = node.args
+    return (q, kw1[0], kT, kw1[1], v, vs, mask, scaling, is_div, qmap, float(qmax), pow2, smap, in_f32, bs, kw1[3], kw1[4], v_code), span
+
+
+def fuse_mx_attention(model: GraphModule) -> int:
+    """Folds the attention core of a block-scaled graph -- matmul_mx(q, kT) -> [mul | div by a static scalar] -> [add mask] ->
+    softmax over the last dim [in fp32, cast back] -> quantize_mx along the last axis -> matmul_mx(p', v), every node of it with one
+    user -- into one `attention_mx` node (decomposed.py), which runs csrc/qt_attention_mxi.hip where its contract and route rule take
+    the call and these very nodes elsewhere: bit for bit the unfused graph wherever the node runs the nodes (CPU, fp32, fp16, a shape
+    outside the contract or the route rule), and within the kernel's tolerance of it where the kernel takes the call (another
+    exponential, P codes that flip at rounding boundaries).  The quantize_mx nodes of q, kT and
+    v stay.  Anything that does not match is left alone (why: under _DEBUG).  Idempotent.  Returns the number of folds."""
+    ops = torch.ops.quantized_ops
+    graph = model.graph
+    fused = 0
+    for mm2 in list(graph.nodes):
+        if not _is(mm2, ops.matmul_mx.default):
+            continue
+        hit = _match_mx_attention(mm2)
+        if isinstance(hit, str):
+            if _DEBUG:
+                print(f"fuse_mx_attention: {mm2.name} left alone: {hit}", flush=True)
+            continue
+        args, span = hit
+        with graph.inserting_before(mm2):
+            node = graph.call_function(ops.attention_mx.default, args)
+        node.meta = dict(mm2.meta)
+        if "source_fn_stack" in node.meta:
+            node.meta["source_fn_stack"] = [(node.name, node.target)]
+        mm2.replace_all_uses_with(node)
+        for n in [mm2] + span:                          # users first
+            graph.erase_node(n)
         fused += 1
     if fused:
         graph.lint()

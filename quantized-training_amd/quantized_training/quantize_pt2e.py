@@ -463,7 +463,7 @@ def _eliminate_dequantize_with_no_effect(model: GraphModule):
 
 
 def convert_pt2e(model: GraphModule, output_dtype: str = None, eliminate_no_effect: bool = True, native=None, chain_convs=False, split_k=False,
-                 native_stem=False):
+                 native_stem=False, fuse_attention=False):
     """Lower every FusedAmaxObsFakeQuantize `call_module` of a prepared (and calibrated) graph to
     quantized_ops nodes (upstream :975-1002): quantize / dequantize for per-tensor and per-channel specs,
     quantize_mx + *_mx GEMMs for microscaling, stored codes + dequantize for group-wise affine weights.
@@ -471,7 +471,9 @@ def convert_pt2e(model: GraphModule, output_dtype: str = None, eliminate_no_effe
     split_k=True (with native fusion): the int8 gather convolutions may split K over idle CUs (pt2e_native.fuse_native_gemms(split_k=True):
     the same graph, a mark on the layers' codes buffers).
     native_stem=True (with native fusion): the first convolution (groups = 1, Cin <= 4) becomes a conv2d_q node as well, on the stem
-    kernel (pt2e_native.fuse_native_gemms(stem=True)); with chain_convs it may hand its codes to the next convolution."""
+    kernel (pt2e_native.fuse_native_gemms(stem=True)); with chain_convs it may hand its codes to the next convolution.
+    fuse_attention=True (with native fusion): the attention core of a block-scaled graph becomes one attention_mx node
+    (pt2e_native.fuse_mx_attention)."""
     from . import pt2e_fusion
     pt2e_fusion.unfuse_prepared_graph(model)                  # the lowering below works on the plain prepared graph
     modules = dict(model.named_modules(remove_duplicate=False))
@@ -499,6 +501,8 @@ def convert_pt2e(model: GraphModule, output_dtype: str = None, eliminate_no_effe
     if native or (native is None and pt2e_native.enabled_for(model)):
         pt2e_native.fuse_native_gemms(model, split_k=split_k, stem=native_stem)
         pt2e_native.fuse_mx_pairs(model)                         # calculate_mx_qparam + quantize of an activation -> one quantize_mx
+        if fuse_attention:
+            pt2e_native.fuse_mx_attention(model)                 # matmul_mx -> scaling -> mask -> softmax -> quantize_mx -> matmul_mx: one node
         pt2e_native.fuse_gwa_linears(model)                      # group-wise affine weight: dequantize + linear -> linear_gwa on packed codes
         if chain_convs:
             pt2e_native.fuse_conv_q_chains(model)                # conv2d_q -> relu / hardtanh -> conv2d_q: the producer writes the consumer's codes
