@@ -1347,6 +1347,24 @@ int qt_attention_mxi(const int8_t *q_codes, const float *q_scales, const int8_t 
                      int force_scale_power_of_two, const uint16_t *scale_map_dev, uint16_t *out_dev, long B, int H, int Q, int C,
                      int head_dim, int block_size, void *stream);
 
+/* ---- the attention core of the block-scaled FLOAT recipes (csrc/qt_attention_mxf.hip) -----------------------------------------------
+ * The same span of a converted bf16 graph whose attention matmuls are fp8_e4m3 / fp8_e5m2 / fp4_e2m1 `qs=microscaling,bs=32` pairs with
+ * power-of-two scales, every rounding of the nodes kept (the file header states the chain), in ONE launch on the packed operands that
+ * qt_quantize_mx_bf16 / qt_quantize_mx_strided_bf16 / qt_mx_pack write, read in place: q_codes [B][H][Q][D bits/8] with q_e8m0
+ * [B][H][Q][D/32]; k_codes [B][H][C][D bits/8] with k_e8m0 [B][H][C][D/32] (K^T's SECOND layout); v_codes [B][H][D][C bits/8] with
+ * v_e8m0 [B][H][D][C/32] (V's SECOND layout, V^T).  p_format: the QT_MX_* id shared by all four operands, QT_MX_E4M3, QT_MX_E5M2 or
+ * QT_MX_E2M1; p_map_dev: the 65 536-entry bf16 value map of that format, as P's quantize_mx node holds it (its fpN_eXmY rounding is
+ * the map's, not a closed form); quant_max as quantize_mx gets it; P's scales are powers of two.  Mask, scaling, scaling_is_div and
+ * out_dev as in qt_attention_mxi.  block_size 32, head_dim 64 or 128, C % 128 == 0, 128 <= C <= 16384, Q >= 0, B H <= 65535.
+ * QT_ERR_BAD_ARG: a NULL operand, map or output, any other shape, block size or format id, quant_max not finite and positive, a NaN
+ * scaling, scaling_is_div not 0 / 1.  QT_ERR_UNALIGNED: codes off a 16-byte boundary, k_e8m0 / v_e8m0 off a 4-byte one, out_dev or
+ * the mask off an 8-byte one, mask strides that are no multiples of 4.  All answered before the first HIP call; an empty problem is
+ * QT_OK without a launch.  No atomics, no allocation, no scratch: the same bits on every launch, safe under stream capture. */
+int qt_attention_mxf(const uint8_t *q_codes, const uint8_t *q_e8m0, const uint8_t *k_codes, const uint8_t *k_e8m0, const uint8_t *v_codes,
+                     const uint8_t *v_e8m0, const uint16_t *mask_dev, long mask_sb, long mask_sh, long mask_sq, float scaling,
+                     int scaling_is_div, int p_format, const uint16_t *p_map_dev, float quant_max, uint16_t *out_dev, long B, int H, int Q,
+                     int C, int head_dim, int block_size, void *stream);
+
 /* ---- plain FP8 GEMM on already fake-quantized operands, through hipBLASLt with the algorithm NAMED by the caller ----------
  * C[b][M][N] (bf16) = A[b][M][K] . op(B) (+ bias[N], bf16); A, B are OCP FP8 bytes (format 0 = E4M3, 1 = E5M2) whose
  * values are exactly the fake-quantized bf16 values (unit scale), so the products are the reference's

@@ -1,4 +1,5 @@
-"""attention_mx on the block-scaled integer attention core (csrc/qt_attention_mxi.hip).
+"""attention_mx on the block-scaled attention cores: integer operands (csrc/qt_attention_mxi.hip) and, in front of them, the float
+formats of the scaled matrix instruction (csrc/qt_attention_mxf.hip; the section "The float core" below).
 
 A converted graph of the block-scaled integer recipe holds, per attention layer,
     matmul_mx(q, k^T) -> mul / div by a scalar -> + mask -> softmax(-1) -> quantize_mx(p, ax=-1) -> matmul_mx(p', v)
@@ -19,10 +20,10 @@ import torch
 from . import _native, mx_gemm, mx_operand, switches
 from .fake_quantize import _stream_ptr
 
-__all__ = ["attention_mx_or_none", "pack_operands", "launch", "STATS", "ATTENTION_MXI_ROUTES"]
+__all__ = ["attention_mx_or_none", "pack_operands", "launch", "pack_operands_mxf", "launch_mxf", "STATS", "ATTENTION_MXI_ROUTES"]
 
 STATS = {"attention_native": 0, "attention_fallback": 0}        # calls of the operator on device tensors, by route
-ATTENTION_MXI_ROUTES = {}                 # "attention_mxi:BxHxQxCxD" -> route of the first call with that shape (fused.routes_report)
+ATTENTION_MXI_ROUTES = {}                 # "attention_mxi:BxHxQxCxD" | "attention_mxf:BxHxQxCxD" -> route of the first call with that shape (fused.routes_report)
 _DEBUG = False                            # set mx_attention._DEBUG = True to print why a call ran the nodes
 
 # (B, H, Q, C, D) -> does the packs + qt_attention_mxi route beat the span of nodes?  The bar of attention_route._FP8_LONG_TABLE: a class
@@ -74,6 +75,9 @@ def attention_mx_or_none(q, q_scale, kT, kT_scale, v, v_scale, mask, scaling, sc
         return None
     if not switches.on("QT_MX_GEMM") or switches.mode("QT_FUSED_ATTENTION") == "0":
         return _decline("switched off")
+    fid = _mxf_format(q, q_scale, kT, kT_scale, v, v_scale, p_qmap, p_pow2, p_scale_qmap, block_size)
+    if fid is not None:
+        return _attention_mxf(fid, q, q_scale, kT, kT_scale, v, v_scale, mask, scaling, scaling_is_div, p_qmap, p_quant_max)
     if block_size != 64 or isinstance(block_size, bool):
         return _decline(f"block size {block_size}")
     ts = (q, q_scale, kT, kT_scale, v, v_scale)
@@ -142,3 +146,99 @@ def launch(packed, mask, mask_strides, scaling, scaling_is_div, p_name, p_quant_
         vs_work.data_ptr(), mask.data_ptr() if mask is not None else None, *mask_strides, float(scaling), int(bool(scaling_is_div)),
         ctypes.byref(fmt), float(p_quant_max), int(bool(p_pow2)), p_scale_qmap.data_ptr() if p_scale_qmap is not None else None,
         out.data_ptr(), B, H, Q, C, D, block_size, _stream_ptr(out))
+
+
+# ---- The float core: fp8_e4m3 / fp8_e5m2 / fp4_e2m1 under block size 32 and power-of-two scales (csrc/qt_attention_mxf.hip) ----------
+# Contract: bf16, block size 32 for all four operands, ONE element format for q, k^T, v and P, power-of-two scales (P's forced, no
+# scale map), head_dim 64 or 128, a key count that is a multiple of 128 in 128 .. 16384, B H <= 65535, the mask as above.  The kernel
+# reads the packed operands quantize_mx already wrote (mx_operand's records); an operand without one is packed here, check off.
+
+# (B, H, Q, C, D) -> does qt_attention_mxf beat the span of nodes?  The bar of _MXI_ATTENTION_TABLE, for fp8_e4m3 AND fp4_e2m1
+# (tools/exp_attention_mxf.py -> profiles/attention_mxf.txt).  The table lists exactly the classes that cleared it.
+_MXF_ATTENTION_TABLE = {
+    (1, 32, 512, 512, 128): True, (1, 32, 1024, 1024, 128): True, (1, 32, 2048, 2048, 128): True, (1, 32, 4096, 4096, 128): True,
+    (4, 12, 512, 512, 64): True, (4, 12, 2048, 2048, 64): True,
+}
+
+
+def _mxf_attention_route_takes(B, H, Q, C, D):
+    """The default route of the float core: the committed table, a fixed function of the shape."""
+    return _MXF_ATTENTION_TABLE.get((B, H, Q, C, D), False)
+
+
+def _mxf_format(q, q_scale, kT, kT_scale, v, v_scale, p_qmap, p_pow2, p_scale_qmap, block_size):
+    """The QT_MX_* id when the call is the float core's to answer -- block size 32, forced power-of-two scales for P without a scale
+    map, one of the three formats on q, k^T, v and P's map alike, power-of-two scales on all three operands -- else None."""
+    if block_size != 32 or isinstance(block_size, bool) or not p_pow2 or p_scale_qmap is not None:
+        return None
+    name = mx_operand.format_of(q)
+    if name not in ("fp8_e4m3", "fp8_e5m2", "fp4_e2m1") or mx_operand.format_of(kT) != name or mx_operand.format_of(v) != name \
+            or mx_operand.format_of_qmap(p_qmap) != name:
+        return None
+    if not all(mx_operand.is_pow2(s) for s in (q_scale, kT_scale, v_scale)):
+        return None
+    return mx_operand.FMT_ID[name]
+
+
+def _attention_mxf(fid, q, q_scale, kT, kT_scale, v, v_scale, mask, scaling, scaling_is_div, p_qmap, p_quant_max):
+    ts = (q, q_scale, kT, kT_scale, v, v_scale, p_qmap)
+    if any(t.dtype != torch.bfloat16 or t.device != q.device for t in ts) or q.dim() != 4 or kT.dim() != 4 or v.dim() != 4:
+        return _decline("not bf16 [B, H, ., .] operands on one device")
+    B, H, Q, D = q.shape
+    C = kT.shape[3]
+    nd, nc = D // 32, C // 32
+    if D not in (64, 128) or C % 128 or not 128 <= C <= 16384 or Q < 1 or B * H < 1 or B * H > 65535:
+        return _decline(f"shape B {B} H {H} Q {Q} C {C} D {D}")
+    if tuple(kT.shape) != (B, H, D, C) or tuple(v.shape) != (B, H, C, D) or tuple(q_scale.shape) != (B, H, Q, nd) \
+            or tuple(kT_scale.shape) != (B, H, nd, C) or tuple(v_scale.shape) != (B, H, nc, D):
+        return _decline("operand or scale shapes")
+    key = f"attention_mxf:{B}x{H}x{Q}x{C}x{D}"
+    if not p_quant_max > 0 or p_qmap.numel() != 65536 or not p_qmap.is_contiguous():
+        return _decline("P's quantizer arguments", key)
+    strides = (0, 0, 0)
+    if mask is not None:
+        strides = _mask_strides(mask, B, H, Q, C) if mask.device == q.device else None
+        if strides is None:
+            return _decline("a mask the kernel does not read in place", key)
+    if switches.mode("QT_FUSED_ATTENTION") != "1" and not _mxf_attention_route_takes(B, H, Q, C, D):
+        return _decline("the route rule keeps the nodes", key)
+    packed = pack_operands_mxf(fid, q, q_scale, kT, kT_scale, v, v_scale)
+    out = torch.empty((B, H, Q, D), dtype=torch.bfloat16, device=q.device)
+    code = launch_mxf(fid, packed, mask, strides, scaling, scaling_is_div, p_qmap, p_quant_max, out)
+    if _native.declined(code):
+        return _decline(f"qt_attention_mxf declined ({code})", key)
+    _native.check(code, "qt_attention_mxf")
+    STATS["attention_native"] += 1
+    ATTENTION_MXI_ROUTES.setdefault(key, "qt_attention_mxf")
+    return out
+
+
+def pack_operands_mxf(fid, q, q_scale, kT, kT_scale, v, v_scale):
+    """The packed operands as mx_gemm._float_matmul finds them: the record quantize_mx left (q under ROWS; k^T and v under SECOND, their
+    logical rows being their columns), or a pack with the check off.  -> ((codes, e8m0) of q, of k, of v)."""
+    B, H, Q, D = q.shape
+    C = kT.shape[3]
+    BH = B * H
+
+    def second(t, s, rows, k):                   # t [B, H, k, rows], s [B, H, k / 32, rows]
+        t3, s3 = t.contiguous().view(BH, k, rows), s.contiguous().view(BH, k // 32, rows)
+        return mx_gemm._pack(t3, s3, fid, 32, BH, rows, k, (k * rows, 1, rows), (s3.stride(0), 1, s3.stride(1)), check=False)
+
+    pq = mx_operand.operand(q, mx_operand.ROWS, fid, 32, BH * Q, D)
+    if pq is None:
+        q3, s3 = q.contiguous().view(BH, Q, D), q_scale.contiguous().view(BH, Q, D // 32)
+        pq = mx_gemm._pack(q3, s3, fid, 32, BH, Q, D, (Q * D, D, 1), (s3.stride(0), s3.stride(1), 1), check=False)
+    pk = mx_operand.operand(kT, mx_operand.SECOND, fid, 32, BH * C, D) or second(kT, kT_scale, C, D)
+    pv = mx_operand.operand(v, mx_operand.SECOND, fid, 32, BH * D, C) or second(v, v_scale, D, C)
+    return pq, pk, pv
+
+
+def launch_mxf(fid, packed, mask, mask_strides, scaling, scaling_is_div, p_qmap, p_quant_max, out, block_size=32):
+    """qt_attention_mxf on packed operands into `out` [B, H, Q, D] bf16.  Returns the status code."""
+    pq, pk, pv = packed
+    B, H, Q, D = out.shape
+    C = pk[0].numel() // (B * H * mx_operand.row_bytes(D, fid))
+    return _native.lib().qt_attention_mxf(
+        pq[0].data_ptr(), pq[1].data_ptr(), pk[0].data_ptr(), pk[1].data_ptr(), pv[0].data_ptr(), pv[1].data_ptr(),
+        mask.data_ptr() if mask is not None else None, *mask_strides, float(scaling), int(bool(scaling_is_div)), fid, p_qmap.data_ptr(),
+        float(p_quant_max), out.data_ptr(), B, H, Q, C, D, block_size, _stream_ptr(out))
